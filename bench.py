@@ -11,16 +11,21 @@ guidance with n_iter=20 inner phi iterations, scale 7,7,7,0.9, clip 0.005, aux l
 One "step" = one iteration of the reference loop (gaussian_diffusion.py:213): UNet forward, posterior,
 20x (physics loss + phi SGD), UNet input-gradient, guidance update, noise.  Timed steps are taken
 from the phi-update regime (t <= 0.7 T, the expensive 70 % of the chain), starting at t = 0.3 T from a bounded
-x_t so that the un-trained network's x0 prediction stays inside the physical model's range.  Weights are seeded
+x_t so that the un-trained network's x0 prediction stays inside the physical model's range (t = 0.3 T .. 0 holds 300 steps:
+warm-up and timed steps beyond it repeat the window from the same start).  Weights are seeded
 synthetic (no checkpoint is available offline), inputs synthetic; timing is value independent.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the Winograd 3x3 convolution): `frac` is the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` guided steps and prints the headline figure
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what the timed path
+returned after its last step as DIR/<name>.npy.  Everything else -- `roofline` and the kernel breakdown, `long_window`, the complete
+chains, the bf16x6 / config 3 / 4 / 5 legs, `cpu_baseline` -- is measured only with `--full`.
+`roofline` (`--full`) is for the dominant kernel (the Winograd 3x3 convolution): `frac` is the
 EXECUTED fraction -- MFMA flops the matrix cores ran per launch (algorithmic flops x 16/36 x MFMAs per product) / the
 kernel's duration / the dense MFMA peak of the operand type -- with the duration taken from a kernel trace of a child run
 of this script (`kernel_only_avg_us`) and, beside it, from HIP events around the launches on the launch stream
 (`frac_hip_event`, `avg_launch_ms`: kernel + split-K combine); the algorithmic figure is `algorithmic_frac_of_direct_roof`.
 `cpu_baseline` times the CPU oracle (oracle/, torch-CPU fp32 restatement of the reference) on the host cores, rank 0, N=1.
-`--scale-only`: the N = 2 / 4 / 8 form (headline leg + config-4 leg, nothing else).
+`--full --scale-only`: the N = 2 / 4 / 8 form (headline leg + config-4 leg, nothing else).
 """
 import argparse
 import json
@@ -149,10 +154,18 @@ def timed_steps(args, dev, model, sampler, cond, batch, image_index, steps, warm
     torch.manual_seed(4242 + image_index)       # the per-step noise of this image's chain (device generator)
 
     def run(n_steps, start):
-        return sampler.p_sample_loop(model=model, x_start=x_T, measurement=y, measurement_cond_fn=cond.conditioning,
-                                     record=False, save_root=None, pretrain_model="osmosis", rgb_guidance=False,
-                                     sample_pattern=PATTERN, index_range=(start, start - n_steps + 1),
-                                     reference_rng_order=False)
+        # n_steps guided steps from index `start` down.  The window t = 0.3 T .. 0 holds first + 1 steps: a longer run is a
+        # sequence of windows, each one restarted from the same bounded x_T at index `first` (one p_sample_loop call each)
+        out = None
+        while n_steps > 0:
+            n = min(n_steps, start + 1)
+            out = sampler.p_sample_loop(model=model, x_start=x_T, measurement=y, measurement_cond_fn=cond.conditioning,
+                                        record=False, save_root=None, pretrain_model="osmosis", rgb_guidance=False,
+                                        sample_pattern=PATTERN, index_range=(start, start - n + 1),
+                                        reference_rng_order=False)
+            n_steps -= n
+            start = first
+        return out
 
     if warmup > 0:
         run(warmup, first)
@@ -162,13 +175,14 @@ def timed_steps(args, dev, model, sampler, cond, batch, image_index, steps, warm
         sync.barrier()
     dsync()
     t0 = time.perf_counter()
-    out = run(steps, first - warmup)
+    out = run(steps, first - warmup % (first + 1))      # (the index after the warm-up's last step)
     dsync()
     t_own = time.perf_counter() - t0        # this rank alone (reported per rank; the job time is the MAX below)
     if world > 1:
         sync.barrier()
     dt = time.perf_counter() - t0
     timed_steps.last_own_s = t_own
+    timed_steps.last_out = out              # (x_t, phi variables, loss, pred_xstart) after the last timed step: --dump-outputs
     dump = os.environ.get("OSM_BENCH_DUMP") if dump else None   # tests: per-rank checksum of the headline leg's final x_t
     if dump:
         import hashlib
@@ -177,6 +191,30 @@ def timed_steps(args, dev, model, sampler, cond, batch, image_index, steps, warm
             json.dump({"image_index": image_index, "sha1": hashlib.sha1(x.numpy().tobytes()).hexdigest(),
                        "abs_sum": float(x.double().abs().sum()), "finite": bool(torch.isfinite(x).all())}, f)
     return dt, bool(torch.isfinite(out[0]).all())
+
+
+# elements per array over ALL ranks: each rank writes at most 6 arrays (x_t, pred_xstart, <= 3 phi, loss) of at most
+# DUMP_MAX_ELEMS / world elements, float32 but the loss (float64): at most 5 x 8 MiB + 16 MiB = 56 MiB in all
+DUMP_MAX_ELEMS = 2 << 20
+
+
+def dump_outputs(out_dir, out, rank=0, world=1):
+    """--dump-outputs: what p_sample_loop handed its caller after the last timed step -- the sample x_t, pred_xstart, the phi
+    variables and the per-image loss -- as out_dir/<name>.npy (tensors float32, loss float64; ranks > 0 prefix `rank<r>_`).
+    An array of more than DUMP_MAX_ELEMS / world elements is replaced by a fixed seeded sample of its flattened values."""
+    import numpy as np
+    img, variables, loss, x0 = out
+    arrays = {"x_t": img, "pred_xstart": x0, **(variables or {})}
+    if loss is not None:
+        arrays["loss"] = np.asarray(loss, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(1, DUMP_MAX_ELEMS // world)
+    for name, v in arrays.items():
+        a = v.detach().float().cpu().numpy() if torch.is_tensor(v) else v
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, ("" if rank == 0 else f"rank{rank}_") + name + ".npy"), a)
 
 
 def run_gpu(args, rank, world, dev, sync):
@@ -649,7 +687,7 @@ def live_kernel_time(args, kname):
     match = _kernel_matcher(kname)
     d = tempfile.mkdtemp(prefix="osm_kt_", dir="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-           "--steps", "1", "--warmup", "1", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off",
+           "--steps", "1", "--warmup", "1", "--full", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off",
            "--conv-mode", args.conv_mode, "--batch", str(args.batch), "--image-size", str(args.image_size)]
     try:
         env = {k: v for k, v in os.environ.items() if k != "OSM_BENCH_DUMP"}
@@ -702,7 +740,7 @@ def live_traffic(args, kname):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="osm_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "1", "--warmup", "1", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off",
+               "--steps", "1", "--warmup", "1", "--full", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off",
                "--conv-mode", args.conv_mode, "--batch", str(args.batch), "--image-size", str(args.image_size)]
         try:
             env = {k: v for k, v in os.environ.items() if k != "OSM_BENCH_DUMP"}
@@ -797,7 +835,7 @@ def main():
     ap.add_argument("--conv-mode", default=os.environ.get("OSM_CONV_MODE", "f16x3"), choices=["f32", "bf16x6", "bf16x3", "f16", "f16x3"],
                     help="conv arithmetic: f16x3 (default: Winograd 3x3 layers on 3 fp16 MFMAs per product, the rest bf16x6), "
                          "exact-fp32 MFMA, or fp32 split into 3 / 2 bf16 terms (6 / 3 bf16 MFMAs)")
-    ap.add_argument("--dump-layers", default="", help="write per-conv-shape timings (JSON) to this path")
+    ap.add_argument("--dump-layers", default="", help="with --full: write per-conv-shape timings (JSON) to this path")
     ap.add_argument("--tiny", action="store_true", help="tiny UNet (plumbing check only; NOT a valid bench)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "off"],
                     help="auto: roofline.traffic is measured in this run (two short child runs under rocprofv3 --pmc, rank 0, N = 1); "
@@ -811,21 +849,32 @@ def main():
     ap.add_argument("--secondary-steps", type=int, default=3,
                     help="timed steps of each secondary configuration (BASELINE configs 3 and 5; N = 1 only; 0 = skip)")
     ap.add_argument("--scale-only", action="store_true",
-                    help="scaling runs (N = 2 / 4 / 8): the headline leg and the config-4 leg only -- no rocprofv3 child runs, no CPU "
-                         "baseline, no complete chain, no long window, no bf16x6 / config 3 / config 5 legs: < 60 s per N after setup")
+                    help="with --full, scaling runs (N = 2 / 4 / 8): the headline leg and the config-4 leg only -- no rocprofv3 child "
+                         "runs, no CPU baseline, no complete chain, no long window, no bf16x6 / config 3 / config 5 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: roofline and kernel breakdown (rocprofv3 child runs with "
+                         "--pmc auto), long window, complete chains, bf16x6 / config 3 / 4 / 5 legs, CPU baseline.  Without it the "
+                         "options of those legs have no effect")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned after its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs --full (the per-shape table comes from the roofline replay)")
     if args.scale_only:
         args.pmc, args.cpu_steps, args.full_chain, args.long_window = "off", 0, 0, 0
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        # started plainly with --gpus N: become the one-process-per-GPU job the contract describes
+        # started plainly with --gpus N: run the one-process-per-GPU job the contract describes as a child process
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                   f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-                                   "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(rc if rc >= 0 else 128 - rc)       # killed by signal s: 128 + s, as a shell reports it
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -852,11 +901,15 @@ def main():
         model, sampler, cond = build_case(args, dev, c["batch"], c["unet"], c["diffusion"], c["operator"], c["cond"], c["aux"],
                                           conv_mode=args.conv_mode)
         dt, finite = timed_steps(args, dev, model, sampler, cond, c["batch"], 7, args.steps, args.warmup)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_steps.last_out)
         print(json.dumps({"workload": c["workload"], "images_per_gpu": c["batch"], "conv_arithmetic": model.conv_mode,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
                           "image_steps_per_s": round(c["batch"] * args.steps / dt, 2), "finite_outputs": finite}), flush=True)
         return
     model, dt, finite, rank_rows = run_gpu(args, rank, world, dev, sync)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_steps.last_out, rank, world)
     units = world * args.batch * args.steps
     line = {
         "metric": "denoise-steps/sec (256x256 RGBD, 1000-step DDPM+guidance)",
@@ -903,7 +956,7 @@ def main():
             raise SystemExit(f"bench.py: ranks shared a device ({line['per_rank_device']}) on a node with {ndev} GPUs")
     rl = breakdown = None
     long_window = chain = rgb_chain = None
-    if rank == 0:               # replays the headline engine's plans: before the config-4 leg replaces that engine
+    if rank == 0 and args.full:     # replays the headline engine's plans: before the config-4 leg replaces that engine
         rl, breakdown = roofline(model, args)
         if world == 1 and not args.tiny and args.secondary_steps > 0 and not args.scale_only:     # (--secondary-steps 0 = the headline leg alone: profiling runs)
             # same model, same engine, same start state as the headline leg -- only longer (the driver passes --steps 20)
@@ -926,8 +979,8 @@ def main():
                     rgb_chain = rgb_guidance_chain(args, dev, model)
                 except Exception as e:
                     rgb_chain = {"error": f"{type(e).__name__}: {e}"[:300]}
-    cfg4 = run_config4(args, dev, model, rank, world, sync) if (args.secondary_steps > 0 and not args.tiny) else None
-    if rank == 0:
+    cfg4 = run_config4(args, dev, model, rank, world, sync) if (args.full and args.secondary_steps > 0 and not args.tiny) else None
+    if rank == 0 and args.full:
         line["roofline"] = rl
         att = breakdown.pop("_attention", None)
         if att:
@@ -970,6 +1023,7 @@ def main():
             del model
             line["cpu_baseline"] = cpu_baseline(args)
             line["speedup_vs_cpu_baseline"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         sync.barrier()

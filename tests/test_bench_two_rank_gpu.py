@@ -24,7 +24,7 @@ def test_bench_two_ranks_one_json_line():
     env = dict(os.environ, OSM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--tiny", "--image-size", "32", "--cpu-steps", "0"]
+           "--tiny", "--image-size", "32", "--cpu-steps", "0", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -37,14 +37,14 @@ def test_bench_two_ranks_one_json_line():
 
 def test_bench_eight_ranks_full_size_dry_run(tmp_path):
     """The launcher at the world size the driver's SCALE run uses, on the one GPU of the test box: plain
-    `bench.py --gpus 8` (it re-executes itself under torch.distributed.run), OSM_BENCH_BACKEND=gloo so that the 8 ranks
+    `bench.py --gpus 8` (it runs itself under torch.distributed.run in a child process), OSM_BENCH_BACKEND=gloo so that the 8 ranks
     share cuda:0 (8 x (weight images + 2.8 GB of activations) fits 288 GB).  Full-size model, 2 timed steps: one JSON line,
     n_gpus 8, value = 8 ranks x steps / max-rank time, every rank worked on ITS image (images[rank::8]) and rank 0's
     result is bit-identical to a 1-rank run of the same command."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     env = dict(os.environ, OSM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OSM_BENCH_DUMP=str(tmp_path))
-    tail = ["--steps", "2", "--warmup", "1", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off", "--scale-only"]
+    tail = ["--steps", "2", "--warmup", "1", "--cpu-steps", "0", "--secondary-steps", "0", "--pmc", "off", "--full", "--scale-only"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + tail, env=env, capture_output=True,
                          text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -76,13 +76,13 @@ def test_bench_eight_ranks_full_size_dry_run(tmp_path):
 
 
 def test_bench_single_gpu_line_with_the_whole_chain_legs():
-    """The N = 1 line the driver records (BENCH_rNN.json), with the slow side legs switched off (no PMC child runs, no CPU baseline,
+    """The N = 1 `--full` line, with the slow side legs switched off (no PMC child runs, no CPU baseline,
     one step of the config 3 / 5 legs): the contract fields, `long_window`, `full_chain` (one complete Osmosis image) and
     `rgb_guidance_chain` (one complete image of the shipped rgb-guidance config: fused, FINITE outputs -- clip_denoised bounds the chain)."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--cpu-steps", "0", "--pmc", "off",
-                          "--secondary-steps", "1", "--long-window", "8"], capture_output=True, text=True, timeout=1500, cwd=ROOT,
+                          "--secondary-steps", "1", "--long-window", "8", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT,
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -100,6 +100,68 @@ def test_bench_single_gpu_line_with_the_whole_chain_legs():
     assert rg["fused_loop"] is True and rg["finite_outputs"] is True and rg["steps"] == 1000 and rg["max_abs_sample"] < 1.5
     assert 10 < rg["wall_s"] < 40 and abs(rg["ms_per_step"] - rg["wall_s"]) < 1e-6 * 1000
     assert [s["workload"][:8] for s in d["secondary"]] == ["config 4", "config 3", "config 5"]
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """Without --full the line is the headline figure alone (no roofline, side legs or CPU baseline), --steps is the number of
+    timed steps, and --dump-outputs writes the timed path's last-step outputs (x_t is the one the timed leg checksums under
+    OSM_BENCH_DUMP); two runs with the same arguments write the same arrays.  Tiny UNet: a plumbing check, not a benchmark."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import hashlib
+
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        (tmp_path / f"sum_{tag}").mkdir()
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tiny",
+                              "--image-size", "32", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT,
+                             env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OSM_BENCH_DUMP=str(tmp_path / f"sum_{tag}")))
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "denoise-steps/sec"
+    assert abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) < 1e-2 * d["value"]
+    for k in ("roofline", "kernel_breakdown_ms_per_step", "long_window", "full_chain", "rgb_guidance_chain", "secondary",
+              "same_workload_bf16x6", "cpu_baseline"):
+        assert k not in d, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "phi_a.npy", "phi_b.npy", "phi_inf.npy", "pred_xstart.npy", "x_t.npy"], names
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+    x = np.load(tmp_path / "a" / "x_t.npy")
+    assert x.dtype == np.float32 and x.shape == (1, 4, 32, 32)
+    assert hashlib.sha1(x.tobytes()).hexdigest() == json.load(open(tmp_path / "sum_a" / "rank0_of_1.json"))["sha1"]
+    assert np.load(tmp_path / "a" / "pred_xstart.npy").shape == (1, 4, 32, 32)
+
+
+def test_bench_steps_beyond_one_window(tmp_path):
+    """The timed window t = 0.3 T .. 0 holds 300 steps: --warmup 301 --steps 305 (both longer than it) runs as consecutive windows
+    from the same start and still times exactly 305 steps, with finite outputs; the dumped x_t is the timed leg's final one."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import hashlib
+
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "305", "--warmup", "301", "--tiny",
+                          "--image-size", "32", "--dump-outputs", str(tmp_path / "d")], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OSM_BENCH_DUMP=str(tmp_path)))
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 305 and d["warmup"] == 301 and d["config"]["finite_outputs"] is True
+    assert abs(d["value"] - 305 / (d["ms_per_step"] * 305e-3)) < 1e-2 * d["value"]
+    x = np.load(tmp_path / "d" / "x_t.npy")
+    assert np.isfinite(x).all() and hashlib.sha1(x.tobytes()).hexdigest() == json.load(open(tmp_path / "rank0_of_1.json"))["sha1"]
 
 
 def _bench_two(tmp, env_extra, tag):
@@ -146,14 +208,14 @@ def test_bench_survives_rccl_failure(tmp_path):
 
 
 def test_bench_two_ranks_full_size_with_the_config4_leg(tmp_path):
-    """What the driver's SCALE run executes at N > 1 with the default flags, on the one GPU of the test box (gloo, two ranks share
+    """What a `--full` scaling run executes at N > 1, on the one GPU of the test box (gloo, two ranks share
     cuda:0): the headline leg, then the config-4 leg on EVERY rank (a batch of `--images-per-gpu` chains per rank through the same
     model / weight images, barriers through RankSync), one JSON line whose first `secondary` entry is that leg."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     env = dict(os.environ, OSM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OSM_BENCH_DUMP=str(tmp_path))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-steps", "0",
-                          "--secondary-steps", "1", "--images-per-gpu", "2"], env=env, capture_output=True, text=True, timeout=1200,
+                          "--secondary-steps", "1", "--images-per-gpu", "2", "--full"], env=env, capture_output=True, text=True, timeout=1200,
                          cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -479,3 +479,25 @@ def test_get_optimizer_factory():
     assert U.get_optimizer("GD", groups) is None and U.get_optimizer("", groups) is None
     with pytest.raises(ValueError, match="not supported"):
         U.get_optimizer("nadam", groups)
+
+
+def test_bench_dump_outputs_names_dtypes_and_sample(tmp_path):
+    """bench.py --dump-outputs: one .npy per output of the timed path (tensors float32, loss float64, ranks > 0 prefixed), and an
+    output larger than DUMP_MAX_ELEMS replaced by the same seeded sample of its values on every call."""
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 1000
+    big = torch.arange(n, dtype=torch.float64)
+    out = (big, {"phi_a": torch.ones(1, 3), "phi_inf": torch.zeros(1, 3)}, [0.25], torch.ones(1, 4, 8, 8, dtype=torch.float16))
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out, rank=1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "phi_a.npy", "phi_inf.npy", "pred_xstart.npy", "x_t.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == ["rank1_" + f for f in sorted(os.listdir(tmp_path / "a"))]
+    x = np.load(tmp_path / "a" / "x_t.npy")
+    assert x.dtype == np.float32 and x.shape == (bench.DUMP_MAX_ELEMS,) and len(np.unique(x)) == x.size
+    assert np.array_equal(x, np.load(tmp_path / "b" / "rank1_x_t.npy"))
+    x0 = np.load(tmp_path / "a" / "pred_xstart.npy")
+    assert x0.dtype == np.float32 and x0.shape == (1, 4, 8, 8) and (x0 == 1).all()
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [0.25]
+    bench.dump_outputs(str(tmp_path / "c"), out, rank=3, world=4)        # the cap is shared by the ranks of the job
+    assert np.load(tmp_path / "c" / "rank3_x_t.npy").shape == (bench.DUMP_MAX_ELEMS // 4,)

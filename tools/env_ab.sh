@@ -7,7 +7,7 @@ R=${1:-2}; shift
 for r in $(seq $R); do
   for e in "$@"; do
     echo -n "$e  "
-    env $e timeout 300 python bench.py --steps 60 --warmup 5 --cpu-steps 0 --pmc off --secondary-steps 0 2>/dev/null | tail -1 |
+    env $e timeout 300 python bench.py --full --steps 60 --warmup 5 --cpu-steps 0 --pmc off --secondary-steps 0 2>/dev/null | tail -1 |
       python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'attention', d['kernel_breakdown_ms_per_step'].get('attention_core'), d['config']['finite_outputs'])"
   done
 done

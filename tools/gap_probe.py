@@ -2,7 +2,7 @@
 """Kernel-busy time vs wall time over the timed steps of a bench.py run, from a rocprofv3 --kernel-trace CSV.
 
     cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $OUT -- \
-        python bench.py --steps 20 --warmup 3 --cpu-steps 0 --secondary-steps 0
+        python bench.py --steps 20 --warmup 3
     tools/gap_probe.py $OUT/**/*kernel_trace.csv
 The window is the span between the first and the last `phys_finalize_kernel` (only the sampler's steps launch it); prints
 wall, busy (union of kernel intervals), the gap histogram and the kernels that follow the longest gaps.

@@ -8,7 +8,7 @@ i=0
 for grp in "SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_WAIT_INST_LDS"; do
   i=$((i+1))
-  timeout -k 5 400 rocprofv3 --pmc $grp --output-format csv -d "$out/g$i" -- python $repo/bench.py --steps 2 --warmup 1 --cpu-steps 0 --pmc off --secondary-steps 0 > "$out/g$i.log" 2>&1
+  timeout -k 5 400 rocprofv3 --pmc $grp --output-format csv -d "$out/g$i" -- python $repo/bench.py --full --steps 2 --warmup 1 --cpu-steps 0 --pmc off --secondary-steps 0 > "$out/g$i.log" 2>&1
 done
 python - "$out" <<'PY'
 import csv, glob, sys, collections
