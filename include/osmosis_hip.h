@@ -310,6 +310,28 @@ int osm_posterior_typed(const float* model_out, const float* x, const float* coe
  * not: ATen's clamp_backward).  With clip_denoised the guidance gradient d loss/d x0 is masked by it before osm_posterior_bwd and the
  * update kernels read it. */
 int osm_clamp_bwd(float* g, const float* x_raw, float lo, float hi, long long n, void* stream);
+/* Exact quantile of |x| over n fp32 elements (util/img_utils.py:8-15 `torch.quantile(img.abs(), s)`, linear interpolation):
+ * r = s*(n-1) in fp32, lo = floor(r), hi = ceil(r), w = r - lo, q = lerp(|x|_(lo), |x|_(hi), w) (torch.lerp's two-branch form);
+ * any NaN in x makes q NaN.  q: device float[1]; idx: device int[2] = the flat indices of the two order statistics in stable-sort
+ * order (among equal |x|, the (k - #smaller)-th occurrence by index).  Radix select on bits(x) & 0x7fffffff: 9 launches, integer
+ * histograms, deterministic.  1 <= n <= 2^24 (torch.quantile refuses more); 0 <= s <= 1.  ws: device workspace of
+ * osm_quantile_abs_ws_bytes(n) bytes (16-byte aligned; -1 for an n out of range). */
+long long osm_quantile_abs_ws_bytes(long long n);
+int osm_quantile_abs(const float* x, long long n, float s, float* q, int* idx, void* ws, void* stream);
+/* osm_posterior_typed with `dynamic_threshold` (process_xstart, posterior_mean_variance.py:43-50; util/img_utils.py:8-15):
+ *   x0_raw = the prediction (as osm_posterior_typed forms it), q = quantile(|x0_raw|, s) over ALL B*4*HW elements (osm_quantile_abs:
+ *   q / idx outputs, ws its workspace), x0 = clip(q*x0_raw, -1, 1) (NaN kept; the reference MULTIPLIES by the quantile), mean formed
+ *   from that x0 per mean_kind (previous_x: mean = out), logvar per var_kind.  A clip_denoised clamp after it changes nothing, so
+ *   the one entry point serves both.  B*4*HW <= 2^24.  11 launches; q stays on the device. */
+int osm_posterior_dynthr(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                         float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int HW,
+                         void* stream);
+/* Backward of x0 = clip(x0_raw * quantile(|x0_raw|, s), -1, 1) applied to g = d loss/d x0 in place (n elements; q / idx from
+ * osm_quantile_abs or osm_posterior_dynthr on the same x0_raw and s; ws: osm_quantile_abs_ws_bytes(n) bytes):
+ *   g <- q*m*g, m = [-1 <= q*x0_raw <= 1] (ATen clamp_backward), then g[idx[0]] += sgn(x0_raw[idx[0]])*(1-w)*S and
+ *   g[idx[1]] += sgn(x0_raw[idx[1]])*w*S, S = sum m*g*x0_raw (d loss/d q) summed in a fixed order.  2 launches.  With clip_denoised
+ * also on, the second clamp masks nothing more: this is the whole backward. */
+int osm_dynthr_bwd(float* g, const float* x_raw, const float* q, const int* idx, float s, long long n, void* ws, void* stream);
 
 /* physical forward model + guidance loss (measurements.py:138-151,251-264,363-376;
  * condition_methods.py:109-144; losses.py:29-83; utils.py:544-566,674-700) */

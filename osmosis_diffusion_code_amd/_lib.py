@@ -110,6 +110,9 @@ _SIGS = {
     "osm_posterior": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "osm_posterior_typed": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P],
     "osm_clamp_bwd": [_P, _P, _F, _F, _LL, _P],
+    "osm_quantile_abs": [_P, _LL, _F, _P, _P, _P, _P],
+    "osm_posterior_dynthr": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "osm_dynthr_bwd": [_P, _P, _P, _P, _F, _LL, _P, _P],
     "osm_phys_nblk": [_I],
     "osm_phys_reduce": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P],
     "osm_phys_finalize": [C.POINTER(PhysDesc), _P, _P, _P, _I, _P, _P, _P],
@@ -131,7 +134,7 @@ for _n in ("osm_conv2d_nhwc", "osm_gn_stats", "osm_gn_apply", "osm_gn_fwd", "osm
     _SIGS[_n + "_h"] = _SIGS[_n]
 _SIGS["osm_half_to_f32"] = [_P, _LL, _P, _LL, _LL, _I, _P]
 _SIGS["osm_f32_to_half"] = [_P, _LL, _P, _LL, _LL, _I, _P]
-EXPORTS = sorted(list(_SIGS) + ["osm_last_error", "osm_packed_weight_elems", "osm_winograd_weight_elems"])
+EXPORTS = sorted(list(_SIGS) + ["osm_last_error", "osm_packed_weight_elems", "osm_winograd_weight_elems", "osm_quantile_abs_ws_bytes"])
 
 _lib = None
 _lock = threading.Lock()
@@ -158,6 +161,8 @@ def load():
             lib.osm_packed_weight_elems.restype = C.c_longlong
             lib.osm_winograd_weight_elems.argtypes = [_I, _I, _I, _I]
             lib.osm_winograd_weight_elems.restype = C.c_longlong
+            lib.osm_quantile_abs_ws_bytes.argtypes = [_LL]
+            lib.osm_quantile_abs_ws_bytes.restype = C.c_longlong
             lib.osm_last_error.argtypes = []
             lib.osm_last_error.restype = C.c_char_p
             _lib = lib

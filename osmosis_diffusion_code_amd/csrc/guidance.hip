@@ -340,6 +340,55 @@ __global__ __launch_bounds__(256) void posterior_kernel(const float* __restrict_
   }
 }
 
+// posterior_kernel's raw pass for dynamic_threshold: the prediction to x0_raw, logvar, and the previous_x mean (= out); x0 and the
+// other means wait for the batch-wide quantile (dynthr_apply_kernel).
+template <int MK, int VK>
+__global__ __launch_bounds__(256) void posterior_raw_kernel(const float* __restrict__ mo, const float* __restrict__ x,
+                                                             const float* __restrict__ coef, float* __restrict__ x0_raw,
+                                                             float* __restrict__ mean, float* __restrict__ logvar, int B, int HW) {
+  const long long total = (long long)B * 4 * HW;
+  const float c0 = coef[0], c1 = coef[1], mn = coef[4], mxl = coef[5];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / (4LL * HW);
+    const long long rem = i - b * 4LL * HW;
+    const float eps = mo[b * 8LL * HW + rem];
+    x0_raw[i] = MK == 1 ? eps : c0 * x[i] - c1 * eps;
+    if (MK == 2) mean[i] = eps;
+    if (VK == 1) {
+      logvar[i] = mn;
+    } else {
+      const float v = mo[b * 8LL * HW + 4LL * HW + rem];
+      if (VK == 2) {
+        logvar[i] = v;
+      } else {
+        const float frac = (v + 1.0f) / 2.0f;
+        logvar[i] = frac * mxl + (1.0f - frac) * mn;
+      }
+    }
+  }
+}
+
+// dynamic_threshold (util/img_utils.py:8-15): x0 = clip(q x0_raw, -1, 1) with q = quantile(|x0_raw|, s) over the whole batch (NaN
+// kept, as torch.clip), then the mean from that x0 as posterior_kernel forms it (previous_x: the raw pass already wrote mean = out).
+// A following clip_denoised clamp changes nothing.
+template <int MK>
+__global__ __launch_bounds__(256) void dynthr_apply_kernel(const float* __restrict__ x0_raw, const float* __restrict__ x,
+                                                            const float* __restrict__ coef, const float* __restrict__ q,
+                                                            float* __restrict__ x0, float* __restrict__ mean, long long total) {
+  const float c2 = coef[2], c3 = coef[3], qv = q[0];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const float u = x0_raw[i] * qv;
+    const float xs = (u != u) ? u : fminf(fmaxf(u, -1.0f), 1.0f);
+    x0[i] = xs;
+    if (MK != 2) {
+      const float xv = x[i];
+      mean[i] = c2 * xs + c3 * xv;
+    }
+  }
+}
+
 // backward of x.clamp(lo, hi) (ATen clamp_backward: the gradient passes where lo <= x <= hi, bounds included; NaN -> 0)
 __global__ __launch_bounds__(256) void clamp_bwd_kernel(float* __restrict__ g, const float* __restrict__ x_raw, float lo, float hi,
                                                          long long n) {
@@ -652,6 +701,42 @@ extern "C" int osm_posterior_typed(const float* model_out, const float* x, const
   }
 #undef OSM_POST
   return osm::check_launch("posterior_kernel");
+}
+
+extern "C" int osm_posterior_dynthr(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                                    float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int HW,
+                                    void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && HW > 0,
+              "osm_posterior_dynthr: bad argument");
+  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "osm_posterior_dynthr: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)");
+  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "osm_posterior_dynthr: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)");
+  const long long total = (long long)B * 4 * HW;
+  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr: quantile() input tensor is too large (%lld elements > 2^24)", total);
+  const dim3 grid(grid_for(total)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define OSM_POST(MK, VK) \
+  hipLaunchKernelGGL((posterior_raw_kernel<MK, VK>), grid, block, 0, st, model_out, x, coef, x0_raw, mean, logvar, B, HW)
+  switch (mean_kind * 3 + var_kind) {
+    case 0: OSM_POST(0, 0); break;
+    case 1: OSM_POST(0, 1); break;
+    case 2: OSM_POST(0, 2); break;
+    case 3: OSM_POST(1, 0); break;
+    case 4: OSM_POST(1, 1); break;
+    case 5: OSM_POST(1, 2); break;
+    case 6: OSM_POST(2, 0); break;
+    case 7: OSM_POST(2, 1); break;
+    default: OSM_POST(2, 2); break;
+  }
+#undef OSM_POST
+  int rc = osm::check_launch("posterior_raw_kernel");
+  if (rc) return rc;
+  if ((rc = osm_quantile_abs(x0_raw, total, s, q, idx, ws, stream))) return rc;
+  if (mean_kind == 2) {
+    hipLaunchKernelGGL(dynthr_apply_kernel<2>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  } else {
+    hipLaunchKernelGGL(dynthr_apply_kernel<0>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  }
+  return osm::check_launch("dynthr_apply_kernel");
 }
 
 extern "C" int osm_posterior(const float* model_out, const float* x, const float* coef, float* x0, float* mean,

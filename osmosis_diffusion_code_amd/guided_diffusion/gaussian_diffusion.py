@@ -17,8 +17,9 @@ configuration (`rgb_guidance=True`: DDPM / DDIM `p_sample` + 'ps' conditioning o
 gaussian noiser) runs through the same loop: osm_phys_* with the identity operator (kind 3) for
 ||y - x0[:, 0:3]|| and its gradient, osm_guide_update(_rng) or osm_ddim_update for the step.  The per-step
 noise is drawn inside the update kernel (Philox-4x32-10) unless `noise="aten"` asks for torch's stream.
-Any other combination (third-party conditioners / operators / processors, dynamic_threshold) falls back to a
-generic loop that follows the reference control flow on top of the HIP UNet operator through torch.autograd.
+`dynamic_threshold` runs there too (osm_posterior_dynthr / osm_dynthr_bwd: an on-device exact quantile of the whole batch) when the
+batch is one engine pass.  Any other combination (third-party conditioners / operators / processors, a chunked batch with
+dynamic_threshold) falls back to a generic loop that follows the reference control flow on top of the HIP UNet operator through torch.autograd.
 """
 import math
 
@@ -30,6 +31,7 @@ from ..osmosis_utils import utils as utilso
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
 __SAMPLER__ = {}
+DYNAMIC_THRESHOLD_S = 0.98     # the quantile process_xstart asks dynamic_thresholding for (posterior_mean_variance.py:45)
 
 
 def register_sampler(name: str):
@@ -176,11 +178,13 @@ class GaussianDiffusion:
         raise NotImplementedError
 
     # ------------------------------------------------------------------ fused (HIP) loop
-    def _fast_path_ok(self, model, cond_fn, pretrain_model, rgb_guidance, sample_pattern):
+    def _fast_path_ok(self, model, cond_fn, pretrain_model, rgb_guidance, sample_pattern, shape=None):
         """The conditioner whose step the fused loop implements, or None (-> `_generic_loop`).  Two configurations:
         the Osmosis one (pretrain_model 'osmosis', 'osmosis' conditioning with gradient_x_prev, a physical operator) and the
         rgb-guidance one (`rgb_guidance=True`: `DDPM.p_sample` / `DDIM.p_sample` + 'ps' conditioning on an identity operator
-        with the gaussian noiser; gaussian_diffusion.py:231-232,296-302, condition_methods.py:234-251)."""
+        with the gaussian noiser; gaussian_diffusion.py:231-232,296-302, condition_methods.py:234-251).  shape: x_start's
+        [B, C, H, W] (`dynamic_threshold` needs it)."""
+        import os
         from .condition_methods import PosteriorSampling, PosteriorSamplingOsmosis
         from .unet import UNetModel
         cond = getattr(cond_fn, "__self__", None)
@@ -188,8 +192,15 @@ class GaussianDiffusion:
             return None
         if self.mean_processor.hip_kernel != "osm_posterior" or self.var_processor.hip_kernel != "osm_posterior":
             return None
-        if self.mean_processor.dynamic_threshold:            # (a batch-wide quantile: no shipped config; `_generic_loop`)
-            return None
+        if self.mean_processor.dynamic_threshold:
+            # the reference's quantile is taken over the WHOLE batch (util/img_utils.py:8-15): fused only when the batch runs as ONE
+            # engine pass and within torch.quantile's 2^24 elements (a larger one raises in `_generic_loop`, as the reference does);
+            # OSM_FUSED_DYNTHR=0 keeps such chains on `_generic_loop`
+            if os.environ.get("OSM_FUSED_DYNTHR", "1") == "0" or shape is None:
+                return None
+            B, C, H, W = shape
+            if B * C * H * W > ops.QUANTILE_MAX_N or len(self.chunk_sizes(B, model.images_in_flight(B, H, W))) != 1:
+                return None
         if sample_pattern is not None and sample_pattern.get("pattern") not in (None, "original"):
             if sample_pattern.get("local_M", 1) != 1:
                 return None
@@ -305,7 +316,14 @@ class GaussianDiffusion:
         x0, mean, logvar = (torch.empty(B, 4, H, W, **f32) for _ in range(3))
         # `clip_denoised: True` (configs/rgb_guidance_sample_config.yaml; posterior_mean_variance.py:43-50): x0 is clamped inside
         # osm_posterior_typed, the unclamped prediction is kept for the clamp's backward (osm_clamp_bwd masks d loss / d x0)
-        x0_raw = torch.empty(B, 4, H, W, **f32) if self.mean_processor.clip_denoised else None
+        # `dynamic_threshold: True` (util/img_utils.py:8-15): x0 = clip(x0_raw * quantile(|x0_raw|, 0.98), -1, 1) over the whole batch
+        # (osm_posterior_dynthr; q and its order statistics stay on the device for osm_dynthr_bwd); `_fast_path_ok` guarantees one chunk
+        dyn = bool(self.mean_processor.dynamic_threshold)
+        x0_raw = torch.empty(B, 4, H, W, **f32) if (self.mean_processor.clip_denoised or dyn) else None
+        if dyn:
+            assert len(chunks) == 1, "dynamic_threshold couples every image: the fused loop takes it in one engine pass only"
+            q_dev, q_idx = torch.zeros(1, **f32), torch.zeros(2, device=dev, dtype=torch.int32)
+            q_ws = ops.quantile_workspace(B * 4 * HW, dev)
         g = torch.empty(B, 4, H, W, **f32)
         loss_all = torch.zeros(B, **f32)
         scale4 = cond.scale4(dev)
@@ -370,9 +388,13 @@ class GaussianDiffusion:
                 if not single:
                     ce.x_in.copy_(x_state[c0:c1])
                 ce.run_forward()
-                ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW,
-                              self.mean_processor.kernel_kind, self.var_processor.kernel_kind,
-                              None if x0_raw is None else x0_raw[c0:c1])
+                if dyn:
+                    ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
+                                         self.mean_processor.kernel_kind, self.var_processor.kernel_kind, DYNAMIC_THRESHOLD_S)
+                else:
+                    ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW,
+                                  self.mean_processor.kernel_kind, self.var_processor.kernel_kind,
+                                  None if x0_raw is None else x0_raw[c0:c1])
                 if trace is not None:
                     model_out[c0:c1].copy_(ce.out)
                 gg = dxu = grad_out = None
@@ -383,7 +405,9 @@ class GaussianDiffusion:
                         cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
                                           loss_out=loss_all[c0:c1])
                     have_loss = True
-                    if x0_raw is not None:
+                    if dyn:                               # (a clip_denoised clamp after it masks nothing more)
+                        ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
+                    elif x0_raw is not None:
                         ops.clamp_bwd(g[c0:c1], x0_raw[c0:c1])
                     ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
                     ce.run_backward()
@@ -404,6 +428,8 @@ class GaussianDiffusion:
                            loss=loss_all.clone() if have_loss else None, phi=None if phi is None else phi.clone())
                 if noise_used is not None:
                     rec["noise"] = noise_used.clone()
+                if dyn:
+                    rec["q"] = q_dev.clone()
                 if guided:
                     rec["grad"] = grad_all
                 trace.append(rec)
@@ -453,7 +479,7 @@ class GaussianDiffusion:
             # (gaussian_diffusion.py:268 / :499, condition_methods.py:223 / :249) -- autograd refuses that on a multi-output view.
             raise RuntimeError("Output 0 of SplitBackward0 is a view and is being modified inplace: the 'previous_x' mean processor "
                                "only runs with the DDIM sampler on the rgb-guidance branch (as in the reference)")
-        cond = self._fast_path_ok(model, measurement_cond_fn, pretrain_model, rgb_guidance, sample_pattern)
+        cond = self._fast_path_ok(model, measurement_cond_fn, pretrain_model, rgb_guidance, sample_pattern, tuple(x_start.shape))
         if cond is not None:
             return self._fused_loop(model, cond, x_start, measurement, sample_pattern, kwargs, record=record,
                                     record_every=record_every)

@@ -384,6 +384,43 @@ def clamp_bwd(g, x_raw, lo=-1.0, hi=1.0):
     call("osm_clamp_bwd", ptr(g), ptr(x_raw), float(lo), float(hi), g.numel(), _s(), keep=(g, x_raw))
 
 
+QUANTILE_MAX_N = 1 << 24      # torch.quantile's limit, kept by osm_quantile_abs
+
+
+def quantile_ws_bytes(n: int) -> int:
+    """Bytes of the device workspace `quantile_abs` / `posterior_dynthr` / `dynthr_bwd` take for n elements."""
+    b = query("osm_quantile_abs_ws_bytes", int(n))
+    if b < 0:
+        raise _lib.OsmosisHipError(f"quantile() input tensor is too large ({n} elements > 2^24)" if n > QUANTILE_MAX_N
+                                   else f"quantile of {n} elements")
+    return int(b)
+
+
+def quantile_workspace(n: int, device) -> torch.Tensor:
+    """A workspace for `quantile_abs` / `posterior_dynthr` / `dynthr_bwd` over n elements (int32, 16-byte aligned)."""
+    return torch.empty(-(-quantile_ws_bytes(n) // 4), device=device, dtype=torch.int32)
+
+
+def quantile_abs(x, s, q, idx, ws):
+    """q[0] = torch.quantile(x.abs(), s) (linear), idx[0:2] = flat indices of the two order statistics (stable-sort order); x is read
+    as a flat fp32 tensor.  q: fp32 [1], idx: int32 [2], ws: `quantile_workspace(x.numel())`."""
+    assert x.is_contiguous() and q.numel() >= 1 and idx.numel() >= 2 and idx.dtype == torch.int32
+    call("osm_quantile_abs", ptr(x), x.numel(), float(s), ptr(q), ptr(idx), ptr(ws), _s(), keep=(x, q, idx, ws))
+
+
+def posterior_dynthr(model_out, x, coef, x0, mean, logvar, x0_raw, q, idx, ws, B, HW, mean_kind=0, var_kind=0, s=0.98):
+    """`posterior` with dynamic_threshold: x0 = clip(q x0_raw, -1, 1), q = quantile(|x0_raw|, s) over the whole [B,4,H,W] batch (left on
+    the device in q, its order statistics in idx), the mean formed from that x0."""
+    call("osm_posterior_dynthr", ptr(model_out), ptr(x), ptr(coef), int(mean_kind), int(var_kind), float(s), ptr(x0_raw), ptr(x0),
+         ptr(mean), ptr(logvar), ptr(q), ptr(idx), ptr(ws), B, HW, _s(), keep=(model_out, x, coef, x0_raw, x0, mean, logvar, q, idx, ws))
+
+
+def dynthr_bwd(g, x_raw, q, idx, ws, s=0.98):
+    """g (in place) = d loss/d x0_raw from d loss/d x0 through x0 = clip(x_raw * quantile(|x_raw|, s), -1, 1) (q / idx of the forward)."""
+    assert g.numel() == x_raw.numel() and g.is_contiguous() and x_raw.is_contiguous()
+    call("osm_dynthr_bwd", ptr(g), ptr(x_raw), ptr(q), ptr(idx), float(s), g.numel(), ptr(ws), _s(), keep=(g, x_raw, q, idx, ws))
+
+
 def phys_nblk(HW):
     return query("osm_phys_nblk", HW)
 

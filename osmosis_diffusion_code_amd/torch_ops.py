@@ -12,6 +12,9 @@ registered for the "cuda" device type only, which is HIP on ROCm).
                                                            posterior_mean_variance.py (every registered processor pair)
     osmosis::posterior_clip(...) -> (pred_xstart clamped, mean, log_variance, raw prediction), osmosis::clamp_bwd(g, raw) -> masked g
                                                            (`clip_denoised: True` of the shipped rgb-guidance config)
+    osmosis::posterior_dynthr(...) -> (pred_xstart thresholded, mean, log_variance, raw prediction, q, idx),
+    osmosis::dynthr_bwd(g, raw, q, idx, s) -> d loss/d raw  (`dynamic_threshold`: clip(x * quantile(|x|, s), -1, 1) over the batch,
+                                                           util/img_utils.py:8-15), osmosis::quantile_abs(x, s) -> (q, idx)
     osmosis::posterior_bwd(g, coef) -> d_model_out         d(pred_xstart)/d(model_out)^T g  (the chain rule into the UNet)
     osmosis::guide_update(mean, log_variance, g, dx_unet, noise, coef, scale4, clip) -> (x_next, grad)
                                                            condition_methods.py:186-221 update rule + the noise add of :262-271
@@ -147,6 +150,55 @@ def _clamp_bwd_fake(g, x_raw, lo=-1.0, hi=1.0):
     return torch.empty_like(g)
 
 
+@torch.library.custom_op("osmosis::quantile_abs", mutates_args=(), device_types="cuda")
+def quantile_abs(x: torch.Tensor, s: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(torch.quantile(x.abs(), s) as an fp32 [1] tensor, int32 [2] flat indices of its two order statistics in stable-sort order)."""
+    if x.dtype != torch.float32:
+        raise OsmosisHipError("osmosis::quantile_abs takes an fp32 tensor")
+    xc = x.contiguous()
+    q, idx = torch.empty(1, device=x.device, dtype=torch.float32), torch.empty(2, device=x.device, dtype=torch.int32)
+    ops.quantile_abs(xc, s, q, idx, ops.quantile_workspace(xc.numel(), x.device))
+    return q, idx
+
+
+@quantile_abs.register_fake
+def _quantile_abs_fake(x, s):
+    return x.new_empty((1,)), x.new_empty((2,), dtype=torch.int32)
+
+
+@torch.library.custom_op("osmosis::posterior_dynthr", mutates_args=(), device_types="cuda")
+def posterior_dynthr(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0, var_kind: int = 0,
+                     s: float = 0.98) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::posterior with `dynamic_threshold` (process_xstart, posterior_mean_variance.py:43-50): (pred_xstart = clip(raw *
+    quantile(|raw|, s), -1, 1) over the whole batch, mean formed from it, log_variance, the raw prediction, q [1], idx [2]) -- the last
+    three are what osmosis::dynthr_bwd takes."""
+    B, HW = _chw(x)
+    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
+    q, idx = torch.empty(1, device=x.device, dtype=torch.float32), torch.empty(2, device=x.device, dtype=torch.int32)
+    ops.posterior_dynthr(model_out.contiguous(), x, coef, x0, mean, logvar, raw, q, idx, ops.quantile_workspace(x.numel(), x.device),
+                         B, HW, mean_kind, var_kind, s)
+    return x0, mean, logvar, raw, q, idx
+
+
+@posterior_dynthr.register_fake
+def _posterior_dynthr_fake(model_out, x, coef, mean_kind=0, var_kind=0, s=0.98):
+    return (torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), x.new_empty((1,)),
+            x.new_empty((2,), dtype=torch.int32))
+
+
+@torch.library.custom_op("osmosis::dynthr_bwd", mutates_args=(), device_types="cuda")
+def dynthr_bwd(g: torch.Tensor, x_raw: torch.Tensor, q: torch.Tensor, idx: torch.Tensor, s: float = 0.98) -> torch.Tensor:
+    """d loss/d x_raw from g = d loss/d x0 through x0 = clip(x_raw * quantile(|x_raw|, s), -1, 1) (q, idx: its forward's; osm_dynthr_bwd)."""
+    out = g.detach().clone().contiguous()
+    ops.dynthr_bwd(out, x_raw.contiguous(), q, idx, ops.quantile_workspace(out.numel(), g.device), s)
+    return out
+
+
+@dynthr_bwd.register_fake
+def _dynthr_bwd_fake(g, x_raw, q, idx, s=0.98):
+    return torch.empty_like(g)
+
+
 @torch.library.custom_op("osmosis::posterior_bwd", mutates_args=(), device_types="cuda")
 def posterior_bwd(g: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     B, HW = _chw(g)
@@ -251,4 +303,4 @@ def _phys_loss_grad_fake(x0, y, phi, icfg, fcfg, n_inner, freeze_phi):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
 
 
-OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad")
+OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad")
