@@ -395,10 +395,23 @@ int osm_guide_update(const float* mean, const float* logvar, const float* g, con
 int osm_guide_update_rng(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
                          const float* scale4, float clip, float* x_next, float* grad_out, float* noise_out, int B, int HW,
                          unsigned long long seed, const int* step, int step_offset, int img0, int img_stride, void* stream);
+/* osm_guide_update_rng for sub-step `sub` of a step repeated at the same t (the PCGS inner loop, local_M > 1:
+ * gaussian_diffusion.py:225-309): counter word 2 = (*step + step_offset) | sub << 16, so the full counter is
+ *   (element / 4, img0 + b * img_stride, step | sub << 16, 0x6f736d31 "osm1").
+ * Every sub-step draws fresh noise; sub = 0 is osm_guide_update_rng bit for bit.  0 <= sub < 65536; the step word must stay below
+ * 65536 for sub != 0 (a chain of at most 65536 indices) so that distinct (step, sub) pairs give distinct counters. */
+int osm_guide_update_rng_sub(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
+                             const float* scale4, float clip, float* x_next, float* grad_out, float* noise_out, int B, int HW,
+                             unsigned long long seed, const int* step, int step_offset, int sub, int img0, int img_stride,
+                             void* stream);
 /* out[b][0..n) ~ N(0,1) from the same generator (image b: counter word 1 = img0 + b * img_stride; word 2 = *step_dev if given, else
  * step_const): what osm_guide_update_rng draws for (seed, image, step) when n = 4*H*W.  out 16-byte aligned; B > 1 needs n % 4 == 0. */
 int osm_randn(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int img0,
               int img_stride, void* stream);
+/* osm_randn for sub-step `sub`: counter word 2 = step | sub << 16 (the layout of osm_guide_update_rng_sub); sub = 0 is osm_randn
+ * bit for bit.  0 <= sub < 65536; with sub != 0 and no step_dev, 0 <= step_const < 65536. */
+int osm_randn_sub(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int sub, int img0,
+                  int img_stride, void* stream);
 /* out[4 q .. 4 q + 3] = Philox-4x32-10(counter = (q, c1, c2, c3), key = (k0, k1)) for q < n4: the raw generator, checked in the
  * tests against the Random123 known-answer vectors. */
 int osm_philox_raw(unsigned* out, long long n4, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, void* stream);

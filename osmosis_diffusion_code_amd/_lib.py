@@ -121,7 +121,9 @@ _SIGS = {
     "osm_posterior_bwd": [_P, _P, _P, _I, _I, _P],
     "osm_guide_update": [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P],
     "osm_guide_update_rng": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _P],
+    "osm_guide_update_rng_sub": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
     "osm_randn": [_P, _I, _LL, C.c_ulonglong, _P, _I, _I, _I, _P],
+    "osm_randn_sub": [_P, _I, _LL, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
     "osm_philox_raw": [_P, _LL, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _P],
     "osm_ddim_update": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P],
     "osm_fetch_coefs": [_P, _I, _P, _I, _P, _P, _I, _P],

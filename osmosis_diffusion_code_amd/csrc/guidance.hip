@@ -462,9 +462,10 @@ __global__ __launch_bounds__(256) void ancestral_step_kernel(const float* __rest
 
 
 // ---------------------------------------------------------------- step noise inside the library (gaussian_diffusion.py:266-268)
-// Philox-4x32-10 (Salmon et al., SC'11; the Random123 constants), counter = (element quad, image, step, stream id), key = the
-// 64-bit seed: one counter gives the four normals of four consecutive elements of one image (two Box-Muller pairs), so the
-// noise of an image depends on (seed, image index, step) only -- not on the batch it is processed in, its chunking or the grid.
+// Philox-4x32-10 (Salmon et al., SC'11; the Random123 constants), counter = (element quad, image, step | sub << 16, stream id),
+// key = the 64-bit seed: one counter gives the four normals of four consecutive elements of one image (two Box-Muller pairs), so
+// the noise of an image depends on (seed, image index, step, sub-step) only -- not on the batch it is processed in, its chunking
+// or the grid.  sub: the repeat of a step at the same t (PCGS local_M, gaussian_diffusion.py:225-309); sub = 0 leaves word 2 = step.
 struct Philox4 { unsigned v[4]; };
 __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
 #pragma unroll
@@ -487,6 +488,7 @@ __device__ __forceinline__ void normal4(const Philox4& r, float z[4]) {
   z[0] = r0 * c0; z[1] = r0 * s0; z[2] = r1 * c1; z[3] = r1 * s1;
 }
 constexpr unsigned OSM_RNG_STREAM_STEP_NOISE = 0x6f736d31u;   // "osm1": the per-step noise of a chain
+__device__ __forceinline__ unsigned step_word(unsigned step, unsigned sub) { return step | (sub << 16); }
 
 __global__ __launch_bounds__(256) void philox_raw_kernel(unsigned* __restrict__ out, long long n4, unsigned c1, unsigned c2,
                                                           unsigned c3, unsigned k0, unsigned k1) {
@@ -497,10 +499,11 @@ __global__ __launch_bounds__(256) void philox_raw_kernel(unsigned* __restrict__ 
   }
 }
 
-// out[b][0..n) ~ N(0, 1): image b uses counter word 1 = img0 + b, word 2 = the step (from the device counter when given)
+// out[b][0..n) ~ N(0, 1): image b uses counter word 1 = img0 + b, word 2 = the step (from the device counter when given) | sub << 16
 __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int B, long long n, unsigned k0, unsigned k1,
-                                                     const int* __restrict__ step_dev, int step_const, int img0, int img_stride) {
-  const unsigned step = (unsigned)(step_dev ? *step_dev : step_const);
+                                                     const int* __restrict__ step_dev, int step_const, unsigned sub, int img0,
+                                                     int img_stride) {
+  const unsigned step = step_word((unsigned)(step_dev ? *step_dev : step_const), sub);
   const long long nq = (n + 3) >> 2;
   const long long total = (long long)B * nq;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -519,12 +522,12 @@ __global__ __launch_bounds__(256) void guide_update_rng_kernel(const float* __re
                                                                 const float* __restrict__ coef, const float* __restrict__ scale4,
                                                                 float clip, float* __restrict__ x_next, float* __restrict__ grad_out,
                                                                 float* __restrict__ noise_out, int B, int HW, unsigned k0, unsigned k1,
-                                                                const int* __restrict__ step_dev, int step_offset, int img0,
-                                                                int img_stride) {
+                                                                const int* __restrict__ step_dev, int step_offset, unsigned sub,
+                                                                int img0, int img_stride) {
   const long long nq = (long long)HW;             // 4 HW elements per image = HW quads
   const long long total = (long long)B * nq;
   const float c0 = coef[0], noise_on = coef[6];
-  const unsigned step = (unsigned)(*step_dev + step_offset);
+  const unsigned step = step_word((unsigned)(*step_dev + step_offset), sub);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / nq, q = i - b * nq;
     const long long e0 = b * 4LL * HW + 4 * q;
@@ -769,30 +772,62 @@ extern "C" int osm_guide_update(const float* mean, const float* logvar, const fl
 }
 
 
+namespace {
+int guide_update_rng_launch(const char* name, const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                            const float* coef, const float* scale4, float clip, float* x_next, float* grad_out, float* noise_out,
+                            int B, int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
+                            int img_stride, void* stream) {
+  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && HW > 0, "%s: bad argument", name);
+  OSM_REQUIRE(!g || scale4, "%s: guidance needs the per-channel scale", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements)", name);
+  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
+                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
+                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "%s: tensors must be 16-byte aligned", name);
+  hipLaunchKernelGGL(guide_update_rng_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
+                     g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out, B, HW, (unsigned)(seed & 0xffffffffull),
+                     (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("guide_update_rng_kernel");
+}
+
+int randn_launch(const char* name, float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const,
+                 int sub, int img0, int img_stride, void* stream) {
+  OSM_REQUIRE(out && B > 0 && n > 0, "%s: bad argument", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(sub == 0 || step_dev || (step_const >= 0 && step_const < 65536),
+              "%s: with sub != 0 the step must be in [0, 65536), got %d", name, step_const);
+  OSM_REQUIRE((reinterpret_cast<size_t>(out) & 15) == 0, "%s: out must be 16-byte aligned", name);
+  OSM_REQUIRE(n % 4 == 0 || B == 1, "%s: a batch needs n %% 4 == 0 (every image's row starts 16-byte aligned)", name);
+  hipLaunchKernelGGL(randn_kernel, dim3(grid_for((long long)B * ((n + 3) / 4))), dim3(256), 0, (hipStream_t)stream, out, B, n,
+                     (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step_dev, step_const, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("randn_kernel");
+}
+}  // namespace
+
 extern "C" int osm_guide_update_rng(const float* mean, const float* logvar, const float* g, const float* dx_unet,
                                     const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
                                     float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
                                     int img0, int img_stride, void* stream) {
-  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && HW > 0, "osm_guide_update_rng: bad argument");
-  OSM_REQUIRE(!g || scale4, "osm_guide_update_rng: guidance needs the per-channel scale");
-  OSM_REQUIRE(HW % 4 == 0, "osm_guide_update_rng: H*W must be a multiple of 4 (one Philox counter per four elements)");
-  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
-                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
-                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "osm_guide_update_rng: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(guide_update_rng_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
-                     g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out, B, HW, (unsigned)(seed & 0xffffffffull),
-                     (unsigned)(seed >> 32), step, step_offset, img0, img_stride);
-  return osm::check_launch("guide_update_rng_kernel");
+  return guide_update_rng_launch("osm_guide_update_rng", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out,
+                                 B, HW, seed, step, step_offset, 0, img0, img_stride, stream);
+}
+
+extern "C" int osm_guide_update_rng_sub(const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                                        const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
+                                        float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
+                                        int sub, int img0, int img_stride, void* stream) {
+  return guide_update_rng_launch("osm_guide_update_rng_sub", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out,
+                                 noise_out, B, HW, seed, step, step_offset, sub, img0, img_stride, stream);
 }
 
 extern "C" int osm_randn(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int img0,
                          int img_stride, void* stream) {
-  OSM_REQUIRE(out && B > 0 && n > 0, "osm_randn: bad argument");
-  OSM_REQUIRE((reinterpret_cast<size_t>(out) & 15) == 0, "osm_randn: out must be 16-byte aligned");
-  OSM_REQUIRE(n % 4 == 0 || B == 1, "osm_randn: a batch needs n %% 4 == 0 (every image's row starts 16-byte aligned)");
-  hipLaunchKernelGGL(randn_kernel, dim3(grid_for((long long)B * ((n + 3) / 4))), dim3(256), 0, (hipStream_t)stream, out, B, n,
-                     (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step_dev, step_const, img0, img_stride);
-  return osm::check_launch("randn_kernel");
+  return randn_launch("osm_randn", out, B, n, seed, step_dev, step_const, 0, img0, img_stride, stream);
+}
+
+extern "C" int osm_randn_sub(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int sub,
+                             int img0, int img_stride, void* stream) {
+  return randn_launch("osm_randn_sub", out, B, n, seed, step_dev, step_const, sub, img0, img_stride, stream);
 }
 
 extern "C" int osm_philox_raw(unsigned* out, long long n4, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,

@@ -18,8 +18,10 @@ gaussian noiser) runs through the same loop: osm_phys_* with the identity operat
 ||y - x0[:, 0:3]|| and its gradient, osm_guide_update(_rng) or osm_ddim_update for the step.  The per-step
 noise is drawn inside the update kernel (Philox-4x32-10) unless `noise="aten"` asks for torch's stream.
 `dynamic_threshold` runs there too (osm_posterior_dynthr / osm_dynthr_bwd: an on-device exact quantile of the whole batch) when the
-batch is one engine pass.  Any other combination (third-party conditioners / operators / processors, a chunked batch with
-dynamic_threshold) falls back to a generic loop that follows the reference control flow on top of the HIP UNet operator through torch.autograd.
+batch is one engine pass.  The PCGS inner alternation (`local_M > 1`: the step repeated at the same t inside [s_end, s_start],
+:225-309) runs there as `alternate_len` sub-steps per index (`pcgs_schedule`).  Any other combination (third-party conditioners /
+operators / processors, a chunked batch with dynamic_threshold) falls back to a generic loop that follows the reference control flow on
+top of the HIP UNet operator through torch.autograd.
 """
 import math
 
@@ -100,6 +102,24 @@ def space_timesteps(num_timesteps, section_counts):
             pos += stride
         start += size
     return set(picked)
+
+
+def guidance_flag(sample_pattern, idx, T):
+    """Whether index idx of a T-step chain is guided (gaussian_diffusion.py:214-218)."""
+    if sample_pattern is None or sample_pattern["pattern"] == "original" or sample_pattern["pattern"] is None:
+        return True
+    return sample_pattern["start_guidance"] * T >= idx >= sample_pattern["stop_guidance"] * T
+
+
+def pcgs_schedule(sample_pattern, T):
+    """[(guided, freeze_phi, alternate_len)] for idx = T-1 .. 0 (entry T-1-idx): the per-index decisions of the reference's loop
+    (gaussian_diffusion.py:214-225, osmosis_utils/utils.py:574-630).  alternate_len > 1 is the PCGS inner loop (local_M sub-steps at
+    the same t inside [s_end, s_start]).  Raises the reference's AssertionError for an invalid pattern (update_start <= update_end,
+    s_start <= s_end, or with local_M > 1 a sub-step window outside the update window)."""
+    if sample_pattern is None:
+        return [(True, False, 1)] * T
+    return [(guidance_flag(sample_pattern, idx, T), bool(utilso.is_freeze_phi(sample_pattern, idx, T)),
+             int(utilso.set_alternate_length(sample_pattern, idx, T))) for idx in range(T - 1, -1, -1)]
 
 
 def extract_and_expand(array, time, target):
@@ -201,8 +221,9 @@ class GaussianDiffusion:
             B, C, H, W = shape
             if B * C * H * W > ops.QUANTILE_MAX_N or len(self.chunk_sizes(B, model.images_in_flight(B, H, W))) != 1:
                 return None
-        if sample_pattern is not None and sample_pattern.get("pattern") not in (None, "original"):
-            if sample_pattern.get("local_M", 1) != 1:
+        if sample_pattern is not None and sample_pattern.get("pattern") != "original" and sample_pattern.get("local_M", 1) != 1:
+            # the PCGS inner alternation runs as sub-steps of the fused loop; OSM_FUSED_PCGS=0 keeps such chains on `_generic_loop`
+            if os.environ.get("OSM_FUSED_PCGS", "1") == "0":
                 return None
         if pretrain_model != "osmosis" and not rgb_guidance:
             return None       # the reference's mean-only step (:234-236: p_mean_variance, sample = mean, no p_sample): `_generic_loop`
@@ -214,8 +235,6 @@ class GaussianDiffusion:
             if getattr(type(self), "p_sample", None) not in (DDPM.p_sample, DDIM.p_sample):
                 return None
             if sample_pattern is not None and not all(self._guidance_flag(sample_pattern, i) for i in (0, self.num_timesteps - 1)):
-                return None
-            if sample_pattern is not None and utilso.set_alternate_length(sample_pattern, 0, self.num_timesteps) != 1:
                 return None
             return cond
         if not isinstance(cond, PosteriorSamplingOsmosis):
@@ -268,17 +287,18 @@ class GaussianDiffusion:
             n += 1
 
     def _guidance_flag(self, sample_pattern, idx):
-        if sample_pattern is None or sample_pattern["pattern"] == "original" or sample_pattern["pattern"] is None:
-            return True
-        T = self.num_timesteps
-        return sample_pattern["start_guidance"] * T >= idx >= sample_pattern["stop_guidance"] * T
+        return guidance_flag(sample_pattern, idx, self.num_timesteps)
 
     def _fused_loop(self, model, cond, x_start, measurement, sample_pattern, kwargs, record=False, record_every=150):
         """One device-resident step per index, for the Osmosis configuration and for the rgb-guidance ('ps') one (`_fast_path_ok`).
         Per-step noise (gaussian_diffusion.py:266-268 / :497 / :522): by default drawn INSIDE osm_guide_update_rng from the
         library's Philox-4x32-10 stream (seed: `noise_seed=`, else one draw per chain from the device's torch generator, so
         `torch.manual_seed` still fixes the chain); `noise="aten"` (or OSM_STEP_NOISE=aten) draws it with torch on the device in the reference's
-        call order instead (the reference's own realisation for the same seed); `noise_fn=` injects it (parity runs)."""
+        call order instead (the reference's own realisation for the same seed); `noise_fn=` injects it (parity runs).
+        PCGS (`pcgs_schedule`): index idx runs alternate_len sub-steps at the same t, each a full step (network, posterior, conditioning
+        with its own n_iter phi steps, noise) on the previous sub-step's x_t.  Only the last sub-step's fetch moves the step counter;
+        noise_fn's k, the library stream's `sub` counter word and the trace count sub-steps; `record` snapshots (and the returned loss,
+        phi, x0) are those after the index's last sub-step (:274, :309)."""
         import os
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
@@ -295,6 +315,9 @@ class GaussianDiffusion:
         first, last = kwargs.get("index_range", (T - 1, 0))
         if not (0 <= last <= first <= T - 1):
             raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({first}, {last})")
+        sched = pcgs_schedule(sample_pattern, T)          # (before anything launches: an invalid pattern raises here)
+        if T > 1 << 16 and max(a for _, _, a in sched) > 1:
+            raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
         # Images are independent chains: a batch whose kept activations would not fit the device
         # (~8 GB per 256 x 256 image in fp32) is walked in chunks per step; per-image state (x_t, phi, losses) stays in
         # [B]-sized tensors, the chunks are contiguous row blocks.
@@ -355,85 +378,94 @@ class GaussianDiffusion:
         noise1 = torch.zeros(1, 4, H, W, **f32) if (shared and source == "aten") else None
         noise_used = torch.empty(B, 4, H, W, **f32) if (lib_rng and trace is not None) else None
         have_loss = False
-        for k, idx in enumerate(range(first, last - 1, -1)):
-            guided = True if ps else self._guidance_flag(sample_pattern, idx)
-            freeze = False if ps else utilso.is_freeze_phi(sample_pattern, idx, T)
-            if source == "fn":
-                noise.copy_(noise_fn(k, noise.shape))
-            elif source == "aten":
-                if ps:                                    # DDPM / DDIM.p_sample draw first (:497, :522), then q_sample (:241)
-                    noise1.normal_() if noise1 is not None else noise.normal_()
-                if draw_measurement_noise:
-                    torch.randn_like(y[:1] if noise1 is not None else y)
-                if not ps:
-                    noise1.normal_() if noise1 is not None else noise.normal_()
-                if noise1 is not None:
-                    noise.copy_(noise1.expand_as(noise))
-            elif not lib_rng:                             # library stream, DDIM: as a tensor (used only for eta > 0)
-                ops.randn(noise, B, 4 * HW, seed, step=step, img0=img_base, img_stride=img_stride)   # (before the fetch: counter = idx)
-            # every engine's timestep vector is filled from the SAME step counter; the counter moves once, in the last fetch,
-            # which always goes through the first engine (stream order: the delta-0 fetches read it before it moves)
-            for e2 in engs.values():
-                if e2 is not eng:
-                    ops.fetch_coefs(table, step, 0, coef, e2.t_dev, e2.B)
-            if ddim:
-                ops.fetch_coefs(dtable, step, 0, dcoef, eng.t_dev, eng.B)
-            ops.fetch_coefs(table, step, -1, coef, eng.t_dev, eng.B)
-            if trace is not None:
-                rec = {"x_in": x_state.clone()}
-                grad_all = torch.empty_like(g) if guided else None
-                model_out = torch.empty(B, eng.out.shape[1], H, W, **f32)
-            for c0, c1 in chunks:
-                ce, Bc = engs[c1 - c0], c1 - c0            # this chunk's engine (`eng` stays the first one)
-                if not single:
-                    ce.x_in.copy_(x_state[c0:c1])
-                ce.run_forward()
-                if dyn:
-                    ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
-                                         self.mean_processor.kernel_kind, self.var_processor.kernel_kind, DYNAMIC_THRESHOLD_S)
-                else:
-                    ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW,
-                                  self.mean_processor.kernel_kind, self.var_processor.kernel_kind,
-                                  None if x0_raw is None else x0_raw[c0:c1])
-                if trace is not None:
-                    model_out[c0:c1].copy_(ce.out)
-                gg = dxu = grad_out = None
-                if guided:
-                    if ps:
-                        cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1])
-                    else:
-                        cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
-                                          loss_out=loss_all[c0:c1])
-                    have_loss = True
-                    if dyn:                               # (a clip_denoised clamp after it masks nothing more)
-                        ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
-                    elif x0_raw is not None:
-                        ops.clamp_bwd(g[c0:c1], x0_raw[c0:c1])
-                    ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
-                    ce.run_backward()
-                    gg, dxu = g[c0:c1], ce.dx
-                    grad_out = grad_all[c0:c1] if trace is not None else None
-                nz = None if noise is None else noise[c0:c1]
-                sc, cl = (scale4, clip) if guided else (None, -1.0)
+        k = 0                                             # sub-step count (noise_fn's k)
+        for idx in range(first, last - 1, -1):
+            guided, freeze, alt = sched[T - 1 - idx]
+            if ps:
+                guided, freeze = True, False
+            for sub in range(alt):
+                final = sub == alt - 1
+                if source == "fn":
+                    noise.copy_(noise_fn(k, noise.shape))
+                elif source == "aten":
+                    if ps:                                # DDPM / DDIM.p_sample draw first (:497, :522), then q_sample (:241)
+                        noise1.normal_() if noise1 is not None else noise.normal_()
+                    if draw_measurement_noise:
+                        torch.randn_like(y[:1] if noise1 is not None else y)
+                    if not ps:
+                        noise1.normal_() if noise1 is not None else noise.normal_()
+                    if noise1 is not None:
+                        noise.copy_(noise1.expand_as(noise))
+                elif not lib_rng:                         # library stream, DDIM: as a tensor (used only for eta > 0)
+                    ops.randn_sub(noise, B, 4 * HW, seed, step=step, sub=sub, img0=img_base,
+                                  img_stride=img_stride)  # (before the fetch: counter = idx)
+                # every engine's timestep vector is filled from the SAME step counter; the counter moves once per index, in the last
+                # fetch of its last sub-step, which always goes through the first engine (stream order: the delta-0 fetches read it
+                # before it moves)
+                for e2 in engs.values():
+                    if e2 is not eng:
+                        ops.fetch_coefs(table, step, 0, coef, e2.t_dev, e2.B)
                 if ddim:
-                    ops.ddim_update(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
-                elif lib_rng:
-                    ops.guide_update_rng(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
-                                         None if noise_used is None else noise_used[c0:c1], Bc, HW, seed, step, step_offset=1,
-                                         img0=img_base + (0 if shared else c0), img_stride=img_stride)   # (+1: the fetch moved the counter)
-                else:
-                    ops.guide_update(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
-            if trace is not None:
-                rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out,
-                           loss=loss_all.clone() if have_loss else None, phi=None if phi is None else phi.clone())
-                if noise_used is not None:
-                    rec["noise"] = noise_used.clone()
-                if dyn:
-                    rec["q"] = q_dev.clone()
-                if guided:
-                    rec["grad"] = grad_all
-                trace.append(rec)
-            # snapshots of pred_xstart during the chain (reference :308-327): same steps, one D2H copy each
+                    ops.fetch_coefs(dtable, step, 0, dcoef, eng.t_dev, eng.B)
+                ops.fetch_coefs(table, step, -1 if final else 0, coef, eng.t_dev, eng.B)
+                if trace is not None:
+                    rec = {"idx": idx, "sub": sub, "x_in": x_state.clone()}
+                    grad_all = torch.empty_like(g) if guided else None
+                    model_out = torch.empty(B, eng.out.shape[1], H, W, **f32)
+                for c0, c1 in chunks:
+                    ce, Bc = engs[c1 - c0], c1 - c0        # this chunk's engine (`eng` stays the first one)
+                    if not single:
+                        ce.x_in.copy_(x_state[c0:c1])
+                    ce.run_forward()
+                    if dyn:
+                        ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
+                                             self.mean_processor.kernel_kind, self.var_processor.kernel_kind, DYNAMIC_THRESHOLD_S)
+                    else:
+                        ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW,
+                                      self.mean_processor.kernel_kind, self.var_processor.kernel_kind,
+                                      None if x0_raw is None else x0_raw[c0:c1])
+                    if trace is not None:
+                        model_out[c0:c1].copy_(ce.out)
+                    gg = dxu = grad_out = None
+                    if guided:
+                        if ps:
+                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1])
+                        else:
+                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
+                                              loss_out=loss_all[c0:c1])
+                        have_loss = True
+                        if dyn:                           # (a clip_denoised clamp after it masks nothing more)
+                            ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
+                        elif x0_raw is not None:
+                            ops.clamp_bwd(g[c0:c1], x0_raw[c0:c1])
+                        ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
+                        ce.run_backward()
+                        gg, dxu = g[c0:c1], ce.dx
+                        grad_out = grad_all[c0:c1] if trace is not None else None
+                    nz = None if noise is None else noise[c0:c1]
+                    sc, cl = (scale4, clip) if guided else (None, -1.0)
+                    if ddim:
+                        ops.ddim_update(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
+                    elif lib_rng:                         # (+1 after the last sub-step's fetch: it moved the counter)
+                        ops.guide_update_rng_sub(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
+                                                 None if noise_used is None else noise_used[c0:c1], Bc, HW, seed, step,
+                                                 step_offset=1 if final else 0, sub=sub,
+                                                 img0=img_base + (0 if shared else c0), img_stride=img_stride)
+                    else:
+                        ops.guide_update(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
+                if trace is not None:
+                    rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out,
+                               loss=loss_all.clone() if have_loss else None, phi=None if phi is None else phi.clone(),
+                               step=step.clone())         # (the device step counter after this sub-step)
+                    if noise_used is not None:
+                        rec["noise"] = noise_used.clone()
+                    if dyn:
+                        rec["q"] = q_dev.clone()
+                    if guided:
+                        rec["grad"] = grad_all
+                    trace.append(rec)
+                k += 1
+            # snapshots of pred_xstart during the chain (reference :308-327): same steps, one D2H copy each, after the last sub-step
             if records is not None and ((idx % record_every == 0) or idx == 0 or idx == 999):
                 records.append((idx, x0.detach().cpu()))
         img = x_state.clone()

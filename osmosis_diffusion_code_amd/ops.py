@@ -465,10 +465,25 @@ def guide_update_rng(mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_
          keep=(mean, logvar, g, dx_unet, coef, scale4, x_next, grad_out, noise_out, step))
 
 
+def guide_update_rng_sub(mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out, B, HW, seed, step, step_offset=0,
+                         sub=0, img0=0, img_stride=1):
+    """guide_update_rng for sub-step `sub` of a step repeated at the same t (PCGS local_M): counter word 2 =
+    (*step + step_offset) | sub << 16; sub = 0 draws what guide_update_rng draws."""
+    call("osm_guide_update_rng_sub", ptr(mean), ptr(logvar), ptr(g), ptr(dx_unet), ptr(coef), ptr(scale4), float(clip), ptr(x_next),
+         ptr(grad_out), ptr(noise_out), B, HW, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), int(step_offset), int(sub), int(img0),
+         int(img_stride), _s(), keep=(mean, logvar, g, dx_unet, coef, scale4, x_next, grad_out, noise_out, step))
+
+
 def randn(out, B, n, seed, step=None, step_const=0, img0=0, img_stride=1):
     """out[B][n] ~ N(0, 1) from the library's generator (what osm_guide_update_rng draws for (seed, image, step) when n = 4 H W)."""
     call("osm_randn", ptr(out), int(B), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), int(step_const), int(img0), int(img_stride), _s(),
          keep=(out, step))
+
+
+def randn_sub(out, B, n, seed, step=None, step_const=0, sub=0, img0=0, img_stride=1):
+    """randn for sub-step `sub` (counter word 2 = step | sub << 16): what guide_update_rng_sub draws for (seed, image, step, sub)."""
+    call("osm_randn_sub", ptr(out), int(B), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), int(step_const), int(sub), int(img0),
+         int(img_stride), _s(), keep=(out, step))
 
 
 def philox_raw(out, n4, c1, c2, c3, k0, k1):

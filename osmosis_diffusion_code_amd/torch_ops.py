@@ -229,18 +229,19 @@ def _guide_update_fake(mean, log_variance, g, dx_unet, noise, coef, scale4, clip
 @torch.library.custom_op("osmosis::guide_update_rng", mutates_args=(), device_types="cuda")
 def guide_update_rng(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, coef: torch.Tensor,
                      scale4: torch.Tensor, clip: float, seed: int, step: torch.Tensor, step_offset: int, img0: int,
-                     img_stride: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                     img_stride: int, sub: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """osmosis::guide_update with the step noise drawn in the kernel (Philox-4x32-10: key = seed, counter = (element / 4,
-    img0 + b * img_stride, step[0] + step_offset)); a pure function of its inputs.  Returns (x_next, grad, the noise drawn)."""
+    img0 + b * img_stride, (step[0] + step_offset) | sub << 16)); a pure function of its inputs.  sub: the sub-step of a step
+    repeated at the same t (PCGS local_M; 0 = the plain step).  Returns (x_next, grad, the noise drawn)."""
     B, HW = _chw(mean)
     x_next, grad, noise = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    ops.guide_update_rng(mean, log_variance, g, dx_unet, coef, scale4, clip, x_next, grad, noise, B, HW, seed, step,
-                         step_offset=step_offset, img0=img0, img_stride=img_stride)
+    ops.guide_update_rng_sub(mean, log_variance, g, dx_unet, coef, scale4, clip, x_next, grad, noise, B, HW, seed, step,
+                             step_offset=step_offset, sub=sub, img0=img0, img_stride=img_stride)
     return x_next, grad, noise
 
 
 @guide_update_rng.register_fake
-def _guide_update_rng_fake(mean, log_variance, g, dx_unet, coef, scale4, clip, seed, step, step_offset, img0, img_stride):
+def _guide_update_rng_fake(mean, log_variance, g, dx_unet, coef, scale4, clip, seed, step, step_offset, img0, img_stride, sub=0):
     return torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
 
 
