@@ -430,6 +430,45 @@ int osm_ddim_update(const float* x0, const float* x, const float* g, const float
  * coef: device float[8] = {c_a, c_b, c_s, c_r, c_m, -, -, t}.  x_next may alias x (in-place update). */
 int osm_ancestral_step(const float* model_out, const float* x, const float* z, const float* coef,
                        float* x_next, float* x0, int B, int C, int Cout, int HW, void* stream);
+/* ------------------------------------------------------------------ channel-generic step: state [B,C,HW], network output [B,Cout,HW]
+ * The RGB model family (create_model with pretrain_model != "osmosis": 3 -> 6, or 3 -> 3 without learn_sigma) and C -> C models with
+ * a fixed variance.  Cout must be C or 2 C.  Element by element the arithmetic (and its operation order) is that of the [B,4,HW] /
+ * [B,8,HW] entry points above: at (C, Cout) = (4, 8) the outputs are bit-identical to theirs.
+ *
+ * osm_posterior_c = osm_posterior_typed:  out = model_out[:, :C] ;
+ *   x0 = c0*x - c1*out (mean_kind 0) | out (1) ; clip_denoised: x0_raw = x0, x0 = clamp(x0, -1, 1) ; mean = c2*x0 + c3*x | out (2)
+ *   v = model_out[:, C:2C] when Cout == 2 C, else v = model_out (gaussian_diffusion.py:349-355, model_var_values = model_output)
+ *   logvar = f*coef[5] + (1-f)*coef[4], f = (v+1)/2 (var_kind 0) | coef[4] (1) | v (2) */
+int osm_posterior_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, int clip_denoised,
+                    float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout, int HW, void* stream);
+/* osm_posterior_dynthr for [B,C,HW]: q = quantile(|x0_raw|, s) over ALL B*C*HW elements (<= 2^24), x0 = clip(q*x0_raw, -1, 1), the mean
+ * from that x0; ws: osm_quantile_abs_ws_bytes(B*C*HW) bytes.  osm_dynthr_bwd serves its backward (it takes the element count). */
+int osm_posterior_dynthr_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                           float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int C, int Cout,
+                           int HW, void* stream);
+/* d_out[B,Cout,HW]: channels 0..C-1 = -c1*g[B,C,HW], C..Cout-1 = 0: exactly B*Cout*HW floats are written */
+int osm_posterior_bwd_c(const float* g, const float* coef, float* d_out, int B, int C, int Cout, int HW, void* stream);
+/* osm_guide_update on [B,C,HW] with scale[C]:
+ *   grad = c0*g + dx_unet ; x_t = mean - scale[c]*clamp(grad,+-clip) ; x_next = x_t + exp(.5*logvar)*noise*noise_on */
+int osm_guide_update_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* noise,
+                       const float* coef, const float* scale, float clip, float* x_next, float* grad_out, int B, int C, int HW,
+                       void* stream);
+/* osm_guide_update_rng_sub on [B,C,HW]: the same Philox stream, counter = (element / 4 within the image's C*HW elements,
+ * img0 + b * img_stride, (*step + step_offset) | sub << 16, "osm1"); H*W % 4 == 0, so a quad never straddles two channels.
+ * osm_randn_sub with n = C*H*W draws the same normals; sub = 0 is the layout of osm_guide_update_rng. */
+int osm_guide_update_rng_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
+                           const float* scale, float clip, float* x_next, float* grad_out, float* noise_out, int B, int C, int HW,
+                           unsigned long long seed, const int* step, int step_offset, int sub, int img0, int img_stride,
+                           void* stream);
+/* osm_ddim_update on [B,C,HW] with scale[C]:
+ *   eps = (r0*x - x0)/r1 ; x_next = x0*sqrt(abp) + sqrt(1-abp-sigma^2)*eps + noise_on*sigma*noise - scale[c]*clamp(c0*g + dx_unet,+-clip) */
+int osm_ddim_update_c(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise, const float* coef,
+                      const float* dcoef, const float* scale, float clip, float* x_next, float* grad_out, int B, int C, int HW,
+                      void* stream);
+/* The 'ps' data term with the identity operator and the gaussian noiser (condition_methods.py:35-41) on x0[B,C,HW], y[B,3,HW], C >= 3:
+ *   loss[b] = || y[b] - x0[b, 0:3] ||_2 ;  g[b, 0:3] = -(y[b] - x0[b, 0:3]) / loss[b] ;  g[b, 3:] = 0
+ * per image, in a fixed reduction order (deterministic).  part: float[B * osm_phys_nblk(HW)] workspace. */
+int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss, float* g, int B, int C, int HW, void* stream);
 /* coef_out[8] = table[clamp(*step, 0, n_rows-1)][8]; t_out[b] = coef_out[7]; then *step += delta
  * (graph-replayable; B <= 256) */
 int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out, int B,

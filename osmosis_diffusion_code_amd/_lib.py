@@ -128,6 +128,13 @@ _SIGS = {
     "osm_ddim_update": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P],
     "osm_fetch_coefs": [_P, _I, _P, _I, _P, _P, _I, _P],
     "osm_ancestral_step": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "osm_posterior_c": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "osm_posterior_dynthr_c": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "osm_posterior_bwd_c": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "osm_guide_update_c": [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P],
+    "osm_guide_update_rng_c": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
+    "osm_ddim_update_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P],
+    "osm_ps_loss_grad_c": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "osm_version": [],
 }
 # fp16-storage family (activations as IEEE half, `_h` suffix): same argument lists

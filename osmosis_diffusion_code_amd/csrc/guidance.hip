@@ -862,3 +862,328 @@ extern "C" int osm_ancestral_step(const float* model_out, const float* x, const 
                      model_out, x, z, coef, x_next, x0, B, C, Cout, HW);
   return osm::check_launch("ancestral_step_kernel");
 }
+
+
+// ================================================================ channel-generic step ([B,C,HW] state, [B,Cout,HW] network output)
+// The RGB model family (create_model with pretrain_model != "osmosis": 3 -> 6, or 3 -> 3 without learn_sigma) and any C -> C model
+// with a fixed variance.  Same arithmetic, element by element and in the same operation order, as the [B,4,HW] / [B,8,HW] kernels
+// above (which keep their compile-time shapes); C and Cout are launch arguments.  Cout == C: the network has no variance half and
+// the variance processor reads model_out itself (reference gaussian_diffusion.py:349-355, model_var_values = model_output).
+namespace {
+
+// RAW: posterior_raw_kernel's pass for dynamic_threshold (x0_raw, logvar, the previous_x mean); else posterior_kernel's.
+template <int MK, int VK, bool RAW>
+__global__ __launch_bounds__(256) void posterior_c_kernel(const float* __restrict__ mo, const float* __restrict__ x,
+                                                           const float* __restrict__ coef, float* __restrict__ x0_raw,
+                                                           float* __restrict__ x0, float* __restrict__ mean,
+                                                           float* __restrict__ logvar, int B, int C, int Cout, int HW) {
+  const long long n = (long long)C * HW, no = (long long)Cout * HW;
+  const long long total = (long long)B * n;
+  const long long voff = Cout == C ? 0 : n;
+  const float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], mn = coef[4], mxl = coef[5];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / n;
+    const long long rem = i - b * n;
+    const float eps = mo[b * no + rem];
+    const float xv = x[i];
+    float xs = MK == 1 ? eps : c0 * xv - c1 * eps;
+    if (RAW) {
+      x0_raw[i] = xs;
+      if (MK == 2) mean[i] = eps;
+    } else {
+      if (x0_raw) {
+        x0_raw[i] = xs;
+        xs = (xs != xs) ? xs : fminf(fmaxf(xs, -1.0f), 1.0f);          // torch.clamp keeps NaN
+      }
+      x0[i] = xs;
+      mean[i] = MK == 2 ? eps : c2 * xs + c3 * xv;
+    }
+    if (VK == 1) {
+      logvar[i] = mn;
+    } else {
+      const float v = mo[b * no + voff + rem];
+      if (VK == 2) {
+        logvar[i] = v;
+      } else {
+        const float frac = (v + 1.0f) / 2.0f;
+        logvar[i] = frac * mxl + (1.0f - frac) * mn;
+      }
+    }
+  }
+}
+
+// d_out[:, :C] = -c1 g, d_out[:, C:] = 0: exactly B * Cout * HW floats
+__global__ __launch_bounds__(256) void posterior_bwd_c_kernel(const float* __restrict__ g, const float* __restrict__ coef,
+                                                               float* __restrict__ d_out, int B, int C, int Cout, int HW) {
+  const long long n = (long long)C * HW, no = (long long)Cout * HW;
+  const long long total = (long long)B * no;
+  const float c1 = coef[1];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / no;
+    const long long rem = i - b * no;
+    d_out[i] = rem < n ? -c1 * g[b * n + rem] : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void guide_update_c_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
+                                                              const float* __restrict__ g, const float* __restrict__ dxu,
+                                                              const float* __restrict__ noise, const float* __restrict__ coef,
+                                                              const float* __restrict__ scale, float clip,
+                                                              float* __restrict__ x_next, float* __restrict__ grad_out, int B, int C,
+                                                              int HW) {
+  const long long total = (long long)B * C * HW;
+  const float c0 = coef[0], noise_on = coef[6];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)((i / HW) % C);
+    float grad = 0.f;
+    if (g) grad = c0 * g[i] + (dxu ? dxu[i] : 0.f);
+    if (grad_out) grad_out[i] = grad;
+    float gc = grad;
+    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);   // torch.clamp keeps NaN
+    float xt = mean[i] - (g ? scale[c] * gc : 0.f);
+    if (noise_on != 0.f && noise) xt += expf(0.5f * logvar[i]) * noise[i];
+    x_next[i] = xt;
+  }
+}
+
+// guide_update_c with the noise drawn in the kernel: counter word 0 = element / 4 within the image's C HW elements (HW % 4 == 0: a
+// quad never straddles two channels), the other words as guide_update_rng_kernel's -- osm_randn(_sub) with n = C HW draws the same
+__global__ __launch_bounds__(256) void guide_update_rng_c_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
+                                                                  const float* __restrict__ g, const float* __restrict__ dxu,
+                                                                  const float* __restrict__ coef, const float* __restrict__ scale,
+                                                                  float clip, float* __restrict__ x_next, float* __restrict__ grad_out,
+                                                                  float* __restrict__ noise_out, int B, int C, int HW, unsigned k0,
+                                                                  unsigned k1, const int* __restrict__ step_dev, int step_offset,
+                                                                  unsigned sub, int img0, int img_stride) {
+  const long long nq = (long long)C * (HW >> 2);
+  const long long total = (long long)B * nq;
+  const float c0 = coef[0], noise_on = coef[6];
+  const unsigned step = step_word((unsigned)(*step_dev + step_offset), sub);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / nq, q = i - b * nq;
+    const long long e0 = b * (long long)C * HW + 4 * q;
+    const int c = (int)((4 * q) / HW);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noise_on != 0.f) normal4(philox4x32_10((unsigned)q, (unsigned)(img0 + (int)b * img_stride), step, OSM_RNG_STREAM_STEP_NOISE, k0, k1), z);
+    const float4 m = *reinterpret_cast<const float4*>(mean + e0);
+    const float4 lv = *reinterpret_cast<const float4*>(logvar + e0);
+    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), du = gv;
+    if (g) gv = *reinterpret_cast<const float4*>(g + e0);
+    if (g && dxu) du = *reinterpret_cast<const float4*>(dxu + e0);
+    const float mm[4] = {m.x, m.y, m.z, m.w}, ll[4] = {lv.x, lv.y, lv.z, lv.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w},
+                dd[4] = {du.x, du.y, du.z, du.w};
+    float xo[4], go[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float grad = g ? c0 * gg[e] + dd[e] : 0.f;
+      go[e] = grad;
+      float gc = grad;
+      if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);
+      float xt = mm[e] - (g ? scale[c] * gc : 0.f);
+      if (noise_on != 0.f) xt += expf(0.5f * ll[e]) * z[e];
+      xo[e] = xt;
+    }
+    *reinterpret_cast<float4*>(x_next + e0) = make_float4(xo[0], xo[1], xo[2], xo[3]);
+    if (grad_out) *reinterpret_cast<float4*>(grad_out + e0) = make_float4(go[0], go[1], go[2], go[3]);
+    if (noise_out) *reinterpret_cast<float4*>(noise_out + e0) = make_float4(z[0], z[1], z[2], z[3]);
+  }
+}
+
+// x_next may alias x (each element is read, then written, by one thread)
+__global__ __launch_bounds__(256) void ddim_update_c_kernel(const float* __restrict__ x0, const float* x, const float* __restrict__ g,
+                                                             const float* __restrict__ dxu, const float* __restrict__ noise,
+                                                             const float* __restrict__ coef, const float* __restrict__ dcoef,
+                                                             const float* __restrict__ scale, float clip, float* x_next,
+                                                             float* __restrict__ grad_out, int B, int C, int HW) {
+  const long long total = (long long)B * C * HW;
+  const float c0 = coef[0];
+  const float ab = dcoef[0], abp = dcoef[1], eta = dcoef[2], noise_on = dcoef[3], r0 = dcoef[4], r1 = dcoef[5];
+  const float sigma = eta * sqrtf((1.0f - abp) / (1.0f - ab)) * sqrtf(1.0f - ab / abp);
+  const float sa = sqrtf(abp), sb = sqrtf(1.0f - abp - sigma * sigma);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)((i / HW) % C);
+    const float xs = x0[i];
+    const float eps = (r0 * x[i] - xs) / r1;
+    float xt = xs * sa + sb * eps;
+    if (noise_on != 0.f && noise) xt += sigma * noise[i];
+    float grad = 0.f;
+    if (g) grad = c0 * g[i] + (dxu ? dxu[i] : 0.f);
+    if (grad_out) grad_out[i] = grad;
+    float gc = grad;
+    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);
+    x_next[i] = xt - (g ? scale[c] * gc : 0.f);
+  }
+}
+
+// 'ps' data term on a C-channel x0 (condition_methods.py:35-41): per image, the partial sums of (y - x0[0:3])^2 in the order of
+// phys_reduce_kernel (PPB pixels per workgroup, wave sums, the four waves pairwise): deterministic
+__global__ __launch_bounds__(256) void ps_reduce_c_kernel(const float* __restrict__ x0, const float* __restrict__ y,
+                                                           float* __restrict__ part, int C, int HW, int nblk) {
+  __shared__ float red[4];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  const int pend = min(HW, (blk + 1) * PPB);
+  const float* xb = x0 + (long long)b * C * HW;
+  const float* yb = y + (long long)b * 3 * HW;
+  float s = 0.f;
+  for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float r = yb[(long long)c * HW + p] - xb[(long long)c * HW + p];
+      s += r * r;
+    }
+  }
+  const float t = osm::wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(long long)b * nblk + blk] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// loss[b] = sqrt(sum of the image's partials) (fp64, fixed order), g = -(y - x0) / loss on channels 0..2, 0 on any further channel
+__global__ __launch_bounds__(256) void ps_grad_c_kernel(const float* __restrict__ x0, const float* __restrict__ y,
+                                                         const float* __restrict__ part, float* __restrict__ loss,
+                                                         float* __restrict__ g, int C, int HW, int nblk) {
+  __shared__ float tot;
+  const int b = blockIdx.y;
+  if (threadIdx.x < 64) {         // the first wave: lane l owns partials l, l + 64, ...; five shuffle folds
+    double a = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 64) a += (double)part[(long long)b * nblk + k];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+    if (threadIdx.x == 0) {
+      tot = (float)a;
+      if (blockIdx.x == 0) loss[b] = (float)sqrt(a);
+    }
+  }
+  __syncthreads();
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const float gscale = 1.0f / sqrtf(tot);
+  const long long base = (long long)b * C * HW + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float r = y[(long long)b * 3 * HW + (long long)c * HW + p] - x0[base + (long long)c * HW];
+    g[base + (long long)c * HW] = -(r * gscale);
+  }
+  for (int c = 3; c < C; ++c) g[base + (long long)c * HW] = 0.f;
+}
+
+int posterior_c_launch(const char* name, bool raw, const float* model_out, const float* x, const float* coef, int mean_kind,
+                       int var_kind, float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout, int HW,
+                       hipStream_t st) {
+  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "%s: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)", name);
+  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "%s: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)", name);
+  OSM_REQUIRE(C > 0 && (Cout == C || Cout == 2 * C), "%s: Cout must be C or 2 C, got C = %d, Cout = %d", name, C, Cout);
+  const dim3 grid(grid_for((long long)B * C * HW)), block(256);
+#define OSM_POST1(MK, VK, RAW) \
+  hipLaunchKernelGGL((posterior_c_kernel<MK, VK, RAW>), grid, block, 0, st, model_out, x, coef, x0_raw, x0, mean, logvar, B, C, Cout, HW)
+#define OSM_POST(MK, VK) do { if (raw) OSM_POST1(MK, VK, true); else OSM_POST1(MK, VK, false); } while (0)
+  switch (mean_kind * 3 + var_kind) {
+    case 0: OSM_POST(0, 0); break;
+    case 1: OSM_POST(0, 1); break;
+    case 2: OSM_POST(0, 2); break;
+    case 3: OSM_POST(1, 0); break;
+    case 4: OSM_POST(1, 1); break;
+    case 5: OSM_POST(1, 2); break;
+    case 6: OSM_POST(2, 0); break;
+    case 7: OSM_POST(2, 1); break;
+    default: OSM_POST(2, 2); break;
+  }
+#undef OSM_POST
+#undef OSM_POST1
+  return osm::check_launch("posterior_c_kernel");
+}
+
+}  // namespace
+
+extern "C" int osm_posterior_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
+                               int clip_denoised, float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout,
+                               int HW, void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0 && mean && logvar && B > 0 && HW > 0, "osm_posterior_c: bad argument");
+  OSM_REQUIRE(!clip_denoised || x0_raw, "osm_posterior_c: clip_denoised needs x0_raw (the unclamped prediction, read by osm_clamp_bwd)");
+  if (!clip_denoised) x0_raw = nullptr;
+  return posterior_c_launch("osm_posterior_c", false, model_out, x, coef, mean_kind, var_kind, x0_raw, x0, mean, logvar, B, C, Cout,
+                            HW, (hipStream_t)stream);
+}
+
+extern "C" int osm_posterior_dynthr_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                                      float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int C,
+                                      int Cout, int HW, void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && C > 0 && HW > 0,
+              "osm_posterior_dynthr_c: bad argument");
+  const long long total = (long long)B * C * HW;
+  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr_c: quantile() input tensor is too large (%lld elements > 2^24)", total);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = posterior_c_launch("osm_posterior_dynthr_c", true, model_out, x, coef, mean_kind, var_kind, x0_raw, x0, mean, logvar, B, C,
+                              Cout, HW, st);
+  if (rc) return rc;
+  if ((rc = osm_quantile_abs(x0_raw, total, s, q, idx, ws, stream))) return rc;
+  const dim3 grid(grid_for(total)), block(256);
+  if (mean_kind == 2) {
+    hipLaunchKernelGGL(dynthr_apply_kernel<2>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  } else {
+    hipLaunchKernelGGL(dynthr_apply_kernel<0>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  }
+  return osm::check_launch("dynthr_apply_kernel");
+}
+
+extern "C" int osm_posterior_bwd_c(const float* g, const float* coef, float* d_out, int B, int C, int Cout, int HW, void* stream) {
+  OSM_REQUIRE(g && coef && d_out && B > 0 && HW > 0, "osm_posterior_bwd_c: bad argument");
+  OSM_REQUIRE(C > 0 && (Cout == C || Cout == 2 * C), "osm_posterior_bwd_c: Cout must be C or 2 C, got C = %d, Cout = %d", C, Cout);
+  hipLaunchKernelGGL(posterior_bwd_c_kernel, dim3(grid_for((long long)B * Cout * HW)), dim3(256), 0, (hipStream_t)stream, g, coef,
+                     d_out, B, C, Cout, HW);
+  return osm::check_launch("posterior_bwd_c_kernel");
+}
+
+extern "C" int osm_guide_update_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* noise,
+                                  const float* coef, const float* scale, float clip, float* x_next, float* grad_out, int B, int C,
+                                  int HW, void* stream) {
+  OSM_REQUIRE(mean && logvar && coef && x_next && B > 0 && C > 0 && HW > 0, "osm_guide_update_c: bad argument");
+  OSM_REQUIRE(!g || scale, "osm_guide_update_c: guidance needs the per-channel scale");
+  hipLaunchKernelGGL(guide_update_c_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
+                     g, dx_unet, noise, coef, scale, clip, x_next, grad_out, B, C, HW);
+  return osm::check_launch("guide_update_c_kernel");
+}
+
+extern "C" int osm_guide_update_rng_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
+                                      const float* scale, float clip, float* x_next, float* grad_out, float* noise_out, int B, int C,
+                                      int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
+                                      int img_stride, void* stream) {
+  const char* name = "osm_guide_update_rng_c";
+  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && C > 0 && HW > 0, "%s: bad argument", name);
+  OSM_REQUIRE(!g || scale, "%s: guidance needs the per-channel scale", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements of one channel)", name);
+  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
+                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
+                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "%s: tensors must be 16-byte aligned", name);
+  hipLaunchKernelGGL(guide_update_rng_c_kernel, dim3(grid_for((long long)B * C * (HW / 4))), dim3(256), 0, (hipStream_t)stream, mean,
+                     logvar, g, dx_unet, coef, scale, clip, x_next, grad_out, noise_out, B, C, HW, (unsigned)(seed & 0xffffffffull),
+                     (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("guide_update_rng_c_kernel");
+}
+
+extern "C" int osm_ddim_update_c(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
+                                 const float* coef, const float* dcoef, const float* scale, float clip, float* x_next,
+                                 float* grad_out, int B, int C, int HW, void* stream) {
+  OSM_REQUIRE(x0 && x && coef && dcoef && x_next && B > 0 && C > 0 && HW > 0, "osm_ddim_update_c: bad argument");
+  OSM_REQUIRE(!g || scale, "osm_ddim_update_c: guidance needs the per-channel scale");
+  hipLaunchKernelGGL(ddim_update_c_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, x0, x, g,
+                     dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, C, HW);
+  return osm::check_launch("ddim_update_c_kernel");
+}
+
+extern "C" int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss, float* g, int B, int C, int HW,
+                                  void* stream) {
+  OSM_REQUIRE(x0 && y && part && loss && g && B > 0 && HW > 0, "osm_ps_loss_grad_c: bad argument");
+  OSM_REQUIRE(C >= 3, "osm_ps_loss_grad_c: the data term reads channels 0..2 of x0, got C = %d", C);
+  const int nblk = osm_phys_nblk(HW);
+  hipLaunchKernelGGL(ps_reduce_c_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, x0, y, part, C, HW, nblk);
+  int rc = osm::check_launch("ps_reduce_c_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ps_grad_c_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, x0, y, part, loss, g, C, HW,
+                     nblk);
+  return osm::check_launch("ps_grad_c_kernel");
+}

@@ -38,6 +38,27 @@ def _winograd_on() -> bool:
     return os.environ.get("OSM_WINOGRAD", "1") != "0"
 
 
+def _pad4(c: int) -> int:
+    return (c + 3) & ~3
+
+
+def _padded_slot(slot, cin_p=None, cout_p=None):
+    """The conv parameters `slot` with zero input-channel columns / zero output-channel rows (and bias entries) added up to
+    cin_p / cout_p: the convolution kernels take channel counts in multiples of 4, so the stem of a 3-channel model and the
+    head of a 3 -> 6 / 3 -> 3 one are packed at the next multiple.  The extra lanes compute exact zeros."""
+    import types
+    w, b = slot.weight.detach(), slot.bias.detach()
+    co, ci = w.shape[0], w.shape[1]
+    cin_p, cout_p = cin_p or ci, cout_p or co
+    if (cin_p, cout_p) == (ci, co):
+        return slot
+    wp = w.new_zeros((cout_p, cin_p) + tuple(w.shape[2:]))
+    wp[:co, :ci] = w
+    bp = b.new_zeros(cout_p)
+    bp[:co] = b
+    return types.SimpleNamespace(weight=wp, bias=bp)
+
+
 class _Conv:
     def __init__(self, slot, dev, wfmt=0):
         """wfmt: ops.WFMT code of the model's conv arithmetic.  "f16x3" (4) exists for Winograd images only: such a model keeps
@@ -137,6 +158,9 @@ class UNetWeights:
         self.mc = model.model_channels
         self.ted = 4 * self.mc
         self.cin, self.cout = model.in_channels, model.out_channels
+        # channel counts of the NHWC staging of x / out and their gradients: the next multiple of 4 (equal to cin / cout
+        # for the RGBD model, where nothing below differs)
+        self.cin_p, self.cout_p = _pad4(self.cin), _pad4(self.cout)
         self.nlev = len(model.channel_mult)
         self.arch = describe_architecture(model)
 
@@ -150,7 +174,8 @@ class UNetWeights:
                 return _Down(m, dev, wfmt)
             if isinstance(m, UpsampleParams):
                 return _Up(m, dev, wfmt)
-            return _Conv(m, dev, wfmt)
+            # (a bare convolution slot is the stem: its input channels padded to the staging width, a no-op for the RGBD model)
+            return _Conv(_padded_slot(m, cin_p=_pad4(m.weight.shape[1])), dev, wfmt)
 
         def seq(s):
             return [wrap(m) for _, m in sorted(((int(k), v) for k, v in s._modules.items()), key=lambda kv: kv[0])]
@@ -160,12 +185,13 @@ class UNetWeights:
         self.te2 = (te.at(2).weight.detach().to(dev).contiguous(), te.at(2).bias.detach().to(dev).contiguous())
         self.num_classes = getattr(model, "num_classes", None)      # class-conditional: the engine adds label_emb rows to emb
         self.inp = [seq(s) for s in model.input_blocks]
+        assert self.inp[0][0].cin == self.cin_p
         self.mid = seq(model.middle_block)
         self.outb = [seq(s) for s in model.output_blocks]
         self.out_norm = _Norm(model.out.at(0), dev)
         # the reference's convert_to_fp16 leaves self.out in fp32 and casts h back before it (unet.py:697-703, 743-744):
         # in the f16 arithmetic the head's weights are bf16x6 images (fp32-class) and the head runs in the fp32 family
-        self.out_conv = _Conv(model.out.at(2), dev, 3 if wfmt == 1 else wfmt)
+        self.out_conv = _Conv(_padded_slot(model.out.at(2), cout_p=self.cout_p), dev, 3 if wfmt == 1 else wfmt)
 
         # every ResBlock's FiLM projection Linear(SiLU(emb)) depends on emb only: one stacked weight, ONE launch
         res_blocks = [m for seqs in (self.inp, [self.mid], self.outb) for sq in seqs for m in sq if isinstance(m, _Res)]
@@ -253,7 +279,7 @@ def activation_bytes_per_image(arch: dict, H: int, W: int, itemsize: int = 4) ->
     stem_cout = arch["inp"][0][0][2]
     chans, hws = [stem_cout], [(H, W)]
     hw, c = (H, W), stem_cout
-    fixed += H * W * (arch["cin"] + arch["cout"]) * 3      # x / out / gradients in NHWC
+    fixed += H * W * (_pad4(arch["cin"]) + _pad4(arch["cout"])) * 3      # x / out / gradients in NHWC
     for layers in arch["inp"][1:]:
         hw, c = seq_cost(layers, hw, c, True)
         chans.append(c)
@@ -280,6 +306,7 @@ class UNetEngine:
         # reference's use_fp16), fp32 otherwise.  Sampler-side tensors (x_in, out, d_out, dx) are always fp32 NCHW.
         self.adt = torch.float16 if weights.conv_mode == "f16" else torch.float32
         self.mc, self.ted, self.cin, self.cout = weights.mc, weights.ted, weights.cin, weights.cout
+        self.cin_p, self.cout_p = getattr(weights, "cin_p", self.cin), getattr(weights, "cout_p", self.cout)
         nlev = weights.nlev
         if H % (1 << (nlev - 1)) or W % (1 << (nlev - 1)):
             raise ValueError(f"H, W must be divisible by {1 << (nlev - 1)}")
@@ -332,6 +359,12 @@ class UNetEngine:
         self.out = torch.zeros(B, self.cout, H, W, **f32)
         self.d_out = torch.zeros(B, self.cout, H, W, **f32)
         self.dx = torch.zeros(B, self.cin, H, W, **f32)
+        # padded channel counts: the NHWC images the stem reads (x) and the head's data-gradient reads (d_out) live in
+        # persistent ZEROED buffers.  The transposes write lanes [0, cin) / [0, cout) only, so the pad lanes stay zero on
+        # the recording pass, on plan replay and on hipGraph replay alike (an uninitialised lane holding NaN / Inf would
+        # poison 0 * lane in the convolution)
+        self._x_pad = torch.zeros(B * H * W, self.cin_p, device=dev, dtype=self.adt) if self.cin_p != self.cin else None
+        self._do_pad = torch.zeros(B * H * W, self.cout_p, **f32) if self.cout_p != self.cout else None
         self.gn_part = torch.empty(B * ops.gn_nchunk(H * W) * G * 2, **f32)
         self.num_classes = getattr(weights, "num_classes", None)
         self.label_rows = torch.zeros(B, self.ted, **f32) if self.num_classes is not None else None   # label_emb[y], set per call
@@ -968,7 +1001,7 @@ class UNetEngine:
             return self.cat[i].cols_slice(self.cat_split[i], self.cat[i].cols)
 
         # ---- input blocks
-        x_nhwc = self._buf(B * H * W, self.cin)
+        x_nhwc = Mat.of(self._x_pad) if self._x_pad is not None else self._buf(B * H * W, self.cin)
         ops.nchw_to_nhwc(self.x_in, x_nhwc, B, self.cin, H * W)
         h = skip_dst(0)
         self._conv(x_nhwc, stem, h, (H, W))
@@ -993,7 +1026,7 @@ class UNetEngine:
             h = h32
         self.h_last = h
         self.st_out = self._small(B * G * 2)
-        o = self._buf(B * H * W, self.cout, dtype=torch.float32)
+        o = self._buf(B * H * W, self.cout_p, dtype=torch.float32)     # (pad lanes: zero weights and bias, never read)
         self._gn_conv(h, self.out_norm, self.st_out, self.out_conv, o, (H, W))
         ops.nhwc_to_nchw(o, self.out, B, self.cout, H * W)
         self.x_nhwc = x_nhwc
@@ -1003,7 +1036,7 @@ class UNetEngine:
         n_in = len(self.inp)
         self._xmax_reg = {}         # (pointer, rows, ld) of a gradient buffer -> max |.| slot its last writer filled
         f32 = torch.float32         # the head's gradient runs in the fp32 family in every arithmetic (see _forward_impl)
-        do = self._buf(B * H * W, self.cout, dtype=f32)
+        do = Mat.of(self._do_pad) if self._do_pad is not None else self._buf(B * H * W, self.cout, dtype=f32)
         ops.nchw_to_nhwc(self.d_out, do, B, self.cout, H * W)
         da = self._scr("a", B * H * W, self.h_last.cols, dtype=f32)
         self._conv(do, self.out_conv, da, (H, W), dgrad=True)
@@ -1033,7 +1066,7 @@ class UNetEngine:
         self._run_layers_bwd(self.mid, dy, dskip(n_in - 1), accumulate=True)
         for j in range(n_in - 1, 0, -1):
             self._run_layers_bwd(self.inp[j], dskip(j), dskip(j - 1), accumulate=True)
-        dxn = self._buf(B * H * W, self.cin)
+        dxn = self._buf(B * H * W, self.cin_p)
         self._conv(dskip(0), self.inp[0][0], dxn, (H, W), dgrad=True)
         ops.nhwc_to_nchw(dxn, self.dx, B, self.cin, H * W)
 

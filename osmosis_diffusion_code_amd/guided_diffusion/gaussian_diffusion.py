@@ -199,16 +199,25 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ fused (HIP) loop
     def _fast_path_ok(self, model, cond_fn, pretrain_model, rgb_guidance, sample_pattern, shape=None):
-        """The conditioner whose step the fused loop implements, or None (-> `_generic_loop`).  Two configurations:
-        the Osmosis one (pretrain_model 'osmosis', 'osmosis' conditioning with gradient_x_prev, a physical operator) and the
-        rgb-guidance one (`rgb_guidance=True`: `DDPM.p_sample` / `DDIM.p_sample` + 'ps' conditioning on an identity operator
-        with the gaussian noiser; gaussian_diffusion.py:231-232,296-302, condition_methods.py:234-251).  shape: x_start's
+        """The conditioner whose step the fused loop implements, or None (-> `_generic_loop`).  Three configurations:
+        the Osmosis one (pretrain_model 'osmosis', a 4 -> 8 network, 'osmosis' conditioning with gradient_x_prev, a physical
+        operator), the rgb-guidance one (`rgb_guidance=True`: `DDPM.p_sample` / `DDIM.p_sample` + 'ps' conditioning on an identity
+        operator with the gaussian noiser; gaussian_diffusion.py:231-232,296-302, condition_methods.py:234-251) and, for a
+        3-channel network, the mean-only one (`rgb_guidance=False`, pretrain_model != 'osmosis': p_mean_variance, sample = mean,
+        'ps' conditioning, no noise; :235-238, :298-306).  Networks: C = 3 or 4 input channels and C or 2 C output channels
+        (create_model's 4 -> 8, 3 -> 6, 3 -> 3; a C -> C network goes with any variance processor, which then reads the
+        network output itself, :349-355); OSM_FUSED_RGB=0 keeps 3-channel chains on `_generic_loop`.  shape: x_start's
         [B, C, H, W] (`dynamic_threshold` needs it)."""
         import os
         from .condition_methods import PosteriorSampling, PosteriorSamplingOsmosis
         from .unet import UNetModel
         cond = getattr(cond_fn, "__self__", None)
-        if not isinstance(model, UNetModel) or model.in_channels != 4:
+        if not isinstance(model, UNetModel):
+            return None
+        C = model.in_channels
+        if C not in (3, 4) or model.out_channels not in (C, 2 * C):
+            return None       # the step kernels serve [B,C,HW] with C in {3, 4} and a network output of C or 2 C channels
+        if C == 3 and os.environ.get("OSM_FUSED_RGB", "1") == "0":
             return None
         if self.mean_processor.hip_kernel != "osm_posterior" or self.var_processor.hip_kernel != "osm_posterior":
             return None
@@ -225,19 +234,25 @@ class GaussianDiffusion:
             # the PCGS inner alternation runs as sub-steps of the fused loop; OSM_FUSED_PCGS=0 keeps such chains on `_generic_loop`
             if os.environ.get("OSM_FUSED_PCGS", "1") == "0":
                 return None
-        if pretrain_model != "osmosis" and not rgb_guidance:
-            return None       # the reference's mean-only step (:234-236: p_mean_variance, sample = mean, no p_sample): `_generic_loop`
-        if rgb_guidance:
+        mean_only = pretrain_model != "osmosis" and not rgb_guidance
+        if mean_only and C != 3:
+            return None       # the reference's mean-only step (:234-236: p_mean_variance, sample = mean, no p_sample) on a 4-channel
+            #                   network: `_generic_loop`; fused for the RGB model family only
+        if rgb_guidance or mean_only:
             # the 'ps' step: only the two registered step rules, un-overridden, and a chain that is guided at every index (the
-            # reference calls the conditioner at every step of this branch: an unguided index raises in its autograd.grad)
-            if type(cond) is not PosteriorSampling or not cond.hip_ok():
+            # reference calls the conditioner at every step of these branches: an unguided index raises in its autograd.grad)
+            if type(cond) is not PosteriorSampling or not cond.hip_ok(C):
                 return None
-            if getattr(type(self), "p_sample", None) not in (DDPM.p_sample, DDIM.p_sample):
+            if mean_only:     # (p_mean_variance, not p_sample, is the step rule of this branch)
+                if getattr(type(self), "p_mean_variance", None) not in (SpacedDiffusion.p_mean_variance,
+                                                                        GaussianDiffusion.p_mean_variance):
+                    return None
+            elif getattr(type(self), "p_sample", None) not in (DDPM.p_sample, DDIM.p_sample):
                 return None
             if sample_pattern is not None and not all(self._guidance_flag(sample_pattern, i) for i in (0, self.num_timesteps - 1)):
                 return None
             return cond
-        if not isinstance(cond, PosteriorSamplingOsmosis):
+        if not isinstance(cond, PosteriorSamplingOsmosis) or (C, model.out_channels) != (4, 8):
             return None
         if not cond.gradient_x_prev or not cond.hip_ok():       # (a third-party operator / auxiliary loss: autograd conditioning)
             return None
@@ -289,7 +304,8 @@ class GaussianDiffusion:
     def _guidance_flag(self, sample_pattern, idx):
         return guidance_flag(sample_pattern, idx, self.num_timesteps)
 
-    def _fused_loop(self, model, cond, x_start, measurement, sample_pattern, kwargs, record=False, record_every=150):
+    def _fused_loop(self, model, cond, x_start, measurement, sample_pattern, kwargs, record=False, record_every=150,
+                    mean_only=False):
         """One device-resident step per index, for the Osmosis configuration and for the rgb-guidance ('ps') one (`_fast_path_ok`).
         Per-step noise (gaussian_diffusion.py:266-268 / :497 / :522): by default drawn INSIDE osm_guide_update_rng from the
         library's Philox-4x32-10 stream (seed: `noise_seed=`, else one draw per chain from the device's torch generator, so
@@ -298,13 +314,21 @@ class GaussianDiffusion:
         PCGS (`pcgs_schedule`): index idx runs alternate_len sub-steps at the same t, each a full step (network, posterior, conditioning
         with its own n_iter phi steps, noise) on the previous sub-step's x_t.  Only the last sub-step's fetch moves the step counter;
         noise_fn's k, the library stream's `sub` counter word and the trace count sub-steps; `record` snapshots (and the returned loss,
-        phi, x0) are those after the index's last sub-step (:274, :309)."""
+        phi, x0) are those after the index's last sub-step (:274, :309).
+        mean_only: the mean-only 'ps' step (:235-238, :298-306): x_next = mean - scale grad at every index, no noise drawn or added
+        (`noise="aten"` with reference_rng_order draws q_sample's only; noise_fn is not called).
+        Channels: x_start [B,C,H,W] with the network's C; (C, Cout) = (4, 8) runs the [B,4,HW] entry points, anything else the
+        channel-generic ones (osm_*_c)."""
         import os
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
-        ddim = ps and getattr(type(self), "p_sample", None) is DDIM.p_sample
+        ddim = ps and not mean_only and getattr(type(self), "p_sample", None) is DDIM.p_sample
         dev = x_start.device
         B, C, H, W = x_start.shape
+        Cout = model.out_channels
+        if C != model.in_channels:
+            raise ValueError(f"expected x_start [B,{model.in_channels},H,W], got {tuple(x_start.shape)}")
+        rgbd = (C, Cout) == (4, 8)                        # the compile-time [B,4,HW] / [B,8,HW] kernels
         HW = H * W
         T = self.num_timesteps
         # the loop drives the engine's plans directly and calls the network as model(x, t) (gaussian_diffusion.py:243): a
@@ -336,25 +360,25 @@ class GaussianDiffusion:
         coef = torch.zeros(8, **f32)
         dtable = torch.from_numpy(self.ddim_table(float(kwargs.get("eta", 0.0)))).to(dev) if ddim else None
         dcoef = torch.zeros(8, **f32) if ddim else None
-        x0, mean, logvar = (torch.empty(B, 4, H, W, **f32) for _ in range(3))
+        x0, mean, logvar = (torch.empty(B, C, H, W, **f32) for _ in range(3))
         # `clip_denoised: True` (configs/rgb_guidance_sample_config.yaml; posterior_mean_variance.py:43-50): x0 is clamped inside
         # osm_posterior_typed, the unclamped prediction is kept for the clamp's backward (osm_clamp_bwd masks d loss / d x0)
         # `dynamic_threshold: True` (util/img_utils.py:8-15): x0 = clip(x0_raw * quantile(|x0_raw|, 0.98), -1, 1) over the whole batch
         # (osm_posterior_dynthr; q and its order statistics stay on the device for osm_dynthr_bwd); `_fast_path_ok` guarantees one chunk
         dyn = bool(self.mean_processor.dynamic_threshold)
-        x0_raw = torch.empty(B, 4, H, W, **f32) if (self.mean_processor.clip_denoised or dyn) else None
+        x0_raw = torch.empty(B, C, H, W, **f32) if (self.mean_processor.clip_denoised or dyn) else None
         if dyn:
             assert len(chunks) == 1, "dynamic_threshold couples every image: the fused loop takes it in one engine pass only"
             q_dev, q_idx = torch.zeros(1, **f32), torch.zeros(2, device=dev, dtype=torch.int32)
-            q_ws = ops.quantile_workspace(B * 4 * HW, dev)
-        g = torch.empty(B, 4, H, W, **f32)
+            q_ws = ops.quantile_workspace(B * C * HW, dev)
+        g = torch.empty(B, C, H, W, **f32)
         loss_all = torch.zeros(B, **f32)
-        scale4 = cond.scale4(dev)
+        scale4 = cond.scale4(dev, C) if ps else cond.scale4(dev)
         clip = -1.0 if ps else cond.clip_value
         y = measurement.detach().to(dev, torch.float32).contiguous()
         phi = None if ps else cond.operator.phi
         single = len(chunks) == 1
-        x_state = eng.x_in if single else torch.empty(B, 4, H, W, **f32)
+        x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
         x_state.copy_(x_start.detach())
         noise_fn = kwargs.get("noise_fn", None)           # (k, shape) -> tensor : injected noise (parity runs)
         trace = kwargs.get("trace", None)                 # list collecting per-step tensors (tests)
@@ -367,16 +391,16 @@ class GaussianDiffusion:
             source = "aten"                               # (one Philox counter covers four consecutive elements of an image)
         # q_sample's unused draw (reference :241) and, for 'ps', p_sample's draw before it: only meaningful on torch's generator
         draw_measurement_noise = kwargs.get("reference_rng_order", source == "aten") and source == "aten"
-        lib_rng = source == "library" and not ddim        # (DDIM at eta = 0 adds no noise; osm_ddim_update takes a tensor for eta > 0)
+        lib_rng = source == "library" and not ddim and not mean_only        # (DDIM at eta = 0 adds no noise; osm_ddim_update takes a tensor for eta > 0)
         seed = 0
         if source == "library":
             seed = kwargs.get("noise_seed")
             if seed is None:      # one draw per CHAIN from the device's generator (what torch.manual_seed seeds, and only device ops consume)
                 seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev).item())
         img_base, img_stride = int(kwargs.get("image_index0", 0)), 0 if shared else 1
-        noise = None if lib_rng else torch.zeros(B, 4, H, W, **f32)
-        noise1 = torch.zeros(1, 4, H, W, **f32) if (shared and source == "aten") else None
-        noise_used = torch.empty(B, 4, H, W, **f32) if (lib_rng and trace is not None) else None
+        noise = None if (lib_rng or mean_only) else torch.zeros(B, C, H, W, **f32)
+        noise1 = torch.zeros(1, C, H, W, **f32) if (shared and source == "aten" and not mean_only) else None
+        noise_used = torch.empty(B, C, H, W, **f32) if (lib_rng and trace is not None) else None
         have_loss = False
         k = 0                                             # sub-step count (noise_fn's k)
         for idx in range(first, last - 1, -1):
@@ -385,7 +409,10 @@ class GaussianDiffusion:
                 guided, freeze = True, False
             for sub in range(alt):
                 final = sub == alt - 1
-                if source == "fn":
+                if mean_only:                             # no step noise; the reference's only draw per call is q_sample's (:241)
+                    if draw_measurement_noise:
+                        torch.randn_like(y[:1] if shared else y)
+                elif source == "fn":
                     noise.copy_(noise_fn(k, noise.shape))
                 elif source == "aten":
                     if ps:                                # DDPM / DDIM.p_sample draw first (:497, :522), then q_sample (:241)
@@ -397,7 +424,7 @@ class GaussianDiffusion:
                     if noise1 is not None:
                         noise.copy_(noise1.expand_as(noise))
                 elif not lib_rng:                         # library stream, DDIM: as a tensor (used only for eta > 0)
-                    ops.randn_sub(noise, B, 4 * HW, seed, step=step, sub=sub, img0=img_base,
+                    ops.randn_sub(noise, B, C * HW, seed, step=step, sub=sub, img0=img_base,
                                   img_stride=img_stride)  # (before the fetch: counter = idx)
                 # every engine's timestep vector is filled from the SAME step counter; the counter moves once per index, in the last
                 # fetch of its last sub-step, which always goes through the first engine (stream order: the delta-0 fetches read it
@@ -417,13 +444,19 @@ class GaussianDiffusion:
                     if not single:
                         ce.x_in.copy_(x_state[c0:c1])
                     ce.run_forward()
-                    if dyn:
+                    mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
+                    if dyn and rgbd:
                         ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
-                                             self.mean_processor.kernel_kind, self.var_processor.kernel_kind, DYNAMIC_THRESHOLD_S)
-                    else:
-                        ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW,
-                                      self.mean_processor.kernel_kind, self.var_processor.kernel_kind,
+                                             mk, vk, DYNAMIC_THRESHOLD_S)
+                    elif dyn:
+                        ops.posterior_dynthr_c(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, C, Cout, HW,
+                                               mk, vk, DYNAMIC_THRESHOLD_S)
+                    elif rgbd:
+                        ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW, mk, vk,
                                       None if x0_raw is None else x0_raw[c0:c1])
+                    else:
+                        ops.posterior_c(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, C, Cout, HW, mk, vk,
+                                        None if x0_raw is None else x0_raw[c0:c1])
                     if trace is not None:
                         model_out[c0:c1].copy_(ce.out)
                     gg = dxu = grad_out = None
@@ -438,21 +471,32 @@ class GaussianDiffusion:
                             ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
                         elif x0_raw is not None:
                             ops.clamp_bwd(g[c0:c1], x0_raw[c0:c1])
-                        ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
+                        if rgbd:
+                            ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
+                        else:
+                            ops.posterior_bwd_c(g[c0:c1], coef, ce.d_out, Bc, C, Cout, HW)
                         ce.run_backward()
                         gg, dxu = g[c0:c1], ce.dx
                         grad_out = grad_all[c0:c1] if trace is not None else None
                     nz = None if noise is None else noise[c0:c1]
                     sc, cl = (scale4, clip) if guided else (None, -1.0)
-                    if ddim:
+                    nu = None if noise_used is None else noise_used[c0:c1]
+                    if ddim and rgbd:
                         ops.ddim_update(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
-                    elif lib_rng:                         # (+1 after the last sub-step's fetch: it moved the counter)
+                    elif ddim:
+                        ops.ddim_update_c(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, C, HW)
+                    elif lib_rng and rgbd:                # (+1 after the last sub-step's fetch: it moved the counter)
                         ops.guide_update_rng_sub(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
-                                                 None if noise_used is None else noise_used[c0:c1], Bc, HW, seed, step,
-                                                 step_offset=1 if final else 0, sub=sub,
+                                                 nu, Bc, HW, seed, step, step_offset=1 if final else 0, sub=sub,
                                                  img0=img_base + (0 if shared else c0), img_stride=img_stride)
-                    else:
+                    elif lib_rng:
+                        ops.guide_update_rng_c(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
+                                               nu, Bc, C, HW, seed, step, step_offset=1 if final else 0, sub=sub,
+                                               img0=img_base + (0 if shared else c0), img_stride=img_stride)
+                    elif rgbd:
                         ops.guide_update(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
+                    else:                                 # (mean_only: nz is None -> the kernel adds no noise at any index)
+                        ops.guide_update_c(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, C, HW)
                 if trace is not None:
                     rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out,
                                loss=loss_all.clone() if have_loss else None, phi=None if phi is None else phi.clone(),
@@ -511,10 +555,14 @@ class GaussianDiffusion:
             # (gaussian_diffusion.py:268 / :499, condition_methods.py:223 / :249) -- autograd refuses that on a multi-output view.
             raise RuntimeError("Output 0 of SplitBackward0 is a view and is being modified inplace: the 'previous_x' mean processor "
                                "only runs with the DDIM sampler on the rgb-guidance branch (as in the reference)")
+        if record and x_start.shape[1] < 4:
+            # the reference's record branch reads the depth channel of pred_xstart (gaussian_diffusion.py:319) and fails there
+            raise IndexError(f"index 3 is out of bounds for dimension 1 with size {x_start.shape[1]}: record=True snapshots the "
+                             "depth channel of pred_xstart, which a 3-channel (RGB) chain does not have (as in the reference)")
         cond = self._fast_path_ok(model, measurement_cond_fn, pretrain_model, rgb_guidance, sample_pattern, tuple(x_start.shape))
         if cond is not None:
             return self._fused_loop(model, cond, x_start, measurement, sample_pattern, kwargs, record=record,
-                                    record_every=record_every)
+                                    record_every=record_every, mean_only=pretrain_model != "osmosis" and not rgb_guidance)
         return self._generic_loop(model, x_start, measurement, measurement_cond_fn, pretrain_model,
                                   rgb_guidance, sample_pattern, kwargs, record=record, record_every=record_every)
 

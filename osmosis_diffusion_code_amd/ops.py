@@ -504,3 +504,47 @@ def fetch_coefs(table, step, delta, coef_out, t_out, B):
 def ancestral_step(model_out, x, z, coef, x_next, x0, B, Cc, Cout, HW):
     call("osm_ancestral_step", ptr(model_out), ptr(x), ptr(z), ptr(coef), ptr(x_next), ptr(x0), B, Cc, Cout, HW, _s(),
          keep=(model_out, x, z, coef, x_next, x0))
+
+
+# ----------------------------------------------------------------------------- channel-generic sampler step ([B,C,HW] / [B,Cout,HW])
+def posterior_c(model_out, x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind=0, var_kind=0, x0_raw=None):
+    """`posterior` for a C-channel state and a Cout-channel network output (Cout = C: no variance half, the variance processor
+    reads model_out itself)."""
+    call("osm_posterior_c", ptr(model_out), ptr(x), ptr(coef), int(mean_kind), int(var_kind), 0 if x0_raw is None else 1,
+         ptr(x0_raw), ptr(x0), ptr(mean), ptr(logvar), B, Cc, Cout, HW, _s(), keep=(model_out, x, coef, x0_raw, x0, mean, logvar))
+
+
+def posterior_dynthr_c(model_out, x, coef, x0, mean, logvar, x0_raw, q, idx, ws, B, Cc, Cout, HW, mean_kind=0, var_kind=0, s=0.98):
+    """`posterior_dynthr` over a [B,C,H,W] batch (ws: `quantile_workspace(B * C * HW)`)."""
+    call("osm_posterior_dynthr_c", ptr(model_out), ptr(x), ptr(coef), int(mean_kind), int(var_kind), float(s), ptr(x0_raw), ptr(x0),
+         ptr(mean), ptr(logvar), ptr(q), ptr(idx), ptr(ws), B, Cc, Cout, HW, _s(),
+         keep=(model_out, x, coef, x0_raw, x0, mean, logvar, q, idx, ws))
+
+
+def posterior_bwd_c(g, coef, d_out, B, Cc, Cout, HW):
+    call("osm_posterior_bwd_c", ptr(g), ptr(coef), ptr(d_out), B, Cc, Cout, HW, _s(), keep=(g, coef, d_out))
+
+
+def guide_update_c(mean, logvar, g, dx_unet, noise, coef, scale, clip, x_next, grad_out, B, Cc, HW):
+    call("osm_guide_update_c", ptr(mean), ptr(logvar), ptr(g), ptr(dx_unet), ptr(noise), ptr(coef), ptr(scale),
+         float(clip), ptr(x_next), ptr(grad_out), B, Cc, HW, _s(),
+         keep=(mean, logvar, g, dx_unet, noise, coef, scale, x_next, grad_out))
+
+
+def guide_update_rng_c(mean, logvar, g, dx_unet, coef, scale, clip, x_next, grad_out, noise_out, B, Cc, HW, seed, step, step_offset=0,
+                       sub=0, img0=0, img_stride=1):
+    """`guide_update_rng_sub` on [B,C,HW]: counter (element / 4 of the image's C HW elements, img0 + b * img_stride,
+    (*step + step_offset) | sub << 16)."""
+    call("osm_guide_update_rng_c", ptr(mean), ptr(logvar), ptr(g), ptr(dx_unet), ptr(coef), ptr(scale), float(clip), ptr(x_next),
+         ptr(grad_out), ptr(noise_out), B, Cc, HW, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), int(step_offset), int(sub), int(img0),
+         int(img_stride), _s(), keep=(mean, logvar, g, dx_unet, coef, scale, x_next, grad_out, noise_out, step))
+
+
+def ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, Cc, HW):
+    call("osm_ddim_update_c", ptr(x0), ptr(x), ptr(g), ptr(dx_unet), ptr(noise), ptr(coef), ptr(dcoef), ptr(scale), float(clip),
+         ptr(x_next), ptr(grad_out), B, Cc, HW, _s(), keep=(x0, x, g, dx_unet, noise, coef, dcoef, scale, x_next, grad_out))
+
+
+def ps_loss_grad_c(x0, y, part, loss, g, B, Cc, HW):
+    """loss[b] = ||y[b] - x0[b, 0:3]||, g = d loss / d x0 (zero beyond channel 2); part: fp32 [B * phys_nblk(HW)] workspace."""
+    call("osm_ps_loss_grad_c", ptr(x0), ptr(y), ptr(part), ptr(loss), ptr(g), B, Cc, HW, _s(), keep=(x0, y, part, loss, g))

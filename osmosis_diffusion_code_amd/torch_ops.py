@@ -304,4 +304,150 @@ def _phys_loss_grad_fake(x0, y, phi, icfg, fcfg, n_inner, freeze_phi):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
 
 
-OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad")
+# ---- channel-generic step (the RGB model family: [B,C,H,W] state, [B,Cout,H,W] network output with Cout = C or 2 C)
+def _cc(model_out, x):
+    if model_out.dim() != 4 or model_out.shape[1] not in (x.shape[1], 2 * x.shape[1]):
+        raise OsmosisHipError("osmosis:: the network output must have C or 2 C channels")
+    return x.shape[1], model_out.shape[1]
+
+
+@torch.library.custom_op("osmosis::posterior_c", mutates_args=(), device_types="cuda")
+def posterior_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
+                var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::posterior for any channel count (osm_posterior_c); model_out with C channels: the variance processor reads it too."""
+    B, HW = _chw(x)
+    Cc, Cout = _cc(model_out, x)
+    x0, mean, logvar = (torch.empty_like(x) for _ in range(3))
+    ops.posterior_c(model_out.contiguous(), x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind, var_kind)
+    return x0, mean, logvar
+
+
+@posterior_c.register_fake
+def _posterior_c_fake(model_out, x, coef, mean_kind=0, var_kind=0):
+    return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+
+
+@torch.library.custom_op("osmosis::posterior_clip_c", mutates_args=(), device_types="cuda")
+def posterior_clip_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
+                     var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::posterior_clip for any channel count."""
+    B, HW = _chw(x)
+    Cc, Cout = _cc(model_out, x)
+    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
+    ops.posterior_c(model_out.contiguous(), x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind, var_kind, x0_raw=raw)
+    return x0, mean, logvar, raw
+
+
+@posterior_clip_c.register_fake
+def _posterior_clip_c_fake(model_out, x, coef, mean_kind=0, var_kind=0):
+    return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+
+
+@torch.library.custom_op("osmosis::posterior_dynthr_c", mutates_args=(), device_types="cuda")
+def posterior_dynthr_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0, var_kind: int = 0,
+                       s: float = 0.98) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::posterior_dynthr for any channel count (the quantile over all B C H W elements)."""
+    B, HW = _chw(x)
+    Cc, Cout = _cc(model_out, x)
+    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
+    q, idx = torch.empty(1, device=x.device, dtype=torch.float32), torch.empty(2, device=x.device, dtype=torch.int32)
+    ops.posterior_dynthr_c(model_out.contiguous(), x, coef, x0, mean, logvar, raw, q, idx,
+                           ops.quantile_workspace(x.numel(), x.device), B, Cc, Cout, HW, mean_kind, var_kind, s)
+    return x0, mean, logvar, raw, q, idx
+
+
+@posterior_dynthr_c.register_fake
+def _posterior_dynthr_c_fake(model_out, x, coef, mean_kind=0, var_kind=0, s=0.98):
+    return (torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), x.new_empty((1,)),
+            x.new_empty((2,), dtype=torch.int32))
+
+
+@torch.library.custom_op("osmosis::posterior_bwd_c", mutates_args=(), device_types="cuda")
+def posterior_bwd_c(g: torch.Tensor, coef: torch.Tensor, cout: int) -> torch.Tensor:
+    """d loss / d model_out [B,cout,H,W] from g = d loss / d x0 [B,C,H,W] (osm_posterior_bwd_c); cout = C or 2 C."""
+    B, HW = _chw(g)
+    d_out = torch.empty(B, cout, g.shape[2], g.shape[3], device=g.device, dtype=torch.float32)
+    ops.posterior_bwd_c(g, coef, d_out, B, g.shape[1], cout, HW)
+    return d_out
+
+
+@posterior_bwd_c.register_fake
+def _posterior_bwd_c_fake(g, coef, cout):
+    return g.new_empty((g.shape[0], cout, g.shape[2], g.shape[3]))
+
+
+@torch.library.custom_op("osmosis::guide_update_c", mutates_args=(), device_types="cuda")
+def guide_update_c(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor,
+                   coef: torch.Tensor, scale: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """osmosis::guide_update for any channel count; scale: [C]."""
+    B, HW = _chw(mean)
+    if scale.numel() != mean.shape[1]:
+        raise OsmosisHipError("osmosis::guide_update_c: scale must have one entry per channel")
+    x_next, grad = torch.empty_like(mean), torch.empty_like(mean)
+    ops.guide_update_c(mean, log_variance, g, dx_unet, noise, coef, scale, clip, x_next, grad, B, mean.shape[1], HW)
+    return x_next, grad
+
+
+@guide_update_c.register_fake
+def _guide_update_c_fake(mean, log_variance, g, dx_unet, noise, coef, scale, clip):
+    return torch.empty_like(mean), torch.empty_like(mean)
+
+
+@torch.library.custom_op("osmosis::guide_update_rng_c", mutates_args=(), device_types="cuda")
+def guide_update_rng_c(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, coef: torch.Tensor,
+                       scale: torch.Tensor, clip: float, seed: int, step: torch.Tensor, step_offset: int, img0: int,
+                       img_stride: int, sub: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::guide_update_rng for any channel count (counter word 0 = element / 4 within the image's C H W elements)."""
+    B, HW = _chw(mean)
+    if scale.numel() != mean.shape[1]:
+        raise OsmosisHipError("osmosis::guide_update_rng_c: scale must have one entry per channel")
+    x_next, grad, noise = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
+    ops.guide_update_rng_c(mean, log_variance, g, dx_unet, coef, scale, clip, x_next, grad, noise, B, mean.shape[1], HW, seed, step,
+                           step_offset=step_offset, sub=sub, img0=img0, img_stride=img_stride)
+    return x_next, grad, noise
+
+
+@guide_update_rng_c.register_fake
+def _guide_update_rng_c_fake(mean, log_variance, g, dx_unet, coef, scale, clip, seed, step, step_offset, img0, img_stride, sub=0):
+    return torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
+
+
+@torch.library.custom_op("osmosis::ddim_update_c", mutates_args=(), device_types="cuda")
+def ddim_update_c(x0: torch.Tensor, x: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor,
+                  dcoef: torch.Tensor, scale: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """osmosis::ddim_update for any channel count; scale: [C]."""
+    B, HW = _chw(x0)
+    if scale.numel() != x0.shape[1]:
+        raise OsmosisHipError("osmosis::ddim_update_c: scale must have one entry per channel")
+    x_next, grad = torch.empty_like(x0), torch.empty_like(x0)
+    ops.ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad, B, x0.shape[1], HW)
+    return x_next, grad
+
+
+@ddim_update_c.register_fake
+def _ddim_update_c_fake(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip):
+    return torch.empty_like(x0), torch.empty_like(x0)
+
+
+@torch.library.custom_op("osmosis::ps_loss_grad_c", mutates_args=(), device_types="cuda")
+def ps_loss_grad_c(x0: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The 'ps' data term (identity operator, gaussian noiser) on x0 [B,C,H,W], y [B,3,H,W]: (loss [B] = ||y - x0[:, 0:3]|| per
+    image, g = d loss / d x0) (osm_ps_loss_grad_c)."""
+    B, HW = _chw(x0)
+    if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] < 3:
+        raise OsmosisHipError("osmosis::ps_loss_grad_c: expected x0 [B,C>=3,H,W] and y [B,3,H,W]")
+    loss = torch.empty(B, device=x0.device, dtype=torch.float32)
+    g = torch.empty_like(x0)
+    part = torch.empty(B * ops.phys_nblk(HW), device=x0.device, dtype=torch.float32)
+    ops.ps_loss_grad_c(x0, y.contiguous(), part, loss, g, B, x0.shape[1], HW)
+    return loss, g
+
+
+@ps_loss_grad_c.register_fake
+def _ps_loss_grad_c_fake(x0, y):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
+
+
+OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
+         "ddim_update_c", "ps_loss_grad_c")
+OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad") + OPS_C
