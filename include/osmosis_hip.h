@@ -474,6 +474,41 @@ int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss
 int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out, int B,
                     void* stream);
 
+/* ================================================================== full-resolution reconstruction
+ * The closed-form inversion of the physical model (osmosis_sampling.py:253-255,287-289; sampling.postprocess `rgb_recon`)
+ *   D = convert_depth(d) ; back_c = phi_inf_c (1 - exp(-phi_b_c D)) ; rgb_c = exp(phi_a_c D) (I_c - back_c)
+ * on the ORIGINAL pixel grid: I = the photo before Resize / CenterCrop (a rectangle [3][Hc][Wc] of it, planar, in [0,1]),
+ * d = the raw network depth [h][w] in [-1,1] upsampled to that grid.  Pixel (i, j) of the rectangle has the network-grid
+ * coordinate v = (ay i + by, ax j + bx), evaluated in double with one rounding per operation; 0 < ay, ax <= 1 (upsampling only).
+ *   mode 0  bilinear on clamp(v, [0,h-1] x [0,w-1]): F.grid_sample(bilinear, padding_mode="border", align_corners=False)
+ *   mode 1  joint bilateral upsampling: q over the integer network pixels [floor(v_y)-R+1, floor(v_y)+R] x [floor(v_x)-R+1,
+ *           floor(v_x)+R]; depth and guide are read at q clamped to the image (replicate border), the spatial term uses q itself:
+ *             w(q) = exp(-(|q - v|^2 / (2 sigma_s^2) + sum_c (I_c - G_c(q))^2 / (2 sigma_r^2))) ; d = sum w d(q) / sum w
+ *           and the bilinear value where sum w underflows to 0.  guide [3][h][w] in [0,1] = the image the sampler saw.
+ * phi_a / phi_b / phi_inf: device float[3] each (operators with one phi_ab pass it for both).  depth_type / dval: as in
+ * the physics descriptor: 0 original, 1 gamma, 2 move.  rgb is unclipped; rgb_u8 (optional, [Hc][Wc][3]) = (uint8)(clamp(rgb,0,1)*255),
+ * truncated; depth_full (optional, [Hc][Wc]) = the upsampled raw depth.  radius (1..4) and the sigmas (> 0) are checked in both
+ * modes.  16-byte accesses when Wc % 4 == 0 and image / rgb / depth_full are 16-byte (rgb_u8 4-byte) aligned; any Wc works.
+ * No atomics: bit-reproducible. */
+typedef struct osm_recon_desc {
+  const float* depth;
+  const float* guide;
+  const float* image;
+  const float* phi_a;
+  const float* phi_b;
+  const float* phi_inf;
+  float* rgb;
+  unsigned char* rgb_u8;
+  float* depth_full;
+  int h, w, Hc, Wc;
+  int depth_type;
+  float dval[3];
+  double ay, by, ax, bx;
+  int mode, radius;
+  float sigma_s, sigma_r;
+} osm_recon_desc;
+int osm_recon_fullres(const osm_recon_desc* d, void* stream);
+
 /* ================================================================== fp16-storage family (`use_fp16: True`)
  * The reference's fp16 mode (guided_diffusion/unet.py:544,697-703,733; fp16_util.py:13-20 convert_module_to_f16)
  * keeps activations and conv weights in IEEE half, accumulates in fp32 (ATen/cuDNN) and runs GroupNorm32 in

@@ -62,6 +62,16 @@ class PhysDesc(C.Structure):
                 ("eta", C.c_float * 3), ("B", C.c_int), ("HW", C.c_int), ("optimizer", C.c_int)]
 
 
+class ReconDesc(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("guide", C.c_void_p), ("image", C.c_void_p),
+                ("phi_a", C.c_void_p), ("phi_b", C.c_void_p), ("phi_inf", C.c_void_p),
+                ("rgb", C.c_void_p), ("rgb_u8", C.c_void_p), ("depth_full", C.c_void_p),
+                ("h", C.c_int), ("w", C.c_int), ("Hc", C.c_int), ("Wc", C.c_int),
+                ("depth_type", C.c_int), ("dval", C.c_float * 3),
+                ("ay", C.c_double), ("by", C.c_double), ("ax", C.c_double), ("bx", C.c_double),
+                ("mode", C.c_int), ("radius", C.c_int), ("sigma_s", C.c_float), ("sigma_r", C.c_float)]
+
+
 # name -> argtypes (restype is int unless listed in _SPECIAL)
 _LL = C.c_longlong
 _P = C.c_void_p
@@ -135,6 +145,7 @@ _SIGS = {
     "osm_guide_update_rng_c": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
     "osm_ddim_update_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P],
     "osm_ps_loss_grad_c": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "osm_recon_fullres": [C.POINTER(ReconDesc), _P],
     "osm_version": [],
 }
 # fp16-storage family (activations as IEEE half, `_h` suffix): same argument lists

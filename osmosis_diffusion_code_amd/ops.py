@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, GemmDesc, PhysDesc, call, current_stream_ptr, ptr, query
+from ._lib import AttnDesc, ConvDesc, GemmDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
 
 
 @dataclass
@@ -548,3 +548,40 @@ def ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, gr
 def ps_loss_grad_c(x0, y, part, loss, g, B, Cc, HW):
     """loss[b] = ||y[b] - x0[b, 0:3]||, g = d loss / d x0 (zero beyond channel 2); part: fp32 [B * phys_nblk(HW)] workspace."""
     call("osm_ps_loss_grad_c", ptr(x0), ptr(y), ptr(part), ptr(loss), ptr(g), B, Cc, HW, _s(), keep=(x0, y, part, loss, g))
+
+
+RECON_MODES = {"bilinear": 0, "joint_bilateral": 1}
+
+
+def recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, rgb, rgb_u8=None, depth_full=None,
+                  mode=0, radius=2, sigma_s=1.0, sigma_r=0.1):
+    """rgb [3,Hc,Wc] = exp(phi_a D) (image - phi_inf (1 - exp(-phi_b D))), D = convert_depth(raw depth [h,w] upsampled to the
+    image's grid) (osm_recon_fullres).  guide [3,h,w] and image [3,Hc,Wc] in [0,1]; phi_*: fp32 [3]; amap = (ay, by, ax, bx):
+    image pixel (i, j) -> network-grid coordinate (ay i + by, ax j + bx); mode 0 bilinear, 1 joint bilateral upsampling.
+    Optional outputs: rgb_u8 [Hc,Wc,3] uint8 (truncated), depth_full [Hc,Wc] (the upsampled raw depth)."""
+    h, w = depth.shape[-2:]
+    Hc, Wc = image.shape[-2:]
+    f32 = [depth, guide, image, phi_a, phi_b, phi_inf, rgb] + ([depth_full] if depth_full is not None else [])
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in f32):
+        raise _lib.OsmosisHipError("recon_fullres takes contiguous fp32 tensors")
+    if (depth.numel() != h * w or tuple(guide.shape) != (3, h, w) or image.dim() != 3 or image.shape[0] != 3
+            or tuple(rgb.shape) != (3, Hc, Wc) or min(phi_a.numel(), phi_b.numel(), phi_inf.numel()) < 3):
+        raise _lib.OsmosisHipError("recon_fullres: expected depth [h,w], guide [3,h,w], image / rgb [3,Hc,Wc], phi [3]")
+    if depth_full is not None and tuple(depth_full.shape) != (Hc, Wc):
+        raise _lib.OsmosisHipError("recon_fullres: depth_full must be [Hc,Wc]")
+    u8p = None
+    if rgb_u8 is not None:
+        if not rgb_u8.is_cuda or rgb_u8.dtype != torch.uint8 or not rgb_u8.is_contiguous() or tuple(rgb_u8.shape) != (Hc, Wc, 3):
+            raise _lib.OsmosisHipError("recon_fullres: rgb_u8 must be a contiguous CUDA(HIP) uint8 [Hc,Wc,3] tensor")
+        u8p = rgb_u8.data_ptr()
+    d = ReconDesc()
+    d.depth, d.guide, d.image = ptr(depth), ptr(guide), ptr(image)
+    d.phi_a, d.phi_b, d.phi_inf = ptr(phi_a), ptr(phi_b), ptr(phi_inf)
+    d.rgb, d.rgb_u8, d.depth_full = ptr(rgb), u8p, ptr(depth_full)
+    d.h, d.w, d.Hc, d.Wc = h, w, Hc, Wc
+    d.depth_type = int(depth_type)
+    for i in range(3):
+        d.dval[i] = float(dval[i])
+    d.ay, d.by, d.ax, d.bx = (float(v) for v in amap)
+    d.mode, d.radius, d.sigma_s, d.sigma_r = int(mode), int(radius), float(sigma_s), float(sigma_r)
+    call("osm_recon_fullres", C.byref(d), _s(), keep=(d, depth, guide, image, phi_a, phi_b, phi_inf, rgb, rgb_u8, depth_full))

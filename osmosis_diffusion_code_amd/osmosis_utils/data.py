@@ -13,6 +13,7 @@ Host-side code; the sampler takes the resulting [B,3,256,256] tensor in [-1, 1].
 import glob
 import os
 import re
+from dataclasses import dataclass
 from os.path import join as pjoin
 
 import numpy as np
@@ -88,6 +89,78 @@ def default_transform(size=256):
     """osmosis_sampling.py:46-49."""
     def apply(pic):
         return normalize(center_crop(resize(to_tensor(pic), size), [size, size]))
+    return apply
+
+
+# ----------------------------------------------------------------------------- geometry of the transform chain
+@dataclass(frozen=True)
+class Geometry:
+    """Where the network grid sits in the original photo (`transform_geometry`).
+
+    An original pixel centre (i, j) has the network-grid coordinate v = (ay * i + by, ax * j + bx); the covered rectangle
+    [y0, y0 + Hc) x [x0, x0 + Wc) holds exactly the original pixels whose v lies in [-0.5, h - 0.5) x [-0.5, w - 0.5)."""
+    H0: int
+    W0: int
+    nh: int          # size after Resize
+    nw: int
+    top: int         # crop window in resized pixels
+    left: int
+    h: int           # network grid
+    w: int
+    ay: float
+    by: float
+    ax: float
+    bx: float
+    y0: int          # covered rectangle in original pixels
+    x0: int
+    Hc: int
+    Wc: int
+
+    def rect_map(self):
+        """(ay, by, ax, bx) for indices counted from the covered rectangle's corner instead of the photo's."""
+        return self.ay, self.ay * self.y0 + self.by, self.ax, self.ax * self.x0 + self.bx
+
+
+def _covered(n0, n, lo, length):
+    """Original indices i in [0, n0) with lo <= (i + 0.5) * n / n0 < lo + length, in integers: (first, count)."""
+    first = max(0, -((n - 2 * lo * n0) // (2 * n)))                  # ceil((2 lo n0 - n) / (2 n))
+    end = min(n0, -((n - 2 * (lo + length) * n0) // (2 * n)))
+    return first, max(0, end - first)
+
+
+def transform_geometry(H0, W0, size=256, crop="center", multiple=32):
+    """The geometry of Resize(size) -> CenterCrop on an H0 x W0 photo, in the arithmetic of `resize` / `center_crop` (int()
+    truncation of the long edge, round() of the crop offset).  crop="center": the [size, size] crop of `default_transform`;
+    crop="fit": the whole resized image, each side center-cropped down to the largest multiple of `multiple` (what the engine
+    accepts).  Raises ValueError when the network grid would be finer than the photo: the full-resolution path only upsamples."""
+    H0, W0, size = int(H0), int(W0), int(size)
+    short, long_ = (W0, H0) if W0 <= H0 else (H0, W0)
+    new_long = int(size * long_ / short)
+    nw, nh = (size, new_long) if W0 <= H0 else (new_long, size)
+    if nh > H0 or nw > W0:
+        raise ValueError(f"a {H0} x {W0} image is coarser than its {nh} x {nw} network grid: nothing to upsample")
+    if crop == "center":
+        h = w = size
+    elif crop == "fit":
+        h, w = nh // multiple * multiple, nw // multiple * multiple
+    else:
+        raise ValueError(f"crop must be 'center' or 'fit', got {crop!r}")
+    if h < 1 or w < 1 or h > nh or w > nw:
+        raise ValueError(f"a {h} x {w} crop does not fit the {nh} x {nw} resized image")
+    top, left = int(round((nh - h) / 2.0)), int(round((nw - w) / 2.0))
+    ay, ax = nh / H0, nw / W0
+    y0, Hc = _covered(H0, nh, top, h)
+    x0, Wc = _covered(W0, nw, left, w)
+    return Geometry(H0, W0, nh, nw, top, left, h, w, ay, 0.5 * ay - 0.5 - top, ax, 0.5 * ax - 0.5 - left, y0, x0, Hc, Wc)
+
+
+def fit_transform(size=256, multiple=32):
+    """ToTensor -> Resize(size) -> center crop to multiples of `multiple` -> Normalize: the whole photo instead of its central
+    square.  Returns a function pic -> (tensor [3,h,w] in [-1,1], Geometry)."""
+    def apply(pic):
+        t = to_tensor(pic)
+        geo = transform_geometry(t.shape[-2], t.shape[-1], size, "fit", multiple)
+        return normalize(center_crop(resize(t, size), [geo.h, geo.w])), geo
     return apply
 
 

@@ -11,6 +11,11 @@
 
     load_config(path)                       the YAML file -> that dictionary (osmosis_utils/utils.py:357-360,466-476)
     save_outputs(post, out_dir, name, ...)  the files the reference writes per image (osmosis_sampling.py:319-353)
+
+Beyond the reference (which only ever writes 256 x 256 results):
+
+    reconstruct_full_resolution(post, original, geometry, operator_cfg, ...)
+                                            the physical model inverted on the ORIGINAL pixel grid from phi and the upsampled depth
 """
 import os
 
@@ -153,13 +158,15 @@ def output_images(post, ref_img, gt_rgb_01=None, gt_depth_01=None):
 
 
 def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, save_grids=True, gt_rgb_01=None,
-                 gt_depth_01=None, rgb_guidance=None):
+                 gt_depth_01=None, rgb_guidance=None, full_res=None):
     """Writes what the reference writes for one image (osmosis_sampling.py:84-104 directory layout, :319-353 files):
     `<out_dir>/single_images/{input,rgb,depth_color,depth_raw}/<name>.png` and `<out_dir>/grid_results/<name>_g<ii>_grid.png`.
     Returns {kind: path}.  (`<name>_process.png` is written by the sampler itself when `record` is on.)
     A result of the rgb-guidance branch (`restore_image` with `rgb_guidance: True`: the dict carries `sample`, no phi; override
     with `rgb_guidance=`) is written as the reference's second branch writes it (:382-401): the same four single images -- the
-    min-max depth as a three-channel PNG, it is `depth.repeat(3, 1, 1)` there -- and the grid as `<name>.png`."""
+    min-max depth as a three-channel PNG, it is `depth.repeat(3, 1, 1)` there -- and the grid as `<name>.png`.
+    `full_res` (a result of `reconstruct_full_resolution`) adds `<out_dir>/full_resolution/<name>_recon_full.png` and
+    `<name>_depth_full.png` (viridis of the percentile-normalised full-resolution depth); without it nothing else is written."""
     if rgb_guidance is None:
         rgb_guidance = "sample" in post and "phi" not in post
     from PIL import Image
@@ -176,7 +183,81 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         os.makedirs(d, exist_ok=True)
         paths["grid"] = os.path.join(d, f"{name}.png" if rgb_guidance else f"{name}_g{global_ii}_grid.png")
         Image.fromarray(imgs["grid"], mode="RGB").save(paths["grid"])
+    if full_res is not None:
+        d = os.path.join(out_dir, "full_resolution")
+        os.makedirs(d, exist_ok=True)
+        paths["recon_full"] = os.path.join(d, f"{name}_recon_full.png")
+        Image.fromarray(full_res["rgb_recon_full_u8"].numpy(), mode="RGB").save(paths["recon_full"])
+        paths["depth_full"] = os.path.join(d, f"{name}_depth_full.png")
+        Image.fromarray(full_depth_color_u8(full_res), mode="RGB").save(paths["depth_full"])
     return paths
+
+
+def full_depth_color_u8(full_res):
+    """uint8 [Hc,Wc,3] viridis of the percentile-normalised full-resolution depth (the helpers and percentiles of `depth_color`)."""
+    d = full_res["depth_full"].unsqueeze(0)
+    if d.numel() <= 1 << 24:
+        pmm = utilso.min_max_norm_range_percentile(d, vmin=0, vmax=1, percent_low=0.03, percent_high=0.99, is_uint8=False)
+    else:       # torch.quantile stops at 2^24 elements (a 16.7-megapixel photo): the same quantiles from exact order statistics
+        flat = d.reshape(-1)
+
+        def quantile(q):
+            pos = q * (flat.numel() - 1)
+            k = int(pos)
+            lo = flat.kthvalue(k + 1)[0]
+            return lo + (flat.kthvalue(min(k + 2, flat.numel()))[0] - lo) * (pos - k)
+        pmm = utilso.min_max_norm_range(torch.clamp(d, quantile(0.03), quantile(0.99)), vmin=0, vmax=1)
+    return _to_pil_u8(utilso.depth_tensor_to_color_image(pmm))
+
+
+UPSAMPLE_MODES = {"bilinear": 0, "joint_bilateral": 1}
+
+
+def reconstruct_full_resolution(post, original, geometry, operator_cfg, upsample="bilinear", device=None, radius=2,
+                                sigma_s=1.0, sigma_r=0.1):
+    """`rgb_recon` at the photo's own resolution: exp(phi_a D) (I - phi_inf (1 - exp(-phi_b D))) with I = the ORIGINAL image and
+    D = convert_depth of the network's depth map upsampled to the original pixel grid (one HIP kernel, osm_recon_fullres).
+
+    post: a result dict of `postprocess` / `restore_image` (its `pred_xstart`, `phi` and `measurement` are read, image 0);
+    original: the `to_tensor` photo [3,H0,W0] in [0,1], used as the 256-class path uses `ref_img` (no degamma);
+    geometry: `data.transform_geometry(H0, W0, ...)` of the transform that produced the sampler's input;
+    upsample: "bilinear", or "joint_bilateral" (joint bilateral upsampling guided by the photo; `radius`, `sigma_s` in network
+    pixels, `sigma_r` in [0,1] intensity -- parameters, not tuned values).
+    Returns CPU tensors: rgb_recon_full [3,Hc,Wc] (unclipped), rgb_recon_full_u8 [Hc,Wc,3], depth_full [Hc,Wc] (raw network depth)
+    and `rect` = (y0, x0, Hc, Wc), the covered rectangle of the photo.  At identity geometry rgb_recon_full is `rgb_recon`."""
+    from . import ops
+    if upsample not in UPSAMPLE_MODES:
+        raise ValueError(f"upsample must be one of {sorted(UPSAMPLE_MODES)}, got {upsample!r}")
+    x0 = post["pred_xstart"]
+    device = device if device is not None else (x0.device if x0.is_cuda else "cuda")
+    h, w = x0.shape[-2:]
+    if (h, w) != (geometry.h, geometry.w):
+        raise ValueError(f"the result is {h} x {w} but the geometry describes a {geometry.h} x {geometry.w} network grid")
+    if original.dim() != 3 or tuple(original.shape) != (3, geometry.H0, geometry.W0):
+        raise ValueError(f"original must be [3,{geometry.H0},{geometry.W0}], got {tuple(original.shape)}")
+    name = operator_cfg["name"]
+    phi = post["phi"]
+    if "underwater_physical_revised" in name:
+        pa, pb = phi["phi_a"], phi["phi_b"]
+    elif "haze" in name or "underwater_physical" in name:
+        pa = pb = phi["phi_ab"]
+    else:
+        raise NotImplementedError("Operator can be for 'underwater' or 'haze' ")
+
+    def vec3(p):        # image 0 of [B,3,1,1] / [B,1,1,1] -> fp32 [3] on the device
+        return p.detach().to(device=device, dtype=torch.float32)[0].reshape(-1).expand(3).contiguous()
+    code, dval = utilso.depth_code_and_values(operator_cfg["depth_type"], operator_cfg["value"])
+    y0, xl, Hc, Wc = geometry.y0, geometry.x0, geometry.Hc, geometry.Wc
+    image = original[:, y0:y0 + Hc, xl:xl + Wc].to(device=device, dtype=torch.float32).contiguous()
+    depth = x0[0, -1].detach().to(device=device, dtype=torch.float32).contiguous()
+    guide = (0.5 * (post["measurement"][0].detach().to(device=device, dtype=torch.float32) + 1)).contiguous()
+    rgb = torch.empty((3, Hc, Wc), device=device, dtype=torch.float32)
+    u8 = torch.empty((Hc, Wc, 3), device=device, dtype=torch.uint8)
+    full = torch.empty((Hc, Wc), device=device, dtype=torch.float32)
+    ops.recon_fullres(depth, guide, image, vec3(pa), vec3(pb), vec3(phi["phi_inf"]), code, dval, geometry.rect_map(), rgb, u8, full,
+                      UPSAMPLE_MODES[upsample], radius, sigma_s, sigma_r)
+    return {"rgb_recon_full": rgb.cpu(), "rgb_recon_full_u8": u8.cpu(), "depth_full": full.cpu(), "rect": (y0, xl, Hc, Wc),
+            "upsample": upsample}
 
 
 def depth_color(post):
@@ -264,13 +345,19 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
     return outs
 
 
-def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, **loop_kwargs):
+def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
+                   geometries=None, full_res_upsample="bilinear", **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
     `batch_size` > 1 carries that many of this rank's images per pass (BASELINE config 4: 8 images per GPU): they
     are independent chains with per-image phi, per-image reductions and -- like the reference's per-image
-    `manual_seed` -- the same x_T / noise stream each, so image i's result is the one a batch-1 run gives."""
+    `manual_seed` -- the same x_T / noise stream each, so image i's result is the one a batch-1 run gives.
+
+    `originals` (list of `to_tensor` photos [3,H0,W0]) with `geometries` (their `data.Geometry`) attaches
+    `reconstruct_full_resolution(..., upsample=full_res_upsample)` to every result that carries phi, under `full_res`."""
+    if (originals is None) != (geometries is None):
+        raise ValueError("originals and geometries go together")
     out = {}
     mine = shard_indices(len(images), rank, world)
     for k in range(0, len(mine), max(1, batch_size)):
@@ -291,5 +378,8 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
         for i, r in zip(idxs, res):
             if gt_rgb is not None:
                 r["psnr"] = float(utilso.psnr(r["rgb_01_clip"], gt_rgb[i]))
+            if originals is not None and "phi" in r:
+                r["full_res"] = reconstruct_full_resolution(r, originals[i], geometries[i], cfg["measurement"]["operator"],
+                                                            upsample=full_res_upsample, device=device)
             out[i] = r
     return out

@@ -21,6 +21,9 @@ registered for the "cuda" device type only, which is HIP on ROCm).
     osmosis::phys_loss_grad(x0, y, phi, icfg, fcfg, n_inner, freeze_phi) -> (loss, grad_x0, phi_new)
                                                            measurements.py forward models + the inner phi optimisation
                                                            (cm.py:141-184), functional (phi is returned, not updated in place)
+    osmosis::recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, mode, radius, sigma_s, sigma_r)
+                                                           -> (rgb, rgb_u8, depth_full): the physical model inverted on the ORIGINAL
+                                                           pixel grid from phi and the upsampled depth (osmosis_sampling.py:253-255)
 
 `engine` is an integer handle (`engine_handle(eng)`) because operator schemas carry tensors and scalars only; the handle
 table holds weak references, so an engine dies with its model.  An engine keeps the activations of its LAST forward pass:
@@ -448,6 +451,34 @@ def _ps_loss_grad_c_fake(x0, y):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
 
 
+@torch.library.custom_op("osmosis::recon_fullres", mutates_args=(), device_types="cuda")
+def recon_fullres(depth: torch.Tensor, guide: torch.Tensor, image: torch.Tensor, phi_a: torch.Tensor, phi_b: torch.Tensor,
+                  phi_inf: torch.Tensor, depth_type: int, dval: List[float], amap: List[float], mode: int = 0, radius: int = 2,
+                  sigma_s: float = 1.0, sigma_r: float = 0.1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The physical model inverted on the original pixel grid (osm_recon_fullres): raw network depth [h,w], guide [3,h,w] (the image
+    the sampler saw, [0,1]), image [3,Hc,Wc] (the photo's covered rectangle, [0,1]), phi_a / phi_b / phi_inf [3], depth_type / dval
+    from utils.depth_code_and_values, amap = [ay, by, ax, bx] (image pixel -> network-grid coordinate), mode 0 bilinear / 1 joint
+    bilateral upsampling -> (rgb [3,Hc,Wc] fp32 unclipped, rgb_u8 [Hc,Wc,3] uint8 truncated, depth_full [Hc,Wc] raw depth)."""
+    if len(dval) != 3 or len(amap) != 4:
+        raise OsmosisHipError("osmosis::recon_fullres: dval has 3 entries, amap 4")
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise OsmosisHipError("osmosis::recon_fullres: image must be [3,Hc,Wc]")
+    Hc, Wc = image.shape[1], image.shape[2]
+    rgb = torch.empty((3, Hc, Wc), device=image.device, dtype=torch.float32)
+    u8 = torch.empty((Hc, Wc, 3), device=image.device, dtype=torch.uint8)
+    full = torch.empty((Hc, Wc), device=image.device, dtype=torch.float32)
+    ops.recon_fullres(depth.contiguous(), guide.contiguous(), image.contiguous(), phi_a.contiguous(), phi_b.contiguous(),
+                      phi_inf.contiguous(), depth_type, dval, amap, rgb, u8, full, mode, radius, sigma_s, sigma_r)
+    return rgb, u8, full
+
+
+@recon_fullres.register_fake
+def _recon_fullres_fake(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, mode=0, radius=2, sigma_s=1.0,
+                        sigma_r=0.1):
+    Hc, Wc = image.shape[1], image.shape[2]
+    return (image.new_empty((3, Hc, Wc)), image.new_empty((Hc, Wc, 3), dtype=torch.uint8), image.new_empty((Hc, Wc)))
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
-OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad") + OPS_C
+OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "recon_fullres") + OPS_C

@@ -1,0 +1,198 @@
+"""Full-resolution reconstruction, host side: the geometry of Resize -> CenterCrop (`data.transform_geometry`) against brute
+force through `resize` / `center_crop` themselves, the uncropped `fit_transform`, the C ABI entry, and the files
+`save_outputs(full_res=...)` adds.  No GPU."""
+import ctypes
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+import pytest
+import torch
+
+from osmosis_diffusion_code_amd import _lib, sampling
+from osmosis_diffusion_code_amd.osmosis_utils import data as DT
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (H0, W0): the three shipped samples in both orientations, sizes where int(size * long / short) truncates, squares, an exact
+# multiple, the smallest size that still upsamples, and a panorama
+SIZES = [(653, 900), (900, 653), (913, 1369), (1369, 913), (768, 1024), (1024, 768), (256, 256), (512, 512), (257, 300),
+         (300, 257), (1000, 333), (333, 1000), (4000, 6000), (260, 776), (577, 1862), (719, 431)]
+
+
+def index_image(H0, W0):
+    """channel 0 = row index, channel 1 = column index (float32: exact for these sizes)."""
+    ii = torch.arange(H0, dtype=torch.float32).view(H0, 1).expand(H0, W0)
+    jj = torch.arange(W0, dtype=torch.float32).view(1, W0).expand(H0, W0)
+    return torch.stack([ii, jj], 0).contiguous()
+
+
+def brute_rect(n0, n, lo, length):
+    """original indices whose network coordinate v = (i + 1/2) n / n0 - 1/2 - lo lies in [-1/2, length - 1/2), exactly."""
+    inside = [i for i in range(n0)
+              if Fraction(-1, 2) <= Fraction(2 * i + 1, 2) * Fraction(n, n0) - Fraction(1, 2) - lo < Fraction(2 * length - 1, 2)]
+    assert inside == list(range(inside[0], inside[-1] + 1))
+    return inside[0], len(inside)
+
+
+@pytest.mark.parametrize("crop", ["center", "fit"])
+@pytest.mark.parametrize("H0,W0", SIZES)
+def test_transform_geometry_against_resize_and_center_crop(H0, W0, crop):
+    geo = DT.transform_geometry(H0, W0, 256, crop)
+    img = index_image(H0, W0)
+    res = DT.resize(img, 256)
+    assert tuple(res.shape[-2:]) == (geo.nh, geo.nw) and min(geo.nh, geo.nw) == 256
+    if crop == "fit":
+        assert geo.h % 32 == 0 and geo.w % 32 == 0 and geo.h <= geo.nh and geo.w <= geo.nw
+        assert geo.nh - geo.h < 32 and geo.nw - geo.w < 32
+    else:
+        assert (geo.h, geo.w) == (256, 256)
+    cut = DT.center_crop(res, [geo.h, geo.w])
+    assert tuple(cut.shape[-2:]) == (geo.h, geo.w)
+    # the crop window: the only offset at which the resized index image reproduces the crop (rows / columns are strictly increasing)
+    tops = [t for t in range(geo.nh - geo.h + 1) if torch.equal(res[0, t:t + geo.h, 0], cut[0, :, 0])]
+    lefts = [l for l in range(geo.nw - geo.w + 1) if torch.equal(res[1, 0, l:l + geo.w], cut[1, 0, :])]
+    assert tops == [geo.top] and lefts == [geo.left]
+    # the affine map inverts what `resize` sampled: network pixel r holds original coordinate u with ay u + by = r
+    u, v = cut[0, :, 0].double(), cut[1, 0, :].double()
+    ry, rx = torch.arange(geo.h, dtype=torch.float64), torch.arange(geo.w, dtype=torch.float64)
+    iy, ix = (u > 0) & (u < H0 - 1), (v > 0) & (v < W0 - 1)            # away from the border clamp of the interpolation
+    assert iy.sum() >= geo.h - 2 and ix.sum() >= geo.w - 2
+    assert float((geo.ay * u + geo.by - ry)[iy].abs().max()) < 2e-3 * max(1.0, H0 / 4096)
+    assert float((geo.ax * v + geo.bx - rx)[ix].abs().max()) < 2e-3 * max(1.0, W0 / 4096)
+    # the covered rectangle, exactly
+    assert (geo.y0, geo.Hc) == brute_rect(H0, geo.nh, geo.top, geo.h)
+    assert (geo.x0, geo.Wc) == brute_rect(W0, geo.nw, geo.left, geo.w)
+    ay, by, ax, bx = geo.rect_map()
+    assert -0.5 <= by < -0.5 + geo.ay + 1e-9 and -0.5 <= ay * (geo.Hc - 1) + by < geo.h - 0.5
+    assert -0.5 <= bx < -0.5 + geo.ax + 1e-9 and -0.5 <= ax * (geo.Wc - 1) + bx < geo.w - 0.5
+
+
+def test_geometry_examples_and_errors():
+    g = DT.transform_geometry(900, 653, crop="fit")
+    assert (g.nh, g.nw, g.h, g.w) == (352, 256, 352, 256) and (g.y0, g.x0, g.Hc, g.Wc) == (0, 0, 900, 653)
+    g = DT.transform_geometry(1369, 913, crop="fit")
+    assert (g.nh, g.nw, g.h, g.w, g.top) == (383, 256, 352, 256, 16)
+    g = DT.transform_geometry(256, 256)
+    assert g.rect_map() == (1.0, 0.0, 1.0, 0.0) and (g.Hc, g.Wc) == (256, 256)
+    with pytest.raises(ValueError, match="coarser"):
+        DT.transform_geometry(200, 300)
+    with pytest.raises(ValueError):
+        DT.transform_geometry(900, 653, crop="none")
+
+
+@pytest.mark.parametrize("H0,W0", [(653, 900), (1369, 913), (300, 257)])
+def test_center_geometry_is_the_default_transform_and_fit_keeps_the_whole_image(H0, W0):
+    from PIL import Image
+    rng = np.random.default_rng(H0)
+    pic = Image.fromarray(rng.integers(0, 256, (H0, W0, 3), dtype=np.uint8), mode="RGB")
+    geo = DT.transform_geometry(H0, W0, 256, "center")
+    out = DT.default_transform(256)(pic)
+    assert tuple(out.shape) == (3, geo.h, geo.w)
+    res = DT.normalize(DT.resize(DT.to_tensor(pic), 256))
+    assert torch.equal(out, res[:, geo.top:geo.top + geo.h, geo.left:geo.left + geo.w])
+    t, fit = DT.fit_transform(256)(pic)
+    assert fit == DT.transform_geometry(H0, W0, 256, "fit") and tuple(t.shape) == (3, fit.h, fit.w)
+    assert torch.equal(t, res[:, fit.top:fit.top + fit.h, fit.left:fit.left + fit.w])
+    assert fit.Hc >= geo.Hc and fit.Wc >= geo.Wc and fit.Hc * fit.Wc > geo.Hc * geo.Wc      # more of the photo than the central square
+
+
+def test_recon_entry_is_exported_declared_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_hip.h")).read()
+    assert re.search(r"\bint\s+osm_recon_fullres\s*\(\s*const\s+osm_recon_desc\s*\*", hdr)
+    assert "osm_recon_fullres" in _lib.EXPORTS
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    assert hasattr(lib, "osm_recon_fullres")
+    # header and exports still agree one for one
+    declared = set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", hdr)) - {"osm_status"}
+    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    # the descriptor's layout is the C struct's: 9 pointers, 5 ints + 3 floats, 4 doubles, 2 ints + 2 floats
+    assert ctypes.sizeof(_lib.ReconDesc) == 9 * 8 + 8 * 4 + 4 * 8 + 4 * 4
+    assert _lib.ReconDesc.ay.offset == 104 and _lib.ReconDesc.mode.offset == 136
+
+
+def test_recon_entry_validates_its_arguments_without_a_gpu():
+    lib = _lib.load()
+    assert lib.osm_recon_fullres(None, None) != 0 and b"null pointer" in lib.osm_last_error()
+    d = _lib.ReconDesc()
+    for f in ("depth", "guide", "image", "phi_a", "phi_b", "phi_inf", "rgb"):
+        setattr(d, f, 4096)                 # never dereferenced: validation fails first
+    d.h, d.w, d.Hc, d.Wc, d.depth_type = 8, 8, 16, 16, 0
+    d.ay, d.by, d.ax, d.bx = 0.5, -0.25, 0.5, -0.25
+    d.mode, d.radius, d.sigma_s, d.sigma_r = 1, 2, 1.0, 0.1
+    for field, bad, msg in [("mode", 2, b"mode"), ("radius", 0, b"radius"), ("radius", 5, b"radius"), ("sigma_r", 0.0, b"sigma"),
+                            ("sigma_s", -1.0, b"sigma"), ("ay", 1.5, b"scale"), ("ax", 0.0, b"scale"), ("depth_type", 3, b"depth_type"),
+                            ("Wc", 0, b"rectangle"), ("h", 0, b"grid"), ("bx", float("nan"), b"finite")]:
+        good = getattr(d, field)
+        setattr(d, field, bad)
+        assert lib.osm_recon_fullres(ctypes.byref(d), None) != 0, field
+        assert msg in lib.osm_last_error(), (field, lib.osm_last_error())
+        setattr(d, field, good)
+
+
+def test_operator_is_registered_and_has_no_cpu_path():
+    from osmosis_diffusion_code_amd import ops, torch_ops
+    assert "recon_fullres" in torch_ops.OPS
+    schema = str(torch.ops.osmosis.recon_fullres.default._schema)
+    assert schema.startswith("osmosis::recon_fullres(Tensor depth, Tensor guide, Tensor image, Tensor phi_a, Tensor phi_b, Tensor phi_inf")
+    assert schema.endswith("-> (Tensor, Tensor, Tensor)")
+    z = torch.zeros
+    with pytest.raises((NotImplementedError, RuntimeError)):
+        torch.ops.osmosis.recon_fullres(z(8, 8), z(3, 8, 8), z(3, 16, 16), z(3), z(3), z(3), 0, [0.0, 1.0, 1.0], [0.5, -0.25, 0.5, -0.25])
+    with pytest.raises(_lib.OsmosisHipError, match="no CPU fallback"):
+        ops.recon_fullres(z(8, 8), z(3, 8, 8), z(3, 16, 16), z(3), z(3), z(3), 0, [0.0, 1.0, 1.0], (0.5, -0.25, 0.5, -0.25), z(3, 16, 16))
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    with FakeTensorMode():
+        e = lambda *s: torch.empty(*s, device="cuda")
+        rgb, u8, full = torch.ops.osmosis.recon_fullres(e(8, 8), e(3, 8, 8), e(3, 16, 19), e(3), e(3), e(3), 1, [1.4, 1.4, 1.0],
+                                                        [0.5, -0.25, 0.5, -0.25], 1)
+        assert rgb.shape == (3, 16, 19) and u8.shape == (16, 19, 3) and u8.dtype == torch.uint8 and full.shape == (16, 19)
+
+
+def _post_case():
+    g = torch.Generator().manual_seed(2)
+    x0 = torch.randn(1, 4, 16, 12, generator=g) * 0.6
+    ref = torch.rand(1, 3, 16, 12, generator=g) * 1.6 - 0.8
+    phi = {"phi_ab": torch.tensor([1.0, 0.9, 0.8]).view(1, 3, 1, 1), "phi_inf": torch.tensor([0.2, 0.4, 0.5]).view(1, 3, 1, 1)}
+    op = dict(name="underwater_physical", depth_type="gamma", value="1.4,1.4,1")
+    return sampling.postprocess(x0, phi, ref, op), ref, g
+
+
+def test_save_outputs_writes_the_full_resolution_files_only_when_asked(tmp_path):
+    from PIL import Image
+    post, ref, g = _post_case()
+    full = {"rgb_recon_full": torch.rand(3, 40, 31, generator=g), "depth_full": torch.rand(40, 31, generator=g) * 2 - 1,
+            "rgb_recon_full_u8": (torch.rand(40, 31, 3, generator=g) * 255).to(torch.uint8), "rect": (0, 0, 40, 31)}
+
+    def files(root):
+        return sorted(os.path.relpath(os.path.join(dp, f), root) for dp, _, fs in os.walk(root) for f in fs)
+    plain = sampling.save_outputs(post, ref, str(tmp_path / "a"), "img")
+    assert sorted(plain) == ["depth_color", "depth_raw", "grid", "input", "rgb"]
+    paths = sampling.save_outputs(post, ref, str(tmp_path / "b"), "img", full_res=full)
+    assert sorted(paths) == ["depth_color", "depth_full", "depth_raw", "grid", "input", "recon_full", "rgb"]
+    extra = sorted(set(files(tmp_path / "b")) - set(files(tmp_path / "a")))
+    assert extra == [os.path.join("full_resolution", "img_depth_full.png"), os.path.join("full_resolution", "img_recon_full.png")]
+    assert set(files(tmp_path / "a")) <= set(files(tmp_path / "b"))
+    for k in plain:                                      # today's files, byte for byte
+        assert open(plain[k], "rb").read() == open(paths[k], "rb").read(), k
+    assert np.array_equal(np.asarray(Image.open(paths["recon_full"])), full["rgb_recon_full_u8"].numpy())
+    dcol = np.asarray(Image.open(paths["depth_full"]))
+    assert dcol.shape == (40, 31, 3) and np.array_equal(dcol, sampling.full_depth_color_u8(full))
+    from osmosis_diffusion_code_amd.osmosis_utils import utils as U
+    pmm = U.min_max_norm_range_percentile(full["depth_full"].unsqueeze(0), 0, 1, 0.03, 0.99)
+    assert np.array_equal(dcol, sampling._to_pil_u8(U.depth_tensor_to_color_image(pmm)))
+
+
+def test_reconstruct_full_resolution_rejects_mismatched_inputs():
+    post, ref, g = _post_case()
+    post.update(pred_xstart=torch.zeros(1, 4, 16, 12), measurement=ref)
+    op = dict(name="underwater_physical", depth_type="gamma", value="1.4,1.4,1")
+    geo = DT.transform_geometry(512, 512)
+    with pytest.raises(ValueError, match="network grid"):
+        sampling.reconstruct_full_resolution(post, torch.zeros(3, 512, 512), geo, op)
+    with pytest.raises(ValueError, match="upsample"):
+        sampling.reconstruct_full_resolution(post, torch.zeros(3, 512, 512), geo, op, upsample="bicubic")
+    with pytest.raises(ValueError, match="together"):
+        sampling.restore_images(None, [], {}, originals=[])
