@@ -376,6 +376,25 @@ int osm_phys_grad(const osm_phys_desc* d, const float* x0, const float* y, const
 int osm_phys_optimize(const osm_phys_desc* d, const float* x0, const float* y, float* phi, float* part, float* red,
                       float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream);
 
+/* Per-pixel validity mask in the data term.  mask: device float [B,3,HW] in [0, 1], laid out like y (0 ignore, 1 trust fully,
+ * fractions are confidences).  The residual of channel c becomes (y_c - (2 I_c - 1)) w M_c (kind 3: M_c (y_c - x0_c)); the loss
+ * keeps its normalisation (mse still divides by 3 HW, so M = 1 is the unmasked loss); dL/dphi and dL/dx0 carry M_c twice; the
+ * auxiliary losses act on the prediction and are not masked.  mask == NULL: the plain entry point's launches, bit for bit.
+ * An image whose every pixel is masked out (sum r^2 = 0, norm loss): the data term has no gradient and does not step phi --
+ * osm_phys_finalize_m with masked != 0 applies that guard (masked = 0: osm_phys_finalize), osm_phys_grad_m applies it whenever
+ * mask != NULL, osm_phys_optimize_m passes masked = (mask != NULL). */
+int osm_phys_reduce_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                      float* part, void* stream);
+int osm_phys_finalize_m(const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
+                        float* loss_out, float* opt_state, int masked, void* stream);
+int osm_phys_grad_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                    const float* red, float* g, void* stream);
+int osm_phys_optimize_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi, float* part,
+                        float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream);
+/* mask_out[B,3,HW] from the exposure of y [B,3,HW] in [-1, 1], v = (y + 1) / 2: soft > 0: clamp((hi - v) / soft, 0, 1) *
+ * clamp((v - lo) / soft, 0, 1); soft = 0: [lo < v < hi]; per_pixel != 0: every channel gets the minimum of the three. */
+int osm_exposure_mask(const float* y, float lo, float hi, float soft, int per_pixel, float* mask_out, int B, int HW, void* stream);
+
 /* d_out[B,8,HW]: channels 0..3 = -c1*g, 4..7 = 0   (chain rule through x0 = c0*x - c1*eps) */
 int osm_posterior_bwd(const float* g, const float* coef, float* d_out, int B, int HW, void* stream);
 /* condition_methods.py:211-224 + gaussian_diffusion.py:266-268:
@@ -469,6 +488,10 @@ int osm_ddim_update_c(const float* x0, const float* x, const float* g, const flo
  *   loss[b] = || y[b] - x0[b, 0:3] ||_2 ;  g[b, 0:3] = -(y[b] - x0[b, 0:3]) / loss[b] ;  g[b, 3:] = 0
  * per image, in a fixed reduction order (deterministic).  part: float[B * osm_phys_nblk(HW)] workspace. */
 int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss, float* g, int B, int C, int HW, void* stream);
+/* the same with a mask [B,3,HW] (see osm_phys_reduce_m): loss[b] = ||M (y - x0[0:3])||, g = -M^2 (y - x0) / loss, g = 0 for an
+ * image with loss 0; mask == NULL: osm_ps_loss_grad_c */
+int osm_ps_loss_grad_mc(const float* x0, const float* y, const float* mask, float* part, float* loss, float* g, int B, int C, int HW,
+                        void* stream);
 /* coef_out[8] = table[clamp(*step, 0, n_rows-1)][8]; t_out[b] = coef_out[7]; then *step += delta
  * (graph-replayable; B <= 256) */
 int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out, int B,

@@ -128,6 +128,11 @@ _SIGS = {
     "osm_phys_finalize": [C.POINTER(PhysDesc), _P, _P, _P, _I, _P, _P, _P],
     "osm_phys_grad": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P, _P],
     "osm_phys_optimize": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "osm_phys_reduce_m": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P, _P],
+    "osm_phys_finalize_m": [C.POINTER(PhysDesc), _P, _P, _P, _I, _P, _P, _I, _P],
+    "osm_phys_grad_m": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P, _P, _P],
+    "osm_phys_optimize_m": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "osm_exposure_mask": [_P, _F, _F, _F, _I, _P, _I, _I, _P],
     "osm_posterior_bwd": [_P, _P, _P, _I, _I, _P],
     "osm_guide_update": [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _P],
     "osm_guide_update_rng": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _P],
@@ -145,6 +150,7 @@ _SIGS = {
     "osm_guide_update_rng_c": [_P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
     "osm_ddim_update_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P],
     "osm_ps_loss_grad_c": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "osm_ps_loss_grad_mc": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "osm_recon_fullres": [C.POINTER(ReconDesc), _P],
     "osm_version": [],
 }

@@ -34,20 +34,33 @@ __device__ __forceinline__ float conv_depth(float D, int type, const float* v, f
   return 0.5f * (D + 1.0f);
 }
 
-struct Pix {
+// MASKED: a per-pixel validity / confidence map M [B,3,HW] in [0, 1] (the layout of y) scales the residual: the effective weight of
+// channel c is wm[c] = w M_c wherever the unmasked code uses w (the residual, k2 and dLdI).  The `false` instantiations carry no
+// wm and are the unmasked code.
+template <bool MASKED> struct PixMask { float wm[3]; };
+template <> struct PixMask<false> {};
+
+template <bool MASKED>
+struct Pix : PixMask<MASKED> {
   float rgb[3], D, y[3];
   float d, dd, w;
   float Ea[3], Eb[3], J[3], r[3];
 };
 
+// FMA_I (the masked gradient kernel): J Ea + pinf (1 - Eb) with its one fused multiply-add spelled out -- the contraction the unmasked
+// gradient kernel compiles to on every channel; left to the compiler, the masked kernel's extra multiplies changed what got packed
+// and one channel lost the fusion, so M = 1 was one ulp off the unmasked gradient.
+template <bool MASKED, bool FMA_I = false>
 __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float* __restrict__ x0,
-                                           const float* __restrict__ y, const float* __restrict__ phi,
-                                           int b, int p, Pix& q) {
+                                           const float* __restrict__ y, const float* __restrict__ mask,
+                                           const float* __restrict__ phi, int b, int p, Pix<MASKED>& q) {
   const long long base = (long long)b * 4 * ds.HW + p;
+  float m[3] = {1.f, 1.f, 1.f};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     q.rgb[c] = x0[base + (long long)c * ds.HW];
     q.y[c] = y[(long long)b * 3 * ds.HW + (long long)c * ds.HW + p];
+    if constexpr (MASKED) m[c] = mask[(long long)b * 3 * ds.HW + (long long)c * ds.HW + p];
   }
   q.D = x0[base + 3LL * ds.HW];
   if (ds.kind == 3) {   // identity forward model of the rgb-guidance ('ps') path: I = x0[:, 0:3], unweighted (condition_methods.py:35-41)
@@ -57,6 +70,7 @@ __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float*
       q.Ea[c] = q.Eb[c] = 1.f;
       q.J[c] = 0.5f * (q.rgb[c] + 1.0f);
       q.r[c] = q.y[c] - q.rgb[c];
+      if constexpr (MASKED) { q.wm[c] = m[c]; q.r[c] *= m[c]; }
     }
     return;
   }
@@ -72,13 +86,25 @@ __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float*
     q.Ea[c] = expf(-pa * q.d);
     q.Eb[c] = expf(-pb * q.d);
     q.J[c] = 0.5f * (q.rgb[c] + 1.0f);
-    const float I = q.J[c] * q.Ea[c] + pinf * (1.0f - q.Eb[c]);
-    q.r[c] = (q.y[c] - (2.0f * I - 1.0f)) * q.w;
+    float I;
+    if constexpr (FMA_I) {
+      I = fmaf(q.J[c], q.Ea[c], pinf * (1.0f - q.Eb[c]));
+    } else {
+      I = q.J[c] * q.Ea[c] + pinf * (1.0f - q.Eb[c]);
+    }
+    if constexpr (MASKED) {
+      q.wm[c] = q.w * m[c];
+      q.r[c] = (q.y[c] - (2.0f * I - 1.0f)) * q.wm[c];
+    } else {
+      q.r[c] = (q.y[c] - (2.0f * I - 1.0f)) * q.w;
+    }
   }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, const float* __restrict__ x0,
                                                            const float* __restrict__ y,
+                                                           const float* __restrict__ mask,
                                                            const float* __restrict__ phi,
                                                            float* __restrict__ part, int nblk) {
   __shared__ float red[4][NRED];
@@ -89,12 +115,14 @@ __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, cons
   const int pend = min(ds.HW, (blk + 1) * PPB);
   const float* ph = phi + b * 9;
   for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
-    Pix q;
-    eval_pixel(ds, x0, y, phi, b, p, q);
+    Pix<MASKED> q;
+    eval_pixel<MASKED>(ds, x0, y, mask, phi, b, p, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float pinf = ph[6 + c];
-      const float k2 = -2.0f * q.w * q.r[c];                 // r_c * d r_c / d I_c
+      float wc = q.w;
+      if constexpr (MASKED) wc = q.wm[c];
+      const float k2 = -2.0f * wc * q.r[c];                  // r_c * d r_c / d I_c
       s[0] += q.r[c] * q.r[c];
       s[1 + c] += k2 * (-q.d * q.J[c] * q.Ea[c]);            // d I / d phi_a
       s[4 + c] += k2 * (pinf * q.d * q.Eb[c]);               // d I / d phi_b
@@ -121,7 +149,7 @@ __device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0
 
 __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__ part, float* __restrict__ red,
                                      float* __restrict__ phi, int do_update, float* __restrict__ loss_out,
-                                     float* __restrict__ opt_state, int nblk) {
+                                     float* __restrict__ opt_state, int nblk, int zero_guard) {
   __shared__ double tot[NRED];
   const int b = blockIdx.x;
   {   // one wave: component lane >> 2, four lanes share its nblk partials (fixed order: deterministic), fp64, two shuffle folds
@@ -145,6 +173,9 @@ __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__
     if (ds.loss_type == 0) {
       L = sqrt(tot[0]);
       gscale = 1.0 / L;
+      // masked path, every pixel of the image masked out: the data term has no gradient (torch.linalg.norm's backward at 0) and
+      // does not step phi (no optimizer state moves either)
+      if (zero_guard && tot[0] == 0.0) { gscale = 0.0; do_update = 0; }
     } else {
       L = tot[0] / n;
       gscale = 2.0 / n;
@@ -260,24 +291,32 @@ __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__
   }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void phys_grad_kernel(osm_phys_desc ds, const float* __restrict__ x0,
                                                          const float* __restrict__ y,
+                                                         const float* __restrict__ mask,
                                                          const float* __restrict__ phi,
                                                          const float* __restrict__ red, float* __restrict__ g) {
   const int b = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= ds.HW) return;
-  Pix q;
-  eval_pixel(ds, x0, y, phi, b, p, q);
+  Pix<MASKED> q;
+  eval_pixel<MASKED, MASKED>(ds, x0, y, mask, phi, b, p, q);
   const float* rd = red + b * NRED;
   const float n = 3.0f * (float)ds.HW;
-  const float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / n;
+  float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / n;
+  if constexpr (MASKED) {   // a fully masked image: no data-term gradient (the auxiliary losses, which act on the prediction, remain)
+    if (ds.loss_type == 0 && rd[0] == 0.f) gscale = 0.f;
+  }
   const float* ph = phi + b * 9;
   float gD = 0.f;
   const long long base = (long long)b * 4 * ds.HW + p;
   if (ds.kind == 3) {   // d ||y - x0[:, 0:3]|| / d x0 = -(y - x0) / ||.|| on the colour channels, nothing on depth
 #pragma unroll
-    for (int c = 0; c < 3; ++c) g[base + (long long)c * ds.HW] = -(q.r[c] * gscale);
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (MASKED) g[base + (long long)c * ds.HW] = -(q.wm[c] * (q.r[c] * gscale));
+      else g[base + (long long)c * ds.HW] = -(q.r[c] * gscale);
+    }
     g[base + 3LL * ds.HW] = 0.f;
     return;
   }
@@ -286,7 +325,9 @@ __global__ __launch_bounds__(256) void phys_grad_kernel(osm_phys_desc ds, const 
     const float pa = ds.kind == 2 ? ph[0] : ph[c];
     const float pb = ds.kind == 0 ? ph[3 + c] : pa;
     const float pinf = ph[6 + c];
-    const float dLdI = -2.0f * q.w * (q.r[c] * gscale);
+    float wc = q.w;
+    if constexpr (MASKED) wc = q.wm[c];
+    const float dLdI = -2.0f * wc * (q.r[c] * gscale);
     float grgb = dLdI * 0.5f * q.Ea[c];
     if (ds.gamma_avrg != 0.f) grgb += ds.gamma_avrg * sgn(rd[10 + c]) / (float)ds.HW;
     if (ds.gamma_val != 0.f) {
@@ -620,38 +661,110 @@ int check_desc(const osm_phys_desc* d, const char* who) {
 
 extern "C" int osm_phys_nblk(int HW) { return (HW + PPB - 1) / PPB; }
 
+namespace {
+int phys_reduce_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                       float* part, void* stream) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && y && phi && part, "%s: null pointer", who);
+  const int nblk = osm_phys_nblk(d->HW);
+  if (mask) {
+    hipLaunchKernelGGL(phys_reduce_kernel<true>, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, y, mask, phi, part,
+                       nblk);
+  } else {
+    hipLaunchKernelGGL(phys_reduce_kernel<false>, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, y, nullptr, phi,
+                       part, nblk);
+  }
+  return osm::check_launch("phys_reduce_kernel");
+}
+
+int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
+                         float* loss_out, float* opt_state, int zero_guard, void* stream) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(part && red && phi, "%s: null pointer", who);
+  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+  OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
+  hipLaunchKernelGGL(phys_finalize_kernel, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
+                     do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard);
+  return osm::check_launch("phys_finalize_kernel");
+}
+
+int phys_grad_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                     const float* red, float* g, void* stream) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && y && phi && red && g, "%s: null pointer", who);
+  const dim3 grid((d->HW + 255) / 256, d->B);
+  if (mask) {
+    hipLaunchKernelGGL(phys_grad_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *d, x0, y, mask, phi, red, g);
+  } else {
+    hipLaunchKernelGGL(phys_grad_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *d, x0, y, nullptr, phi, red, g);
+  }
+  return osm::check_launch("phys_grad_kernel");
+}
+
+// n_inner x { reduce; finalize (+ phi step) } + the x0-gradient: the launches of osm_phys_optimize, with or without a mask
+int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi,
+                         float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
+                         void* stream) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && y && phi && part && red && loss_out && g, "%s: null pointer", who);
+  OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
+  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
+  const int zg = mask != nullptr;
+  for (int it = 0; it < n_inner; ++it) {
+    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream))) return rc;
+    if (it == n_inner - 1) {
+      if ((rc = phys_finalize_launch(who, d, part, red, phi, 0, loss_out, nullptr, zg, stream))) return rc;
+      if ((rc = phys_grad_launch(who, d, x0, y, mask, phi, red, g, stream))) return rc;
+      if (!freeze_phi && (rc = phys_finalize_launch(who, d, part, red, phi, 1, nullptr, opt_state, zg, stream))) return rc;
+    } else if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream))) {
+      return rc;
+    }
+  }
+  return OSM_OK;
+}
+}  // namespace
+
 extern "C" int osm_phys_reduce(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
                                float* part, void* stream) {
-  int rc = check_desc(d, "osm_phys_reduce");
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && part, "osm_phys_reduce: null pointer");
-  const int nblk = osm_phys_nblk(d->HW);
-  hipLaunchKernelGGL(phys_reduce_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, y, phi,
-                     part, nblk);
-  return osm::check_launch("phys_reduce_kernel");
+  return phys_reduce_launch("osm_phys_reduce", d, x0, y, nullptr, phi, part, stream);
+}
+
+// The masked entry points (`_m`): mask [B,3,HW] in [0, 1], laid out like y; mask == NULL is the plain entry point, launch for launch.
+extern "C" int osm_phys_reduce_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                                 float* part, void* stream) {
+  return phys_reduce_launch("osm_phys_reduce_m", d, x0, y, mask, phi, part, stream);
+}
+
+extern "C" int osm_phys_finalize_m(const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
+                                   float* loss_out, float* opt_state, int masked, void* stream) {
+  return phys_finalize_launch("osm_phys_finalize_m", d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream);
+}
+
+extern "C" int osm_phys_grad_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                               const float* red, float* g, void* stream) {
+  return phys_grad_launch("osm_phys_grad_m", d, x0, y, mask, phi, red, g, stream);
+}
+
+extern "C" int osm_phys_optimize_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi, float* part,
+                                   float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
+                                   void* stream) {
+  return phys_optimize_launch("osm_phys_optimize_m", d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                              stream);
 }
 
 extern "C" int osm_phys_finalize(const osm_phys_desc* d, const float* part, float* red, float* phi,
                                  int do_update, float* loss_out, float* opt_state, void* stream) {
-  int rc = check_desc(d, "osm_phys_finalize");
-  if (rc) return rc;
-  OSM_REQUIRE(part && red && phi, "osm_phys_finalize: null pointer");
-  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "osm_phys_finalize: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)");
-  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "osm_phys_finalize: a stateful optimizer needs opt_state [B][20]");
-  OSM_REQUIRE(!(d->kind == 3 && do_update), "osm_phys_finalize: the identity operator (kind 3) has no parameters to step");
-  hipLaunchKernelGGL(phys_finalize_kernel, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
-                     do_update, loss_out, opt_state, osm_phys_nblk(d->HW));
-  return osm::check_launch("phys_finalize_kernel");
+  return phys_finalize_launch("osm_phys_finalize", d, part, red, phi, do_update, loss_out, opt_state, 0, stream);
 }
 
 extern "C" int osm_phys_grad(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
                              const float* red, float* g, void* stream) {
-  int rc = check_desc(d, "osm_phys_grad");
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && red && g, "osm_phys_grad: null pointer");
-  hipLaunchKernelGGL(phys_grad_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d,
-                     x0, y, phi, red, g);
-  return osm::check_launch("phys_grad_kernel");
+  return phys_grad_launch("osm_phys_grad", d, x0, y, nullptr, phi, red, g, stream);
 }
 
 // The inner phi optimisation + dL/dx0 of one guided step, enqueued by ONE call (measurements.py:266-303, condition_methods.py:109-144):
@@ -661,22 +774,8 @@ extern "C" int osm_phys_grad(const osm_phys_desc* d, const float* x0, const floa
 //   0.24 ms per step between them).
 extern "C" int osm_phys_optimize(const osm_phys_desc* d, const float* x0, const float* y, float* phi, float* part, float* red,
                                  float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
-  int rc = check_desc(d, "osm_phys_optimize");
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && part && red && loss_out && g, "osm_phys_optimize: null pointer");
-  OSM_REQUIRE(n_inner >= 1, "osm_phys_optimize: n_inner must be >= 1");
-  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "osm_phys_optimize: freeze_phi goes with n_inner = 1");
-  for (int it = 0; it < n_inner; ++it) {
-    if ((rc = osm_phys_reduce(d, x0, y, phi, part, stream))) return rc;
-    if (it == n_inner - 1) {
-      if ((rc = osm_phys_finalize(d, part, red, phi, 0, loss_out, nullptr, stream))) return rc;
-      if ((rc = osm_phys_grad(d, x0, y, phi, red, g, stream))) return rc;
-      if (!freeze_phi && (rc = osm_phys_finalize(d, part, red, phi, 1, nullptr, opt_state, stream))) return rc;
-    } else if ((rc = osm_phys_finalize(d, part, red, phi, 1, loss_out, opt_state, stream))) {
-      return rc;
-    }
-  }
-  return OSM_OK;
+  return phys_optimize_launch("osm_phys_optimize", d, x0, y, nullptr, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                              stream);
 }
 
 extern "C" int osm_posterior_typed(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
@@ -1020,8 +1119,11 @@ __global__ __launch_bounds__(256) void ddim_update_c_kernel(const float* __restr
 
 // 'ps' data term on a C-channel x0 (condition_methods.py:35-41): per image, the partial sums of (y - x0[0:3])^2 in the order of
 // phys_reduce_kernel (PPB pixels per workgroup, wave sums, the four waves pairwise): deterministic
+// MASKED: the residual is M (y - x0[0:3]) with M [B,3,HW] laid out like y
+template <bool MASKED>
 __global__ __launch_bounds__(256) void ps_reduce_c_kernel(const float* __restrict__ x0, const float* __restrict__ y,
-                                                           float* __restrict__ part, int C, int HW, int nblk) {
+                                                           const float* __restrict__ mask, float* __restrict__ part, int C, int HW,
+                                                           int nblk) {
   __shared__ float red[4];
   const int b = blockIdx.y, blk = blockIdx.x;
   const int pend = min(HW, (blk + 1) * PPB);
@@ -1031,7 +1133,8 @@ __global__ __launch_bounds__(256) void ps_reduce_c_kernel(const float* __restric
   for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float r = yb[(long long)c * HW + p] - xb[(long long)c * HW + p];
+      float r = yb[(long long)c * HW + p] - xb[(long long)c * HW + p];
+      if constexpr (MASKED) r *= mask[(long long)b * 3 * HW + (long long)c * HW + p];
       s += r * r;
     }
   }
@@ -1042,7 +1145,10 @@ __global__ __launch_bounds__(256) void ps_reduce_c_kernel(const float* __restric
 }
 
 // loss[b] = sqrt(sum of the image's partials) (fp64, fixed order), g = -(y - x0) / loss on channels 0..2, 0 on any further channel
+// MASKED: g = -M^2 (y - x0) / loss, and 0 for an image whose every pixel is masked out (loss = 0)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void ps_grad_c_kernel(const float* __restrict__ x0, const float* __restrict__ y,
+                                                         const float* __restrict__ mask,
                                                          const float* __restrict__ part, float* __restrict__ loss,
                                                          float* __restrict__ g, int C, int HW, int nblk) {
   __shared__ float tot;
@@ -1060,14 +1166,48 @@ __global__ __launch_bounds__(256) void ps_grad_c_kernel(const float* __restrict_
   __syncthreads();
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= HW) return;
-  const float gscale = 1.0f / sqrtf(tot);
+  float gscale = 1.0f / sqrtf(tot);
+  if constexpr (MASKED) {
+    if (tot == 0.f) gscale = 0.f;
+  }
   const long long base = (long long)b * C * HW + p;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float r = y[(long long)b * 3 * HW + (long long)c * HW + p] - x0[base + (long long)c * HW];
-    g[base + (long long)c * HW] = -(r * gscale);
+    if constexpr (MASKED) {
+      const float m = mask[(long long)b * 3 * HW + (long long)c * HW + p];
+      g[base + (long long)c * HW] = -(m * ((m * r) * gscale));
+    } else {
+      g[base + (long long)c * HW] = -(r * gscale);
+    }
   }
   for (int c = 3; c < C; ++c) g[base + (long long)c * HW] = 0.f;
+}
+
+// validity mask from the exposure of the measurement itself: y [B,3,HW] in [-1, 1], v = (y + 1) / 2 in [0, 1];
+// soft > 0: M_c = clamp((hi - v) / soft, 0, 1) clamp((v - lo) / soft, 0, 1), a ramp of width `soft` inside each bound;
+// soft = 0: M_c = [lo < v < hi].  per_pixel: every channel gets the minimum of the three (a clipped channel invalidates the pixel).
+__global__ __launch_bounds__(256) void exposure_mask_kernel(const float* __restrict__ y, float lo, float hi, float soft, int per_pixel,
+                                                             float* __restrict__ mask, int B, int HW) {
+  const long long total = (long long)B * HW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long b = i / HW, p = i - b * HW;
+    const long long base = b * 3LL * HW + p;
+    float m[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = 0.5f * (y[base + (long long)c * HW] + 1.0f);
+      if (soft > 0.f) {
+        const float a = fminf(fmaxf((hi - v) / soft, 0.f), 1.f), bl = fminf(fmaxf((v - lo) / soft, 0.f), 1.f);
+        m[c] = a * bl;
+      } else {
+        m[c] = (v > lo && v < hi) ? 1.f : 0.f;
+      }
+    }
+    if (per_pixel) m[0] = m[1] = m[2] = fminf(m[0], fminf(m[1], m[2]));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mask[base + (long long)c * HW] = m[c];
+  }
 }
 
 int posterior_c_launch(const char* name, bool raw, const float* model_out, const float* x, const float* coef, int mean_kind,
@@ -1175,15 +1315,40 @@ extern "C" int osm_ddim_update_c(const float* x0, const float* x, const float* g
   return osm::check_launch("ddim_update_c_kernel");
 }
 
-extern "C" int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss, float* g, int B, int C, int HW,
-                                  void* stream) {
-  OSM_REQUIRE(x0 && y && part && loss && g && B > 0 && HW > 0, "osm_ps_loss_grad_c: bad argument");
-  OSM_REQUIRE(C >= 3, "osm_ps_loss_grad_c: the data term reads channels 0..2 of x0, got C = %d", C);
+namespace {
+int ps_loss_grad_launch(const char* who, const float* x0, const float* y, const float* mask, float* part, float* loss, float* g, int B,
+                        int C, int HW, void* stream) {
+  OSM_REQUIRE(x0 && y && part && loss && g && B > 0 && HW > 0, "%s: bad argument", who);
+  OSM_REQUIRE(C >= 3, "%s: the data term reads channels 0..2 of x0, got C = %d", who, C);
   const int nblk = osm_phys_nblk(HW);
-  hipLaunchKernelGGL(ps_reduce_c_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, x0, y, part, C, HW, nblk);
+  const dim3 rgrid(nblk, B), ggrid((HW + 255) / 256, B);
+  hipStream_t st = (hipStream_t)stream;
+  if (mask) hipLaunchKernelGGL(ps_reduce_c_kernel<true>, rgrid, dim3(256), 0, st, x0, y, mask, part, C, HW, nblk);
+  else hipLaunchKernelGGL(ps_reduce_c_kernel<false>, rgrid, dim3(256), 0, st, x0, y, nullptr, part, C, HW, nblk);
   int rc = osm::check_launch("ps_reduce_c_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(ps_grad_c_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, x0, y, part, loss, g, C, HW,
-                     nblk);
+  if (mask) hipLaunchKernelGGL(ps_grad_c_kernel<true>, ggrid, dim3(256), 0, st, x0, y, mask, part, loss, g, C, HW, nblk);
+  else hipLaunchKernelGGL(ps_grad_c_kernel<false>, ggrid, dim3(256), 0, st, x0, y, nullptr, part, loss, g, C, HW, nblk);
   return osm::check_launch("ps_grad_c_kernel");
+}
+}  // namespace
+
+extern "C" int osm_ps_loss_grad_c(const float* x0, const float* y, float* part, float* loss, float* g, int B, int C, int HW,
+                                  void* stream) {
+  return ps_loss_grad_launch("osm_ps_loss_grad_c", x0, y, nullptr, part, loss, g, B, C, HW, stream);
+}
+
+extern "C" int osm_ps_loss_grad_mc(const float* x0, const float* y, const float* mask, float* part, float* loss, float* g, int B, int C,
+                                   int HW, void* stream) {
+  return ps_loss_grad_launch("osm_ps_loss_grad_mc", x0, y, mask, part, loss, g, B, C, HW, stream);
+}
+
+extern "C" int osm_exposure_mask(const float* y, float lo, float hi, float soft, int per_pixel, float* mask_out, int B, int HW,
+                                 void* stream) {
+  OSM_REQUIRE(y && mask_out && B > 0 && HW > 0, "osm_exposure_mask: bad argument");
+  OSM_REQUIRE(lo <= hi, "osm_exposure_mask: low must not exceed high, got %g > %g", (double)lo, (double)hi);
+  OSM_REQUIRE(soft >= 0.f, "osm_exposure_mask: soft must be >= 0, got %g", (double)soft);
+  hipLaunchKernelGGL(exposure_mask_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, (hipStream_t)stream, y, lo, hi, soft,
+                     per_pixel, mask_out, B, HW);
+  return osm::check_launch("exposure_mask_kernel");
 }

@@ -51,10 +51,71 @@ def _parse_scale(s):
         return torch.tensor([float(p.strip()) for p in s.split(",")])
 
 
+def validate_measurement_mask(mask, batch=None):
+    """A validity mask of the measurement as fp32 [B or 1, 3, H, W]: rank 4, [B,3,H,W] / [B,1,H,W] / [1,3,H,W] / [1,1,H,W],
+    finite, within [0, 1] (0 ignore, 1 trust fully, fractions are confidences).  batch: the chain's batch size, when known."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 4:
+        raise ValueError(f"measurement mask must have rank 4 ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W]), got {tuple(mask.shape)}")
+    if mask.shape[1] not in (1, 3):
+        raise ValueError(f"measurement mask must have 1 or 3 channels, got {tuple(mask.shape)}")
+    if batch is not None and mask.shape[0] not in (1, int(batch)):
+        raise ValueError(f"measurement mask has batch {mask.shape[0]}, the chain has {int(batch)} images (1 broadcasts)")
+    mask = mask.detach().to(torch.float32)
+    if not bool(torch.isfinite(mask).all()):
+        raise ValueError("measurement mask must be finite")
+    if mask.numel() and (float(mask.min()) < 0.0 or float(mask.max()) > 1.0):
+        raise ValueError(f"measurement mask must lie within [0, 1], got [{float(mask.min())}, {float(mask.max())}]")
+    return mask
+
+
 class ConditioningMethod(ABC):
+    _mask = None            # [B or 1, 3, HW] fp32 (`set_measurement_mask`); class default: conditioners without one are unmasked
+    _mask_hw = None
+
     def __init__(self, operator, noiser, **kwargs):
         self.operator = operator
         self.noiser = noiser
+
+    # ---------------------------------------------------------------- per-pixel validity mask of the measurement
+    def set_measurement_mask(self, mask, batch=None, device=None):
+        """Weigh the data term per pixel: the residual of channel c becomes (y_c - A(x0)_c) w M_c (osmosis; w the none / depth weight)
+        or M_c (y_c - x0_c) ('ps', which makes the data term inpainting).  mask: [B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
+        [0, 1] (0 ignore, 1 trust fully, fractions are confidences); None clears it.  Stored as contiguous [B,3,HW] on `device`
+        (default: the mask's own), the layout of the measurement; a batch-1 mask serves every image of a batch.  The losses keep
+        their normalisation: mse still divides by 3 HW, so a mask of ones IS the unmasked loss; the auxiliary losses act on the
+        prediction and are not masked.  An image that is masked out entirely has loss 0, no data-term gradient and (norm) no phi
+        step."""
+        if mask is None:
+            self._mask = self._mask_hw = None
+            return None
+        mask = validate_measurement_mask(mask, batch)
+        B0 = mask.shape[0] if batch is None else int(batch)
+        H, W = mask.shape[2], mask.shape[3]
+        if device is not None:
+            mask = mask.to(device)
+        self._mask = mask.expand(B0, 3, H, W).reshape(B0, 3, H * W).contiguous()
+        self._mask_hw = (H, W)
+        return self._mask
+
+    def measurement_mask(self, B, HW, device):
+        """The stored mask as [B,3,HW] rows on `device` (None: no mask)."""
+        m = self._mask
+        if m is None:
+            return None
+        if m.shape[2] != HW or m.shape[0] not in (1, B):
+            raise ValueError(f"measurement mask [{m.shape[0]},3,{m.shape[2]}] does not fit a measurement [{B},3,{HW}]")
+        if m.shape[0] != B or m.device != torch.device(device):
+            m = m.to(device).expand(B, 3, HW).contiguous()
+            self._mask = m
+        return m
+
+    def _mask_like(self, measurement):
+        """The stored mask shaped like the measurement [B,3,H,W] (autograd paths), or None."""
+        if self._mask is None:
+            return None
+        B, _, H, W = measurement.shape
+        return self.measurement_mask(B, H * W, measurement.device).view(B, 3, H, W)
 
     def project(self, data, noisy_measurement, **kwargs):
         return self.operator.project(data=data, measurement=noisy_measurement, **kwargs)
@@ -63,6 +124,9 @@ class ConditioningMethod(ABC):
         """DPS data term for the rgb-guidance variant (reference :35-53); torch autograd."""
         if self.noiser.__name__ == "gaussian":
             diff = measurement - self.operator.forward(x_0_hat[:, 0:3], **kwargs)
+            m = self._mask_like(measurement)
+            if m is not None:
+                diff = diff * m
             loss = torch.linalg.norm(diff)
         elif self.noiser.__name__ == "poisson":
             diff = measurement - self.operator.forward(x_0_hat, **kwargs)
@@ -164,11 +228,12 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         self._state = st
         return st
 
-    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None):
+    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
         """Inner phi-optimisation + dL/dx0.  x0 [B,4,H,W], y [B,3,H,W] contiguous device fp32.
         Returns (g [B,4,H,W] view of an internal buffer (or g_out), per-image data loss [B] (device)).
-        `phi` / `loss_out`: rows of the operator's [B][9] state / of a [B] loss vector when the caller walks
-        a batch in chunks of independent images (default: the operator's whole state)."""
+        `phi` / `loss_out` / `mask`: rows of the operator's [B][9] state / of a [B] loss vector / of the [B,3,HW] mask when the
+        caller walks a batch in chunks of independent images (default: the operator's whole state, the mask of
+        `set_measurement_mask`)."""
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] != 4:
             raise ValueError("expected x0 [B,4,H,W] and measurement [B,3,H,W]")
@@ -182,7 +247,23 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("phi must be a contiguous [B][9] block")
         g = g_out if g_out is not None else st["g"]
         x0c, yc = x0.contiguous(), y.contiguous()
+        if mask is None:
+            mask = self.measurement_mask(B, HW, x0.device)
         n_inner = 1 if freeze_phi else self.n_iter
+        if mask is not None:        # the same launches with the mask in the residual (osm_phys_*_m)
+            if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+                ops.phys_optimize_m(d, x0c, yc, mask, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=self._opt_rows(opt, phi))
+                return g.view(x0.shape), loss
+            for it in range(n_inner):
+                ops.phys_reduce_m(d, x0c, yc, mask, phi, part)
+                if it == n_inner - 1:
+                    ops.phys_finalize_m(d, part, red, phi, False, loss)
+                    ops.phys_grad_m(d, x0c, yc, mask, phi, red, g)
+                    if not freeze_phi:
+                        ops.phys_finalize_m(d, part, red, phi, True, None, opt_state=self._opt_rows(opt, phi))
+                else:
+                    ops.phys_finalize_m(d, part, red, phi, True, loss, opt_state=self._opt_rows(opt, phi))
+            return g.view(x0.shape), loss
         # n_inner x { reduce; finalize + phi step }; loss and dL/dx0 use the phi of the LAST iteration, which is stepped afterwards:
         # one C call enqueues the 2 n_inner + 2 launches (one Python call per launch left the GPU idle between them)
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
@@ -249,6 +330,9 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         w = utilso.set_loss_weight(loss_weight_type=self.loss_weight, weight_function=self.weight_function,
                                    degraded_image=image.detach(), x_0_hat=x_0_hat.detach())
         diff = (measurement - (2 * image - 1)) * w
+        m = self._mask_like(measurement)
+        if m is not None:           # (mse below keeps its 3 HW denominator: a mask of ones is the unmasked loss)
+            diff = diff * m
         if self.loss_function == "norm":
             return torch.norm(diff.detach().cpu(), p=2, dim=[1, 2, 3]).numpy(), torch.linalg.norm(diff), image.detach()
         if self.loss_function == "mse":
@@ -339,10 +423,11 @@ class PosteriorSampling(ConditioningMethod):
             raise ValueError(f"scale must have 1 or {channels} entries")
         return (s.repeat(channels) if s.numel() == 1 else s).to(device).contiguous()
 
-    def loss_grad_x0(self, x0, y, g_out=None, loss_out=None):
+    def loss_grad_x0(self, x0, y, g_out=None, loss_out=None, mask=None):
         """loss[b] = ||y[b] - x0[b, 0:3]||_2 and g = d loss / d x0 (zero on any channel beyond the colours), per image (B = 1: the
         reference's batch-global norm).  x0 [B,C,H,W] with C = 4 (RGBD) or 3 (the RGB model family), y [B,3,H,W] contiguous device
-        fp32."""
+        fp32.  With a mask M (`mask`: [B,3,HW] rows, default the one of `set_measurement_mask`): loss[b] = ||M (y - x0[0:3])||,
+        g = -M^2 (y - x0) / loss, and g = 0 for an image that is masked out entirely."""
         B, C, HW = x0.shape[0], x0.shape[1], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or C not in (3, 4):
             raise ValueError("expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,H,W]")
@@ -365,7 +450,13 @@ class PosteriorSampling(ConditioningMethod):
             self._states[key] = st
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
-        if C == 4:
+        if mask is None:
+            mask = self.measurement_mask(B, HW, x0.device)
+        if mask is not None and C == 4:
+            ops.phys_optimize_m(st["desc"], x0.contiguous(), y.contiguous(), mask, st["phi"], st["part"], st["red"], loss, g, 1, True)
+        elif mask is not None:
+            ops.ps_loss_grad_mc(x0.contiguous(), y.contiguous(), mask, st["part"], loss, g, B, C, HW)
+        elif C == 4:
             ops.phys_optimize(st["desc"], x0.contiguous(), y.contiguous(), st["phi"], st["part"], st["red"], loss, g, 1, True)
         else:
             ops.ps_loss_grad_c(x0.contiguous(), y.contiguous(), st["part"], loss, g, B, C, HW)

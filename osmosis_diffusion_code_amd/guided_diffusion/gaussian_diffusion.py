@@ -376,6 +376,7 @@ class GaussianDiffusion:
         scale4 = cond.scale4(dev, C) if ps else cond.scale4(dev)
         clip = -1.0 if ps else cond.clip_value
         y = measurement.detach().to(dev, torch.float32).contiguous()
+        mask = cond.measurement_mask(B, HW, dev)          # [B,3,HW] rows like y, or None (`measurement_mask=`)
         phi = None if ps else cond.operator.phi
         single = len(chunks) == 1
         x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
@@ -402,6 +403,8 @@ class GaussianDiffusion:
         noise1 = torch.zeros(1, C, H, W, **f32) if (shared and source == "aten" and not mean_only) else None
         noise_used = torch.empty(B, C, H, W, **f32) if (lib_rng and trace is not None) else None
         have_loss = False
+        # (no mask: the call as it always was -- a conditioner subclass whose loss_grad_x0 predates the kwarg keeps working)
+        mk_rows = (lambda a, b: {}) if mask is None else (lambda a, b: {"mask": mask[a:b]})
         k = 0                                             # sub-step count (noise_fn's k)
         for idx in range(first, last - 1, -1):
             guided, freeze, alt = sched[T - 1 - idx]
@@ -462,10 +465,10 @@ class GaussianDiffusion:
                     gg = dxu = grad_out = None
                     if guided:
                         if ps:
-                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1])
+                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
                         else:
                             cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
-                                              loss_out=loss_all[c0:c1])
+                                              loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
                         have_loss = True
                         if dyn:                           # (a clip_denoised clamp after it masks nothing more)
                             ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
@@ -546,8 +549,19 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ public loop
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root,
                       pretrain_model=None, image_idx=None, record_every=150, rgb_guidance=False,
-                      sample_pattern=None, **kwargs):
+                      sample_pattern=None, measurement_mask=None, **kwargs):
+        """measurement_mask: a per-pixel validity mask of the measurement ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
+        [0, 1]; `ConditioningMethod.set_measurement_mask`), handed to the conditioner for this chain -- the fused loop and
+        `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default)."""
         from .posterior_mean_variance import PreviousXMeanProcessor
+        if measurement_mask is not None:
+            cond_obj = getattr(measurement_cond_fn, "__self__", None)
+            if not hasattr(cond_obj, "set_measurement_mask"):
+                raise TypeError("measurement_mask needs a conditioner with set_measurement_mask (a ConditioningMethod)")
+            if tuple(measurement_mask.shape[2:]) != tuple(x_start.shape[2:]):
+                raise ValueError(f"measurement_mask {tuple(measurement_mask.shape)} does not match the image grid "
+                                 f"{tuple(x_start.shape[2:])}")
+            cond_obj.set_measurement_mask(measurement_mask, batch=x_start.shape[0], device=x_start.device)
         if isinstance(self.mean_processor, PreviousXMeanProcessor) and not (
                 rgb_guidance and getattr(type(self), "p_sample", None) is DDIM.p_sample):
             # Error behaviour of the reference: `previous_x` hands the network's split output on AS the mean

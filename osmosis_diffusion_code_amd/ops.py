@@ -446,6 +446,45 @@ def phys_optimize(desc: PhysDesc, x0, y, phi, part, red, loss_out, g, n_inner: i
          int(bool(freeze_phi)), ptr(opt_state), _s(), keep=(desc, x0, y, phi, part, red, loss_out, g, opt_state))
 
 
+def _check_mask(mask, y):
+    """A mask travels as [B,3,HW] rows laid out like the measurement it weighs (the kernels address it like y)."""
+    if mask is not None and (mask.numel() != y.numel() or not mask.is_contiguous() or mask.dtype != torch.float32):
+        raise ValueError(f"mask must be contiguous fp32 with the measurement's {y.numel()} elements ([B,3,HW]), "
+                         f"got {tuple(mask.shape)} {mask.dtype}")
+
+
+def phys_reduce_m(desc: PhysDesc, x0, y, mask, phi, part):
+    """osm_phys_reduce with a validity mask [B,3,HW] in the residual (None: the plain launch)."""
+    _check_mask(mask, y)
+    call("osm_phys_reduce_m", C.byref(desc), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(part), _s(), keep=(desc, x0, y, mask, phi, part))
+
+
+def phys_finalize_m(desc: PhysDesc, part, red, phi, do_update, loss_out, opt_state=None, masked=True):
+    """The finalize of the masked path: an image whose residual sum is exactly 0 (fully masked) takes no phi step."""
+    call("osm_phys_finalize_m", C.byref(desc), ptr(part), ptr(red), ptr(phi), int(do_update), ptr(loss_out), ptr(opt_state),
+         int(bool(masked)), _s(), keep=(part, red, phi, loss_out, opt_state))
+
+
+def phys_grad_m(desc: PhysDesc, x0, y, mask, phi, red, g):
+    _check_mask(mask, y)
+    call("osm_phys_grad_m", C.byref(desc), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(red), ptr(g), _s(),
+         keep=(desc, x0, y, mask, phi, red, g))
+
+
+def phys_optimize_m(desc: PhysDesc, x0, y, mask, phi, part, red, loss_out, g, n_inner: int, freeze_phi: bool, opt_state=None):
+    """`phys_optimize` with a validity mask [B,3,HW] (None: the same launches as `phys_optimize`)."""
+    _check_mask(mask, y)
+    call("osm_phys_optimize_m", C.byref(desc), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(part), ptr(red), ptr(loss_out), ptr(g),
+         int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(), keep=(desc, x0, y, mask, phi, part, red, loss_out, g, opt_state))
+
+
+def exposure_mask(y, mask_out, B, HW, low, high, soft=0.0, per_pixel=False):
+    """mask_out [B,3,HW] from the exposure of y [B,3,HW] in [-1, 1] (osm_exposure_mask)."""
+    assert y.numel() == B * 3 * HW and mask_out.numel() == B * 3 * HW and y.is_contiguous() and mask_out.is_contiguous()
+    call("osm_exposure_mask", ptr(y), float(low), float(high), float(soft), int(bool(per_pixel)), ptr(mask_out), B, HW, _s(),
+         keep=(y, mask_out))
+
+
 def posterior_bwd(g, coef, d_out, B, HW):
     call("osm_posterior_bwd", ptr(g), ptr(coef), ptr(d_out), B, HW, _s(), keep=(g, coef, d_out))
 
@@ -548,6 +587,13 @@ def ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, gr
 def ps_loss_grad_c(x0, y, part, loss, g, B, Cc, HW):
     """loss[b] = ||y[b] - x0[b, 0:3]||, g = d loss / d x0 (zero beyond channel 2); part: fp32 [B * phys_nblk(HW)] workspace."""
     call("osm_ps_loss_grad_c", ptr(x0), ptr(y), ptr(part), ptr(loss), ptr(g), B, Cc, HW, _s(), keep=(x0, y, part, loss, g))
+
+
+def ps_loss_grad_mc(x0, y, mask, part, loss, g, B, Cc, HW):
+    """`ps_loss_grad_c` with a validity mask [B,3,HW]: loss[b] = ||M (y - x0[0:3])||, g = -M^2 (y - x0) / loss (None: unmasked)."""
+    _check_mask(mask, y)
+    call("osm_ps_loss_grad_mc", ptr(x0), ptr(y), ptr(mask), ptr(part), ptr(loss), ptr(g), B, Cc, HW, _s(),
+         keep=(x0, y, mask, part, loss, g))
 
 
 RECON_MODES = {"bilinear": 0, "joint_bilateral": 1}

@@ -164,6 +164,30 @@ def fit_transform(size=256, multiple=32):
     return apply
 
 
+def transform_mask(mask, size=256, crop="center", multiple=32, geometry=None):
+    """A validity mask given at the photo's own resolution, taken through the geometry of the photo's transform: `resize`
+    (bilinear, as the photo) and `center_crop`, clamped to [0, 1]; no Normalize.  crop="center": the [size, size] crop of
+    `default_transform`; crop="fit" or a
+    `geometry` (the `Geometry` that `fit_transform` returned for the photo): the grid of `fit_transform`.
+    mask: [H0,W0], [1,H0,W0] or [3,H0,W0] (anything `torch.as_tensor` takes; bool / uint8 0-1 maps included).
+    Returns fp32 [1,C,h,w] with C = 1 or 3: what `restore_image(mask=)` and `p_sample_loop(measurement_mask=)` accept."""
+    m = torch.as_tensor(np.asarray(mask) if not torch.is_tensor(mask) else mask).to(torch.float32)
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if m.dim() != 3 or m.shape[0] not in (1, 3):
+        raise ValueError(f"mask must be [H0,W0], [1,H0,W0] or [3,H0,W0], got {tuple(m.shape)}")
+    if geometry is not None:
+        if (m.shape[-2], m.shape[-1]) != (geometry.H0, geometry.W0):
+            raise ValueError(f"the mask is {m.shape[-2]} x {m.shape[-1]} but the geometry describes a {geometry.H0} x {geometry.W0} photo")
+        out_hw = [geometry.h, geometry.w]
+    elif crop == "center":
+        out_hw = [size, size]
+    else:
+        geo = transform_geometry(m.shape[-2], m.shape[-1], size, crop, multiple)
+        out_hw = [geo.h, geo.w]
+    return center_crop(resize(m, size), out_hw).clamp(0.0, 1.0).unsqueeze(0).contiguous()
+
+
 # ----------------------------------------------------------------------------- datasets
 class ImagesFolder(Dataset):
     """data.py:15-38: every file of `root_dir` in natural order -> (transformed image, file name)."""

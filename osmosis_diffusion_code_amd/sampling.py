@@ -159,6 +159,7 @@ def output_images(post, ref_img, gt_rgb_01=None, gt_depth_01=None):
 
 def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, save_grids=True, gt_rgb_01=None,
                  gt_depth_01=None, rgb_guidance=None, full_res=None):
+    # (a result that carries `mask` -- a chain guided through a validity mask -- also gets single_images/mask/<name>_mask.png)
     """Writes what the reference writes for one image (osmosis_sampling.py:84-104 directory layout, :319-353 files):
     `<out_dir>/single_images/{input,rgb,depth_color,depth_raw}/<name>.png` and `<out_dir>/grid_results/<name>_g<ii>_grid.png`.
     Returns {kind: path}.  (`<name>_process.png` is written by the sampler itself when `record` is on.)
@@ -178,6 +179,11 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
             os.makedirs(d, exist_ok=True)
             paths[kind] = os.path.join(d, f"{name}.png")
             Image.fromarray(imgs[kind], mode="L" if imgs[kind].ndim == 2 else "RGB").save(paths[kind])
+    if save_singles and post.get("mask") is not None:       # only when the chain used a validity mask
+        d = os.path.join(out_dir, "single_images", "mask")
+        os.makedirs(d, exist_ok=True)
+        paths["mask"] = os.path.join(d, f"{name}_mask.png")
+        Image.fromarray(_to_pil_u8(post["mask"][0].clamp(0, 1)), mode="RGB").save(paths["mask"])
     if save_grids:
         d = os.path.join(out_dir, "grid_results")
         os.makedirs(d, exist_ok=True)
@@ -276,8 +282,36 @@ def rgb_guidance_result(sample, measurement):
             "measurement": measurement}
 
 
+def measurement_mask(ref_img, mask_cfg=None, mask=None):
+    """The validity mask of a chain, [B,3,H,W] fp32 on ref_img's device, or None when neither source is given.
+    mask_cfg: the optional config key `measurement.mask`; `{auto_exposure: {low, high, soft, per_pixel}}` builds the mask from
+    the exposure of the photo as loaded (ref_img in [-1, 1], before the noiser and `degamma_input`) with osm_exposure_mask:
+    0 where a channel's value leaves (low, high), a ramp of width `soft` inside; `per_pixel: true` drops the whole pixel when
+    any channel is clipped.  mask: an explicit one ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in [0, 1]); both: their product."""
+    from .guided_diffusion.condition_methods import validate_measurement_mask
+    out = None
+    if mask is not None:
+        m = validate_measurement_mask(mask, ref_img.shape[0])
+        if tuple(m.shape[2:]) != tuple(ref_img.shape[2:]):
+            raise ValueError(f"mask {tuple(m.shape)} does not match the image grid {tuple(ref_img.shape[2:])}")
+        out = m.to(ref_img.device).expand(ref_img.shape[0], 3, *ref_img.shape[2:]).contiguous()
+    if mask_cfg:
+        unknown = set(mask_cfg) - {"auto_exposure"}
+        if unknown:
+            raise ValueError(f"measurement.mask: unknown key(s) {sorted(unknown)} (known: auto_exposure)")
+        ae = mask_cfg.get("auto_exposure")
+        if ae:
+            from . import ops
+            y = ref_img.detach().to(torch.float32).contiguous()
+            auto = torch.empty_like(y)
+            ops.exposure_mask(y, auto, y.shape[0], y.shape[2] * y.shape[3], float(ae.get("low", 0.0)), float(ae.get("high", 1.0)),
+                              float(ae.get("soft", 0.0)), bool(ae.get("per_pixel", False)))
+            out = auto if out is None else out * auto
+    return out
+
+
 def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
-                  postprocess_batch=True, **loop_kwargs):
+                  postprocess_batch=True, mask=None, **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -286,7 +320,12 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     the batch starts from the SAME x_T and receives the SAME per-step noise -- exactly what B separate calls (each
     re-seeded with `manual_seed`, as the reference driver does per image) would draw -- so an image's result does not
     depend on how images are grouped into batches or spread over ranks.  `postprocess_batch=False` skips the
-    reference's image-0-only post-processing (a caller that post-processes every image of the batch itself)."""
+    reference's image-0-only post-processing (a caller that post-processes every image of the batch itself).
+
+    `mask` (and / or the optional config key `measurement.mask`, see `measurement_mask`): a per-pixel validity mask of the
+    measurement on the network grid (`data.transform_mask` takes one from the photo's resolution there).  The chain is guided
+    through it (`p_sample_loop(measurement_mask=)`) and every result carries it as `mask` [B,3,H,W]; without either, nothing
+    is passed and the results have no such key."""
     device = device if device is not None else ref_img.device
     measure, cond_cfg = cfg["measurement"], cfg["conditioning"]
     op_cfg = dict(measure["operator"])
@@ -300,6 +339,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     y_n = noiser(ref_img)
     if cfg.get("degamma_input", False):
         y_n = degamma(y_n)
+    m_dev = measurement_mask(ref_img, measure.get("mask"), mask)
+    if m_dev is not None:
+        loop_kwargs = dict(loop_kwargs, measurement_mask=m_dev)
     pretrain = cfg["unet_model"]["pretrain_model"]
     shape = list(ref_img.shape)
     shape[1] = 4 if pretrain == "osmosis" else shape[1]
@@ -323,6 +365,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             # the rgb-guidance / non-osmosis chain returns the sample only (gaussian_diffusion.py:340); the
             # reference driver splits it into RGB and depth (osmosis_sampling.py:366-380): no phi, no recomposition
             results.append(rgb_guidance_result(ret.detach().cpu(), y_n.detach().cpu()))
+            if m_dev is not None:
+                results[-1]["mask"] = m_dev.detach().cpu()
             continue
         sample, variable_dict, loss, out_xstart = ret
         if postprocess_batch:
@@ -331,6 +375,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             post = dict(phi={k: v.detach().cpu() for k, v in variable_dict.items()},
                         loss=None if loss is None else np.asarray(loss))
         post.update(sample=sample.detach().cpu(), pred_xstart=out_xstart, measurement=y_n.detach().cpu())
+        if m_dev is not None:
+            post["mask"] = m_dev.detach().cpu()
         results.append(post)
     return results
 
@@ -346,7 +392,7 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
-                   geometries=None, full_res_upsample="bilinear", **loop_kwargs):
+                   geometries=None, full_res_upsample="bilinear", masks=None, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -358,16 +404,32 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     `reconstruct_full_resolution(..., upsample=full_res_upsample)` to every result that carries phi, under `full_res`."""
     if (originals is None) != (geometries is None):
         raise ValueError("originals and geometries go together")
+    if masks is not None and len(masks) != len(images):
+        raise ValueError(f"masks must align with images: {len(masks)} masks for {len(images)} images")
+
+    def batch_mask(idxs):
+        """`masks` (a list aligned with `images`: [1,1,H,W] / [1,3,H,W] each, or None for an image without one) of one batch."""
+        if masks is None or all(masks[i] is None for i in idxs):
+            return None
+        rows = []
+        for i in idxs:
+            hw = images[i].shape[-2:]
+            m = torch.ones(1, 3, *hw) if masks[i] is None else torch.as_tensor(masks[i]).to(torch.float32)
+            if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3):
+                raise ValueError(f"masks[{i}] must be [1,1,H,W] or [1,3,H,W], got {tuple(m.shape)}")
+            rows.append(m.expand(1, 3, *m.shape[2:]))
+        return torch.cat([r.to(rows[0].device) for r in rows], 0)
     out = {}
     mine = shard_indices(len(images), rank, world)
     for k in range(0, len(mine), max(1, batch_size)):
         idxs = mine[k:k + max(1, batch_size)]
         if len(idxs) == 1:
-            res = [restore_image(model, images[idxs[0]], cfg, device=device, image_idx=idxs[0], **loop_kwargs)[-1]]
+            res = [restore_image(model, images[idxs[0]], cfg, device=device, image_idx=idxs[0], mask=batch_mask(idxs),
+                                 **loop_kwargs)[-1]]
         else:
             ref = torch.cat([images[i] for i in idxs], 0)
             full = restore_image(model, ref, cfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
-                                 postprocess_batch=False, **loop_kwargs)[-1]
+                                 postprocess_batch=False, mask=batch_mask(idxs), **loop_kwargs)[-1]
             if "pred_xstart" in full:
                 res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"])
                 for b, r in enumerate(res):
@@ -375,6 +437,9 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
                              measurement=full["measurement"][b:b + 1])
             else:
                 res = [rgb_guidance_result(full["sample"][b:b + 1], full["measurement"][b:b + 1]) for b in range(len(idxs))]
+            if full.get("mask") is not None:
+                for b, r in enumerate(res):
+                    r["mask"] = full["mask"][b:b + 1]
         for i, r in zip(idxs, res):
             if gt_rgb is not None:
                 r["psnr"] = float(utilso.psnr(r["rgb_01_clip"], gt_rgb[i]))

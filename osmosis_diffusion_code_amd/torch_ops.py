@@ -278,16 +278,27 @@ def phys_loss_grad(x0: torch.Tensor, y: torch.Tensor, phi: torch.Tensor, icfg: L
                    freeze_phi: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """n_inner x (reduce, finalize + phi step) of the physical model's loss, then loss and dL/dx0 at the last phi and its step
     (osm_phys_optimize).  SGD / GD only here (Adam carries optimizer state across steps: use the conditioning method)."""
+    return _phys_loss_grad_impl("osmosis::phys_loss_grad", x0, y, None, phi, icfg, fcfg, n_inner, freeze_phi)
+
+
+def _mask_rows(name, mask, y):
+    """A mask [B,3,H,W] or [B,1,H,W] as the contiguous [B,3,HW] rows the kernels read."""
+    if mask.dim() != 4 or mask.shape[0] != y.shape[0] or mask.shape[1] not in (1, 3) or mask.shape[2:] != y.shape[2:]:
+        raise OsmosisHipError(f"{name}: expected mask [B,3,H,W] or [B,1,H,W] on the measurement's grid")
+    return mask.expand(y.shape).contiguous()
+
+
+def _phys_loss_grad_impl(name, x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi):
     B, HW = _chw(x0)
     if len(icfg) != len(PHYS_ICFG) or len(fcfg) != len(PHYS_FCFG):
-        raise OsmosisHipError("osmosis::phys_loss_grad: icfg / fcfg must come from torch_ops.phys_config(desc)")
+        raise OsmosisHipError(f"{name}: icfg / fcfg must come from torch_ops.phys_config(desc)")
     d = PhysDesc()
     for k, v in zip(PHYS_ICFG, icfg):
         setattr(d, k, int(v))
     if d.optimizer != 0:
-        raise OsmosisHipError("osmosis::phys_loss_grad is functional: optimizer state (adam, ...) lives with the conditioning method")
+        raise OsmosisHipError(f"{name} is functional: optimizer state (adam, ...) lives with the conditioning method")
     if d.kind == 3 and not freeze_phi:
-        raise OsmosisHipError("osmosis::phys_loss_grad: the identity operator (kind 3) has no parameters: pass freeze_phi=True")
+        raise OsmosisHipError(f"{name}: the identity operator (kind 3) has no parameters: pass freeze_phi=True")
     for i in range(3):
         d.dval[i], d.wval[i], d.eta[i] = fcfg[i], fcfg[3 + i], fcfg[8 + i]
     d.gamma_avrg, d.gamma_val = fcfg[6], fcfg[7]
@@ -298,13 +309,46 @@ def phys_loss_grad(x0: torch.Tensor, y: torch.Tensor, phi: torch.Tensor, icfg: L
     red = torch.zeros(B * 16, device=dev, dtype=torch.float32)
     loss = torch.zeros(B, device=dev, dtype=torch.float32)
     g = torch.empty_like(x0)
-    ops.phys_optimize(d, x0, y.contiguous(), phi_new, part, red, loss, g, 1 if freeze_phi else n_inner, freeze_phi)
+    if mask is None:
+        ops.phys_optimize(d, x0, y.contiguous(), phi_new, part, red, loss, g, 1 if freeze_phi else n_inner, freeze_phi)
+    else:
+        ops.phys_optimize_m(d, x0, y.contiguous(), _mask_rows(name, mask, y), phi_new, part, red, loss, g,
+                            1 if freeze_phi else n_inner, freeze_phi)
     return loss, g, phi_new
 
 
 @phys_loss_grad.register_fake
 def _phys_loss_grad_fake(x0, y, phi, icfg, fcfg, n_inner, freeze_phi):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
+
+
+@torch.library.custom_op("osmosis::phys_loss_grad_m", mutates_args=(), device_types="cuda")
+def phys_loss_grad_m(x0: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, phi: torch.Tensor, icfg: List[int], fcfg: List[float],
+                     n_inner: int, freeze_phi: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::phys_loss_grad with a per-pixel validity mask [B,3,H,W] / [B,1,H,W] in [0, 1] in the data term: the residual of
+    channel c is (y_c - (2 I_c - 1)) w M_c, the losses keep their normalisation (osm_phys_optimize_m)."""
+    return _phys_loss_grad_impl("osmosis::phys_loss_grad_m", x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi)
+
+
+@phys_loss_grad_m.register_fake
+def _phys_loss_grad_m_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
+
+
+@torch.library.custom_op("osmosis::exposure_mask", mutates_args=(), device_types="cuda")
+def exposure_mask(y: torch.Tensor, low: float, high: float, soft: float = 0.0, per_pixel: bool = False) -> torch.Tensor:
+    """Validity mask [B,3,H,W] from the exposure of y [B,3,H,W] in [-1, 1] (osm_exposure_mask): 0 where v = (y + 1) / 2 leaves
+    (low, high), a ramp of width `soft` inside each bound; per_pixel: the channel minimum on every channel."""
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise OsmosisHipError("osmosis::exposure_mask: expected y [B,3,H,W]")
+    out = torch.empty(y.shape, device=y.device, dtype=torch.float32)
+    ops.exposure_mask(y.contiguous(), out, y.shape[0], y.shape[2] * y.shape[3], low, high, soft, per_pixel)
+    return out
+
+
+@exposure_mask.register_fake
+def _exposure_mask_fake(y, low, high, soft=0.0, per_pixel=False):
+    return y.new_empty(y.shape)
 
 
 # ---- channel-generic step (the RGB model family: [B,C,H,W] state, [B,Cout,H,W] network output with Cout = C or 2 C)
@@ -451,6 +495,25 @@ def _ps_loss_grad_c_fake(x0, y):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
 
 
+@torch.library.custom_op("osmosis::ps_loss_grad_mc", mutates_args=(), device_types="cuda")
+def ps_loss_grad_mc(x0: torch.Tensor, y: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """osmosis::ps_loss_grad_c with a validity mask [B,3,H,W] / [B,1,H,W] in [0, 1]: loss [B] = ||M (y - x0[:, 0:3])|| per image,
+    g = -M^2 (y - x0) / loss (0 for an image that is masked out entirely) (osm_ps_loss_grad_mc)."""
+    B, HW = _chw(x0)
+    if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] < 3:
+        raise OsmosisHipError("osmosis::ps_loss_grad_mc: expected x0 [B,C>=3,H,W] and y [B,3,H,W]")
+    loss = torch.empty(B, device=x0.device, dtype=torch.float32)
+    g = torch.empty_like(x0)
+    part = torch.empty(B * ops.phys_nblk(HW), device=x0.device, dtype=torch.float32)
+    ops.ps_loss_grad_mc(x0, y.contiguous(), _mask_rows("osmosis::ps_loss_grad_mc", mask, y), part, loss, g, B, x0.shape[1], HW)
+    return loss, g
+
+
+@ps_loss_grad_mc.register_fake
+def _ps_loss_grad_mc_fake(x0, y, mask):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
+
+
 @torch.library.custom_op("osmosis::recon_fullres", mutates_args=(), device_types="cuda")
 def recon_fullres(depth: torch.Tensor, guide: torch.Tensor, image: torch.Tensor, phi_a: torch.Tensor, phi_b: torch.Tensor,
                   phi_inf: torch.Tensor, depth_type: int, dval: List[float], amap: List[float], mode: int = 0, radius: int = 2,
@@ -481,4 +544,5 @@ def _recon_fullres_fake(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, 
 
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
-OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "recon_fullres") + OPS_C
+OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres") + OPS_C
