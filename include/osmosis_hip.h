@@ -600,6 +600,19 @@ int osm_copy2d_h(const osm_half_t* x, long long ldx, osm_half_t* y, long long ld
 int osm_half_to_f32(const osm_half_t* x, long long ldx, float* y, long long ldy, long long M, int C, void* stream);
 int osm_f32_to_half(const float* x, long long ldx, osm_half_t* y, long long ldy, long long M, int C, void* stream);
 
+/* ---- tiled sampling: one canvas [C,Hc,Wc] (planar fp32) <-> n overlapping tiles [n,C,th,tw] (the engine's x_in / out / d_out / dx
+ * layout).  origins: device int32 [n][2], (y, x) of every tile's first pixel on the canvas.  wy [th], wx [tw], inv_norm [Hc][Wc]
+ * are NULL together or given together.
+ *   gather: tiles[t,c,y,x] = canvas[c,oy+y,ox+x] k, k = 1 (all NULL: a bit-exact crop) or (wy[y] wx[x]) inv_norm[oy+y,ox+x];
+ *           a tile whose origin leaves [0, Hc-th] x [0, Wc-tw] is written as 0.
+ *   blend:  the adjoint.  canvas[c,Y,X] = inv_norm[Y,X] sum_t tiles[t,c,Y-oy,X-ox] (wy[Y-oy] wx[X-ox]) over the covering tiles in
+ *           ascending t, every product and the running sum rounded to fp32 (all NULL: the plain sum); a pixel no tile covers is 0.
+ * No atomics: one lane per four consecutive output elements, so results do not depend on the launch shape. */
+int osm_tile_gather(const float* canvas, float* tiles, const int* origins, const float* wy, const float* wx,
+                    const float* inv_norm, int n, int C, int Hc, int Wc, int th, int tw, void* stream);
+int osm_tile_blend(const float* tiles, float* canvas, const int* origins, const float* wy, const float* wx,
+                   const float* inv_norm, int n, int C, int Hc, int Wc, int th, int tw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

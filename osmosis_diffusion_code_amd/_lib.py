@@ -152,6 +152,8 @@ _SIGS = {
     "osm_ps_loss_grad_c": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "osm_ps_loss_grad_mc": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "osm_recon_fullres": [C.POINTER(ReconDesc), _P],
+    "osm_tile_gather": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "osm_tile_blend": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "osm_version": [],
 }
 # fp16-storage family (activations as IEEE half, `_h` suffix): same argument lists

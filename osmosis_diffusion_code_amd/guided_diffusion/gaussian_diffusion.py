@@ -22,6 +22,8 @@ batch is one engine pass.  The PCGS inner alternation (`local_M > 1`: the step r
 :225-309) runs there as `alternate_len` sub-steps per index (`pcgs_schedule`).  Any other combination (third-party conditioners /
 operators / processors, a chunked batch with dynamic_threshold) falls back to a generic loop that follows the reference control flow on
 top of the HIP UNet operator through torch.autograd.
+`p_sample_loop(tiling=)` runs ONE canvas larger than the network's grid as overlapping tiles of the network's size (`_tiled_loop`,
+`tile_grid`; osm_tile_gather / osm_tile_blend move canvas <-> tiles): the network is tiled, every other part of the step acts on the canvas.
 """
 import math
 
@@ -120,6 +122,80 @@ def pcgs_schedule(sample_pattern, T):
         return [(True, False, 1)] * T
     return [(guidance_flag(sample_pattern, idx, T), bool(utilso.is_freeze_phi(sample_pattern, idx, T)),
              int(utilso.set_alternate_length(sample_pattern, idx, T))) for idx in range(T - 1, -1, -1)]
+
+
+TILE_WINDOWS = ("uniform", "hann")
+TILING_KEYS = ("tile", "stride", "window")
+
+
+def tile_origins(L, t, s):
+    """First pixels of the tiles of side t at stride s along an axis of length L: range(0, L - t, s) and the edge-aligned last
+    tile L - t (so the last overlap may be ragged); L == t -> [0]."""
+    L, t, s = int(L), int(t), int(s)
+    if t < 1 or L < t:
+        raise ValueError(f"a tile of side {t} does not fit a canvas side of {L}")
+    if not 1 <= s <= t:
+        raise ValueError(f"the stride must be in [1, tile side] = [1, {t}], got {s}")
+    return list(range(0, L - t, s)) + [L - t]
+
+
+def tile_window(t, window):
+    """float64 [t]: 'uniform' = ones, 'hann' = sin^2(pi (i + 1/2) / t) (strictly positive: every covered pixel keeps weight)."""
+    if window == "uniform":
+        return np.ones(int(t), dtype=np.float64)
+    if window == "hann":
+        return np.sin(np.pi * (np.arange(int(t), dtype=np.float64) + 0.5) / int(t)) ** 2
+    raise ValueError(f"window must be one of {TILE_WINDOWS}, got {window!r}")
+
+
+def _pair(v, what):
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"{what} must be an integer or a (y, x) pair, got {v!r}")
+        a, b = v
+    else:
+        a = b = v
+    if isinstance(a, bool) or isinstance(b, bool) or int(a) != a or int(b) != b:
+        raise ValueError(f"{what} must be an integer or a (y, x) pair of integers, got {v!r}")
+    return int(a), int(b)
+
+
+def parse_tiling(tiling):
+    """`tiling = dict(tile=int | (th, tw), stride=int | (sy, sx), window='uniform' | 'hann')` -> (th, tw, sy, sx, window).
+    `tile` is required; stride defaults to half the tile, window to 'hann' (parameters, not tuned values).  Unknown keys raise."""
+    if not isinstance(tiling, dict):
+        raise ValueError(f"tiling must be a mapping with the keys {TILING_KEYS}, got {type(tiling).__name__}")
+    unknown = set(tiling) - set(TILING_KEYS)
+    if unknown:
+        raise ValueError(f"tiling: unknown key(s) {sorted(unknown)} (known: {', '.join(TILING_KEYS)})")
+    if "tile" not in tiling:
+        raise ValueError("tiling needs `tile` (the side the network sees)")
+    th, tw = _pair(tiling["tile"], "tiling.tile")
+    sy, sx = _pair(tiling["stride"], "tiling.stride") if tiling.get("stride") is not None else (max(1, th // 2), max(1, tw // 2))
+    window = tiling.get("window", "hann")
+    if window not in TILE_WINDOWS:
+        raise ValueError(f"window must be one of {TILE_WINDOWS}, got {window!r}")
+    return th, tw, sy, sx, window
+
+
+def tile_grid(Hc, Wc, tile, stride, window="hann"):
+    """The tiles of a Hc x Wc canvas (tiled sampling, MultiDiffusion): (origins int32 [n,2] in (y, x) order, row-major -- y outer,
+    x inner --, wy fp32 [th], wx fp32 [tw], inv_norm fp32 [Hc,Wc]), CPU tensors.  The window is separable, w(y, x) = wy[y] wx[x];
+    inv_norm = 1 / sum of the covering tiles' fp32 windows, formed in float64 and cast once, so the blend weights sum to one at
+    every pixel (each pixel is covered: the last tile of an axis is edge-aligned)."""
+    th, tw = _pair(tile, "tile")
+    sy, sx = _pair(stride, "stride")
+    oys, oxs = tile_origins(Hc, th, sy), tile_origins(Wc, tw, sx)
+    wy = torch.from_numpy(tile_window(th, window)).to(torch.float32)
+    wx = torch.from_numpy(tile_window(tw, window)).to(torch.float32)
+    sum_y, sum_x = np.zeros(int(Hc), dtype=np.float64), np.zeros(int(Wc), dtype=np.float64)
+    for oy in oys:
+        sum_y[oy:oy + th] += wy.double().numpy()
+    for ox in oxs:
+        sum_x[ox:ox + tw] += wx.double().numpy()
+    inv_norm = torch.from_numpy(1.0 / np.outer(sum_y, sum_x)).to(torch.float32)
+    origins = torch.tensor([[oy, ox] for oy in oys for ox in oxs], dtype=torch.int32).reshape(-1, 2)
+    return origins, wy, wx, inv_norm
 
 
 def extract_and_expand(array, time, target):
@@ -524,6 +600,175 @@ class GaussianDiffusion:
         loss_np = loss_all.detach().cpu().numpy() if have_loss else None
         return img, variables, loss_np, x0.detach().cpu()
 
+    def _tiled_loop(self, model, cond_fn, x_start, measurement, pretrain_model, rgb_guidance, sample_pattern, kwargs, tiling,
+                    record=False, record_every=150):
+        """Tiled sampling (MultiDiffusion) of ONE canvas x_start [1,4,Hc,Wc] larger than the network's grid, Osmosis configuration.
+        At every sub-step the network sees the n overlapping tiles of `tile_grid` as engine batches (`chunk_sizes` of n); the
+        per-tile outputs are blended per pixel (window weights / their sum) into one canvas-sized network output, and everything
+        else -- posterior, the physical model with its ONE phi, the mask, the auxiliary losses, clip_denoised, the guidance update,
+        the step noise -- acts on the canvas exactly as `_fused_loop` does on an image (B = 1, HW = Hc Wc).  The guidance gradient
+        goes back through the blend: the canvas d_out is gathered with the same weights (the blend's adjoint) into every tile's
+        data-gradient pass and the per-tile dx are summed into the canvas dx.  The engine keeps one pass's activations, so with
+        more than one chunk the forward of a chunk is re-run before its data-gradient pass.
+        Never `_generic_loop` (the network on the whole canvas is another computation): what this loop does not carry raises
+        NotImplementedError naming the option; a bad tiling raises ValueError before anything launches."""
+        import os
+        from .condition_methods import PosteriorSamplingOsmosis
+        from .unet import UNetModel
+        th, tw, sy, sx, window = parse_tiling(tiling)
+        if rgb_guidance:
+            raise NotImplementedError("tiling: rgb_guidance (the 'ps' branch) is not tiled")
+        if pretrain_model != "osmosis":
+            raise NotImplementedError(f"tiling: pretrain_model={pretrain_model!r} (the mean-only branch) is not tiled")
+        if getattr(type(self), "p_sample", None) is DDIM.p_sample:
+            raise NotImplementedError("tiling: the ddim sampler is not tiled")
+        if self.mean_processor.dynamic_threshold:
+            raise NotImplementedError("tiling: dynamic_threshold is not tiled (its quantile couples the whole canvas)")
+        if x_start.dim() != 4 or x_start.shape[0] != 1:
+            raise NotImplementedError(f"tiling: one canvas per call (batch {tuple(x_start.shape)[0]} > 1 is not tiled)")
+        if not isinstance(model, UNetModel) or (model.in_channels, model.out_channels) != (4, 8):
+            raise NotImplementedError("tiling: only the 4 -> 8 (RGBD, learned variance) network is tiled")
+        _, C, Hc, Wc = x_start.shape
+        if C != 4 or tuple(measurement.shape) != (1, 3, Hc, Wc):
+            raise ValueError(f"tiling: expected x_start [1,4,Hc,Wc] and measurement [1,3,Hc,Wc], got {tuple(x_start.shape)} and "
+                             f"{tuple(measurement.shape)}")
+        origins, wy, wx, inv_norm = tile_grid(Hc, Wc, (th, tw), (sy, sx), window)      # (ValueError: tile > canvas, stride, window)
+        div = 1 << (len(model.channel_mult) - 1)
+        if th % div or tw % div:
+            raise ValueError(f"tiling: the network needs tile sides divisible by {div}, got {th} x {tw}")
+        cond = self._fast_path_ok(model, cond_fn, pretrain_model, rgb_guidance, sample_pattern, tuple(x_start.shape))
+        if not isinstance(cond, PosteriorSamplingOsmosis):
+            raise NotImplementedError("tiling: this configuration has no fused step (conditioner / operator / processors the HIP "
+                                      "loop has no kernels for, or a fused path switched off), and the generic loop is not tiled")
+        assert getattr(model, "num_classes", None) is None, "must specify y if and only if the model is class-conditional"
+        dev = x_start.device
+        HW, T, n = Hc * Wc, self.num_timesteps, origins.shape[0]
+        first, last = kwargs.get("index_range", (T - 1, 0))
+        if not (0 <= last <= first <= T - 1):
+            raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({first}, {last})")
+        sched = pcgs_schedule(sample_pattern, T)
+        if T > 1 << 16 and max(a for _, _, a in sched) > 1:
+            raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
+        noise_fn = kwargs.get("noise_fn", None)
+        source = "fn" if noise_fn is not None else str(kwargs.get("noise", os.environ.get("OSM_STEP_NOISE", "library"))).lower()
+        if source not in ("fn", "library", "aten"):
+            raise ValueError(f"noise must be 'library' or 'aten', got {source!r}")
+        if source == "library" and HW % 4 != 0:
+            source = "aten"
+        # ---- everything above is host-side; from here on the device is used
+        sizes = self.chunk_sizes(n, model.images_in_flight(n, th, tw))
+        chunks, c0 = [], 0
+        for sz in sizes:
+            chunks.append((c0, c0 + sz))
+            c0 += sz
+        engs = {}
+        for sz in sorted(set(sizes), reverse=True):
+            engs[sz] = model.engine(sz, th, tw, keep=tuple(engs.values()))
+        eng = engs[sizes[0]]
+        single = len(chunks) == 1
+        f32 = dict(device=dev, dtype=torch.float32)
+        org, wy, wx, inv_norm = origins.to(dev), wy.to(dev), wx.to(dev), inv_norm.to(dev).contiguous()
+        weights = (wy, wx, inv_norm)
+        table = torch.from_numpy(self.coef_table()).to(dev)
+        step = torch.tensor([first], device=dev, dtype=torch.int32)
+        coef = torch.zeros(8, **f32)
+        x_state = x_start.detach().to(**f32).clone().contiguous()
+        x0, mean, logvar, g, dx = (torch.empty(1, 4, Hc, Wc, **f32) for _ in range(5))
+        model_out = torch.empty(1, 8, Hc, Wc, **f32)
+        d_out = torch.zeros(1, 8, Hc, Wc, **f32)          # (osm_posterior_bwd fills the mean half; the variance half stays 0)
+        out_tiles = None if single else torch.empty(n, 8, th, tw, **f32)
+        dx_tiles = None if single else torch.empty(n, 4, th, tw, **f32)
+        x0_raw = torch.empty(1, 4, Hc, Wc, **f32) if self.mean_processor.clip_denoised else None
+        loss_all = torch.zeros(1, **f32)
+        scale4, clip = cond.scale4(dev), cond.clip_value
+        y = measurement.detach().to(dev, torch.float32).contiguous()
+        mask = cond.measurement_mask(1, HW, dev)
+        mk_rows = {} if mask is None else {"mask": mask}
+        phi = cond.operator.phi
+        trace = kwargs.get("trace", None)
+        records = kwargs.get("record_out", [] if record else None)
+        draw_measurement_noise = kwargs.get("reference_rng_order", source == "aten") and source == "aten"
+        lib_rng = source == "library"
+        seed = 0
+        if lib_rng:
+            seed = kwargs.get("noise_seed")
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev).item())
+        img_base = int(kwargs.get("image_index0", 0))
+        noise = None if lib_rng else torch.zeros(1, 4, Hc, Wc, **f32)      # the noise belongs to the canvas
+        noise_used = torch.empty(1, 4, Hc, Wc, **f32) if (lib_rng and trace is not None) else None
+        mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
+        have_loss = False
+
+        def forward_chunk(ce, a, b):
+            ops.tile_gather(x_state, ce.x_in, org[a:b])
+            ce.run_forward()
+        k = 0
+        for idx in range(first, last - 1, -1):
+            guided, freeze, alt = sched[T - 1 - idx]
+            for sub in range(alt):
+                final = sub == alt - 1
+                if source == "fn":
+                    noise.copy_(noise_fn(k, noise.shape))
+                elif source == "aten":
+                    if draw_measurement_noise:
+                        torch.randn_like(y)
+                    noise.normal_()
+                for e2 in engs.values():                  # (every engine's timestep vector from the same step counter: `_fused_loop`)
+                    if e2 is not eng:
+                        ops.fetch_coefs(table, step, 0, coef, e2.t_dev, e2.B)
+                ops.fetch_coefs(table, step, -1 if final else 0, coef, eng.t_dev, eng.B)
+                if trace is not None:
+                    rec = {"idx": idx, "sub": sub, "x_in": x_state.clone()}
+                for a, b in chunks:
+                    ce = engs[b - a]
+                    forward_chunk(ce, a, b)
+                    if not single:
+                        out_tiles[a:b].copy_(ce.out)
+                ops.tile_blend(eng.out if single else out_tiles, model_out, org, *weights)
+                ops.posterior(model_out, x_state, coef, x0, mean, logvar, 1, HW, mk, vk, x0_raw)
+                gg = dxu = grad_out = None
+                if guided:
+                    cond.loss_grad_x0(x0, y, freeze_phi=freeze, g_out=g, phi=phi, loss_out=loss_all, **mk_rows)
+                    have_loss = True
+                    if x0_raw is not None:
+                        ops.clamp_bwd(g, x0_raw)
+                    ops.posterior_bwd(g, coef, d_out, 1, HW)
+                    for a, b in chunks:
+                        ce = engs[b - a]
+                        if not single:                    # this engine's activations are another chunk's by now
+                            forward_chunk(ce, a, b)
+                        ops.tile_gather(d_out, ce.d_out, org[a:b], *weights)
+                        ce.run_backward()
+                        if not single:
+                            dx_tiles[a:b].copy_(ce.dx)
+                    ops.tile_blend(eng.dx if single else dx_tiles, dx, org)
+                    gg, dxu = g, dx
+                    grad_out = torch.empty_like(g) if trace is not None else None
+                sc, cl = (scale4, clip) if guided else (None, -1.0)
+                if lib_rng:
+                    ops.guide_update_rng_sub(mean, logvar, gg, dxu, coef, sc, cl, x_state, grad_out, noise_used, 1, HW, seed, step,
+                                             step_offset=1 if final else 0, sub=sub, img0=img_base, img_stride=1)
+                else:
+                    ops.guide_update(mean, logvar, gg, dxu, noise, coef, sc, cl, x_state, grad_out, 1, HW)
+                if trace is not None:
+                    rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out.clone(),
+                               loss=loss_all.clone() if have_loss else None, phi=phi.clone(), step=step.clone())
+                    if noise_used is not None:
+                        rec["noise"] = noise_used.clone()
+                    if guided:
+                        rec["grad"] = grad_out
+                    trace.append(rec)
+                k += 1
+            if records is not None and ((idx % record_every == 0) or idx == 0 or idx == 999):
+                records.append((idx, x0.detach().cpu()))
+        img = x_state.clone()
+        if record and records:
+            self._save_process_grid(records, kwargs.get("save_grids_path"), kwargs.get("original_file_name"))
+        variables = cond.operator.optimize(freeze_phi=True)
+        loss_np = loss_all.detach().cpu().numpy() if have_loss else None
+        return img, variables, loss_np, x0.detach().cpu()
+
     @staticmethod
     def _save_process_grid(records, save_grids_path, original_file_name):
         """`<name>_process.png` of the reference (:308-333): clipped RGB of image 0 on the first row, the
@@ -549,10 +794,12 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ public loop
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root,
                       pretrain_model=None, image_idx=None, record_every=150, rgb_guidance=False,
-                      sample_pattern=None, measurement_mask=None, **kwargs):
+                      sample_pattern=None, measurement_mask=None, tiling=None, **kwargs):
         """measurement_mask: a per-pixel validity mask of the measurement ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
         [0, 1]; `ConditioningMethod.set_measurement_mask`), handed to the conditioner for this chain -- the fused loop and
-        `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default)."""
+        `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default).
+        tiling: `dict(tile=, stride=, window=)` (`parse_tiling`) runs ONE canvas larger than the network's grid as overlapping
+        tiles of the network's size (`_tiled_loop`); None: nothing changes."""
         from .posterior_mean_variance import PreviousXMeanProcessor
         if measurement_mask is not None:
             cond_obj = getattr(measurement_cond_fn, "__self__", None)
@@ -573,6 +820,9 @@ class GaussianDiffusion:
             # the reference's record branch reads the depth channel of pred_xstart (gaussian_diffusion.py:319) and fails there
             raise IndexError(f"index 3 is out of bounds for dimension 1 with size {x_start.shape[1]}: record=True snapshots the "
                              "depth channel of pred_xstart, which a 3-channel (RGB) chain does not have (as in the reference)")
+        if tiling is not None:
+            return self._tiled_loop(model, measurement_cond_fn, x_start, measurement, pretrain_model, rgb_guidance, sample_pattern,
+                                    kwargs, tiling, record=record, record_every=record_every)
         cond = self._fast_path_ok(model, measurement_cond_fn, pretrain_model, rgb_guidance, sample_pattern, tuple(x_start.shape))
         if cond is not None:
             return self._fused_loop(model, cond, x_start, measurement, sample_pattern, kwargs, record=record,

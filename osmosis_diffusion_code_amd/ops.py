@@ -631,3 +631,43 @@ def recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, 
     d.ay, d.by, d.ax, d.bx = (float(v) for v in amap)
     d.mode, d.radius, d.sigma_s, d.sigma_r = int(mode), int(radius), float(sigma_s), float(sigma_r)
     call("osm_recon_fullres", C.byref(d), _s(), keep=(d, depth, guide, image, phi_a, phi_b, phi_inf, rgb, rgb_u8, depth_full))
+
+
+# ----------------------------------------------------------------------------- tiled sampling (canvas <-> overlapping tiles)
+def _tile_args(what, canvas, tiles, origins, wy, wx, inv_norm):
+    """Shapes of one osm_tile_* call: canvas [C,Hc,Wc] (or [1,C,Hc,Wc]), tiles [n,C,th,tw], origins int32 [n,2] on the device,
+    wy [th] / wx [tw] / inv_norm [Hc,Wc] all None or all given."""
+    if canvas.dim() == 4 and canvas.shape[0] == 1:
+        canvas = canvas[0]
+    if canvas.dim() != 3 or tiles.dim() != 4 or tiles.shape[1] != canvas.shape[0]:
+        raise _lib.OsmosisHipError(f"{what}: expected canvas [C,Hc,Wc] and tiles [n,C,th,tw], got {tuple(canvas.shape)} and "
+                                   f"{tuple(tiles.shape)}")
+    Cc, Hc, Wc = canvas.shape
+    n, _, th, tw = tiles.shape
+    weights = (wy, wx, inv_norm)
+    if any(w is None for w in weights) != all(w is None for w in weights):
+        raise _lib.OsmosisHipError(f"{what}: wy, wx and inv_norm are given together or not at all")
+    for t in (canvas, tiles) + tuple(w for w in weights if w is not None):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError(f"{what} takes contiguous fp32 tensors")
+    if origins.dtype != torch.int32 or not origins.is_contiguous() or tuple(origins.shape) != (n, 2):
+        raise _lib.OsmosisHipError(f"{what}: origins must be a contiguous int32 [{n},2] tensor, got {tuple(origins.shape)} {origins.dtype}")
+    if wy is not None and (wy.numel() != th or wx.numel() != tw or inv_norm.numel() != Hc * Wc):
+        raise _lib.OsmosisHipError(f"{what}: expected wy [{th}], wx [{tw}] and inv_norm [{Hc},{Wc}]")
+    return canvas, (n, Cc, Hc, Wc, th, tw)
+
+
+def tile_gather(canvas, tiles, origins, wy=None, wx=None, inv_norm=None):
+    """tiles[t,c,y,x] = canvas[c,oy+y,ox+x] k (osm_tile_gather): k = 1 without weights (a bit-exact crop), else
+    wy[y] wx[x] inv_norm[oy+y,ox+x] -- the adjoint of `tile_blend` with the same weights."""
+    canvas, dims = _tile_args("tile_gather", canvas, tiles, origins, wy, wx, inv_norm)
+    call("osm_tile_gather", ptr(canvas), ptr(tiles), ptr(origins), ptr(wy), ptr(wx), ptr(inv_norm), *dims, _s(),
+         keep=(canvas, tiles, origins, wy, wx, inv_norm))
+
+
+def tile_blend(tiles, canvas, origins, wy=None, wx=None, inv_norm=None):
+    """canvas[c,Y,X] = inv_norm[Y,X] sum_t wy wx tiles[t,c,Y-oy,X-ox] over the covering tiles in ascending t (osm_tile_blend; no
+    weights: the plain sum; an uncovered pixel is 0).  Deterministic: gather form, no atomics."""
+    canvas, dims = _tile_args("tile_blend", canvas, tiles, origins, wy, wx, inv_norm)
+    call("osm_tile_blend", ptr(tiles), ptr(canvas), ptr(origins), ptr(wy), ptr(wx), ptr(inv_norm), *dims, _s(),
+         keep=(canvas, tiles, origins, wy, wx, inv_norm))

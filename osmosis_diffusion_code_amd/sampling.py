@@ -16,6 +16,9 @@ Beyond the reference (which only ever writes 256 x 256 results):
 
     reconstruct_full_resolution(post, original, geometry, operator_cfg, ...)
                                             the physical model inverted on the ORIGINAL pixel grid from phi and the upsampled depth
+    restore_image(..., tiling=) / config key `tiling: {tile, stride, window}`
+                                            a photo larger than the network's grid sampled as overlapping tiles of the network's size
+    tile_grid(Hc, Wc, tile, stride, window) the tiles of a canvas: origins, the separable window and the blend normalisation
 """
 import os
 
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 from .guided_diffusion.condition_methods import get_conditioning_method
-from .guided_diffusion.gaussian_diffusion import create_sampler
+from .guided_diffusion.gaussian_diffusion import create_sampler, parse_tiling, tile_grid  # noqa: F401  (tile_grid: public helper)
 from .guided_diffusion.measurements import get_noise, get_operator
 from .osmosis_utils import utils as utilso
 from .sharding import shard_indices
@@ -311,7 +314,7 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
 
 
 def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
-                  postprocess_batch=True, mask=None, **loop_kwargs):
+                  postprocess_batch=True, mask=None, tiling=None, **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -325,7 +328,19 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     `mask` (and / or the optional config key `measurement.mask`, see `measurement_mask`): a per-pixel validity mask of the
     measurement on the network grid (`data.transform_mask` takes one from the photo's resolution there).  The chain is guided
     through it (`p_sample_loop(measurement_mask=)`) and every result carries it as `mask` [B,3,H,W]; without either, nothing
-    is passed and the results have no such key."""
+    is passed and the results have no such key.
+
+    `tiling` (or the optional top-level config key `tiling`; the argument wins): `{tile, stride, window}` (`parse_tiling`; unknown
+    keys raise) for ONE image larger than the network's grid, e.g. the 512-class grid of `data.fit_transform(size=512)`: the
+    network sees overlapping tiles of side `tile`, everything else acts on the whole image (`p_sample_loop(tiling=)`).  Every
+    result then carries `tiling` = {tile, stride, window, origins int32 [n,2]}; without it nothing is passed and there is no such key."""
+    tiling = tiling if tiling is not None else cfg.get("tiling")
+    tiling_info = None
+    if tiling is not None:
+        th, tw, sy, sx, window = parse_tiling(tiling)
+        tiling_info = {"tile": (th, tw), "stride": (sy, sx), "window": window,
+                       "origins": tile_grid(ref_img.shape[-2], ref_img.shape[-1], (th, tw), (sy, sx), window)[0]}
+        loop_kwargs = dict(loop_kwargs, tiling={"tile": (th, tw), "stride": (sy, sx), "window": window})
     device = device if device is not None else ref_img.device
     measure, cond_cfg = cfg["measurement"], cfg["conditioning"]
     op_cfg = dict(measure["operator"])
@@ -377,6 +392,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
         post.update(sample=sample.detach().cpu(), pred_xstart=out_xstart, measurement=y_n.detach().cpu())
         if m_dev is not None:
             post["mask"] = m_dev.detach().cpu()
+        if tiling_info is not None:
+            post["tiling"] = tiling_info
         results.append(post)
     return results
 
@@ -392,7 +409,7 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
-                   geometries=None, full_res_upsample="bilinear", masks=None, **loop_kwargs):
+                   geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -401,7 +418,11 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     `manual_seed` -- the same x_T / noise stream each, so image i's result is the one a batch-1 run gives.
 
     `originals` (list of `to_tensor` photos [3,H0,W0]) with `geometries` (their `data.Geometry`) attaches
-    `reconstruct_full_resolution(..., upsample=full_res_upsample)` to every result that carries phi, under `full_res`."""
+    `reconstruct_full_resolution(..., upsample=full_res_upsample)` to every result that carries phi, under `full_res`.
+
+    `tiling` goes to `restore_image` as it is (one canvas per call: `batch_size` stays 1 with it)."""
+    if tiling is not None:
+        loop_kwargs = dict(loop_kwargs, tiling=tiling)
     if (originals is None) != (geometries is None):
         raise ValueError("originals and geometries go together")
     if masks is not None and len(masks) != len(images):

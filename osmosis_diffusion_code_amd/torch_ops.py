@@ -32,7 +32,7 @@ operator output -- outputs are functions of the inputs alone, so fake-tensor tra
 operators) and raises instead of differentiating through activations a later forward has overwritten."""
 import itertools
 import weakref
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -542,7 +542,77 @@ def _recon_fullres_fake(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, 
     return (image.new_empty((3, Hc, Wc)), image.new_empty((Hc, Wc, 3), dtype=torch.uint8), image.new_empty((Hc, Wc)))
 
 
+# ---- tiled sampling: canvas [C,Hc,Wc] <-> overlapping tiles [n,C,th,tw]; each operator is the other's backward (same weights)
+def _tile_weights(name, wy, wx, inv_norm):
+    ws = (wy, wx, inv_norm)
+    if any(w is None for w in ws) != all(w is None for w in ws):
+        raise OsmosisHipError(f"{name}: wy, wx and inv_norm are given together or not at all")
+    return tuple(None if w is None else w.detach().contiguous() for w in ws)
+
+
+@torch.library.custom_op("osmosis::tile_gather", mutates_args=(), device_types="cuda")
+def tile_gather(canvas: torch.Tensor, origins: torch.Tensor, th: int, tw: int, wy: Optional[torch.Tensor] = None,
+                wx: Optional[torch.Tensor] = None, inv_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tiles [n,C,th,tw] of canvas [C,Hc,Wc] at origins int32 [n,2] (y, x) (osm_tile_gather): a bit-exact crop without weights,
+    else scaled by wy[y] wx[x] inv_norm[oy+y,ox+x].  Backward: osmosis::tile_blend with the same weights."""
+    if canvas.dim() != 3:
+        raise OsmosisHipError("osmosis::tile_gather: canvas must be [C,Hc,Wc]")
+    tiles = torch.empty((origins.shape[0], canvas.shape[0], th, tw), device=canvas.device, dtype=torch.float32)
+    ops.tile_gather(canvas.contiguous(), tiles, origins.contiguous(), *_tile_weights("osmosis::tile_gather", wy, wx, inv_norm))
+    return tiles
+
+
+@tile_gather.register_fake
+def _tile_gather_fake(canvas, origins, th, tw, wy=None, wx=None, inv_norm=None):
+    return canvas.new_empty((origins.shape[0], canvas.shape[0], th, tw))
+
+
+@torch.library.custom_op("osmosis::tile_blend", mutates_args=(), device_types="cuda")
+def tile_blend(tiles: torch.Tensor, origins: torch.Tensor, Hc: int, Wc: int, wy: Optional[torch.Tensor] = None,
+               wx: Optional[torch.Tensor] = None, inv_norm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """canvas [C,Hc,Wc] = inv_norm * sum over the covering tiles (ascending index, fp32) of wy wx tiles (osm_tile_blend; without
+    weights the plain sum; an uncovered pixel is 0).  Backward: osmosis::tile_gather with the same weights."""
+    if tiles.dim() != 4:
+        raise OsmosisHipError("osmosis::tile_blend: tiles must be [n,C,th,tw]")
+    canvas = torch.empty((tiles.shape[1], Hc, Wc), device=tiles.device, dtype=torch.float32)
+    ops.tile_blend(tiles.contiguous(), canvas, origins.contiguous(), *_tile_weights("osmosis::tile_blend", wy, wx, inv_norm))
+    return canvas
+
+
+@tile_blend.register_fake
+def _tile_blend_fake(tiles, origins, Hc, Wc, wy=None, wx=None, inv_norm=None):
+    return tiles.new_empty((tiles.shape[1], Hc, Wc))
+
+
+def _tile_gather_setup(ctx, inputs, output):
+    canvas, origins, _th, _tw, wy, wx, inv_norm = inputs
+    ctx.hw = (canvas.shape[1], canvas.shape[2])
+    ctx.save_for_backward(origins, *(w for w in (wy, wx, inv_norm) if w is not None))
+
+
+def _tile_gather_backward(ctx, grad):
+    origins, *ws = ctx.saved_tensors
+    ws = ws if ws else [None, None, None]
+    return (torch.ops.osmosis.tile_blend(grad.contiguous(), origins, ctx.hw[0], ctx.hw[1], *ws), None, None, None, None, None, None)
+
+
+def _tile_blend_setup(ctx, inputs, output):
+    tiles, origins, _Hc, _Wc, wy, wx, inv_norm = inputs
+    ctx.hw = (tiles.shape[2], tiles.shape[3])
+    ctx.save_for_backward(origins, *(w for w in (wy, wx, inv_norm) if w is not None))
+
+
+def _tile_blend_backward(ctx, grad):
+    origins, *ws = ctx.saved_tensors
+    ws = ws if ws else [None, None, None]
+    return (torch.ops.osmosis.tile_gather(grad.contiguous(), origins, ctx.hw[0], ctx.hw[1], *ws), None, None, None, None, None, None)
+
+
+tile_gather.register_autograd(_tile_gather_backward, setup_context=_tile_gather_setup)
+tile_blend.register_autograd(_tile_blend_backward, setup_context=_tile_blend_setup)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
-       "ps_loss_grad_mc", "exposure_mask", "recon_fullres") + OPS_C
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend") + OPS_C
