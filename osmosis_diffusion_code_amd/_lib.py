@@ -1,4 +1,4 @@
-"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h).
+"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h and include/osmosis_linop.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -163,6 +163,11 @@ for _n in ("osm_conv2d_nhwc", "osm_gn_stats", "osm_gn_apply", "osm_gn_fwd", "osm
 _SIGS["osm_half_to_f32"] = [_P, _LL, _P, _LL, _LL, _I, _P]
 _SIGS["osm_f32_to_half"] = [_P, _LL, _P, _LL, _LL, _I, _P]
 EXPORTS = sorted(list(_SIGS) + ["osm_last_error", "osm_packed_weight_elems", "osm_winograd_weight_elems", "osm_quantile_abs_ws_bytes"])
+# the entry points of the library's second header, include/osmosis_linop.h (separable banded linear operators)
+_SIGS_LINOP = {
+    "osm_linop_apply": [_P, _P, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _I, _I, _I, _I, _I, _P],
+}
+EXPORTS_LINOP = sorted(_SIGS_LINOP)
 
 _lib = None
 _lock = threading.Lock()
@@ -181,7 +186,7 @@ def load():
                     "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
-            for name, argtypes in _SIGS.items():
+            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

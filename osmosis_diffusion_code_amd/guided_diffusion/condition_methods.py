@@ -412,9 +412,9 @@ class PosteriorSampling(ConditioningMethod):
         self._states = {}
 
     def hip_ok(self, channels: int = 4) -> bool:
-        from .measurements import _IdentityOperator
-        return isinstance(self.operator, _IdentityOperator) and getattr(self.noiser, "__name__", None) == "gaussian" and \
-            self.scale.numel() in (1, channels)
+        from .measurements import SeparableOperator, _IdentityOperator
+        return isinstance(self.operator, (_IdentityOperator, SeparableOperator)) and \
+            getattr(self.noiser, "__name__", None) == "gaussian" and self.scale.numel() in (1, channels)
 
     def scale4(self, device, channels: int = 4):
         """The per-channel step size as a device vector of `channels` entries (1 entry: the same for every channel)."""
@@ -427,7 +427,12 @@ class PosteriorSampling(ConditioningMethod):
         """loss[b] = ||y[b] - x0[b, 0:3]||_2 and g = d loss / d x0 (zero on any channel beyond the colours), per image (B = 1: the
         reference's batch-global norm).  x0 [B,C,H,W] with C = 4 (RGBD) or 3 (the RGB model family), y [B,3,H,W] contiguous device
         fp32.  With a mask M (`mask`: [B,3,HW] rows, default the one of `set_measurement_mask`): loss[b] = ||M (y - x0[0:3])||,
-        g = -M^2 (y - x0) / loss, and g = 0 for an image that is masked out entirely."""
+        g = -M^2 (y - x0) / loss, and g = 0 for an image that is masked out entirely.
+        With a `SeparableOperator` A (blur, super-resolution) the measurement y [B,3,h,w] lives on A's own grid, and so does the mask:
+        loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`)."""
+        from .measurements import SeparableOperator
+        if isinstance(self.operator, SeparableOperator):
+            return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask)
         B, C, HW = x0.shape[0], x0.shape[1], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or C not in (3, 4):
             raise ValueError("expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,H,W]")
@@ -460,6 +465,39 @@ class PosteriorSampling(ConditioningMethod):
             ops.phys_optimize(st["desc"], x0.contiguous(), y.contiguous(), st["phi"], st["part"], st["red"], loss, g, 1, True)
         else:
             ops.ps_loss_grad_c(x0.contiguous(), y.contiguous(), st["part"], loss, g, B, C, HW)
+        return g.view(x0.shape), loss
+
+    def _loss_grad_x0_separable(self, x0, y, g_out=None, loss_out=None, mask=None):
+        """The data term through a separable linear operator, three stream-ordered launches and no host sync:
+        Ax = A x0[:, 0:3] (osm_linop_apply, P = 3, image stride C HW); loss[b] = ||M (y - Ax)|| and r = d loss / d Ax (the identity
+        term's own reduction, osm_ps_loss_grad_c / _mc at C = 3 on the measurement's h w); g[:, 0:3] = A^T r with the transposed
+        tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3)."""
+        B, C, H, W = x0.shape
+        h, w = self.operator.out_shape(H, W)
+        if C not in (3, 4) or tuple(y.shape) != (B, 3, h, w):
+            raise ValueError(f"expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,{h},{w}], got {tuple(x0.shape)} and {tuple(y.shape)}")
+        HW, hw = H * W, h * w
+        key = ("separable", B, H, W, str(x0.device), C)
+        st = self._states.get(key)
+        if st is None:
+            f32 = dict(device=x0.device, dtype=torch.float32)
+            st = {"part": torch.empty(B * ops.phys_nblk(hw), **f32), "loss": torch.zeros(B, **f32), "g": torch.empty(B, C, HW, **f32),
+                  "Ax": torch.empty(B, 3, hw, **f32), "r": torch.empty(B, 3, hw, **f32)}
+            while len(self._states) >= 4:
+                self._states.pop(next(iter(self._states)))
+            self._states[key] = st
+        g = g_out if g_out is not None else st["g"]
+        loss = loss_out if loss_out is not None else st["loss"]
+        if mask is None:
+            mask = self.measurement_mask(B, hw, x0.device)
+        tabs = self.operator.tables(H, W, x0.device)
+        Ax, r = st["Ax"], st["r"]
+        ops.linop_apply(x0.contiguous(), Ax, *tabs["fwd"], B, 3, C * HW, 3 * hw, H, W)
+        if mask is not None:
+            ops.ps_loss_grad_mc(Ax, y.contiguous(), mask, st["part"], loss, r, B, 3, hw)
+        else:
+            ops.ps_loss_grad_c(Ax, y.contiguous(), st["part"], loss, r, B, 3, hw)
+        ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)
         return g.view(x0.shape), loss
 
     def conditioning(self, x_prev, x_t, x_0_hat, measurement, **kwargs):

@@ -452,7 +452,9 @@ class GaussianDiffusion:
         scale4 = cond.scale4(dev, C) if ps else cond.scale4(dev)
         clip = -1.0 if ps else cond.clip_value
         y = measurement.detach().to(dev, torch.float32).contiguous()
-        mask = cond.measurement_mask(B, HW, dev)          # [B,3,HW] rows like y, or None (`measurement_mask=`)
+        # [B,3,hw] rows like y, or None (`measurement_mask=`): the mask lives on the measurement's grid (the image's, except for a
+        # downsampling operator of the 'ps' branch)
+        mask = cond.measurement_mask(B, y.shape[2] * y.shape[3] if y.dim() == 4 else HW, dev)
         phi = None if ps else cond.operator.phi
         single = len(chunks) == 1
         x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
@@ -805,9 +807,9 @@ class GaussianDiffusion:
             cond_obj = getattr(measurement_cond_fn, "__self__", None)
             if not hasattr(cond_obj, "set_measurement_mask"):
                 raise TypeError("measurement_mask needs a conditioner with set_measurement_mask (a ConditioningMethod)")
-            if tuple(measurement_mask.shape[2:]) != tuple(x_start.shape[2:]):
-                raise ValueError(f"measurement_mask {tuple(measurement_mask.shape)} does not match the image grid "
-                                 f"{tuple(x_start.shape[2:])}")
+            if tuple(measurement_mask.shape[2:]) != tuple(measurement.shape[2:]):
+                raise ValueError(f"measurement_mask {tuple(measurement_mask.shape)} does not match the measurement's grid "
+                                 f"{tuple(measurement.shape[2:])} (the image grid, or a downsampling operator's own)")
             cond_obj.set_measurement_mask(measurement_mask, batch=x_start.shape[0], device=x_start.device)
         if isinstance(self.mean_processor, PreviousXMeanProcessor) and not (
                 rgb_guidance and getattr(type(self), "p_sample", None) is DDIM.p_sample):

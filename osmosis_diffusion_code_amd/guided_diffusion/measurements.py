@@ -89,6 +89,188 @@ class RGBGuidanceOperator(_IdentityOperator):
     pass
 
 
+# ----------------------------------------------------------------------------- separable banded linear operators
+# A = R_h (x) R_w on each colour plane; a factor R [n_out, n_in] travels as a band table: row i has its K non-zeros at the columns
+# start[i] .. start[i] + K - 1 with the values wt[i] (osm_linop_apply, include/osmosis_linop.h).  The transpose of a band is a
+# band, so the adjoint is the same kernel with the transposed table.
+def check_band(start, wt, n_in):
+    """Raise ValueError unless every row of the band table reads inside [0, n_in): 0 <= start and start + K <= n_in."""
+    start, wt = np.asarray(start), np.asarray(wt)
+    if wt.ndim != 2 or start.shape != (wt.shape[0],) or wt.shape[1] < 1:
+        raise ValueError(f"a band table is start [n_out] with wt [n_out, K >= 1], got {start.shape} and {wt.shape}")
+    if start.size and (int(start.min()) < 0 or int(start.max()) + wt.shape[1] > n_in):
+        raise ValueError(f"band table reads outside [0, {n_in}): start in [{int(start.min())}, {int(start.max())}], K = {wt.shape[1]}")
+
+
+def dense_to_band(R):
+    """(start int32 [n_out], wt float64 [n_out, K]) of a dense float64 matrix: K = the widest row span of non-zeros, a row's
+    window shifted left where it would leave the matrix (the extra entries are the matrix's own zeros)."""
+    R = np.asarray(R, dtype=np.float64)
+    n_out, n_in = R.shape
+    nz = R != 0
+    first = np.where(nz.any(1), nz.argmax(1), 0)
+    last = np.where(nz.any(1), n_in - 1 - nz[:, ::-1].argmax(1), 0)
+    K = int((last - first).max()) + 1
+    start = np.minimum(first, n_in - K).astype(np.int32)
+    wt = R[np.arange(n_out)[:, None], start[:, None] + np.arange(K)[None, :]]
+    check_band(start, wt, n_in)
+    return start, np.ascontiguousarray(wt)
+
+
+def band_to_dense(start, wt, n_in):
+    """The dense matrix [n_out, n_in] of a band table, in the table's dtype."""
+    check_band(start, wt, n_in)
+    wt = np.asarray(wt)
+    R = np.zeros((wt.shape[0], n_in), dtype=wt.dtype)
+    R[np.arange(wt.shape[0])[:, None], np.asarray(start)[:, None] + np.arange(wt.shape[1])[None, :]] = wt
+    return R
+
+
+def _linop_op():
+    from .. import torch_ops  # noqa: F401  (registers osmosis::linop_apply)
+    return torch.ops.osmosis.linop_apply
+
+
+class SeparableOperator(LinearOperator):
+    """A linear map of the three colour planes that factors per axis, measurement [B,3,h,w] = R_h image R_w^T with (h, w) =
+    `out_shape(H, W)`: no learnable parameters.  A subclass gives `axis_matrix(n_in)` (dense float64, built once per size on the
+    host); the band tables of it and of its transpose (taken in float64 from the forward table, then cast to fp32) are cached per
+    (H, W, device).  `forward` / `transpose` run osm_linop_apply on device tensors through `osmosis::linop_apply`, which is
+    differentiable (its backward is the same operator with the other pair of tables), so autograd conditioning works too."""
+
+    def __init__(self, device, batch_size=1, **kwargs):
+        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.batch_size = batch_size
+        self._host, self._dev = {}, {}
+
+    def axis_matrix(self, n_in):
+        raise NotImplementedError
+
+    def axis_out(self, n_in):
+        return n_in
+
+    def axis_in(self, n_out):
+        """The image size along an axis whose measurement has n_out samples (`transpose` takes its shape from this)."""
+        return n_out
+
+    def out_shape(self, H, W):
+        return self.axis_out(H), self.axis_out(W)
+
+    def host_tables(self, H, W):
+        """{'fwd': (start_h, wt_h, start_w, wt_w), 'adj': the same of the transposes}: numpy, start int32, wt fp32."""
+        tabs = self._host.get((H, W))
+        if tabs is None:
+            fwd, adj = [], []
+            for n in (H, W):
+                start, wt = dense_to_band(self.axis_matrix(n))
+                tstart, twt = dense_to_band(band_to_dense(start, wt, n).T)      # float64 throughout; cast below
+                fwd += [start, wt.astype(np.float32)]
+                adj += [tstart, twt.astype(np.float32)]
+            tabs = self._host[(H, W)] = {"fwd": tuple(fwd), "adj": tuple(adj)}
+        return tabs
+
+    def tables(self, H, W, device=None):
+        """`host_tables` as device tensors."""
+        device = torch.device(device if device is not None else self.device)
+        key = (H, W, str(device))
+        tabs = self._dev.get(key)
+        if tabs is None:
+            host = self.host_tables(H, W)
+            tabs = self._dev[key] = {k: tuple(torch.from_numpy(a).to(device).contiguous() for a in v) for k, v in host.items()}
+        return tabs
+
+    def forward(self, data, **kwargs):
+        H, W = data.shape[-2:]
+        t = self.tables(H, W, data.device)
+        h, w = self.out_shape(H, W)
+        return _linop_op()(data, *t["fwd"], h, w, *t["adj"])
+
+    def transpose(self, data, **kwargs):
+        H, W = self.axis_in(data.shape[-2]), self.axis_in(data.shape[-1])
+        t = self.tables(H, W, data.device)
+        return _linop_op()(data, *t["adj"], H, W, *t["fwd"])
+
+
+@register_operator(name="gaussian_blur")
+class GaussianBlurOperator(SeparableOperator):
+    """Blur with the k x k kernel g (x) g, g[t] ~ exp(-(t - r)^2 / 2 sigma^2), r = k // 2, normalised to sum 1 in float64, over the
+    image padded by reflection (torch 'reflect': no edge repeat) -- the padding is folded into the band, a reflected tap adds onto
+    the in-range column.  DPS config keys: kernel_size (odd), intensity (sigma).  The measurement has the image's size."""
+
+    def __init__(self, device, kernel_size=61, intensity=3.0, batch_size=1, **kwargs):
+        super().__init__(device, batch_size, **kwargs)
+        self.kernel_size, self.intensity = int(kernel_size), float(intensity)
+        if self.kernel_size != kernel_size or self.kernel_size < 1 or self.kernel_size % 2 == 0:
+            raise ValueError(f"gaussian_blur: kernel_size must be a positive odd integer, got {kernel_size!r}")
+        if not self.intensity > 0:
+            raise ValueError(f"gaussian_blur: intensity (sigma) must be positive, got {intensity!r}")
+
+    def taps(self):
+        r = self.kernel_size // 2
+        g = np.exp(-((np.arange(self.kernel_size, dtype=np.float64) - r) ** 2) / (2.0 * self.intensity ** 2))
+        return g / g.sum()
+
+    def axis_matrix(self, n_in):
+        r = self.kernel_size // 2
+        if r >= n_in:
+            raise ValueError(f"gaussian_blur: reflection padding needs kernel_size // 2 = {r} < the image side {n_in}")
+        g = self.taps()
+        R = np.zeros((n_in, n_in), dtype=np.float64)
+        for i in range(n_in):
+            for t in range(self.kernel_size):
+                c = i + t - r
+                c = -c if c < 0 else (2 * (n_in - 1) - c if c >= n_in else c)
+                R[i, c] += g[t]
+        return R
+
+
+def _cubic(x, a=-0.5):
+    x = np.abs(x)
+    return np.where(x < 1, ((a + 2) * x - (a + 3)) * x * x + 1, np.where(x < 2, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+@register_operator(name="super_resolution")
+class SuperResolutionOperator(SeparableOperator):
+    """Downsampling by the integer `scale_factor` s >= 2: the measurement is H // s x W // s (H and W multiples of s).
+    method 'bicubic' IS F.interpolate(mode='bicubic', align_corners=False, antialias=True), its weights computed analytically
+    (scale = n_in / n_out, support = 2 scale, center = scale (i + 1/2), xmin = max(0, int(center - support + 1/2)), xsize =
+    min(int(center + support + 1/2), n_in) - xmin, w_j = cubic((j + xmin - center + 1/2) / scale) with a = -0.5, normalised by
+    their sum: a band 4 s wide); 'box' is the s x s mean (avg_pool2d)."""
+
+    def __init__(self, device, scale_factor=4, method="bicubic", batch_size=1, **kwargs):
+        super().__init__(device, batch_size, **kwargs)
+        self.scale_factor, self.method = int(scale_factor), str(method)
+        if self.scale_factor != scale_factor or self.scale_factor < 2:
+            raise ValueError(f"super_resolution: scale_factor must be an integer >= 2, got {scale_factor!r}")
+        if self.method not in ("bicubic", "box"):
+            raise ValueError(f"super_resolution: method must be 'bicubic' or 'box', got {method!r}")
+
+    def axis_out(self, n_in):
+        if n_in % self.scale_factor != 0 or n_in < self.scale_factor:
+            raise ValueError(f"super_resolution: the image side {n_in} is no multiple of scale_factor {self.scale_factor}")
+        return n_in // self.scale_factor
+
+    def axis_in(self, n_out):
+        return n_out * self.scale_factor
+
+    def axis_matrix(self, n_in):
+        n_out, s = self.axis_out(n_in), self.scale_factor
+        R = np.zeros((n_out, n_in), dtype=np.float64)
+        if self.method == "box":
+            for i in range(n_out):
+                R[i, i * s:(i + 1) * s] = 1.0 / s
+            return R
+        scale = n_in / n_out
+        support = 2.0 * scale
+        for i in range(n_out):
+            center = scale * (i + 0.5)
+            xmin = max(0, int(center - support + 0.5))
+            xsize = min(int(center + support + 0.5), n_in) - xmin
+            w = _cubic((np.arange(xsize, dtype=np.float64) + xmin - center + 0.5) / scale)
+            R[i, xmin:xmin + xsize] = w / w.sum()
+        return R
+
+
 class LearnableOperator(ABC):
     @abstractmethod
     def forward(self, data, **kwargs):

@@ -671,3 +671,27 @@ def tile_blend(tiles, canvas, origins, wy=None, wx=None, inv_norm=None):
     canvas, dims = _tile_args("tile_blend", canvas, tiles, origins, wy, wx, inv_norm)
     call("osm_tile_blend", ptr(tiles), ptr(canvas), ptr(origins), ptr(wy), ptr(wx), ptr(inv_norm), *dims, _s(),
          keep=(canvas, tiles, origins, wy, wx, inv_norm))
+
+
+# ----------------------------------------------------------------------------- separable banded linear operators
+def linop_apply(x, out, start_h, wt_h, start_w, wt_w, B, P, x_img_stride, out_img_stride, Hin, Win, zero_planes=0):
+    """out[b,p,i,j] = sum_a wt_h[i][a] sum_c wt_w[j][c] x[b,p,start_h[i]+a,start_w[j]+c] for p < P (osm_linop_apply,
+    include/osmosis_linop.h); `zero_planes` further planes of every output image are written as 0.  x / out: contiguous fp32
+    with image strides in elements (the colour planes of a [B,4,HW] tensor: stride 4 HW, P = 3); tables on the device: start int32
+    [n_out], wt fp32 [n_out,K].  With the transposed tables the call is the exact adjoint; deterministic (gather form, no atomics)."""
+    for t in (x, out, wt_h, wt_w):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("linop_apply takes contiguous fp32 tensors")
+    for s, w in ((start_h, wt_h), (start_w, wt_w)):
+        if s.dtype != torch.int32 or not s.is_contiguous() or w.dim() != 2 or s.dim() != 1 or s.shape[0] != w.shape[0]:
+            raise _lib.OsmosisHipError(f"linop_apply: a band table is start int32 [n] with wt fp32 [n,K], got {tuple(s.shape)} {s.dtype} "
+                                       f"and {tuple(w.shape)}")
+    (Hout, Kh), (Wout, Kw) = wt_h.shape, wt_w.shape
+    B, P, Z = int(B), int(P), int(zero_planes)
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * Hin * Win
+                   or out.numel() < (B - 1) * int(out_img_stride) + (P + Z) * Hout * Wout):
+        raise _lib.OsmosisHipError(f"linop_apply: x ({x.numel()} elements) / out ({out.numel()}) are smaller than {B} images of "
+                                   f"{P} x {Hin} x {Win} -> {P + Z} x {Hout} x {Wout} at strides {x_img_stride} / {out_img_stride}")
+    call("osm_linop_apply", ptr(x), ptr(out), ptr(start_h), ptr(wt_h), ptr(start_w), ptr(wt_w), B, P, int(x_img_stride),
+         int(out_img_stride), int(Hin), int(Win), int(Hout), int(Wout), int(Kh), int(Kw), Z, _s(),
+         keep=(x, out, start_h, wt_h, start_w, wt_w))

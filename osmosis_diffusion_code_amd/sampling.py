@@ -27,7 +27,7 @@ import torch
 
 from .guided_diffusion.condition_methods import get_conditioning_method
 from .guided_diffusion.gaussian_diffusion import create_sampler, parse_tiling, tile_grid  # noqa: F401  (tile_grid: public helper)
-from .guided_diffusion.measurements import get_noise, get_operator
+from .guided_diffusion.measurements import SeparableOperator, get_noise, get_operator
 from .osmosis_utils import utils as utilso
 from .sharding import shard_indices
 
@@ -143,6 +143,16 @@ def make_grid(tensors, nrow=8, padding=2, pad_value=0.0):
     return grid
 
 
+def _replicate_to(img, hw):
+    """[C,h,w] -> [C,H,W] by pixel replication (nearest neighbour): a measurement of a downsampling operator beside its sample in
+    a grid; an image already of that size is returned as it is."""
+    if tuple(img.shape[-2:]) == tuple(hw):
+        return img
+    ri = (torch.arange(hw[0]) * img.shape[-2]) // hw[0]
+    ci = (torch.arange(hw[1]) * img.shape[-1]) // hw[1]
+    return img[:, ri][:, :, ci]
+
+
 def output_images(post, ref_img, gt_rgb_01=None, gt_depth_01=None):
     """The uint8 arrays of the five images the reference writes for one restored image (osmosis_sampling.py:319-353):
     `input` = the reference image in [0,1], `rgb` = the clipped restoration, `depth_color` = viridis of the percentile-normalised
@@ -151,7 +161,7 @@ def output_images(post, ref_img, gt_rgb_01=None, gt_depth_01=None):
     clip_image(scale=False, move=False, is_uint8=True) (clamp, truncate)."""
     ref01 = 0.5 * (ref_img.detach().cpu()[0] + 1)
     col = depth_color(post)
-    tiles = [ref01, post["rgb_01_clip"], col]
+    tiles = [_replicate_to(ref01, post["rgb_01_clip"].shape[-2:]), post["rgb_01_clip"], col]
     if gt_rgb_01 is not None:
         tiles += [torch.zeros_like(post["rgb_01"]), gt_rgb_01, utilso.depth_tensor_to_color_image(gt_depth_01)]
     grid = make_grid(tiles, nrow=3, pad_value=1.0)
@@ -285,6 +295,27 @@ def rgb_guidance_result(sample, measurement):
             "measurement": measurement}
 
 
+def measurement_grid(operator_cfg, hw):
+    """(h, w) of the measurement `restore_image` derives from an image of size hw: the operator's `out_shape` for a blur /
+    super-resolution operator that simulates its measurement, hw itself otherwise (every other operator; `simulate: False`,
+    where the image handed in IS the measurement)."""
+    from .guided_diffusion import measurements
+    cls = measurements.__OPERATOR__.get(operator_cfg.get("name"))
+    if cls is None or not issubclass(cls, SeparableOperator) or not operator_cfg.get("simulate", True):
+        return tuple(hw)
+    kw = {k: v for k, v in operator_cfg.items() if k != "name"}
+    return tuple(cls(device="cpu", **kw).out_shape(int(hw[0]), int(hw[1])))
+
+
+def model_grid(model, ref_img):
+    """(H, W) of the image a chain produces when `ref_img` is not on the image's grid (a measurement handed in as it is): the
+    network's `image_size`."""
+    n = getattr(model, "image_size", None)
+    if n is None:
+        raise ValueError("simulate: False needs a network that states its image_size")
+    return (int(n), int(n)) if np.isscalar(n) else (int(n[0]), int(n[1]))
+
+
 def measurement_mask(ref_img, mask_cfg=None, mask=None):
     """The validity mask of a chain, [B,3,H,W] fp32 on ref_img's device, or None when neither source is given.
     mask_cfg: the optional config key `measurement.mask`; `{auto_exposure: {low, high, soft, per_pixel}}` builds the mask from
@@ -351,14 +382,28 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
                                    **cfg["sample_pattern"], **cfg["aux_loss"])
     sampler = create_sampler(**cfg["diffusion"])
     ref_img = ref_img.to(device)
-    y_n = noiser(ref_img)
-    if cfg.get("degamma_input", False):
-        y_n = degamma(y_n)
-    m_dev = measurement_mask(ref_img, measure.get("mask"), mask)
-    if m_dev is not None:
-        loop_kwargs = dict(loop_kwargs, measurement_mask=m_dev)
     pretrain = cfg["unet_model"]["pretrain_model"]
     shape = list(ref_img.shape)
+    y_clean = ref_img
+    if isinstance(operator, SeparableOperator):
+        # a blur / super-resolution operator: the measurement is simulated from the clean image, y = noiser(A ref), as the DPS driver
+        # does; `measurement.operator.simulate: False` takes ref_img as the measurement itself, on the operator's own grid
+        if op_cfg.get("simulate", True):
+            y_clean = operator.forward(ref_img[:, 0:3].to(torch.float32).contiguous())
+        else:
+            grid = model_grid(model, ref_img)
+            if tuple(ref_img.shape[-2:]) != tuple(operator.out_shape(*grid)):
+                raise ValueError(f"simulate: False takes the measurement itself: expected {tuple(operator.out_shape(*grid))} (the "
+                                 f"operator's grid for a {grid[0]} x {grid[1]} image), got {tuple(ref_img.shape[-2:])}")
+            shape[2:] = grid
+        y_n = noiser(y_clean)
+    else:
+        y_n = noiser(ref_img)
+    if cfg.get("degamma_input", False):
+        y_n = degamma(y_n)
+    m_dev = measurement_mask(y_clean, measure.get("mask"), mask)
+    if m_dev is not None:
+        loop_kwargs = dict(loop_kwargs, measurement_mask=m_dev)
     shape[1] = 4 if pretrain == "osmosis" else shape[1]
     results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
@@ -434,7 +479,7 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
             return None
         rows = []
         for i in idxs:
-            hw = images[i].shape[-2:]
+            hw = measurement_grid(cfg["measurement"]["operator"], images[i].shape[-2:])      # the mask lives where the measurement does
             m = torch.ones(1, 3, *hw) if masks[i] is None else torch.as_tensor(masks[i]).to(torch.float32)
             if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3):
                 raise ValueError(f"masks[{i}] must be [1,1,H,W] or [1,3,H,W], got {tuple(m.shape)}")

@@ -24,6 +24,9 @@ registered for the "cuda" device type only, which is HIP on ROCm).
     osmosis::recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, mode, radius, sigma_s, sigma_r)
                                                            -> (rgb, rgb_u8, depth_full): the physical model inverted on the ORIGINAL
                                                            pixel grid from phi and the upsampled depth (osmosis_sampling.py:253-255)
+    osmosis::linop_apply(x, start_h, wt_h, start_w, wt_w, Hout, Wout, [transposed tables]) -> out
+                                                           a separable banded linear operator per plane (gaussian blur, bicubic / box
+                                                           downsampling) and, with the transposed tables, its adjoint = its backward
 
 `engine` is an integer handle (`engine_handle(eng)`) because operator schemas carry tensors and scalars only; the handle
 table holds weak references, so an engine dies with its model.  An engine keeps the activations of its LAST forward pass:
@@ -612,7 +615,59 @@ tile_gather.register_autograd(_tile_gather_backward, setup_context=_tile_gather_
 tile_blend.register_autograd(_tile_blend_backward, setup_context=_tile_blend_setup)
 
 
+# ---- separable banded linear operators (blur, downsampling): out = R_h x R_w^T per plane; the backward is the operator itself with the
+# transposed tables, which the caller hands over beside the forward ones (measurements.SeparableOperator builds both)
+def _linop_tables(name, start_h, wt_h, start_w, wt_w, Hout, Wout):
+    if wt_h.dim() != 2 or wt_w.dim() != 2 or tuple(start_h.shape) != (Hout,) or tuple(start_w.shape) != (Wout,) \
+            or wt_h.shape[0] != Hout or wt_w.shape[0] != Wout:
+        raise OsmosisHipError(f"{name}: expected start_h [{Hout}], wt_h [{Hout},Kh], start_w [{Wout}], wt_w [{Wout},Kw], got "
+                              f"{tuple(start_h.shape)}, {tuple(wt_h.shape)}, {tuple(start_w.shape)}, {tuple(wt_w.shape)}")
+    return start_h.contiguous(), wt_h.detach().contiguous(), start_w.contiguous(), wt_w.detach().contiguous()
+
+
+@torch.library.custom_op("osmosis::linop_apply", mutates_args=(), device_types="cuda")
+def linop_apply(x: torch.Tensor, start_h: torch.Tensor, wt_h: torch.Tensor, start_w: torch.Tensor, wt_w: torch.Tensor, Hout: int,
+                Wout: int, tstart_h: Optional[torch.Tensor] = None, twt_h: Optional[torch.Tensor] = None,
+                tstart_w: Optional[torch.Tensor] = None, twt_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [B,P,Hout,Wout], out[b,p,i,j] = sum_a wt_h[i][a] sum_c wt_w[j][c] x[b,p,start_h[i]+a,start_w[j]+c] of x [B,P,Hin,Win]
+    (osm_linop_apply): band tables on the device, start int32 [n_out], wt fp32 [n_out,K].  tstart_* / twt_*: the tables of the
+    transposed factors ([Hin] / [Hin,K'] and [Win] / [Win,K'']); with them the operator is differentiable w.r.t. x -- its backward is
+    the operator itself with the two pairs of tables exchanged -- and without them it is forward only."""
+    if x.dim() != 4:
+        raise OsmosisHipError("osmosis::linop_apply: x must be [B,P,Hin,Win]")
+    B, P, Hin, Win = x.shape
+    tabs = _linop_tables("osmosis::linop_apply", start_h, wt_h, start_w, wt_w, Hout, Wout)
+    out = torch.empty((B, P, Hout, Wout), device=x.device, dtype=torch.float32)
+    ops.linop_apply(x.contiguous(), out, *tabs, B, P, P * Hin * Win, P * Hout * Wout, Hin, Win)
+    return out
+
+
+@linop_apply.register_fake
+def _linop_apply_fake(x, start_h, wt_h, start_w, wt_w, Hout, Wout, tstart_h=None, twt_h=None, tstart_w=None, twt_w=None):
+    return x.new_empty((x.shape[0], x.shape[1], Hout, Wout))
+
+
+def _linop_setup(ctx, inputs, output):
+    x, start_h, wt_h, start_w, wt_w, _Hout, _Wout, tstart_h, twt_h, tstart_w, twt_w = inputs
+    ctx.hw = (x.shape[2], x.shape[3])
+    ctx.has_t = tstart_h is not None and twt_h is not None and tstart_w is not None and twt_w is not None
+    if ctx.has_t:
+        ctx.save_for_backward(start_h, wt_h, start_w, wt_w, tstart_h, twt_h, tstart_w, twt_w)
+
+
+def _linop_backward(ctx, grad):
+    if not ctx.has_t:
+        raise OsmosisHipError("osmosis::linop_apply: the backward needs the transposed tables (tstart_h, twt_h, tstart_w, twt_w)")
+    start_h, wt_h, start_w, wt_w, tstart_h, twt_h, tstart_w, twt_w = ctx.saved_tensors
+    gx = torch.ops.osmosis.linop_apply(grad.contiguous(), tstart_h, twt_h, tstart_w, twt_w, ctx.hw[0], ctx.hw[1], start_h, wt_h,
+                                       start_w, wt_w)
+    return (gx,) + (None,) * 10
+
+
+linop_apply.register_autograd(_linop_backward, setup_context=_linop_setup)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
-       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend") + OPS_C
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply") + OPS_C

@@ -1,0 +1,222 @@
+"""Blur and super-resolution measurement operators, host side (no GPU): the registry, the band tables against torch on the CPU in
+float64 (the oracle of these operators: the reference has none), their transposes, the C ABI's second header, the driver's files.
+
+    blur:     F.conv2d(F.pad(x, reflect), g (x) g)
+    bicubic:  F.interpolate(mode="bicubic", align_corners=False, antialias=True)
+    box:      F.avg_pool2d
+"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from osmosis_diffusion_code_amd import _lib
+from osmosis_diffusion_code_amd.guided_diffusion import measurements as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+BLUR = [(24, 36, 9, 1.5), (16, 16, 13, 3.0)]
+SR = [(24, 36, 4, "bicubic"), (21, 27, 3, "bicubic"), (24, 36, 4, "box"), (16, 20, 2, "box")]
+
+
+def dense(op, H, W, which="fwd", dtype=np.float64):
+    """(R_h, R_w) of the operator's fp32 band tables (or of their transposes) as dense matrices."""
+    sh, wh, sw, ww = op.host_tables(H, W)[which]
+    h, w = op.out_shape(H, W)
+    n_h, n_w = (H, W) if which == "fwd" else (h, w)
+    return M.band_to_dense(sh, wh, n_h).astype(dtype), M.band_to_dense(sw, ww, n_w).astype(dtype)
+
+
+def band64(op, n):
+    """The float64 band table of one axis (what `host_tables` casts to fp32), expanded to a dense matrix."""
+    start, wt = M.dense_to_band(op.axis_matrix(n))
+    assert wt.dtype == np.float64
+    return M.band_to_dense(start, wt, n)
+
+
+def test_operators_resolve_from_the_registry():
+    blur = M.get_operator("gaussian_blur", device="cpu", kernel_size=9, intensity=1.5)
+    sr = M.get_operator("super_resolution", device="cpu", scale_factor=4)
+    assert blur.__name__ == "gaussian_blur" and sr.__name__ == "super_resolution"
+    assert isinstance(blur, M.SeparableOperator) and isinstance(sr, M.SeparableOperator) and isinstance(sr, M.LinearOperator)
+    assert blur.out_shape(24, 36) == (24, 36) and sr.out_shape(24, 36) == (6, 9)
+    d = M.get_operator("gaussian_blur", device="cpu")
+    assert (d.kernel_size, d.intensity) == (61, 3.0)
+    d = M.get_operator("super_resolution", device="cpu")
+    assert (d.scale_factor, d.method) == (4, "bicubic")
+    assert not hasattr(blur, "phi") and not hasattr(blur, "get_variable_list")       # no learnable parameters
+
+
+@pytest.mark.parametrize("H,W,k,sigma", BLUR)
+def test_blur_band_is_the_reflect_padded_convolution(H, W, k, sigma):
+    op = M.get_operator("gaussian_blur", device="cpu", kernel_size=k, intensity=sigma)
+    r = k // 2
+    g = torch.exp(-((torch.arange(k, dtype=torch.float64) - r) ** 2) / (2 * sigma ** 2))
+    g = g / g.sum()
+    x = torch.randn(2, 3, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(1))
+    want = F.conv2d(F.pad(x, (r, r, r, r), mode="reflect"), (g[:, None] * g[None, :]).expand(3, 1, k, k).contiguous(), groups=3)
+    Rh, Rw = band64(op, H), band64(op, W)                             # the float64 band tables, expanded
+    got = torch.einsum("ia,bpac,jc->bpij", torch.from_numpy(Rh), x, torch.from_numpy(Rw))
+    assert float((got - want).abs().max()) <= 1e-12
+    # the band tables hold those factors (fp32 cast of the same numbers)
+    Bh, Bw = dense(op, H, W)
+    assert np.array_equal(Bh, Rh.astype(np.float32).astype(np.float64)) and np.array_equal(Bw, Rw.astype(np.float32).astype(np.float64))
+    assert np.abs(Rh.sum(1) - 1).max() < 1e-14
+
+
+@pytest.mark.parametrize("H,W,s,method", SR)
+def test_super_resolution_band_is_torch_downsampling(H, W, s, method):
+    op = M.get_operator("super_resolution", device="cpu", scale_factor=s, method=method)
+    x = torch.randn(2, 3, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(2))
+    if method == "bicubic":
+        want = F.interpolate(x, size=(H // s, W // s), mode="bicubic", align_corners=False, antialias=True)
+    else:
+        want = F.avg_pool2d(x, s)
+    Rh, Rw = band64(op, H), band64(op, W)
+    got = torch.einsum("ia,bpac,jc->bpij", torch.from_numpy(Rh), x, torch.from_numpy(Rw))
+    assert got.shape == want.shape == (2, 3, H // s, W // s)
+    assert float((got - want).abs().max()) <= 1e-12
+    Bh, Bw = dense(op, H, W)
+    assert np.array_equal(Bh, Rh.astype(np.float32).astype(np.float64)) and np.array_equal(Bw, Rw.astype(np.float32).astype(np.float64))
+    sh, wh, sw, ww = op.host_tables(H, W)["fwd"]
+    assert wh.shape[1] <= 4 * s and ww.shape[1] <= 4 * s
+
+
+def _all_ops():
+    for H, W, k, sigma in BLUR + [(256, 256, 61, 3.0)]:
+        yield M.get_operator("gaussian_blur", device="cpu", kernel_size=k, intensity=sigma), H, W
+    for H, W, s, method in SR + [(256, 256, 4, "bicubic")]:
+        yield M.get_operator("super_resolution", device="cpu", scale_factor=s, method=method), H, W
+
+
+def test_transposed_tables_are_exactly_the_transposes_and_all_tables_stay_in_bounds():
+    for op, H, W in _all_ops():
+        h, w = op.out_shape(H, W)
+        tabs = op.host_tables(H, W)
+        fh, fw = dense(op, H, W, "fwd", np.float32)
+        th, tw = dense(op, H, W, "adj", np.float32)
+        assert fh.shape == (h, H) and fw.shape == (w, W) and th.shape == (H, h) and tw.shape == (W, w)
+        assert np.array_equal(th, fh.T) and np.array_equal(tw, fw.T)                    # same non-zeros, same fp32 values
+        assert np.array_equal(th != 0, fh.T != 0)
+        for which, (n_h, n_w) in (("fwd", (H, W)), ("adj", (h, w))):
+            sh, wh, sw, ww = tabs[which]
+            assert sh.dtype == sw.dtype == np.int32 and wh.dtype == ww.dtype == np.float32
+            assert wh.shape[1] >= 1 and ww.shape[1] >= 1
+            assert sh.min() >= 0 and sh.max() + wh.shape[1] <= n_h
+            assert sw.min() >= 0 and sw.max() + ww.shape[1] <= n_w
+        assert op.host_tables(H, W) is tabs                                              # cached per size
+
+
+def test_a_band_that_leaves_its_axis_is_rejected_by_the_builder():
+    wt = np.ones((4, 3), dtype=np.float32)
+    M.check_band(np.array([0, 1, 2, 5], dtype=np.int32), wt, 8)
+    with pytest.raises(ValueError, match="outside"):
+        M.check_band(np.array([0, 1, 2, 6], dtype=np.int32), wt, 8)                     # start + K = 9 > 8
+    with pytest.raises(ValueError, match="outside"):
+        M.check_band(np.array([-1, 1, 2, 5], dtype=np.int32), wt, 8)
+    with pytest.raises(ValueError, match="outside"):
+        M.band_to_dense(np.array([0, 1, 2, 6], dtype=np.int32), wt, 8)
+
+
+def test_bad_configurations_raise_value_error():
+    with pytest.raises(ValueError, match="odd"):
+        M.get_operator("gaussian_blur", device="cpu", kernel_size=8)
+    with pytest.raises(ValueError, match="reflection"):
+        M.get_operator("gaussian_blur", device="cpu", kernel_size=33).host_tables(16, 24)     # r = 16 >= min(H, W)
+    M.get_operator("gaussian_blur", device="cpu", kernel_size=31).host_tables(16, 24)         # r = 15: the largest that fits
+    with pytest.raises(ValueError, match="multiple"):
+        M.get_operator("super_resolution", device="cpu", scale_factor=4).out_shape(22, 36)
+    with pytest.raises(ValueError, match="multiple"):
+        M.get_operator("super_resolution", device="cpu", scale_factor=4).host_tables(24, 38)
+    with pytest.raises(ValueError):
+        M.get_operator("super_resolution", device="cpu", scale_factor=1)
+    with pytest.raises(ValueError):
+        M.get_operator("super_resolution", device="cpu", method="lanczos")
+
+
+def test_linop_entry_is_exported_declared_in_its_own_header_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_linop.h")).read()
+    assert set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", hdr)) - {"osm_last_error"} == {"osm_linop_apply"} == set(_lib.EXPORTS_LINOP)
+    assert re.search(r"\bint\s+osm_linop_apply\s*\(\s*const\s+float\s*\*\s*x\s*,\s*float\s*\*\s*out\s*,", hdr)
+    assert len(_lib._SIGS_LINOP["osm_linop_apply"]) == 18
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "osm_linop_apply")
+    assert _lib.load().osm_linop_apply.argtypes == _lib._SIGS_LINOP["osm_linop_apply"]
+    # the first header and its export list are what they were
+    main = open(os.path.join(ROOT, "include", "osmosis_hip.h")).read()
+    declared = set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", main)) - {"osm_status"}
+    assert declared == set(_lib.EXPORTS) and len(_lib.EXPORTS) == 99 and "osm_linop_apply" not in declared
+    assert "linop.hip" in open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
+    from osmosis_diffusion_code_amd import torch_ops
+    assert "linop_apply" in torch_ops.OPS and "linop_apply" not in torch_ops.OPS_C
+    schema = str(torch.ops.osmosis.linop_apply.default._schema)
+    assert schema.startswith("osmosis::linop_apply(Tensor x, Tensor start_h, Tensor wt_h, Tensor start_w, Tensor wt_w, SymInt Hout, "
+                             "SymInt Wout"), schema
+
+
+def test_linop_entry_validates_its_arguments_without_a_gpu():
+    """Null pointer, Hout < 1, K < 1: a non-zero status with a message, nothing launched (the checks come before the launch)."""
+    lib = _lib.load()
+    p = 4096                                                                              # never dereferenced on the host
+    good = [p, p, p, p, p, p, 2, 3, 3 * 64, 3 * 64, 8, 8, 8, 8, 3, 3, 0, None]
+    for pos, val, word in ((0, None, "null"), (3, None, "null"), (12, 0, "output"), (14, 0, "band"), (15, -1, "band"),
+                           (8, 10, "x_img_stride"), (16, -1, "zero_planes")):
+        args = list(good)
+        args[pos] = val
+        assert lib.osm_linop_apply(*args) != 0
+        assert word in lib.osm_last_error().decode(), (pos, lib.osm_last_error().decode())
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
+def test_linop_header_is_strict_c99():
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c",
+                        os.path.join(ROOT, "include", "osmosis_linop.h")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_save_outputs_with_a_measurement_smaller_than_the_sample(tmp_path):
+    from PIL import Image
+    from osmosis_diffusion_code_amd import sampling
+    g = torch.Generator().manual_seed(3)
+    sample = torch.rand(1, 4, 24, 36, generator=g) * 2 - 1
+    y = torch.rand(1, 3, 6, 9, generator=g) * 2 - 1
+    post = sampling.rgb_guidance_result(sample, y)
+    assert post["measurement"].shape == (1, 3, 6, 9)
+    paths = sampling.save_outputs(post, y, str(tmp_path), "im0")
+    assert Image.open(paths["input"]).size == (9, 6)                 # the measurement keeps its own size
+    assert Image.open(paths["rgb"]).size == (36, 24)
+    grid = np.asarray(Image.open(paths["grid"]))
+    assert grid.shape == (24 + 4, 3 * (36 + 2) + 2, 3)
+    tile = grid[2:26, 2:38]                                          # the measurement, each pixel replicated 4 x 4
+    small = np.asarray(Image.open(paths["input"]))
+    assert np.array_equal(tile, np.repeat(np.repeat(small, 4, 0), 4, 1))
+
+
+def test_a_missing_mask_of_a_batch_is_ones_on_the_measurement_grid():
+    """`restore_images(masks=)` fills an image without a mask with ones where the measurement lives: the operator's own grid for a
+    simulated blur / super-resolution measurement, the image's otherwise."""
+    from osmosis_diffusion_code_amd import sampling
+    sr = {"name": "super_resolution", "scale_factor": 4}
+    assert sampling.measurement_grid(sr, (24, 36)) == (6, 9)
+    assert sampling.measurement_grid(dict(sr, simulate=False), (6, 9)) == (6, 9)
+    assert sampling.measurement_grid({"name": "gaussian_blur", "kernel_size": 9, "intensity": 1.5}, (24, 36)) == (24, 36)
+    assert sampling.measurement_grid({"name": "rgb_guidance"}, (24, 36)) == (24, 36)
+    assert sampling.measurement_grid({"name": "underwater_physical_revised", "phi_a": "1,1,1"}, (24, 36)) == (24, 36)
+    seen = {}
+
+    def fake_restore_image(model, ref, cfg, mask=None, **kw):
+        seen["mask"] = mask
+        return [sampling.rgb_guidance_result(torch.zeros(ref.shape[0], 4, 24, 36), torch.zeros(ref.shape[0], 3, 6, 9))]
+    real, sampling.restore_image = sampling.restore_image, fake_restore_image
+    try:
+        images = [torch.zeros(1, 3, 24, 36), torch.zeros(1, 3, 24, 36)]
+        sampling.restore_images(None, images, {"measurement": {"operator": sr}}, batch_size=2, masks=[None, 0.5 * torch.ones(1, 1, 6, 9)])
+    finally:
+        sampling.restore_image = real
+    assert seen["mask"].shape == (2, 3, 6, 9) and float(seen["mask"][0].min()) == 1.0 and float(seen["mask"][1].max()) == 0.5
