@@ -7,6 +7,7 @@
 // (fixed) channel vector(s) it owns; a structured (deterministic, atomics-free) LDS pass folds
 // threads into the 32 groups; chunk partials are combined in fp64 by a finalize kernel.
 //   pass 1 (stats / grad-stats):  read x (and dy)         -> [B][chunk][G][2] partials -> [B][G][2]
+//                                 (forward: sums of x - pivot and its square, see gn_pivot)
 //   pass 2 (apply / grad-apply):  read x (and dy), write y / dx
 #include "osm_common.h"
 #include <cstdlib>
@@ -59,6 +60,23 @@ __device__ __forceinline__ void gn_fwd_elem(float x, float mean, float rstd, flo
   if (film) z = z * (1.0f + sc) + sh;
 }
 
+// Forward statistics are SHIFTED sums: every pass accumulates d = x - pv and d^2 in fp32, pv = the first element of the (image,
+// group) slice, and the finalizers return mean = pv + E[d], var = E[d^2] - E[d]^2.  With raw sums the fp32 rounding of E[x^2]
+// is amplified by (mean / sigma)^2 in the variance: a 2-element group 0.08 apart around 1.0 (tests/test_groupnorm_gpu.py, row
+// G 3, C 6, HW 1) missed the 2e-5 forward bar, and so does any group whose mean sits ~10 sigma from zero.  A pivot inside the
+// data keeps |E[d]| within a few sigma whatever the mean is; a constant slice gives var == 0 exactly.  (gn_finalize_cols takes
+// RAW column sums from a convolution's epilogue and keeps the one-pass form.)
+__device__ __forceinline__ float gn_pivot(const act_t* __restrict__ x, long long ldx, int HW, int gs, int b, int g) {
+  return osm::ld1(x + (long long)b * HW * ldx + g * gs);
+}
+__device__ __forceinline__ void gn_mean_rstd(double s1, double s2, double n, double pv, float eps, float& mean, float& rstd) {
+  const double d = s1 / n;
+  double var = s2 / n - d * d;
+  if (var < 0.0) var = 0.0;
+  mean = (float)(pv + d);
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
 // workgroup `wg` of `nwg` (<= OSM_MAXABS_PARTS) publishes its partial max |out| of image b: slot wg, and zeros in the slots no
 // workgroup owns (every slot is rewritten on every call: no clearing, no atomics).  Called by ALL threads of the workgroup.
 __device__ __forceinline__ void gn_publish_max(unsigned* __restrict__ maxabs, int b, int wg, int nwg, float m, unsigned nanbits) {
@@ -75,7 +93,7 @@ __device__ __forceinline__ void gn_publish_max(unsigned* __restrict__ maxabs, in
   }
 }
 
-// MODE 0: sums of (x, x^2).   MODE 1: sums of (dxh, dxh*xh) for the backward.
+// MODE 0: sums of (x - pv, (x - pv)^2).   MODE 1: sums of (dxh, dxh*xh) for the backward.
 template <int VEC, int MODE>
 __global__ __launch_bounds__(256) void gn_reduce_kernel(GNArgs a) {
   __shared__ float red[256 * NJMAX * 2];
@@ -103,6 +121,7 @@ __global__ __launch_bounds__(256) void gn_reduce_kernel(GNArgs a) {
       const int c = v * VEC;
       const int g = c / a.gs;
       float mean = 0.f, rstd = 0.f;
+      const float pv = MODE == 0 ? gn_pivot(a.x, a.ldx, a.HW, a.gs, b, g) : 0.f;
       float ga[VEC], be[VEC], sc[VEC], sh[VEC];
       if (MODE == 1) {
         mean = a.stats[(b * a.G + g) * 2];
@@ -124,9 +143,10 @@ __global__ __launch_bounds__(256) void gn_reduce_kernel(GNArgs a) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
           if (MODE == 0) {
-            s1[j] += xv[e];
-            s2[j] += xv[e] * xv[e];
             const float fx = (float)xv[e];
+            const float d = fx - pv;
+            s1[j] += d;
+            s2[j] += d * d;
             imax = fmaxf(imax, fabsf(fx));
             if (fx != fx) inan = 0x7fc00000u;
           } else {
@@ -171,7 +191,8 @@ __global__ __launch_bounds__(256) void gn_reduce_kernel(GNArgs a) {
 template <int MODE>
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part,
                                                            float* __restrict__ out, int B, int G, int nchunk,
-                                                           double n, float eps) {
+                                                           double n, float eps, const act_t* __restrict__ x, long long ldx,
+                                                           int HW, int gs) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= B * G) return;
@@ -189,11 +210,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   }
   if (lane != 0) return;
   if (MODE == 0) {
-    const double mean = s1 / n;
-    double var = s2 / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    out[i * 2] = (float)mean;
-    out[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    gn_mean_rstd(s1, s2, n, (double)gn_pivot(x, ldx, HW, gs, b, g), eps, out[i * 2], out[i * 2 + 1]);
   } else {
     out[i * 2] = (float)(s1 / n);
     out[i * 2 + 1] = (float)(s2 / n);
@@ -206,7 +223,7 @@ __global__ __launch_bounds__(256) void gn_finalize_table_kernel(const float* __r
                                                                  float* __restrict__ table, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, const float* __restrict__ film,
                                                                  long long ldf, int B, int G, int C, int nchunk, double n,
-                                                                 float eps) {
+                                                                 float eps, const act_t* __restrict__ x, long long ldx, int HW) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= B * G) return;
@@ -222,15 +239,13 @@ __global__ __launch_bounds__(256) void gn_finalize_table_kernel(const float* __r
     s1 += __shfl_xor(s1, o, 64);
     s2 += __shfl_xor(s2, o, 64);
   }
-  const double mu = s1 / n;
-  double var = s2 / n - mu * mu;
-  if (var < 0.0) var = 0.0;
-  const float mean = (float)mu, rstd = (float)(1.0 / sqrt(var + (double)eps));
+  const int gs = C / G;
+  float mean, rstd;
+  gn_mean_rstd(s1, s2, n, (double)gn_pivot(x, ldx, HW, gs, b, g), eps, mean, rstd);
   if (lane == 0) {
     out[i * 2] = mean;
     out[i * 2 + 1] = rstd;
   }
-  const int gs = C / G;
   float* t = table + (long long)b * 4 * C;
   for (int e = lane; e < gs; e += 64) {
     const int c = g * gs + e;
@@ -372,11 +387,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GNArgs a) {
       if (lane == 0) {
         float o0, o1;
         if (MODE == 0) {
-          const double mu = s1 / a.n;
-          double var = s2 / a.n - mu * mu;
-          if (var < 0.0) var = 0.0;
-          o0 = (float)mu;
-          o1 = (float)(1.0 / sqrt(var + (double)a.eps));
+          gn_mean_rstd(s1, s2, a.n, (double)gn_pivot(a.x, a.ldx, a.HW, a.gs, b, g), a.eps, o0, o1);
         } else {
           o0 = (float)(s1 / a.n);
           o1 = (float)(s2 / a.n);
@@ -504,6 +515,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(GNArgs a) {
     rstd = a.stats[(b * a.G + g) * 2 + 1];
   }
   const long long row0 = (long long)b * a.HW;
+  const float pv = MODE == 0 ? gn_pivot(a.x, a.ldx, a.HW, a.gs, b, g) : 0.f;
   float s1 = 0.f, s2 = 0.f;
   if (live) {
     for (int p = tp; p < a.HW; p += ppi) {
@@ -512,8 +524,9 @@ __global__ __launch_bounds__(256) void gn_small_kernel(GNArgs a) {
       if (MODE == 0) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          s1 += xv[e];
-          s2 += xv[e] * xv[e];
+          const float d = xv[e] - pv;
+          s1 += d;
+          s2 += d * d;
         }
       } else {
         const float4 u = osm::ld4(a.dy + (row0 + p) * a.lddy + c);
@@ -547,11 +560,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(GNArgs a) {
     const double t2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     float o0, o1;
     if (MODE == 0) {
-      const double mu = t1 / a.n;
-      double var = t2 / a.n - mu * mu;
-      if (var < 0.0) var = 0.0;
-      o0 = (float)mu;
-      o1 = (float)(1.0 / sqrt(var + (double)a.eps));
+      gn_mean_rstd(t1, t2, a.n, (double)pv, a.eps, o0, o1);
     } else {
       o0 = (float)(t1 / a.n);
       o1 = (float)(t2 / a.n);
@@ -635,6 +644,8 @@ __global__ __launch_bounds__(512) void gn_reg_kernel(GNArgs a) {
   const long long row0 = (long long)b * a.HW;
   // (backward: the addends are requested here as well -- after the two barriers of the reduction they were one more dependent
   // memory round trip of a ~7-16 us kernel; an addend that aliases `out` is read by the thread that later writes the element)
+  // (forward: a dead slot holds the pivot -- an element of this image, so it adds nothing to the shifted sums or to max |x|)
+  const float pv = MODE == 0 ? gn_pivot(a.x, a.ldx, a.HW, a.gs, b, g) : 0.f;
   float4 xr[NV], dr[MODE == 1 ? NV : 1], ar[MODE == 1 ? NV : 1];
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -642,7 +653,7 @@ __global__ __launch_bounds__(512) void gn_reg_kernel(GNArgs a) {
     const bool live = p < a.HW;
     const long long row = row0 + (live ? p : 0);
     const float4 t = osm::ld4(a.x + row * a.ldx + c);
-    xr[k] = live ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+    xr[k] = live ? t : make_float4(pv, pv, pv, pv);
     if (MODE == 1) {
       const float4 u = osm::ld4(a.dy + row * a.lddy + c);
       dr[k] = live ? u : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -675,8 +686,9 @@ __global__ __launch_bounds__(512) void gn_reg_kernel(GNArgs a) {
     if (MODE == 0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        s1 += xv[e];
-        s2 += xv[e] * xv[e];
+        const float d = xv[e] - pv;
+        s1 += d;
+        s2 += d * d;
         imax = fmaxf(imax, fabsf(xv[e]));
         if (xv[e] != xv[e]) inan = 0x7fc00000u;
       }
@@ -715,11 +727,7 @@ __global__ __launch_bounds__(512) void gn_reg_kernel(GNArgs a) {
     }
     float o0, o1;
     if (MODE == 0) {
-      const double mu = t1 / a.n;
-      double var = t2 / a.n - mu * mu;
-      if (var < 0.0) var = 0.0;
-      o0 = (float)mu;
-      o1 = (float)(1.0 / sqrt(var + (double)a.eps));
+      gn_mean_rstd(t1, t2, a.n, (double)pv, a.eps, o0, o1);
     } else {
       o0 = (float)(t1 / a.n);
       o1 = (float)(t2 / a.n);
@@ -818,7 +826,7 @@ int run_reduce(GNArgs& a, float* finalized, hipStream_t st, bool finalize = true
   if (rc || !finalize) return rc;
   const int n = a.B * a.G;
   hipLaunchKernelGGL((gn_finalize_kernel<MODE>), dim3((n + 3) / 4), dim3(256), 0, st, a.part, finalized, a.B,
-                     a.G, a.nchunk, (double)a.HW * a.gs, a.eps);
+                     a.G, a.nchunk, (double)a.HW * a.gs, a.eps, a.x, a.ldx, a.HW, a.gs);
   return osm::check_launch("gn_finalize_kernel");
 }
 
@@ -924,7 +932,7 @@ extern "C" int OSM_FN(osm_gn_prep)(const abi_act_t* x, long long ldx, int B, int
   if (rc) return rc;
   const int n = B * G;
   hipLaunchKernelGGL(gn_finalize_table_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, stats, table,
-                     gamma, beta, film, ldfilm, B, G, C, a.nchunk, (double)HW * (C / G), eps);
+                     gamma, beta, film, ldfilm, B, G, C, a.nchunk, (double)HW * (C / G), eps, a.x, a.ldx, HW);
   return osm::check_launch("gn_finalize_table_kernel");
 }
 
