@@ -412,8 +412,8 @@ class PosteriorSampling(ConditioningMethod):
         self._states = {}
 
     def hip_ok(self, channels: int = 4) -> bool:
-        from .measurements import SeparableOperator, _IdentityOperator
-        return isinstance(self.operator, (_IdentityOperator, SeparableOperator)) and \
+        from .measurements import GRID_OPERATORS, _IdentityOperator
+        return isinstance(self.operator, (_IdentityOperator,) + GRID_OPERATORS) and \
             getattr(self.noiser, "__name__", None) == "gaussian" and self.scale.numel() in (1, channels)
 
     def scale4(self, device, channels: int = 4):
@@ -429,9 +429,10 @@ class PosteriorSampling(ConditioningMethod):
         fp32.  With a mask M (`mask`: [B,3,HW] rows, default the one of `set_measurement_mask`): loss[b] = ||M (y - x0[0:3])||,
         g = -M^2 (y - x0) / loss, and g = 0 for an image that is masked out entirely.
         With a `SeparableOperator` A (blur, super-resolution) the measurement y [B,3,h,w] lives on A's own grid, and so does the mask:
-        loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`)."""
-        from .measurements import SeparableOperator
-        if isinstance(self.operator, SeparableOperator):
+        loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`); a `PSFOperator` (motion blur, a
+        measured point-spread function) goes the same way with its own kernel."""
+        from .measurements import GRID_OPERATORS
+        if isinstance(self.operator, GRID_OPERATORS):
             return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask)
         B, C, HW = x0.shape[0], x0.shape[1], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or C not in (3, 4):
@@ -471,7 +472,9 @@ class PosteriorSampling(ConditioningMethod):
         """The data term through a separable linear operator, three stream-ordered launches and no host sync:
         Ax = A x0[:, 0:3] (osm_linop_apply, P = 3, image stride C HW); loss[b] = ||M (y - Ax)|| and r = d loss / d Ax (the identity
         term's own reduction, osm_ps_loss_grad_c / _mc at C = 3 on the measurement's h w); g[:, 0:3] = A^T r with the transposed
-        tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3)."""
+        tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3).
+        A `PSFOperator`: the same three launches with osm_psf_apply in the place of osm_linop_apply, `adjoint` set for A^T."""
+        from .measurements import PSFOperator
         B, C, H, W = x0.shape
         h, w = self.operator.out_shape(H, W)
         if C not in (3, 4) or tuple(y.shape) != (B, 3, h, w):
@@ -490,14 +493,21 @@ class PosteriorSampling(ConditioningMethod):
         loss = loss_out if loss_out is not None else st["loss"]
         if mask is None:
             mask = self.measurement_mask(B, hw, x0.device)
-        tabs = self.operator.tables(H, W, x0.device)
         Ax, r = st["Ax"], st["r"]
-        ops.linop_apply(x0.contiguous(), Ax, *tabs["fwd"], B, 3, C * HW, 3 * hw, H, W)
+        if isinstance(self.operator, PSFOperator):
+            taps, (Ry, Rx) = self.operator.taps(x0.device), self.operator.radius()
+            ops.psf_apply(x0.contiguous(), Ax, *taps, Ry, Rx, B, 3, C * HW, 3 * hw, H, W)
+        else:
+            tabs = self.operator.tables(H, W, x0.device)
+            ops.linop_apply(x0.contiguous(), Ax, *tabs["fwd"], B, 3, C * HW, 3 * hw, H, W)
         if mask is not None:
             ops.ps_loss_grad_mc(Ax, y.contiguous(), mask, st["part"], loss, r, B, 3, hw)
         else:
             ops.ps_loss_grad_c(Ax, y.contiguous(), st["part"], loss, r, B, 3, hw)
-        ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)
+        if isinstance(self.operator, PSFOperator):
+            ops.psf_apply(r, g, *taps, Ry, Rx, B, 3, 3 * hw, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+        else:
+            ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)
         return g.view(x0.shape), loss
 
     def conditioning(self, x_prev, x_t, x_0_hat, measurement, **kwargs):

@@ -271,6 +271,181 @@ class SuperResolutionOperator(SeparableOperator):
         return R
 
 
+# ----------------------------------------------------------------------------- point-spread-function operators
+# A 2-D kernel that does not factor per axis (motion blur, a measured PSF) travels as a tap list: the offsets (dy, dx) of its non-zeros
+# from the anchor (the centre) and their weights (osm_psf_apply, include/osmosis_psf.h).  The adjoint is the same kernel launch with
+# `adjoint` set: the transpose of reflection padding folds the mirrored taps back.
+def _psf_op():
+    from .. import torch_ops  # noqa: F401  (registers osmosis::psf_apply)
+    return torch.ops.osmosis.psf_apply
+
+
+def check_kernel2d(kernel, what="psf"):
+    """The float64 [kh, kw] array of a PSF given as an array or a nested list; ValueError unless it is 2-D with odd sides (the anchor
+    is the centre), finite, and not all zero."""
+    try:
+        k = np.asarray(kernel, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: the kernel must be a 2-D array of numbers ({e})")
+    if k.ndim != 2 or k.size == 0:
+        raise ValueError(f"{what}: the kernel must be 2-D [kh, kw], got shape {k.shape}")
+    if k.shape[0] % 2 == 0 or k.shape[1] % 2 == 0:
+        raise ValueError(f"{what}: both sides of the kernel must be odd (the anchor is the centre), got {k.shape[0]} x {k.shape[1]}")
+    if not np.isfinite(k).all():
+        raise ValueError(f"{what}: the kernel holds non-finite values")
+    if not (k != 0).any():
+        raise ValueError(f"{what}: the kernel is all zero")
+    return k
+
+
+class PSFOperator(LinearOperator):
+    """Blur of the three colour planes with one 2-D point-spread function over the image padded by reflection (torch 'reflect'), as
+    cross-correlation -- F.conv2d(F.pad(x, reflect), k), what nn.Conv2d and the DPS `Blurkernel` compute: no learnable parameters, the
+    measurement has the image's size.  A subclass gives `kernel2d()` (float64 [kh, kw], both sides odd, anchor at the centre); the
+    non-zero taps are taken in row-major order, their weights cast to fp32, and cached as device tensors per device.  `forward` /
+    `transpose` run osm_psf_apply through `osmosis::psf_apply`, which is differentiable (its backward is the same operator with
+    `adjoint` flipped), so autograd conditioning works too."""
+
+    def __init__(self, device, batch_size=1, **kwargs):
+        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        self.batch_size = batch_size
+        self._host, self._dev = None, {}
+
+    def kernel2d(self):
+        raise NotImplementedError
+
+    def host_taps(self):
+        """(dy int32 [T], dx int32 [T], w fp32 [T]): the kernel's non-zeros in row-major order, offsets from the centre."""
+        if self._host is None:
+            k = check_kernel2d(self.kernel2d(), getattr(self, "__name__", type(self).__name__))
+            iy, ix = np.nonzero(k)                                                  # row-major
+            self._host = ((iy - k.shape[0] // 2).astype(np.int32), (ix - k.shape[1] // 2).astype(np.int32), k[iy, ix].astype(np.float32))
+        return self._host
+
+    def radius(self):
+        """(Ry, Rx): the largest |dy| and |dx| of the taps."""
+        dy, dx, _ = self.host_taps()
+        return int(np.abs(dy).max()), int(np.abs(dx).max())
+
+    def taps(self, device=None):
+        """`host_taps` as device tensors."""
+        device = torch.device(device if device is not None else self.device)
+        t = self._dev.get(str(device))
+        if t is None:
+            t = self._dev[str(device)] = tuple(torch.from_numpy(a).to(device).contiguous() for a in self.host_taps())
+        return t
+
+    def out_shape(self, H, W):
+        Ry, Rx = self.radius()
+        if Ry >= H or Rx >= W:
+            raise ValueError(f"{getattr(self, '__name__', type(self).__name__)}: reflection padding needs the kernel's reach {Ry} x {Rx} "
+                             f"< the image sides {H} x {W}")
+        return H, W
+
+    def _apply(self, data, adjoint):
+        self.out_shape(*data.shape[-2:])
+        return _psf_op()(data, *self.taps(data.device), *self.radius(), adjoint)
+
+    def forward(self, data, **kwargs):
+        return self._apply(data, False)
+
+    def transpose(self, data, **kwargs):
+        return self._apply(data, True)
+
+
+# the linear operators whose measurement lives on a grid of its own, `out_shape(H, W)`, and whose data term the fused `ps` loop
+# evaluates with their own kernels (condition_methods.PosteriorSampling, sampling.restore_image)
+GRID_OPERATORS = (SeparableOperator, PSFOperator)
+
+MOTION_STEP = 0.5          # pixels between two samples of the trajectory
+MOTION_TURN = 0.3          # standard deviation of the heading's change per sample at intensity 1, radians
+
+
+def motion_trajectory(kernel_size=61, intensity=0.5, seed=0):
+    """The camera path of `motion_kernel`, float64 [2 m + 1, 2] of (y, x) offsets from the centre, r = kernel_size // 2, m = 2 r:
+    with rng = np.random.default_rng(seed), theta = rng.uniform(0, pi) and turn = rng.normal(size=(2, m)) (drawn in this order), arm
+    a in (0, 1) leaves the centre with the heading theta + a pi and takes m steps of MOTION_STEP pixels, the heading changing by
+    intensity * MOTION_TURN * turn[a, i] BEFORE step i; every point is clamped to [-r, r] per axis.  Order: arm 1 reversed, the
+    centre, arm 0 -- one connected path through (0, 0); intensity 0: a straight segment of length 2 r."""
+    k, s = int(kernel_size), float(intensity)
+    if k != kernel_size or k < 1 or k % 2 == 0:
+        raise ValueError(f"motion_blur: kernel_size must be a positive odd integer, got {kernel_size!r}")
+    if not 0.0 <= s <= 1.0:
+        raise ValueError(f"motion_blur: intensity must lie in [0, 1], got {intensity!r}")
+    r = k // 2
+    m = 2 * r
+    rng = np.random.default_rng(seed)
+    theta = rng.uniform(0.0, np.pi)
+    turn = rng.normal(size=(2, m))
+    arms = []
+    for a in range(2):
+        heading = theta + a * np.pi + np.cumsum(s * MOTION_TURN * turn[a])
+        steps = MOTION_STEP * np.stack([np.sin(heading), np.cos(heading)], axis=1)
+        arms.append(np.clip(np.cumsum(steps, axis=0), -r, r))
+    return np.concatenate([arms[1][::-1], np.zeros((1, 2)), arms[0]], axis=0).reshape(2 * m + 1, 2)
+
+
+def motion_kernel(kernel_size=61, intensity=0.5, seed=0):
+    """The motion-blur PSF, float64 [kernel_size, kernel_size]: the points of `motion_trajectory(kernel_size, intensity, seed)`, each
+    splatted with weight 1 onto its four neighbouring pixels bilinearly (pixel (r + floor y + a, r + floor x + b) gets
+    (a ? fy : 1 - fy) (b ? fx : 1 - fx), fy = y - floor y; a pixel beyond the kernel can only get weight 0 and is dropped), the sum
+    normalised to 1.  Deterministic in its three arguments, non-negative, the centre pixel always hit.  (DPS draws its kernels from
+    the `motionblur` package; this definition stands in for it and does not reproduce that package's random stream.)"""
+    pts = motion_trajectory(kernel_size, intensity, seed)
+    k = int(kernel_size)
+    r = k // 2
+    ker = np.zeros((k, k), dtype=np.float64)
+    fl = np.floor(pts)
+    frac = pts - fl
+    for a in range(2):
+        for b in range(2):
+            wgt = (frac[:, 0] if a else 1.0 - frac[:, 0]) * (frac[:, 1] if b else 1.0 - frac[:, 1])
+            iy, ix = fl[:, 0].astype(np.int64) + r + a, fl[:, 1].astype(np.int64) + r + b
+            ok = (iy < k) & (ix < k) & (wgt > 0)
+            np.add.at(ker, (iy[ok], ix[ok]), wgt[ok])
+    return ker / ker.sum()
+
+
+@register_operator(name="motion_blur")
+class MotionBlurOperator(PSFOperator):
+    """Blur with a random camera-shake trajectory, `motion_kernel(kernel_size, intensity, seed)`.  DPS config keys: kernel_size (odd,
+    default 61), intensity (in [0, 1], default 0.5: 0 a straight streak, 1 the most erratic path); `seed` (default 0) picks the path."""
+
+    def __init__(self, device, kernel_size=61, intensity=0.5, seed=0, batch_size=1, **kwargs):
+        super().__init__(device, batch_size, **kwargs)
+        self._kernel = motion_kernel(kernel_size, intensity, seed)                  # validates its arguments
+        self.kernel_size, self.intensity, self.seed = int(kernel_size), float(intensity), seed
+
+    def kernel2d(self):
+        return self._kernel
+
+
+@register_operator(name="psf_blur")
+class PSFBlurOperator(PSFOperator):
+    """Blur with a point-spread function of the user's: `kernel` is a 2-D array, a nested list, or the path of a .npy file holding one
+    (both sides odd, finite; the anchor is the centre, applied as cross-correlation); `normalize` (default True) divides it by its
+    float64 sum, which must not be zero."""
+
+    def __init__(self, device, kernel=None, normalize=True, batch_size=1, **kwargs):
+        super().__init__(device, batch_size, **kwargs)
+        if kernel is None:
+            raise ValueError("psf_blur: a `kernel` is required (a 2-D array, a nested list or the path of a .npy file)")
+        if isinstance(kernel, (str, bytes)) or hasattr(kernel, "__fspath__"):
+            kernel = np.load(kernel, allow_pickle=False)
+        if isinstance(kernel, torch.Tensor):
+            kernel = kernel.detach().cpu().numpy()
+        k = check_kernel2d(kernel, "psf_blur")
+        if normalize:
+            total = float(k.sum())
+            if total == 0.0 or not np.isfinite(total):
+                raise ValueError(f"psf_blur: normalize divides by the kernel's sum, which is {total}")
+            k = k / total
+        self._kernel, self.normalize = k, bool(normalize)
+
+    def kernel2d(self):
+        return self._kernel
+
+
 class LearnableOperator(ABC):
     @abstractmethod
     def forward(self, data, **kwargs):

@@ -695,3 +695,26 @@ def linop_apply(x, out, start_h, wt_h, start_w, wt_w, B, P, x_img_stride, out_im
     call("osm_linop_apply", ptr(x), ptr(out), ptr(start_h), ptr(wt_h), ptr(start_w), ptr(wt_w), B, P, int(x_img_stride),
          int(out_img_stride), int(Hin), int(Win), int(Hout), int(Wout), int(Kh), int(Kw), Z, _s(),
          keep=(x, out, start_h, wt_h, start_w, wt_w))
+
+
+# ----------------------------------------------------------------------------- point-spread-function operators
+def psf_apply(x, out, dy, dx, w, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint=False, zero_planes=0):
+    """out[b,p,i,j] = sum_t w[t] x[b,p,refl(i+dy[t]),refl(j+dx[t])] for p < P over torch 'reflect' padding (osm_psf_apply,
+    include/osmosis_psf.h), or with `adjoint` the exact transpose of that map; `zero_planes` further planes of every output image
+    are written as 0.  x / out: contiguous fp32 on the same H x W grid with image strides in elements (the colour planes of a
+    [B,4,HW] tensor: stride 4 HW, P = 3); the tap list on the device: dy, dx int32 [T], w fp32 [T]; Ry >= max |dy|, Rx >= max |dx|
+    (a tap beyond them is skipped).  Deterministic (gather form, no atomics)."""
+    for t in (x, out, w):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_apply takes contiguous fp32 tensors")
+    for d in (dy, dx):
+        if d.dtype != torch.int32 or not d.is_contiguous() or d.dim() != 1 or w.dim() != 1 or d.shape[0] != w.shape[0]:
+            raise _lib.OsmosisHipError(f"psf_apply: a tap list is dy, dx int32 [T] with w fp32 [T], got {tuple(d.shape)} {d.dtype} "
+                                       f"and {tuple(w.shape)}")
+    B, P, Z, H, W = int(B), int(P), int(zero_planes), int(H), int(W)
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * H * W
+                   or out.numel() < (B - 1) * int(out_img_stride) + (P + Z) * H * W):
+        raise _lib.OsmosisHipError(f"psf_apply: x ({x.numel()} elements) / out ({out.numel()}) are smaller than {B} images of "
+                                   f"{P} -> {P + Z} planes of {H} x {W} at strides {x_img_stride} / {out_img_stride}")
+    call("osm_psf_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), int(w.shape[0]), int(Ry), int(Rx), B, P, int(x_img_stride),
+         int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(), keep=(x, out, dy, dx, w))

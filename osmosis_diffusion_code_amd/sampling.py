@@ -27,7 +27,7 @@ import torch
 
 from .guided_diffusion.condition_methods import get_conditioning_method
 from .guided_diffusion.gaussian_diffusion import create_sampler, parse_tiling, tile_grid  # noqa: F401  (tile_grid: public helper)
-from .guided_diffusion.measurements import SeparableOperator, get_noise, get_operator
+from .guided_diffusion.measurements import GRID_OPERATORS, get_noise, get_operator
 from .osmosis_utils import utils as utilso
 from .sharding import shard_indices
 
@@ -301,7 +301,7 @@ def measurement_grid(operator_cfg, hw):
     where the image handed in IS the measurement)."""
     from .guided_diffusion import measurements
     cls = measurements.__OPERATOR__.get(operator_cfg.get("name"))
-    if cls is None or not issubclass(cls, SeparableOperator) or not operator_cfg.get("simulate", True):
+    if cls is None or not issubclass(cls, GRID_OPERATORS) or not operator_cfg.get("simulate", True):
         return tuple(hw)
     kw = {k: v for k, v in operator_cfg.items() if k != "name"}
     return tuple(cls(device="cpu", **kw).out_shape(int(hw[0]), int(hw[1])))
@@ -385,7 +385,7 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     pretrain = cfg["unet_model"]["pretrain_model"]
     shape = list(ref_img.shape)
     y_clean = ref_img
-    if isinstance(operator, SeparableOperator):
+    if isinstance(operator, GRID_OPERATORS):
         # a blur / super-resolution operator: the measurement is simulated from the clean image, y = noiser(A ref), as the DPS driver
         # does; `measurement.operator.simulate: False` takes ref_img as the measurement itself, on the operator's own grid
         if op_cfg.get("simulate", True):

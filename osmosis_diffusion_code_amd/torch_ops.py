@@ -27,6 +27,8 @@ registered for the "cuda" device type only, which is HIP on ROCm).
     osmosis::linop_apply(x, start_h, wt_h, start_w, wt_w, Hout, Wout, [transposed tables]) -> out
                                                            a separable banded linear operator per plane (gaussian blur, bicubic / box
                                                            downsampling) and, with the transposed tables, its adjoint = its backward
+    osmosis::psf_apply(x, dy, dx, w, Ry, Rx, adjoint) -> out   a point-spread function (tap list) per plane over reflection padding
+                                                           (motion blur, a measured PSF); its backward is itself with `adjoint` flipped
 
 `engine` is an integer handle (`engine_handle(eng)`) because operator schemas carry tensors and scalars only; the handle
 table holds weak references, so an engine dies with its model.  An engine keeps the activations of its LAST forward pass:
@@ -667,7 +669,43 @@ def _linop_backward(ctx, grad):
 linop_apply.register_autograd(_linop_backward, setup_context=_linop_setup)
 
 
+# ---- point-spread-function operators (a 2-D kernel as a tap list): reflection padding + cross-correlation per plane, or (adjoint) the
+# exact transpose of that map; the backward is the operator itself with `adjoint` flipped
+@torch.library.custom_op("osmosis::psf_apply", mutates_args=(), device_types="cuda")
+def psf_apply(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor, Ry: int, Rx: int, adjoint: bool) -> torch.Tensor:
+    """out [B,P,H,W] of x [B,P,H,W] (osm_psf_apply): out[b,p,i,j] = sum_t w[t] x[b,p,refl_H(i+dy[t]),refl_W(j+dx[t])] (torch 'reflect'
+    padding, cross-correlation), or with `adjoint` the transpose of that map.  The tap list lives on the device: dy, dx int32 [T],
+    w fp32 [T]; Ry >= max |dy|, Rx >= max |dx| (Ry < H, Rx < W).  Differentiable w.r.t. x."""
+    if x.dim() != 4:
+        raise OsmosisHipError("osmosis::psf_apply: x must be [B,P,H,W]")
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape) or tuple(w.shape) != tuple(dy.shape):
+        raise OsmosisHipError(f"osmosis::psf_apply: expected dy [T], dx [T], w [T], got {tuple(dy.shape)}, {tuple(dx.shape)}, {tuple(w.shape)}")
+    B, P, H, W = x.shape
+    out = torch.empty((B, P, H, W), device=x.device, dtype=torch.float32)
+    ops.psf_apply(x.contiguous(), out, dy.contiguous(), dx.contiguous(), w.detach().contiguous(), Ry, Rx, B, P, P * H * W, P * H * W, H, W,
+                  adjoint=adjoint)
+    return out
+
+
+@psf_apply.register_fake
+def _psf_apply_fake(x, dy, dx, w, Ry, Rx, adjoint):
+    return x.new_empty(x.shape)
+
+
+def _psf_setup(ctx, inputs, output):
+    _x, dy, dx, w, ctx.Ry, ctx.Rx, ctx.adjoint = inputs
+    ctx.save_for_backward(dy, dx, w)
+
+
+def _psf_backward(ctx, grad):
+    dy, dx, w = ctx.saved_tensors
+    return (torch.ops.osmosis.psf_apply(grad.contiguous(), dy, dx, w, ctx.Ry, ctx.Rx, not ctx.adjoint),) + (None,) * 6
+
+
+psf_apply.register_autograd(_psf_backward, setup_context=_psf_setup)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
-       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply") + OPS_C
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply") + OPS_C

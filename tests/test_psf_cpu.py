@@ -1,0 +1,282 @@
+"""Motion-blur and arbitrary-PSF measurement operators, host side (no GPU): the tap lists against torch on the CPU in float64 (the
+oracle of these operators: the reference has none), the gather form of the adjoint, the trajectory generator and its pinned
+instance, validation, the C ABI's third header and the `osmosis::psf_apply` schema.
+
+    forward:  F.conv2d(F.pad(x, reflect), k)         (cross-correlation over torch 'reflect' padding)
+    adjoint:  its float64 vector-Jacobian product
+"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from osmosis_diffusion_code_amd import _lib
+from osmosis_diffusion_code_amd.guided_diffusion import measurements as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def conv_reflect(x, k):
+    """F.conv2d(F.pad(x, reflect), k) per plane, x [B,P,H,W] and k [kh,kw] float64 tensors."""
+    kh, kw = k.shape
+    P = x.shape[1]
+    xp = F.pad(x, (kw // 2, kw // 2, kh // 2, kh // 2), mode="reflect")
+    return F.conv2d(xp, k.expand(P, 1, kh, kw).contiguous(), groups=P)
+
+
+def refl(c, n):
+    return -c if c < 0 else (2 * (n - 1) - c if c >= n else c)
+
+
+def forward_taps(x, dy, dx, w):
+    """out[b,p,i,j] = sum_t w[t] x[b,p,refl_H(i+dy[t]),refl_W(j+dx[t])] in float64 numpy."""
+    H, W = x.shape[-2:]
+    out = np.zeros_like(x)
+    for t in range(len(w)):
+        rows = [refl(i + int(dy[t]), H) for i in range(H)]
+        cols = [refl(j + int(dx[t]), W) for j in range(W)]
+        out += float(w[t]) * x[..., rows, :][..., cols]
+    return out
+
+
+def pre(r, d, n):
+    """pre_n(r, d): the rows i in [0,n) with refl_n(i + d) = r, as the header lists them."""
+    cand = [r - d]
+    if r >= 1:
+        cand.append(-r - d)
+    if r <= n - 2:
+        cand.append(2 * (n - 1) - r - d)
+    return [i for i in cand if 0 <= i < n]
+
+
+def adjoint_taps(v, dy, dx, w):
+    """g[b,p,r,s] = sum_t w[t] sum_{i in pre_H(r,dy[t])} sum_{j in pre_W(s,dx[t])} v[b,p,i,j] in float64 numpy."""
+    H, W = v.shape[-2:]
+    g = np.zeros_like(v)
+    for t in range(len(w)):
+        for r in range(H):
+            rows = pre(r, int(dy[t]), H)
+            for s in range(W):
+                for i in rows:
+                    for j in pre(s, int(dx[t]), W):
+                        g[..., r, s] += float(w[t]) * v[..., i, j]
+    return g
+
+
+def psf_op(kernel, normalize=False):
+    return M.get_operator("psf_blur", device="cpu", kernel=kernel, normalize=normalize)
+
+
+ASYM = np.arange(1.0, 22.0).reshape(3, 7) * np.array([1.0, -0.5, 0.25])[:, None]       # no symmetry: a flip on either axis shows
+ASYM[0, 2] = ASYM[2, 5] = 0.0
+
+
+def test_operators_resolve_from_the_registry():
+    mb = M.get_operator("motion_blur", device="cpu", kernel_size=9, intensity=0.5)
+    pb = psf_op(ASYM)
+    assert mb.__name__ == "motion_blur" and pb.__name__ == "psf_blur"
+    for op in (mb, pb):
+        assert isinstance(op, M.PSFOperator) and isinstance(op, M.LinearOperator) and not isinstance(op, M.SeparableOperator)
+        assert op.out_shape(24, 36) == (24, 36)
+        assert not hasattr(op, "phi") and not hasattr(op, "get_variable_list")
+    d = M.get_operator("motion_blur", device="cpu")
+    assert (d.kernel_size, d.intensity, d.seed) == (61, 0.5, 0)
+    assert M.GRID_OPERATORS == (M.SeparableOperator, M.PSFOperator)
+    assert isinstance(M.get_operator("gaussian_blur", device="cpu"), M.GRID_OPERATORS)
+    # a nested list and a .npy path give the array's operator
+    assert all(np.array_equal(a, b) for a, b in zip(psf_op(ASYM.tolist()).host_taps(), pb.host_taps()))
+
+
+def test_npy_path_and_normalize(tmp_path):
+    path = str(tmp_path / "psf.npy")
+    np.save(path, ASYM)
+    raw, norm = psf_op(path), M.get_operator("psf_blur", device="cpu", kernel=path)
+    assert np.array_equal(raw.kernel2d(), ASYM) and norm.normalize and not raw.normalize
+    assert np.array_equal(norm.kernel2d(), ASYM / ASYM.sum()) and abs(norm.kernel2d().sum() - 1.0) < 1e-15
+
+
+@pytest.mark.parametrize("case", ["asym3x7", "motion61"])
+def test_tap_list_is_the_reflect_padded_cross_correlation(case):
+    if case == "asym3x7":
+        op, H, W = psf_op(ASYM), 20, 27
+    else:
+        op, H, W = M.get_operator("motion_blur", device="cpu"), 64, 96
+    dy, dx, w = op.host_taps()
+    k = op.kernel2d()
+    assert dy.dtype == dx.dtype == np.int32 and w.dtype == np.float32 and k.dtype == np.float64
+    # the non-zeros in row-major order, offsets from the centre, the weights the fp32 cast of the kernel's
+    assert len(w) == int((k != 0).sum()) and np.all(np.diff(dy.astype(np.int64) * 1000 + dx) > 0)
+    assert np.array_equal(w, k[dy + k.shape[0] // 2, dx + k.shape[1] // 2].astype(np.float32))
+    assert op.radius() == (int(np.abs(dy).max()), int(np.abs(dx).max())) and op.host_taps() is op.host_taps()
+    if case == "asym3x7":
+        assert len(w) == 19 and op.radius() == (1, 3)
+    x = torch.randn(2, 3, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(1))
+    want = conv_reflect(x, torch.from_numpy(k))
+    got = forward_taps(x.numpy(), dy, dx, k[dy + k.shape[0] // 2, dx + k.shape[1] // 2])       # the float64 weights
+    assert float(np.abs(got - want.numpy()).max()) <= 1e-12
+
+
+@pytest.mark.parametrize("H,W,kernel", [(20, 27, "asym"), (8, 6, "dense9"), (5, 9, "dense9x3")])
+def test_gather_form_of_the_adjoint_is_the_float64_vjp(H, W, kernel):
+    """8 x 6 under a 9 x 9 kernel: R = 4 = W - 2, both mirrors of a column land on one pixel."""
+    rng = np.random.default_rng(5)
+    k = {"asym": ASYM, "dense9": rng.standard_normal((9, 9)), "dense9x3": rng.standard_normal((9, 3))}[kernel]
+    op = psf_op(k)
+    dy, dx, _ = op.host_taps()
+    w = k[dy + k.shape[0] // 2, dx + k.shape[1] // 2]
+    if kernel == "dense9":
+        low = {c for c in range(1, W) for d in range(-4, 5) if 0 <= -c - d < W}
+        high = {c for c in range(W - 1) for d in range(-4, 5) if 0 <= 2 * (W - 1) - c - d < W}
+        assert low & high == {1, 2, 3, 4}                                                  # columns that receive both mirrors
+    x = torch.randn(2, 3, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(2)).requires_grad_(True)
+    v = torch.randn(2, 3, H, W, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    want, = torch.autograd.grad(conv_reflect(x, torch.from_numpy(k)), x, v)
+    got = adjoint_taps(v.numpy(), dy, dx, w)
+    assert float(np.abs(got - want.numpy()).max()) <= 1e-12
+    # and <A x, v> = <x, A^T v>
+    Ax = forward_taps(x.detach().numpy(), dy, dx, w)
+    assert abs(float((Ax * v.numpy()).sum()) - float((x.detach().numpy() * got).sum())) <= 1e-10
+
+
+def test_motion_kernel_is_a_normalised_connected_path_through_the_centre():
+    for ks, s, seed in ((61, 0.5, 0), (15, 0.5, 7), (9, 1.0, 3), (9, 0.0, 1), (1, 0.5, 0)):
+        k = M.motion_kernel(ks, s, seed)
+        assert k.shape == (ks, ks) and k.dtype == np.float64
+        assert abs(k.sum() - 1.0) <= 1e-14 and k.min() >= 0.0 and k[ks // 2, ks // 2] > 0.0
+        assert np.array_equal(k, M.motion_kernel(ks, s, seed))                            # deterministic in its arguments
+        pts = M.motion_trajectory(ks, s, seed)
+        r = ks // 2
+        assert pts.shape == (4 * r + 1, 2) and np.array_equal(pts[2 * r], [0.0, 0.0]) and np.abs(pts).max() <= r
+        # connected: consecutive samples at most one step apart (clamping only shortens a step), under one pixel
+        assert np.all(np.linalg.norm(np.diff(pts, axis=0), axis=1) <= M.MOTION_STEP + 1e-12)
+        # the kernel is the bilinear splat of the path: every tap within one pixel (per axis) of a sample, every sample's pixel a tap
+        iy, ix = np.nonzero(k)
+        d = np.abs(np.stack([iy, ix], 1)[:, None, :] - r - pts[None, :, :]).max(2).min(1)
+        assert d.max() < 1.0
+        assert np.all(k[np.floor(pts[:, 0]).astype(int) + r, np.floor(pts[:, 1]).astype(int) + r] > 0)
+    assert not np.array_equal(M.motion_kernel(15, 0.5, 7), M.motion_kernel(15, 0.5, 8))    # another seed, another kernel
+    assert not np.array_equal(M.motion_kernel(15, 0.5, 7), M.motion_kernel(15, 0.6, 7))
+
+
+def test_motion_kernel_equals_the_pinned_fixture():
+    gold = np.load(os.path.join(GOLD, "psf_motion.npz"))
+    assert (int(gold["kernel_size"]), float(gold["intensity"]), int(gold["seed"])) == (15, 0.5, 7)
+    k = M.motion_kernel(15, 0.5, 7)
+    assert np.array_equal(k, gold["kernel"])
+    op = M.get_operator("motion_blur", device="cpu", kernel_size=15, intensity=0.5, seed=7)
+    for got, name in zip(op.host_taps(), ("dy", "dx", "w")):
+        assert got.dtype == gold[name].dtype and np.array_equal(got, gold[name]), name
+
+
+def test_intensity_zero_is_a_straight_segment():
+    """The samples are collinear through the centre, so the taps (their bilinear footprints) lie within one pixel of that line per
+    axis, i.e. under sqrt(2) from it; at intensity 1 the same seed leaves that band."""
+    for ks, seed in ((61, 0), (15, 7), (9, 2)):
+        pts = M.motion_trajectory(ks, 0.0, seed)
+        u = pts[-1] / np.linalg.norm(pts[-1])                                             # the direction of arm 0
+        assert np.abs(pts[:, 0] * u[1] - pts[:, 1] * u[0]).max() <= 1e-12
+        assert abs(np.linalg.norm(pts[-1] - pts[0]) - 2 * (ks // 2)) <= 1e-9              # of length 2 r
+        dy, dx, _ = M.get_operator("motion_blur", device="cpu", kernel_size=ks, intensity=0.0, seed=seed).host_taps()
+        assert np.abs(dy * u[1] - dx * u[0]).max() < np.sqrt(2.0)
+    dy, dx, _ = M.get_operator("motion_blur", device="cpu", kernel_size=61, intensity=1.0, seed=0).host_taps()
+    pts = M.motion_trajectory(61, 1.0, 0)
+    u = np.array([np.sin(np.arctan2(pts[61, 0], pts[61, 1])), np.cos(np.arctan2(pts[61, 0], pts[61, 1]))])
+    assert np.abs(dy * u[1] - dx * u[0]).max() > np.sqrt(2.0)
+
+
+def test_bad_configurations_raise_value_error():
+    with pytest.raises(ValueError, match="odd"):
+        M.get_operator("motion_blur", device="cpu", kernel_size=8)
+    with pytest.raises(ValueError, match="intensity"):
+        M.get_operator("motion_blur", device="cpu", intensity=1.5)
+    with pytest.raises(ValueError, match="odd"):
+        psf_op(np.ones((4, 3)))                                                           # an even side
+    with pytest.raises(ValueError, match="odd"):
+        psf_op(np.ones((3, 6)))
+    bad = np.ones((3, 3))
+    bad[1, 2] = np.nan
+    with pytest.raises(ValueError, match="finite"):
+        psf_op(bad)
+    bad[1, 2] = np.inf
+    with pytest.raises(ValueError, match="finite"):
+        psf_op(bad)
+    with pytest.raises(ValueError, match="2-D"):
+        psf_op(np.ones(5))
+    with pytest.raises(ValueError, match="2-D"):
+        psf_op(np.ones((3, 3, 3)))
+    with pytest.raises(ValueError, match="sum"):
+        M.get_operator("psf_blur", device="cpu", kernel=np.array([[1.0, 0.0, -1.0]]), normalize=True)
+    assert psf_op(np.array([[1.0, 0.0, -1.0]])).radius() == (0, 1)                        # fine without normalize
+    with pytest.raises(ValueError, match="zero"):
+        psf_op(np.zeros((3, 3)))
+    with pytest.raises(ValueError, match="kernel"):
+        M.get_operator("psf_blur", device="cpu")
+    # the radius against the image side, worded like gaussian_blur's
+    op = psf_op(np.ones((9, 9)))
+    with pytest.raises(ValueError, match="reflection"):
+        op.out_shape(4, 16)                                                               # Ry = 4 >= H
+    with pytest.raises(ValueError, match="reflection"):
+        op.out_shape(16, 4)
+    assert op.out_shape(5, 5) == (5, 5)                                                   # R = n - 1: the largest that fits
+    with pytest.raises(ValueError, match="reflection"):
+        M.get_operator("motion_blur", device="cpu").out_shape(16, 24)
+    from osmosis_diffusion_code_amd import sampling
+    assert sampling.measurement_grid({"name": "motion_blur", "kernel_size": 9}, (24, 36)) == (24, 36)
+    assert sampling.measurement_grid({"name": "motion_blur", "kernel_size": 9, "simulate": False}, (24, 36)) == (24, 36)
+
+
+def test_psf_entry_is_exported_declared_in_its_own_header_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_psf.h")).read()
+    assert set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", hdr)) - {"osm_last_error"} == {"osm_psf_apply"} == set(_lib.EXPORTS_PSF)
+    assert re.search(r"\bint\s+osm_psf_apply\s*\(\s*const\s+float\s*\*\s*x\s*,\s*float\s*\*\s*out\s*,", hdr)
+    decl = re.search(r"osm_psf_apply\s*\(([^)]*)\)", re.sub(r"/\*.*?\*/", "", hdr.split("#ifndef")[1], flags=re.S)).group(1)
+    assert len(decl.split(",")) == len(_lib._SIGS_PSF["osm_psf_apply"]) == 17
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "osm_psf_apply")
+    assert _lib.load().osm_psf_apply.argtypes == _lib._SIGS_PSF["osm_psf_apply"]
+    # the first two headers and their export lists are what they were
+    main = open(os.path.join(ROOT, "include", "osmosis_hip.h")).read()
+    declared = set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", main)) - {"osm_status"}
+    assert declared == set(_lib.EXPORTS) and len(_lib.EXPORTS) == 99 and "osm_psf_apply" not in declared
+    assert _lib.EXPORTS_LINOP == ["osm_linop_apply"]
+    mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
+    assert "psf.hip" in mk and "osmosis_psf.h" in mk
+    from osmosis_diffusion_code_amd import torch_ops
+    assert "psf_apply" in torch_ops.OPS and "psf_apply" not in torch_ops.OPS_C
+    schema = str(torch.ops.osmosis.psf_apply.default._schema)
+    assert schema == "osmosis::psf_apply(Tensor x, Tensor dy, Tensor dx, Tensor w, SymInt Ry, SymInt Rx, bool adjoint) -> Tensor", schema
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    with FakeTensorMode():
+        out = torch.ops.osmosis.psf_apply(torch.empty(2, 3, 20, 27, device="cuda"), torch.empty(5, dtype=torch.int32, device="cuda"),
+                                          torch.empty(5, dtype=torch.int32, device="cuda"), torch.empty(5, device="cuda"), 2, 3, True)
+        assert out.shape == (2, 3, 20, 27)
+
+
+def test_psf_entry_validates_its_arguments_without_a_gpu():
+    """Null pointer, T < 1, a radius that reaches the image side, a bad flag: a non-zero status with a message, nothing launched (the
+    checks come before the launch)."""
+    lib = _lib.load()
+    p = 4096                                                                              # never dereferenced on the host
+    good = [p, p, p, p, p, 5, 2, 3, 2, 3, 3 * 64, 3 * 64, 8, 8, 0, 0, None]
+    for pos, val, word in ((0, None, "null"), (3, None, "null"), (4, None, "null"), (5, 0, "tap count"), (6, 8, "Ry"), (7, 8, "Rx"),
+                           (6, -1, "Ry"), (8, 0, "batch"), (12, 0, "image"), (10, 10, "x_img_stride"), (11, 10, "out_img_stride"),
+                           (14, 2, "adjoint"), (15, -1, "zero_planes")):
+        args = list(good)
+        args[pos] = val
+        assert lib.osm_psf_apply(*args) != 0, pos
+        msg = lib.osm_last_error().decode()
+        assert msg.startswith("osm_psf_apply") and word in msg, (pos, msg)
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
+def test_psf_header_is_strict_c99():
+    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c",
+                        os.path.join(ROOT, "include", "osmosis_psf.h")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
