@@ -1,4 +1,5 @@
-"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h and include/osmosis_psf.h).
+"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h and
+include/osmosis_physlin.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -60,6 +61,16 @@ class PhysDesc(C.Structure):
                 ("weight_type", C.c_int), ("wdepth_type", C.c_int), ("wval", C.c_float * 3),
                 ("loss_type", C.c_int), ("gamma_avrg", C.c_float), ("gamma_val", C.c_float),
                 ("eta", C.c_float * 3), ("B", C.c_int), ("HW", C.c_int), ("optimizer", C.c_int)]
+
+
+class LinDesc(C.Structure):
+    """osm_lin_desc (include/osmosis_physlin.h): one linear measurement operator, tables / taps as device addresses."""
+    _fields_ = [("family", C.c_int), ("H", C.c_int), ("W", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("start_h", C.c_void_p), ("wt_h", C.c_void_p), ("start_w", C.c_void_p), ("wt_w", C.c_void_p),
+                ("Kh", C.c_int), ("Kw", C.c_int),
+                ("tstart_h", C.c_void_p), ("twt_h", C.c_void_p), ("tstart_w", C.c_void_p), ("twt_w", C.c_void_p),
+                ("tKh", C.c_int), ("tKw", C.c_int),
+                ("dy", C.c_void_p), ("dx", C.c_void_p), ("tap_w", C.c_void_p), ("T", C.c_int), ("Ry", C.c_int), ("Rx", C.c_int)]
 
 
 class ReconDesc(C.Structure):
@@ -173,6 +184,16 @@ _SIGS_PSF = {
     "osm_psf_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _I, _I, _I, _I, _P],
 }
 EXPORTS_PSF = sorted(_SIGS_PSF)
+# the entry points of the fourth header, include/osmosis_physlin.h (the water / haze data term through a linear operator)
+_SIGS_PHYSLIN = {
+    "osm_phys_forward": [C.POINTER(PhysDesc), _P, _P, _P, _P],
+    "osm_phys_resid": [C.POINTER(PhysDesc), _I, _P, _P, _P, _P, _P, _P],
+    "osm_phys_reduce_lin": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P],
+    "osm_phys_finalize_lin": [C.POINTER(PhysDesc), _I, _P, _P, _P, _P, _I, _P, _P, _I, _P],
+    "osm_phys_grad_lin": [C.POINTER(PhysDesc), _I, _P, _P, _P, _P, _P, _I, _P],
+    "osm_phys_optimize_lin": [C.POINTER(PhysDesc), C.POINTER(LinDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+}
+EXPORTS_PHYSLIN = sorted(_SIGS_PHYSLIN)
 
 _lib = None
 _lock = threading.Lock()
@@ -191,7 +212,7 @@ def load():
                     "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
-            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()):
+            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

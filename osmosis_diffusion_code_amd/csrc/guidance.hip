@@ -9,6 +9,9 @@
 // Batch semantics: every reduction is PER IMAGE (equal to B=1 reference runs image by image,
 // SURVEY.md F1/F2).
 #include "osm_common.h"
+#include "../../include/osmosis_linop.h"
+#include "../../include/osmosis_psf.h"
+#include "../../include/osmosis_physlin.h"
 
 namespace {
 
@@ -50,7 +53,9 @@ struct Pix : PixMask<MASKED> {
 // FMA_I (the masked gradient kernel): J Ea + pinf (1 - Eb) with its one fused multiply-add spelled out -- the contraction the unmasked
 // gradient kernel compiles to on every channel; left to the compiler, the masked kernel's extra multiplies changed what got packed
 // and one channel lost the fusion, so M = 1 was one ulp off the unmasked gradient.
-template <bool MASKED, bool FMA_I = false>
+// MODEL_ONLY (the composed path, where a linear operator stands between the model and the residual): no measurement is read, y and
+// mask may be null, and r[c] carries the image I_c itself.
+template <bool MASKED, bool FMA_I = false, bool MODEL_ONLY = false>
 __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float* __restrict__ x0,
                                            const float* __restrict__ y, const float* __restrict__ mask,
                                            const float* __restrict__ phi, int b, int p, Pix<MASKED>& q) {
@@ -59,7 +64,7 @@ __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float*
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     q.rgb[c] = x0[base + (long long)c * ds.HW];
-    q.y[c] = y[(long long)b * 3 * ds.HW + (long long)c * ds.HW + p];
+    if constexpr (!MODEL_ONLY) q.y[c] = y[(long long)b * 3 * ds.HW + (long long)c * ds.HW + p];
     if constexpr (MASKED) m[c] = mask[(long long)b * 3 * ds.HW + (long long)c * ds.HW + p];
   }
   q.D = x0[base + 3LL * ds.HW];
@@ -92,7 +97,9 @@ __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float*
     } else {
       I = q.J[c] * q.Ea[c] + pinf * (1.0f - q.Eb[c]);
     }
-    if constexpr (MASKED) {
+    if constexpr (MODEL_ONLY) {
+      q.r[c] = I;
+    } else if constexpr (MASKED) {
       q.wm[c] = q.w * m[c];
       q.r[c] = (q.y[c] - (2.0f * I - 1.0f)) * q.wm[c];
     } else {
@@ -147,9 +154,16 @@ __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, cons
 
 __device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
+// LIN (the composed path): component 0, the sum of squared residuals, comes from lin.part_r [B][lin.nblk_r] -- the residual lives
+// on the measurement's grid of lin.hw pixels -- and the losses normalise by that grid.  The `false` instantiation carries no such
+// argument and is the code it always was.
+template <bool LIN> struct FinLin { const float* part_r; int nblk_r, hw; };
+template <> struct FinLin<false> {};
+
+template <bool LIN>
 __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__ part, float* __restrict__ red,
                                      float* __restrict__ phi, int do_update, float* __restrict__ loss_out,
-                                     float* __restrict__ opt_state, int nblk, int zero_guard) {
+                                     float* __restrict__ opt_state, int nblk, int zero_guard, const FinLin<LIN> lin) {
   __shared__ double tot[NRED];
   const int b = blockIdx.x;
   {   // one wave: component lane >> 2, four lanes share its nblk partials (fixed order: deterministic), fp64, two shuffle folds
@@ -159,6 +173,12 @@ __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__
     double a = 0.0;
 #pragma unroll 4
     for (int k = sub; k < nblk; k += 4) a += (double)part[((long long)b * nblk + k) * NRED + comp];
+    if constexpr (LIN) {
+      if (comp == 0) {
+        a = 0.0;
+        for (int k = sub; k < lin.nblk_r; k += 4) a += (double)lin.part_r[(long long)b * lin.nblk_r + k];
+      }
+    }
     a += __shfl_xor(a, 1, 64);
     a += __shfl_xor(a, 2, 64);
     if (sub == 0) {
@@ -168,7 +188,8 @@ __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double n = 3.0 * (double)ds.HW;
+    double n = 3.0 * (double)ds.HW;
+    if constexpr (LIN) n = 3.0 * (double)lin.hw;
     double L, gscale;
     if (ds.loss_type == 0) {
       L = sqrt(tot[0]);
@@ -328,6 +349,124 @@ __global__ __launch_bounds__(256) void phys_grad_kernel(osm_phys_desc ds, const 
     float wc = q.w;
     if constexpr (MASKED) wc = q.wm[c];
     const float dLdI = -2.0f * wc * (q.r[c] * gscale);
+    float grgb = dLdI * 0.5f * q.Ea[c];
+    if (ds.gamma_avrg != 0.f) grgb += ds.gamma_avrg * sgn(rd[10 + c]) / (float)ds.HW;
+    if (ds.gamma_val != 0.f) {
+      const float e = fmaxf(fabsf(q.rgb[c]) - 0.7f, 0.0f);
+      grgb += ds.gamma_val * 2.0f * e * sgn(q.rgb[c]) / n;
+    }
+    g[base + (long long)c * ds.HW] = grgb;
+    gD += dLdI * (-pa * q.J[c] * q.Ea[c] + pinf * pb * q.Eb[c]) * q.dd;
+  }
+  g[base + 3LL * ds.HW] = gD;
+}
+
+// ---------------------------------------------------------------- the data term through a linear operator A (blur, super-resolution)
+// y = A I on A's own grid [h,w]: the image is materialised (forward), A applied (osm_linop_apply / osm_psf_apply), the residual taken on
+// the measurement's grid (resid), A^T brings u = d S / d (A I) back (v), and the phi / x0 gradients read v where the kernels above form
+// k2 = -2 w r inline.  Reductions: fixed order through per-workgroup partial slots, no atomics.
+
+// F [B,P,HW]: planes 0..2 the image I_c, plane 3 (P = 4, weight_type 1) the depth weight w
+__global__ __launch_bounds__(256) void phys_forward_kernel(osm_phys_desc ds, const float* __restrict__ x0,
+                                                            const float* __restrict__ phi, float* __restrict__ F, int P) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= ds.HW) return;
+  Pix<false> q;
+  eval_pixel<false, true, true>(ds, x0, nullptr, nullptr, phi, b, p, q);
+  const long long base = (long long)b * P * ds.HW + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) F[base + (long long)c * ds.HW] = q.r[c];
+  if (P == 4) F[base + 3LL * ds.HW] = q.w;
+}
+
+// On the measurement's grid: r_c = (y_c - (2 (A I)_c - 1)) (A w) M_c, u_c = -2 (A w) M_c r_c, part_r[b][blk] = this workgroup's sum r^2
+__global__ __launch_bounds__(256) void phys_resid_kernel(const float* __restrict__ AF, const float* __restrict__ y,
+                                                          const float* __restrict__ mask, float* __restrict__ u,
+                                                          float* __restrict__ part_r, int P, int hw, int nblk) {
+  __shared__ float red[4];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  float s = 0.f;
+  const int pend = min(hw, (blk + 1) * PPB);
+  for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
+    const float wt = P == 4 ? AF[((long long)b * P + 3) * hw + p] : 1.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const long long e = ((long long)b * 3 + c) * hw + p;
+      const float wm = mask ? wt * mask[e] : wt;
+      const float r = (y[e] - (2.0f * AF[((long long)b * P + c) * hw + p] - 1.0f)) * wm;
+      u[e] = -2.0f * wm * r;
+      s += r * r;
+    }
+  }
+  const float t = osm::wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) part_r[(long long)b * nblk + blk] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// phys_reduce_kernel with v = A^T u [B,3,HW] read in the place of k2; slot 0 of `part` is written as 0 (the finalize takes it from part_r)
+__global__ __launch_bounds__(256) void phys_reduce_lin_kernel(osm_phys_desc ds, const float* __restrict__ x0,
+                                                               const float* __restrict__ phi, const float* __restrict__ v,
+                                                               float* __restrict__ part, int nblk) {
+  __shared__ float red[4][NRED];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  float s[NRED];
+#pragma unroll
+  for (int k = 0; k < NRED; ++k) s[k] = 0.f;
+  const int pend = min(ds.HW, (blk + 1) * PPB);
+  const float* ph = phi + b * 9;
+  for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
+    Pix<false> q;
+    eval_pixel<false, false, true>(ds, x0, nullptr, nullptr, phi, b, p, q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float pinf = ph[6 + c];
+      const float k2 = v[((long long)b * 3 + c) * ds.HW + p];
+      s[1 + c] += k2 * (-q.d * q.J[c] * q.Ea[c]);            // d I / d phi_a
+      s[4 + c] += k2 * (pinf * q.d * q.Eb[c]);               // d I / d phi_b
+      s[7 + c] += k2 * (1.0f - q.Eb[c]);                     // d I / d phi_inf
+      s[10 + c] += q.rgb[c];
+      const float e = fmaxf(fabsf(q.rgb[c]) - 0.7f, 0.0f);
+      s[13] += e * e;
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NRED; ++k) {
+    const float t = osm::wave_sum(s[k]);
+    if (lane == 0) red[wv][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < NRED) {
+    const int k = threadIdx.x;
+    part[((long long)b * nblk + blk) * NRED + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  }
+}
+
+// phys_grad_kernel with dL/dI_c = v_c gscale; mse normalises by the measurement's 3 h w, the auxiliary losses by the image's 3 HW
+__global__ __launch_bounds__(256) void phys_grad_lin_kernel(osm_phys_desc ds, const float* __restrict__ x0,
+                                                             const float* __restrict__ phi, const float* __restrict__ v,
+                                                             const float* __restrict__ red, float* __restrict__ g, int hw,
+                                                             int zero_guard) {
+  const int b = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= ds.HW) return;
+  Pix<false> q;
+  eval_pixel<false, false, true>(ds, x0, nullptr, nullptr, phi, b, p, q);
+  const float* rd = red + b * NRED;
+  const float n = 3.0f * (float)ds.HW;
+  float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / (3.0f * (float)hw);
+  if (zero_guard && ds.loss_type == 0 && rd[0] == 0.f) gscale = 0.f;   // a fully masked image: the auxiliary terms only
+  const float* ph = phi + b * 9;
+  float gD = 0.f;
+  const long long base = (long long)b * 4 * ds.HW + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float pa = ds.kind == 2 ? ph[0] : ph[c];
+    const float pb = ds.kind == 0 ? ph[3 + c] : pa;
+    const float pinf = ph[6 + c];
+    const float dLdI = v[((long long)b * 3 + c) * ds.HW + p] * gscale;
     float grgb = dLdI * 0.5f * q.Ea[c];
     if (ds.gamma_avrg != 0.f) grgb += ds.gamma_avrg * sgn(rd[10 + c]) / (float)ds.HW;
     if (ds.gamma_val != 0.f) {
@@ -686,8 +825,8 @@ int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* p
   OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
   OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
   OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
-  hipLaunchKernelGGL(phys_finalize_kernel, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
-                     do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard);
+  hipLaunchKernelGGL(phys_finalize_kernel<false>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
+                     do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard, FinLin<false>{});
   return osm::check_launch("phys_finalize_kernel");
 }
 
@@ -776,6 +915,143 @@ extern "C" int osm_phys_optimize(const osm_phys_desc* d, const float* x0, const 
                                  float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
   return phys_optimize_launch("osm_phys_optimize", d, x0, y, nullptr, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
                               stream);
+}
+
+// ---------------------------------------------------------------- the composed data term (include/osmosis_physlin.h)
+namespace {
+int check_lin_desc(const osm_phys_desc* d, const char* who) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(d->kind != 3, "%s: the identity operator (kind 3) has no image-formation model to compose with", who);
+  return OSM_OK;
+}
+
+int check_lin(const osm_phys_desc* d, const osm_lin_desc* l, const char* who) {
+  OSM_REQUIRE(l, "%s: null operator descriptor", who);
+  OSM_REQUIRE(l->family == 0 || l->family == 1, "%s: unknown operator family %d (0 separable, 1 psf)", who, l->family);
+  OSM_REQUIRE(l->H >= 1 && l->W >= 1 && l->h >= 1 && l->w >= 1, "%s: bad operator grids %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
+  OSM_REQUIRE((long long)l->H * l->W == (long long)d->HW, "%s: the operator's image grid %d x %d does not have the descriptor's HW = %d pixels",
+              who, l->H, l->W, d->HW);
+  OSM_REQUIRE((long long)l->h * l->w < (1LL << 29), "%s: measurement grid %d x %d too large", who, l->h, l->w);
+  if (l->family == 0) {
+    OSM_REQUIRE(l->start_h && l->wt_h && l->start_w && l->wt_w && l->tstart_h && l->twt_h && l->tstart_w && l->twt_w,
+                "%s: a separable operator needs its forward and transposed band tables", who);
+    OSM_REQUIRE(l->Kh >= 1 && l->Kw >= 1 && l->tKh >= 1 && l->tKw >= 1, "%s: bad band widths Kh %d, Kw %d, tKh %d, tKw %d", who, l->Kh, l->Kw,
+                l->tKh, l->tKw);
+  } else {
+    OSM_REQUIRE(l->h == l->H && l->w == l->W, "%s: a psf operator keeps the image's grid, got %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
+    OSM_REQUIRE(l->dy && l->dx && l->tap_w, "%s: a psf operator needs its tap list", who);
+    OSM_REQUIRE(l->T >= 1, "%s: bad tap count T %d", who, l->T);
+    OSM_REQUIRE(l->Ry >= 0 && l->Rx >= 0 && l->Ry < l->H && l->Rx < l->W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d",
+                who, l->Ry, l->H, l->Rx, l->W);
+  }
+  return OSM_OK;
+}
+
+inline int lin_planes(const osm_phys_desc* d) { return d->weight_type == 1 ? 4 : 3; }
+
+// out [B,P,h w] = A x [B,P,H W] (adjoint = 0) or out [B,P,H W] = A^T x [B,P,h w] (adjoint = 1), P planes, densely packed images
+int lin_apply(const osm_lin_desc* l, const float* x, float* out, int B, int P, int adjoint, void* stream) {
+  const long long HW = (long long)l->H * l->W, hw = (long long)l->h * l->w;
+  if (l->family == 1) return osm_psf_apply(x, out, l->dy, l->dx, l->tap_w, l->T, l->Ry, l->Rx, B, P, P * HW, P * HW, l->H, l->W, adjoint, 0, stream);
+  if (adjoint)
+    return osm_linop_apply(x, out, l->tstart_h, l->twt_h, l->tstart_w, l->twt_w, B, P, P * hw, P * HW, l->h, l->w, l->H, l->W, l->tKh,
+                           l->tKw, 0, stream);
+  return osm_linop_apply(x, out, l->start_h, l->wt_h, l->start_w, l->wt_w, B, P, P * HW, P * hw, l->H, l->W, l->h, l->w, l->Kh, l->Kw, 0,
+                         stream);
+}
+}  // namespace
+
+extern "C" int osm_phys_forward(const osm_phys_desc* d, const float* x0, const float* phi, float* F, void* stream) {
+  const char* who = "osm_phys_forward";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && phi && F, "%s: null pointer", who);
+  hipLaunchKernelGGL(phys_forward_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, F,
+                     lin_planes(d));
+  return osm::check_launch("phys_forward_kernel");
+}
+
+extern "C" int osm_phys_resid(const osm_phys_desc* d, int hw, const float* AF, const float* y, const float* mask, float* u,
+                              float* part_r, void* stream) {
+  const char* who = "osm_phys_resid";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
+  OSM_REQUIRE(AF && y && u && part_r, "%s: null pointer", who);
+  const int nblk = osm_phys_nblk(hw);
+  hipLaunchKernelGGL(phys_resid_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, AF, y, mask, u, part_r, lin_planes(d), hw,
+                     nblk);
+  return osm::check_launch("phys_resid_kernel");
+}
+
+extern "C" int osm_phys_reduce_lin(const osm_phys_desc* d, const float* x0, const float* phi, const float* v, float* part,
+                                   void* stream) {
+  const char* who = "osm_phys_reduce_lin";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && phi && v && part, "%s: null pointer", who);
+  const int nblk = osm_phys_nblk(d->HW);
+  hipLaunchKernelGGL(phys_reduce_lin_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, v, part, nblk);
+  return osm::check_launch("phys_reduce_lin_kernel");
+}
+
+extern "C" int osm_phys_finalize_lin(const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red, float* phi,
+                                     int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
+  const char* who = "osm_phys_finalize_lin";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
+  OSM_REQUIRE(part && part_r && red && phi, "%s: null pointer", who);
+  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+  hipLaunchKernelGGL(phys_finalize_kernel<true>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi, do_update,
+                     loss_out, opt_state, osm_phys_nblk(d->HW), masked != 0, FinLin<true>{part_r, osm_phys_nblk(hw), hw});
+  return osm::check_launch("phys_finalize_kernel<lin>");
+}
+
+extern "C" int osm_phys_grad_lin(const osm_phys_desc* d, int hw, const float* x0, const float* phi, const float* v, const float* red,
+                                 float* g, int masked, void* stream) {
+  const char* who = "osm_phys_grad_lin";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
+  OSM_REQUIRE(x0 && phi && v && red && g, "%s: null pointer", who);
+  hipLaunchKernelGGL(phys_grad_lin_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, v, red, g,
+                     hw, masked != 0);
+  return osm::check_launch("phys_grad_lin_kernel");
+}
+
+extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y, const float* mask,
+                                     float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part, float* red,
+                                     float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
+  const char* who = "osm_phys_optimize_lin";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_lin(d, lin, who))) return rc;
+  OSM_REQUIRE(x0 && y && phi && F && AF && u && v && part_r && part && red && loss_out && g, "%s: null pointer", who);
+  OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
+  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
+  // (before the first launch: a failure of a later entry point would leave the workspaces half-written)
+  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+  OSM_REQUIRE(d->optimizer == 0 || freeze_phi || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+  OSM_REQUIRE((long long)d->B * 4 <= 65535, "%s: batch %d is too large for one launch of the operator", who, d->B);
+  const int zg = mask != nullptr, hw = lin->h * lin->w, P = lin_planes(d);
+  for (int it = 0; it < n_inner; ++it) {
+    if ((rc = osm_phys_forward(d, x0, phi, F, stream))) return rc;
+    if ((rc = lin_apply(lin, F, AF, d->B, P, 0, stream))) return rc;
+    if ((rc = osm_phys_resid(d, hw, AF, y, mask, u, part_r, stream))) return rc;
+    if ((rc = lin_apply(lin, u, v, d->B, 3, 1, stream))) return rc;
+    if ((rc = osm_phys_reduce_lin(d, x0, phi, v, part, stream))) return rc;
+    if (it == n_inner - 1) {
+      if ((rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 0, loss_out, nullptr, zg, stream))) return rc;
+      if ((rc = osm_phys_grad_lin(d, hw, x0, phi, v, red, g, zg, stream))) return rc;
+      if (!freeze_phi && (rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 1, nullptr, opt_state, zg, stream))) return rc;
+    } else if ((rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 1, loss_out, opt_state, zg, stream))) {
+      return rc;
+    }
+  }
+  return OSM_OK;
 }
 
 extern "C" int osm_posterior_typed(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,

@@ -184,8 +184,17 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("scale must have 1 or 4 entries (RGBD)")
         return s.to(device).contiguous()
 
-    def _prepare(self, B, HW, device):
-        st = self._states.get((B, HW, str(device)))
+    def _degradation(self):
+        """The operator's `degradation` when the composed kernels serve it (a blur / super-resolution / PSF operator), else None."""
+        from .measurements import GRID_OPERATORS
+        deg = getattr(self.operator, "degradation", None)
+        return deg if isinstance(deg, GRID_OPERATORS) else None
+
+    def _prepare(self, B, HW, device, grid=None):
+        """The descriptor and buffers of a (B, HW, device) batch; grid = (H, W) with a degradation: keyed by (B, H, W, device), with
+        the operator's descriptor and the workspaces of the composed route (include/osmosis_physlin.h)."""
+        key = (B, HW, str(device)) if grid is None else (B, HW, str(device), int(grid[0]), int(grid[1]))
+        st = self._states.get(key)
         if st is not None:
             self._state = st
             return st
@@ -217,11 +226,17 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             # optimizer state (Adam: moments + step) of the operator's phi (torch.optim state lives with the optimizer = with the operator,
             # which the driver rebuilds per image: osmosis_sampling.py:142-155)
             self._opt = torch.zeros(op.phi.shape[0], 20, device=device, dtype=torch.float32)
-        st = {"key": (B, HW, str(device)), "desc": d,
+        st = {"key": key, "desc": d,
               "part": torch.empty(B * nblk * 16, device=device, dtype=torch.float32),
               "red": torch.zeros(B * 16, device=device, dtype=torch.float32),
               "loss": torch.zeros(B, device=device, dtype=torch.float32),
               "g": torch.empty(B, 4, HW, device=device, dtype=torch.float32)}
+        if grid is not None:
+            lin = ops.lin_desc(self._degradation(), grid[0], grid[1], device)
+            hw, P = lin.h * lin.w, ops.phys_lin_planes(d)
+            f32 = dict(device=device, dtype=torch.float32)
+            st.update(lin=lin, hw=hw, F=torch.empty(B, P, HW, **f32), AF=torch.empty(B, P, hw, **f32), u=torch.empty(B, 3, hw, **f32),
+                      v=torch.empty(B, 3, HW, **f32), part_r=torch.empty(B * ops.phys_nblk(hw), **f32))
         while len(self._states) >= 4:          # a walk uses at most two chunk sizes; older shapes give their buffers back
             self._states.pop(next(iter(self._states)))
         self._states[st["key"]] = st
@@ -234,6 +249,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         `phi` / `loss_out` / `mask`: rows of the operator's [B][9] state / of a [B] loss vector / of the [B,3,HW] mask when the
         caller walks a batch in chunks of independent images (default: the operator's whole state, the mask of
         `set_measurement_mask`)."""
+        if getattr(self.operator, "degradation", None) is not None:
+            return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] != 4:
             raise ValueError("expected x0 [B,4,H,W] and measurement [B,3,H,W]")
@@ -280,6 +297,61 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                 ops.phys_finalize(d, part, red, phi, True, loss, opt_state=self._opt_rows(opt, phi))
         return g.view(x0.shape), loss
 
+    def _loss_grad_x0_lin(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
+        """`loss_grad_x0` with the operator's `degradation` A between the image-formation model and the photo: y and the mask live on
+        A's grid (h, w) = A.out_shape(H, W).  Per inner iteration: the image (and the depth weight) materialised, A, the residual on
+        the measurement's grid, A^T, then the phi reductions and step with v = A^T u where the plain route forms -2 w r inline -- all
+        enqueued by one C call (osm_phys_optimize_lin), no host sync; OSM_PHYS_PY_LOOP=1 walks the single-launch entry points."""
+        deg = self._degradation()
+        if deg is None:
+            raise NotImplementedError(f"degradation {type(self.operator.degradation).__name__} has no HIP kernels (autograd conditioning "
+                                      "serves it)")
+        if x0.dim() != 4 or x0.shape[1] != 4:
+            raise ValueError(f"expected x0 [B,4,H,W], got {tuple(x0.shape)}")
+        B, _, H, W = x0.shape
+        h, w = deg.out_shape(H, W)
+        if tuple(y.shape) != (B, 3, h, w):
+            raise ValueError(f"expected the measurement [{B},3,{h},{w}] (the degradation's grid for a {H} x {W} image), got {tuple(y.shape)}")
+        HW, hw = H * W, h * w
+        st = self._prepare(B, HW, x0.device, grid=(H, W))
+        d, lin, part, red, loss = st["desc"], st["lin"], st["part"], st["red"], st["loss"]
+        F, AF, u, v, part_r = st["F"], st["AF"], st["u"], st["v"], st["part_r"]
+        opt = self._opt if d.optimizer != 0 else None
+        if loss_out is not None:
+            loss = loss_out
+        phi = self.operator.phi if phi is None else phi
+        if phi.shape[0] != B or not phi.is_contiguous():
+            raise ValueError("phi must be a contiguous [B][9] block")
+        g = g_out if g_out is not None else st["g"]
+        x0c, yc = x0.contiguous(), y.contiguous()
+        if mask is None:
+            if self._mask is not None and self._mask.shape[2] != hw:
+                raise ValueError(f"measurement mask [{self._mask.shape[0]},3,{self._mask.shape[2]}] does not fit a measurement "
+                                 f"[{B},3,{h},{w}] (the mask lives on the measurement's grid)")
+            mask = self.measurement_mask(B, hw, x0.device)
+        elif mask.numel() != B * 3 * hw:
+            raise ValueError(f"expected mask rows [{B},3,{hw}] (the measurement's grid {h} x {w}), got {tuple(mask.shape)}")
+        n_inner = 1 if freeze_phi else self.n_iter
+        rows = self._opt_rows(opt, phi)
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            ops.phys_optimize_lin(d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g, n_inner, freeze_phi, opt_state=rows)
+            return g.view(x0.shape), loss
+        P, masked = ops.phys_lin_planes(d), mask is not None
+        for it in range(n_inner):
+            ops.phys_forward(d, x0c, phi, F)
+            ops.phys_lin_apply(lin, F, AF, B, P)
+            ops.phys_resid(d, hw, AF, yc, mask, u, part_r)
+            ops.phys_lin_apply(lin, u, v, B, 3, adjoint=True)
+            ops.phys_reduce_lin(d, x0c, phi, v, part)
+            if it == n_inner - 1:
+                ops.phys_finalize_lin(d, hw, part, part_r, red, phi, False, loss, masked=masked)
+                ops.phys_grad_lin(d, hw, x0c, phi, v, red, g, masked=masked)
+                if not freeze_phi:
+                    ops.phys_finalize_lin(d, hw, part, part_r, red, phi, True, None, opt_state=rows, masked=masked)
+            else:
+                ops.phys_finalize_lin(d, hw, part, part_r, red, phi, True, loss, opt_state=rows, masked=masked)
+        return g.view(x0.shape), loss
+
     def _opt_rows(self, opt, phi):
         """The optimizer-state rows that belong to the phi rows in hand (a chunk of the operator's [B][9] block)."""
         if opt is None:
@@ -320,15 +392,21 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             return False
         if self.loss_weight not in (None, "none", "depth"):
             return False
+        if getattr(self.operator, "degradation", None) is not None and self._degradation() is None:
+            return False            # a degradation the composed kernels do not know: `_conditioning_autograd`
         return self.aux_loss is None or all(getattr(m, "kernel_slot", None) is not None for m in self.aux_loss.losses_list)
 
     hip_ok = _has_kernels
 
     def _loss_autograd(self, x_0_hat, measurement, **kwargs):
         """condition_methods.py:109-144 on torch tensors, for operators the kernels do not know: (sep_loss ndarray[B], loss, image)."""
-        image = self.operator.forward(x_0_hat, **kwargs)
+        deg = getattr(self.operator, "degradation", None)
+        # with a degradation A the photo is A I on A's grid (`observe`); the weight plane goes through A too (a constant of the step)
+        image = self.operator.forward(x_0_hat, **kwargs) if deg is None else self.operator.observe(x_0_hat, **kwargs)
         w = utilso.set_loss_weight(loss_weight_type=self.loss_weight, weight_function=self.weight_function,
                                    degraded_image=image.detach(), x_0_hat=x_0_hat.detach())
+        if deg is not None and torch.is_tensor(w):
+            w = deg.forward(w.detach().contiguous())
         diff = (measurement - (2 * image - 1)) * w
         m = self._mask_like(measurement)
         if m is not None:           # (mse below keeps its 3 HW denominator: a mask of ones is the unmasked loss)

@@ -620,6 +620,8 @@ class GaussianDiffusion:
         th, tw, sy, sx, window = parse_tiling(tiling)
         if rgb_guidance:
             raise NotImplementedError("tiling: rgb_guidance (the 'ps' branch) is not tiled")
+        if getattr(getattr(getattr(cond_fn, "__self__", None), "operator", None), "degradation", None) is not None:
+            raise NotImplementedError("tiling: a degradation inside the physical operator is not tiled")
         if pretrain_model != "osmosis":
             raise NotImplementedError(f"tiling: pretrain_model={pretrain_model!r} (the mean-only branch) is not tiled")
         if getattr(type(self), "p_sample", None) is DDIM.p_sample:

@@ -478,9 +478,30 @@ def _check_optimizer(name):
     raise ValueError(f"Optimizer '{name}' is not supported.")
 
 
+def build_degradation(degradation, device, batch_size=1):
+    """The linear operator between a physical image-formation model and the photo (`_PhysicalOperator(degradation=)`): None, an
+    operator instance (handed through as it is), or a dict {name: <a registered blur / super-resolution / PSF operator>, ...its
+    keys} built here.  NameError for a name nobody registered, ValueError for one that is no `GRID_OPERATORS` class."""
+    if degradation is None or not isinstance(degradation, dict):
+        return degradation
+    cfg = dict(degradation)
+    name = cfg.pop("name", None)
+    cls = __OPERATOR__.get(name)
+    grid = sorted(n for n, c in __OPERATOR__.items() if issubclass(c, GRID_OPERATORS))
+    if cls is None:
+        raise NameError(f"degradation: name {name!r} is not defined (the grid operators: {grid})")
+    if not issubclass(cls, GRID_OPERATORS):
+        raise ValueError(f"degradation: {name!r} is not a linear operator with a grid of its own (one of {grid})")
+    cfg.pop("batch_size", None)
+    return get_operator(name, device=device, batch_size=batch_size, **cfg)
+
+
 class _PhysicalOperator(LearnableOperator):
     """Shared machinery of the three image-formation models
-    I = 0.5(rgb+1) exp(-phi_a d) + phi_inf (1 - exp(-phi_b d)),  d = convert_depth(x[:,3])."""
+    I = 0.5(rgb+1) exp(-phi_a d) + phi_inf (1 - exp(-phi_b d)),  d = convert_depth(x[:,3]).
+    `degradation=` (a `GRID_OPERATORS` instance or its config dict, `build_degradation`; default None) puts a linear operator A
+    between the model and the photo: the photo in [0, 1] is A I on A's grid `out_shape(H, W)`.  `forward` stays the water / haze
+    image on the image grid; `observe` is A of it."""
     KIND = -1
     VARS = ()
 
@@ -492,6 +513,7 @@ class _PhysicalOperator(LearnableOperator):
         self.depth_code, self.depth_vals = utilso.depth_code_and_values(self.depth_type, kwargs.get("value", None))
         self.optimizer = _check_optimizer(kwargs.get("optimizer", None))
         self._requires_grad = {v: False for v in self.VARS}
+        self.degradation = build_degradation(kwargs.get("degradation", None), self.device, batch_size)
 
     # -- state ------------------------------------------------------------------------------
     def _init_phi(self, a, b, inf):
@@ -536,6 +558,16 @@ class _PhysicalOperator(LearnableOperator):
         pa = lv["phi_a"] if "phi_a" in lv else lv["phi_ab"]
         pb = lv["phi_b"] if "phi_b" in lv else pa
         return rgb01 * torch.exp(-pa * d) + lv["phi_inf"] * (1 - torch.exp(-pb * d))
+
+    def observe(self, data, **kwargs):
+        """What the camera records, in [0, 1]: `degradation.forward(forward(data))` on the degradation's grid (differentiable
+        through `osmosis::linop_apply` / `osmosis::psf_apply`); without a degradation, `forward(data)`."""
+        image = self.forward(data, **kwargs)
+        return image if self.degradation is None else self.degradation.forward(image.contiguous())
+
+    def out_shape(self, H, W):
+        """(h, w) of the measurement of an H x W image."""
+        return (int(H), int(W)) if self.degradation is None else tuple(self.degradation.out_shape(int(H), int(W)))
 
     def optimize(self, **kwargs):
         """measurements.py:266-303.  The package's conditioning method steps phi on the device (osm_phys_finalize) and calls this

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, GemmDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
+from ._lib import AttnDesc, ConvDesc, GemmDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
 
 
 @dataclass
@@ -718,3 +718,101 @@ def psf_apply(x, out, dy, dx, w, Ry, Rx, B, P, x_img_stride, out_img_stride, H, 
                                    f"{P} -> {P + Z} planes of {H} x {W} at strides {x_img_stride} / {out_img_stride}")
     call("osm_psf_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), int(w.shape[0]), int(Ry), int(Rx), B, P, int(x_img_stride),
          int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(), keep=(x, out, dy, dx, w))
+
+
+# ----------------------------------------------------------------------------- the water / haze data term through a linear operator
+def lin_desc(operator, H, W, device) -> LinDesc:
+    """The osm_lin_desc of a `measurements.GRID_OPERATORS` instance at the image grid H x W (include/osmosis_physlin.h).  The device
+    tables / taps it points at are the operator's own cached tensors; they are also kept on the descriptor (`_keep`)."""
+    from .guided_diffusion.measurements import PSFOperator, SeparableOperator
+    d = LinDesc()
+    h, w = operator.out_shape(H, W)
+    d.H, d.W, d.h, d.w = int(H), int(W), int(h), int(w)
+    if isinstance(operator, PSFOperator):
+        dy, dx, tw = operator.taps(device)
+        d.family, d.dy, d.dx, d.tap_w, d.T = 1, ptr(dy), ptr(dx), ptr(tw), int(tw.shape[0])
+        d.Ry, d.Rx = operator.radius()
+        d._keep = (dy, dx, tw)
+    elif isinstance(operator, SeparableOperator):
+        t = operator.tables(H, W, device)
+        (sh, wh, sw, ww), (tsh, twh, tsw, tww) = t["fwd"], t["adj"]
+        d.family = 0
+        d.start_h, d.wt_h, d.start_w, d.wt_w, d.Kh, d.Kw = ptr(sh), ptr(wh), ptr(sw), ptr(ww), int(wh.shape[1]), int(ww.shape[1])
+        d.tstart_h, d.twt_h, d.tstart_w, d.twt_w = ptr(tsh), ptr(twh), ptr(tsw), ptr(tww)
+        d.tKh, d.tKw = int(twh.shape[1]), int(tww.shape[1])
+        d._keep = t["fwd"] + t["adj"]
+    else:
+        raise _lib.OsmosisHipError(f"lin_desc: {type(operator).__name__} is neither a SeparableOperator nor a PSFOperator")
+    return d
+
+
+def phys_lin_planes(desc: PhysDesc) -> int:
+    """Planes of the forward workspace F: the image, and the depth weight when the loss is weighted."""
+    return 4 if desc.weight_type == 1 else 3
+
+
+def _check_lin_ws(name, desc, hw, **ws):
+    B, HW, P = desc.B, desc.HW, phys_lin_planes(desc)
+    need = {"F": B * P * HW, "AF": B * P * hw, "u": B * 3 * hw, "v": B * 3 * HW, "part_r": B * phys_nblk(hw), "y": B * 3 * hw,
+            "mask": B * 3 * hw, "part": B * phys_nblk(HW) * 16, "x0": B * 4 * HW, "g": B * 4 * HW, "phi": B * 9, "red": B * 16}
+    for k, t in ws.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need[k] or (k in ("y", "mask") and t.numel() != need[k]):
+            raise ValueError(f"{name}: `{k}` must be contiguous fp32 with {need[k]} elements, got {tuple(t.shape)} {t.dtype}")
+
+
+def phys_forward(desc: PhysDesc, x0, phi, F):
+    """F [B,P,HW] = the water / haze image I (and the depth weight, P = 4) of x0 at phi (osm_phys_forward)."""
+    _check_lin_ws("phys_forward", desc, 1, x0=x0, phi=phi, F=F)
+    call("osm_phys_forward", C.byref(desc), ptr(x0), ptr(phi), ptr(F), _s(), keep=(desc, x0, phi, F))
+
+
+def phys_resid(desc: PhysDesc, hw, AF, y, mask, u, part_r):
+    """u [B,3,hw] = d S / d (A I) and the partial sums of the squared residual on the measurement's grid (osm_phys_resid)."""
+    _check_lin_ws("phys_resid", desc, hw, AF=AF, y=y, mask=mask, u=u, part_r=part_r)
+    call("osm_phys_resid", C.byref(desc), int(hw), ptr(AF), ptr(y), ptr(mask), ptr(u), ptr(part_r), _s(),
+         keep=(desc, AF, y, mask, u, part_r))
+
+
+def phys_reduce_lin(desc: PhysDesc, x0, phi, v, part):
+    _check_lin_ws("phys_reduce_lin", desc, 1, x0=x0, phi=phi, v=v, part=part)
+    call("osm_phys_reduce_lin", C.byref(desc), ptr(x0), ptr(phi), ptr(v), ptr(part), _s(), keep=(desc, x0, phi, v, part))
+
+
+def phys_finalize_lin(desc: PhysDesc, hw, part, part_r, red, phi, do_update, loss_out, opt_state=None, masked=False):
+    _check_lin_ws("phys_finalize_lin", desc, hw, part=part, part_r=part_r, red=red, phi=phi)
+    call("osm_phys_finalize_lin", C.byref(desc), int(hw), ptr(part), ptr(part_r), ptr(red), ptr(phi), int(do_update), ptr(loss_out),
+         ptr(opt_state), int(bool(masked)), _s(), keep=(desc, part, part_r, red, phi, loss_out, opt_state))
+
+
+def phys_grad_lin(desc: PhysDesc, hw, x0, phi, v, red, g, masked=False):
+    _check_lin_ws("phys_grad_lin", desc, hw, x0=x0, phi=phi, v=v, red=red, g=g)
+    call("osm_phys_grad_lin", C.byref(desc), int(hw), ptr(x0), ptr(phi), ptr(v), ptr(red), ptr(g), int(bool(masked)), _s(),
+         keep=(desc, x0, phi, v, red, g))
+
+
+def phys_lin_apply(lin: LinDesc, x, out, B, P, adjoint=False):
+    """out [B,P,hw] = A x [B,P,HW], or with `adjoint` out [B,P,HW] = A^T x [B,P,hw]: the launch osm_phys_optimize_lin makes."""
+    HW, hw = lin.H * lin.W, lin.h * lin.w
+    n_in, n_out = (hw, HW) if adjoint else (HW, hw)
+    keep = lin._keep
+    if lin.family == 1:
+        psf_apply(x, out, *keep, lin.Ry, lin.Rx, B, P, P * n_in, P * n_out, lin.H, lin.W, adjoint=adjoint)
+    elif adjoint:
+        linop_apply(x, out, *keep[4:], B, P, P * n_in, P * n_out, lin.h, lin.w)
+    else:
+        linop_apply(x, out, *keep[:4], B, P, P * n_in, P * n_out, lin.H, lin.W)
+
+
+def phys_optimize_lin(desc: PhysDesc, lin: LinDesc, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, n_inner: int,
+                      freeze_phi: bool, opt_state=None):
+    """The inner phi loop of a guided step with a linear operator between the image-formation model and the residual, enqueued by
+    one call (osm_phys_optimize_lin): per iteration forward, A, resid, A^T, reduce_lin, finalize_lin."""
+    if lin.H * lin.W != desc.HW:
+        raise ValueError(f"phys_optimize_lin: the operator's image grid {lin.H} x {lin.W} does not have HW = {desc.HW} pixels")
+    _check_lin_ws("phys_optimize_lin", desc, lin.h * lin.w, x0=x0, y=y, mask=mask, phi=phi, F=F, AF=AF, u=u, v=v, part_r=part_r,
+                  part=part, red=red, g=g)
+    call("osm_phys_optimize_lin", C.byref(desc), C.byref(lin), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(F), ptr(AF), ptr(u), ptr(v),
+         ptr(part_r), ptr(part), ptr(red), ptr(loss_out), ptr(g), int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(),
+         keep=(desc, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, opt_state) + tuple(lin._keep))

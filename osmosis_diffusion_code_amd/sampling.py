@@ -46,11 +46,15 @@ def degamma(y):
     return 2 * torch.pow(0.5 * (y + 1), 2.2) - 1
 
 
-def postprocess(out_xstart, variable_dict, ref_img, operator_cfg, loss=None):
+def postprocess(out_xstart, variable_dict, ref_img, operator_cfg, loss=None, observed=None):
     """Outputs of one restored image (osmosis_sampling.py:199-300), all CPU tensors.
 
     out_xstart [B,4,H,W] (the final pred_xstart -- the reference saves THAT, not the final x_t), ref_img
-    [B,3,H,W] in [-1,1]; like the reference only image 0 of the batch is post-processed."""
+    [B,3,H,W] in [-1,1]; like the reference only image 0 of the batch is post-processed.
+    observed (a chain whose physical operator carries a `degradation` A; ref_img is then the photo on A's grid [B,3,h,w]):
+    2 A forward_predicted - 1 of image 0, [3,h,w], computed by the caller with the chain's operator.  The result carries it as
+    `observed`, `norm_loss_final` is taken against it, and `rgb_recon` (the closed form from the photo) is present only when the
+    photo has the image's size."""
     out_xstart = out_xstart.detach().cpu()
     ref = ref_img.detach().cpu()
     ref_img_01 = 0.5 * (ref[0] + 1)
@@ -85,12 +89,28 @@ def postprocess(out_xstart, variable_dict, ref_img, operator_cfg, loss=None):
     out.update(
         depth_calc=depth_calc, backscatter=backscatter, attenuation=attenuation,
         forward_predicted=forward_pred, degraded=degraded,
-        norm_loss_final=float(np.round(torch.linalg.norm(degraded - ref).numpy(), decimals=3)),
-        rgb_recon=torch.exp(phi_a * depth_calc) * (ref_img_01 - backscatter),   # "clean" image from phi and the input
         phi={k: v.detach().cpu() for k, v in variable_dict.items()},
         loss=None if loss is None else np.asarray(loss),
     )
+    if observed is None:
+        out["norm_loss_final"] = float(np.round(torch.linalg.norm(degraded - ref).numpy(), decimals=3))
+    else:
+        observed = observed.detach().cpu()
+        if tuple(observed.shape) != tuple(ref.shape[1:]):
+            raise ValueError(f"observed must be {tuple(ref.shape[1:])} (the photo's grid), got {tuple(observed.shape)}")
+        out["observed"] = observed
+        out["norm_loss_final"] = float(np.round(torch.linalg.norm(observed - ref[0]).numpy(), decimals=3))
+    if tuple(ref.shape[-2:]) == tuple(sample_rgb.shape[-2:]):
+        out["rgb_recon"] = torch.exp(phi_a * depth_calc) * (ref_img_01 - backscatter)   # "clean" image from phi and the input
     return out
+
+
+def observed_image(operator, out_xstart):
+    """`postprocess`'s `observed` for a physical operator with a degradation: 2 A I - 1 of every image of the batch at the chain's
+    final phi (per image), [B,3,h,w], computed on the operator's device (the degradation's own kernel); `postprocess` takes row 0,
+    `postprocess_each` row b."""
+    with torch.no_grad():
+        return 2 * operator.observe(out_xstart.detach().to(operator.device, torch.float32).contiguous()) - 1
 
 
 def load_config(path):
@@ -301,6 +321,17 @@ def measurement_grid(operator_cfg, hw):
     where the image handed in IS the measurement)."""
     from .guided_diffusion import measurements
     cls = measurements.__OPERATOR__.get(operator_cfg.get("name"))
+    if operator_cfg.get("degradation") is not None:
+        # a physical operator with a degradation: the image handed in IS the measurement, so is its grid (the chain's image lives on
+        # the network's grid, `model_grid`, whose `out_shape` this must be); the name is checked against the registry, nothing is built
+        deg = operator_cfg["degradation"]
+        if isinstance(deg, dict):
+            dcls = measurements.__OPERATOR__.get(deg.get("name"))
+            if dcls is None:
+                raise NameError(f"degradation: name {deg.get('name')!r} is not defined")
+            if not issubclass(dcls, GRID_OPERATORS):
+                raise ValueError(f"degradation: {deg.get('name')!r} is not a linear operator with a grid of its own")
+        return tuple(hw)
     if cls is None or not issubclass(cls, GRID_OPERATORS) or not operator_cfg.get("simulate", True):
         return tuple(hw)
     kw = {k: v for k, v in operator_cfg.items() if k != "name"}
@@ -377,6 +408,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     op_cfg = dict(measure["operator"])
     op_cfg["batch_size"] = ref_img.shape[0]
     operator = get_operator(device=device, **op_cfg)
+    degraded = getattr(operator, "degradation", None) is not None       # `measurement.operator.degradation: {name: ..., ...}`
+    if degraded and tiling is not None:
+        raise NotImplementedError("tiling: a degradation inside the physical operator is not tiled")
     noiser = get_noise(**measure["noise"])
     cond = get_conditioning_method(cond_cfg["method"], operator, noiser, **cond_cfg["params"],
                                    **cfg["sample_pattern"], **cfg["aux_loss"])
@@ -398,6 +432,13 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             shape[2:] = grid
         y_n = noiser(y_clean)
     else:
+        if degraded:
+            # the photo IS the measurement (it is never simulated here): it lives on the degradation's grid for the network's image
+            grid = model_grid(model, ref_img)
+            if tuple(ref_img.shape[-2:]) != tuple(operator.out_shape(*grid)):
+                raise ValueError(f"degradation: the photo is the measurement itself: expected {tuple(operator.out_shape(*grid))} (the "
+                                 f"degradation's grid for a {grid[0]} x {grid[1]} image), got {tuple(ref_img.shape[-2:])}")
+            shape[2:] = grid
         y_n = noiser(ref_img)
     if cfg.get("degamma_input", False):
         y_n = degamma(y_n)
@@ -430,10 +471,13 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             continue
         sample, variable_dict, loss, out_xstart = ret
         if postprocess_batch:
-            post = postprocess(out_xstart, variable_dict, ref_img, measure["operator"], loss)
+            post = postprocess(out_xstart, variable_dict, ref_img, measure["operator"], loss,
+                               observed=observed_image(operator, out_xstart)[0] if degraded else None)
         else:
             post = dict(phi={k: v.detach().cpu() for k, v in variable_dict.items()},
                         loss=None if loss is None else np.asarray(loss))
+            if degraded:            # every image's `observed`, for the caller's per-image post-processing (`postprocess_each`)
+                post["observed"] = observed_image(operator, out_xstart).cpu()
         post.update(sample=sample.detach().cpu(), pred_xstart=out_xstart, measurement=y_n.detach().cpu())
         if m_dev is not None:
             post["mask"] = m_dev.detach().cpu()
@@ -443,13 +487,19 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     return results
 
 
-def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None):
-    """`postprocess` for every image of a batch (the reference only ever has one)."""
+def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None, observed=None):
+    """`postprocess` for every image of a batch (the reference only ever has one).  observed: [B,3,h,w] (`observed_image`) for a
+    chain whose physical operator carries a degradation -- required then, as the photo lives on the degradation's grid."""
+    if operator_cfg.get("degradation") is not None and observed is None:
+        raise ValueError("postprocess_each: a physical operator with a degradation needs `observed` [B,3,h,w] (observed_image)")
+    if observed is not None and observed.shape[0] != out_xstart.shape[0]:
+        raise ValueError(f"observed must have one row per image: {tuple(observed.shape)} for {out_xstart.shape[0]} images")
     outs = []
     for b in range(out_xstart.shape[0]):
         vd = {k: v[b:b + 1] for k, v in variable_dict.items()}
         outs.append(postprocess(out_xstart[b:b + 1], vd, ref_img[b:b + 1], operator_cfg,
-                                None if loss is None else np.asarray(loss)[b:b + 1]))
+                                None if loss is None else np.asarray(loss)[b:b + 1],
+                                observed=None if observed is None else observed[b]))
     return outs
 
 
@@ -470,6 +520,8 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
         loop_kwargs = dict(loop_kwargs, tiling=tiling)
     if (originals is None) != (geometries is None):
         raise ValueError("originals and geometries go together")
+    if originals is not None and cfg.get("measurement", {}).get("operator", {}).get("degradation") is not None:
+        raise NotImplementedError("full-resolution reconstruction with a degradation inside the physical operator is not implemented")
     if masks is not None and len(masks) != len(images):
         raise ValueError(f"masks must align with images: {len(masks)} masks for {len(images)} images")
 
@@ -497,7 +549,8 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
             full = restore_image(model, ref, cfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
                                  postprocess_batch=False, mask=batch_mask(idxs), **loop_kwargs)[-1]
             if "pred_xstart" in full:
-                res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"])
+                res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"],
+                                       observed=full.get("observed"))
                 for b, r in enumerate(res):
                     r.update(sample=full["sample"][b:b + 1], pred_xstart=full["pred_xstart"][b:b + 1],
                              measurement=full["measurement"][b:b + 1])

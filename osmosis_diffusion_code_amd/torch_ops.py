@@ -19,6 +19,7 @@ registered for the "cuda" device type only, which is HIP on ROCm).
     osmosis::guide_update(mean, log_variance, g, dx_unet, noise, coef, scale4, clip) -> (x_next, grad)
                                                            condition_methods.py:186-221 update rule + the noise add of :262-271
     osmosis::phys_loss_grad(x0, y, phi, icfg, fcfg, n_inner, freeze_phi) -> (loss, grad_x0, phi_new)
+    osmosis::phys_loss_grad_lin(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, family, tables, dims) -> (loss, grad_x0, phi_new)
                                                            measurements.py forward models + the inner phi optimisation
                                                            (cm.py:141-184), functional (phi is returned, not updated in place)
     osmosis::recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, mode, radius, sigma_s, sigma_r)
@@ -705,7 +706,100 @@ def _psf_backward(ctx, grad):
 psf_apply.register_autograd(_psf_backward, setup_context=_psf_setup)
 
 
+# ---- the water / haze data term through a linear operator (blur, super-resolution, a PSF) between the model and the photo
+def lin_config(operator, H, W, device) -> Tuple[int, List[torch.Tensor], List[int]]:
+    """(family, tables, dims) of a `measurements.GRID_OPERATORS` instance for phys_loss_grad_lin at the image grid H x W:
+    family 0 (separable): the four forward band tables then the four transposed ones, dims = [h, w];
+    family 1 (psf): dy, dx, w, dims = [Ry, Rx]."""
+    from .guided_diffusion.measurements import PSFOperator, SeparableOperator
+    if isinstance(operator, PSFOperator):
+        operator.out_shape(H, W)
+        return 1, list(operator.taps(device)), list(operator.radius())
+    if not isinstance(operator, SeparableOperator):
+        raise OsmosisHipError(f"lin_config: {type(operator).__name__} is neither a SeparableOperator nor a PSFOperator")
+    t = operator.tables(H, W, device)
+    return 0, list(t["fwd"]) + list(t["adj"]), list(operator.out_shape(H, W))
+
+
+@torch.library.custom_op("osmosis::phys_loss_grad_lin", mutates_args=(), device_types="cuda")
+def phys_loss_grad_lin(x0: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], phi: torch.Tensor, icfg: List[int],
+                       fcfg: List[float], n_inner: int, freeze_phi: bool, family: int, tables: List[torch.Tensor],
+                       dims: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::phys_loss_grad_m with a linear operator A between the image-formation model and the photo (osm_phys_optimize_lin):
+    x0 [B,4,H,W]; y [B,3,h,w] and the optional mask ([B,3,h,w] / [B,1,h,w]) on A's grid; the residual of channel c is
+    (y_c - (2 (A I)_c - 1)) (A w) M_c, mse divides by 3 h w.  A travels as `lin_config(operator, H, W, device)`.  SGD / GD only."""
+    name = "osmosis::phys_loss_grad_lin"
+    from ._lib import LinDesc
+    B, HW = _chw(x0)
+    H, W = x0.shape[2], x0.shape[3]
+    if len(icfg) != len(PHYS_ICFG) or len(fcfg) != len(PHYS_FCFG):
+        raise OsmosisHipError(f"{name}: icfg / fcfg must come from torch_ops.phys_config(desc)")
+    d = PhysDesc()
+    for k, v in zip(PHYS_ICFG, icfg):
+        setattr(d, k, int(v))
+    if d.optimizer != 0:
+        raise OsmosisHipError(f"{name} is functional: optimizer state (adam, ...) lives with the conditioning method")
+    if d.kind == 3:
+        raise OsmosisHipError(f"{name}: the identity operator (kind 3) has no image-formation model to compose with")
+    for i in range(3):
+        d.dval[i], d.wval[i], d.eta[i] = fcfg[i], fcfg[3 + i], fcfg[8 + i]
+    d.gamma_avrg, d.gamma_val = fcfg[6], fcfg[7]
+    d.B, d.HW = B, HW
+    lin = LinDesc()
+    lin.family, lin.H, lin.W = int(family), H, W
+    if family == 0:
+        if len(tables) != 8 or len(dims) != 2:
+            raise OsmosisHipError(f"{name}: a separable operator is 8 band tables (forward, transposed) and dims = [h, w]")
+        h, w = int(dims[0]), int(dims[1])
+        fwd = _linop_tables(name, *tables[:4], h, w)
+        adj = _linop_tables(name, *tables[4:], H, W)
+        for t in fwd + adj:
+            if t.dtype not in (torch.int32, torch.float32):
+                raise OsmosisHipError(f"{name}: band tables are start int32 / wt fp32")
+        # (four tables, a min and a max each: eight device-to-host reads per call -- this functional operator is off the fused loop,
+        #  which hands the operator's own checked tables to osm_phys_optimize_lin; an out-of-range start would be an out-of-bounds read)
+        for (start, wt), n_in in zip(((fwd[0], fwd[1]), (fwd[2], fwd[3]), (adj[0], adj[1]), (adj[2], adj[3])), (H, W, h, w)):
+            if start.numel() and (int(start.min()) < 0 or int(start.max()) + wt.shape[1] > n_in):
+                raise OsmosisHipError(f"{name}: a band table reads outside [0, {n_in})")
+        lin.h, lin.w = h, w
+        lin.start_h, lin.wt_h, lin.start_w, lin.wt_w = (ops.ptr(t) for t in fwd)
+        lin.tstart_h, lin.twt_h, lin.tstart_w, lin.twt_w = (ops.ptr(t) for t in adj)
+        lin.Kh, lin.Kw, lin.tKh, lin.tKw = fwd[1].shape[1], fwd[3].shape[1], adj[1].shape[1], adj[3].shape[1]
+        lin._keep = fwd + adj
+    elif family == 1:
+        if len(tables) != 3 or len(dims) != 2:
+            raise OsmosisHipError(f"{name}: a psf operator is the tap list dy, dx, w and dims = [Ry, Rx]")
+        dy, dx, tw = (t.contiguous() for t in tables)
+        if dy.dim() != 1 or dy.dtype != torch.int32 or dx.dtype != torch.int32 or tw.dtype != torch.float32 \
+                or tuple(dx.shape) != tuple(dy.shape) or tuple(tw.shape) != tuple(dy.shape) or dy.numel() < 1:
+            raise OsmosisHipError(f"{name}: expected dy int32 [T], dx int32 [T], w fp32 [T]")
+        h, w = H, W
+        lin.h, lin.w, lin.Ry, lin.Rx, lin.T = H, W, int(dims[0]), int(dims[1]), int(tw.shape[0])
+        if not (0 <= lin.Ry < H and 0 <= lin.Rx < W):
+            raise OsmosisHipError(f"{name}: reflection padding needs 0 <= Ry < H and 0 <= Rx < W")
+        lin.dy, lin.dx, lin.tap_w = ops.ptr(dy), ops.ptr(dx), ops.ptr(tw)
+        lin._keep = (dy, dx, tw)
+    else:
+        raise OsmosisHipError(f"{name}: family must be 0 (separable) or 1 (psf)")
+    if tuple(y.shape) != (B, 3, h, w):
+        raise OsmosisHipError(f"{name}: expected y [{B},3,{h},{w}] on the operator's grid, got {tuple(y.shape)}")
+    hw, P, dev = h * w, ops.phys_lin_planes(d), x0.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    phi_new = phi.detach().clone().contiguous()
+    red, loss, g = torch.zeros(B * 16, **f32), torch.zeros(B, **f32), torch.empty_like(x0)
+    ops.phys_optimize_lin(d, lin, x0, y.contiguous(), None if mask is None else _mask_rows(name, mask, y), phi_new,
+                          torch.empty(B, P, HW, **f32), torch.empty(B, P, hw, **f32), torch.empty(B, 3, hw, **f32),
+                          torch.empty(B, 3, HW, **f32), torch.empty(B * ops.phys_nblk(hw), **f32),
+                          torch.empty(B * ops.phys_nblk(HW) * 16, **f32), red, loss, g, 1 if freeze_phi else n_inner, freeze_phi)
+    return loss, g, phi_new
+
+
+@phys_loss_grad_lin.register_fake
+def _phys_loss_grad_lin_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, family, tables, dims):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
-       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply") + OPS_C
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin") + OPS_C

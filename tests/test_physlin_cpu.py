@@ -1,0 +1,348 @@
+"""The water / haze data term through a blur / super-resolution operator, host side (no GPU): the oracle of the composed loss
+(tests/physlin_oracle.py) against the plain oracle at A = identity, the `degradation=` key of the physical operators and of
+`restore_image`'s config with its validation errors, the measurement's grid, the fourth header of the C ABI."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import diffusion_ref as D
+from osmosis_diffusion_code_amd import _lib
+from osmosis_diffusion_code_amd.guided_diffusion import condition_methods as CM
+from osmosis_diffusion_code_amd.guided_diffusion import measurements as M
+from physlin_oracle import DEGRADATIONS, LinGuidance, dense_operator
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OKW = dict(depth_type="gamma", value="1.4,1.4,1", phi_a="1.1,0.95,0.95", phi_b="0.95, 0.8, 0.8", phi_inf="0.14, 0.29, 0.49")
+AUX = {"avrg_loss": 0.5, "val_loss": 20}
+
+
+def inputs(B, H, W, h, w, seed):
+    g = torch.Generator().manual_seed(seed)
+    x0 = (0.6 * torch.randn(B, 4, H, W, generator=g, dtype=torch.float64)).clamp(-1.0, 1.0)
+    y = torch.rand(B, 3, h, w, generator=g, dtype=torch.float64) * 1.6 - 0.8
+    return x0, y
+
+
+@pytest.mark.parametrize("loss_function", ["norm", "mse"])
+@pytest.mark.parametrize("loss_weight", ["none", "depth"])
+def test_the_oracle_with_a_delta_psf_is_the_plain_oracle(loss_function, loss_weight):
+    """A = identity (a 3 x 5 PSF that is 1 at its centre): loss, d / d phi and d / d x0 of the composed oracle equal the plain
+    `OsmosisGuidance` ones to float64 round-off, everything evaluated in float64."""
+    H, W = 13, 11
+    k = np.zeros((3, 5))
+    k[1, 2] = 1.0
+    deg = M.get_operator("psf_blur", device="cpu", kernel=k, normalize=False)
+    x0, y = inputs(1, H, W, H, W, 3)
+    out = []
+    for cls in (D.OsmosisGuidance, LinGuidance):
+        op = D.PhysOperator("underwater_physical_revised", batch_size=1, **OKW)
+        op.phi = {n: p.double() for n, p in op.phi.items()}
+        guide = cls(op, n_iter=1, aux=AUX, loss_function=loss_function, loss_weight=loss_weight)
+        if cls is LinGuidance:
+            guide.A = dense_operator(deg, H, W)
+        xb = x0.clone().requires_grad_(True)
+        op.set_requires_grad(True)
+        sep, loss = guide.loss(xb, y)
+        loss.backward(inputs=[xb] + list(op.phi.values()))
+        out.append((float(sep[0]), float(loss), xb.grad.clone(), [p.grad.clone() for p in op.phi.values()]))
+    (s0, l0, g0, p0), (s1, l1, g1, p1) = out
+    assert abs(s0 - s1) <= 1e-14 * abs(s0) and abs(l0 - l1) <= 1e-14 * abs(l0)
+    assert float((g0 - g1).abs().max()) <= 1e-14 * float(g0.abs().max())
+    for a, b in zip(p0, p1):
+        assert float((a - b).abs().max()) <= 1e-13 * float(a.abs().max())
+    assert float(g0.abs().max()) > 0
+
+
+def test_dense_operator_is_the_tables_and_the_taps():
+    """The oracle's A: for a blur, rows summing to 1 and the reflected band; for the PSF, cross-correlation with the fp32 kernel
+    (an impulse returns the flipped kernel); for super-resolution, the [h,H] x [w,W] pair."""
+    H, W = 12, 10
+    blur = M.get_operator(device="cpu", **DEGRADATIONS["gaussian_blur"])
+    ones = torch.ones(1, 3, H, W)
+    assert float((dense_operator(blur, H, W)(ones) - 1).abs().max()) < 1e-6
+    psf = M.get_operator(device="cpu", **DEGRADATIONS["psf_blur"])
+    k = np.asarray(DEGRADATIONS["psf_blur"]["kernel"], dtype=np.float32).astype(np.float64)
+    imp = torch.zeros(1, 1, H, W)
+    imp[0, 0, 6, 5] = 1.0
+    out = dense_operator(psf, H, W)(imp)[0, 0]
+    assert np.allclose(out[5:8, 2:9].numpy(), k[::-1, ::-1], atol=0) and abs(float(out.sum()) - k.sum()) < 1e-12
+    sr = M.get_operator(device="cpu", **DEGRADATIONS["sr2_box"])
+    x = torch.arange(H * W, dtype=torch.float64).reshape(1, 1, H, W)
+    assert torch.allclose(dense_operator(sr, H, W)(x), torch.nn.functional.avg_pool2d(x, 2), atol=1e-12)
+
+
+def test_degradation_key_builds_the_operator_and_validates_it():
+    for opname, okw in (("underwater_physical_revised", OKW),
+                        ("haze_physical", dict(depth_type="gamma", value="1.4,1.4,1", phi_ab="1.0", phi_inf="0.14, 0.29, 0.49"))):
+        plain = M.get_operator(opname, device="cpu", **okw)
+        assert plain.degradation is None and plain.out_shape(16, 24) == (16, 24)
+        op = M.get_operator(opname, device="cpu", batch_size=2, degradation=DEGRADATIONS["sr2_bicubic"], **okw)
+        assert isinstance(op.degradation, M.SuperResolutionOperator) and op.degradation.batch_size == 2
+        assert op.out_shape(16, 24) == (8, 12)
+        with pytest.raises(ValueError, match="multiple"):
+            op.out_shape(15, 24)
+        inst = M.get_operator("motion_blur", device="cpu", kernel_size=9)
+        assert M.get_operator(opname, device="cpu", degradation=inst, **okw).degradation is inst
+    assert M.get_operator("underwater_physical_revised", device="cpu", degradation=DEGRADATIONS["psf_blur"], **OKW).out_shape(9, 9) == (9, 9)
+    with pytest.raises(NameError, match="not_an_operator"):
+        M.get_operator("underwater_physical_revised", device="cpu", degradation={"name": "not_an_operator"}, **OKW)
+    with pytest.raises(ValueError, match="haze_physical"):          # registered, but no linear operator with a grid
+        M.get_operator("underwater_physical_revised", device="cpu", degradation={"name": "haze_physical"}, **OKW)
+    with pytest.raises(ValueError, match="kernel_size"):            # the degradation's own validation
+        M.get_operator("underwater_physical_revised", device="cpu", degradation={"name": "gaussian_blur", "kernel_size": 4}, **OKW)
+    # forward keeps its meaning (the image grid); the kernels serve the package's grid operators only
+    x = torch.zeros(1, 4, 8, 12)
+    op = M.get_operator("underwater_physical_revised", device="cpu", degradation=DEGRADATIONS["sr2_box"], **OKW)
+    assert op.forward(x).shape == (1, 3, 8, 12)
+    cond = CM.get_conditioning_method("osmosis", op, M.get_noise("clean"), gradient_x_prev=True)
+    assert cond._has_kernels() and cond._degradation() is op.degradation
+
+    class Foreign:
+        def forward(self, data, **kw):
+            return data
+
+        def out_shape(self, H, W):
+            return H, W
+    op3 = M.get_operator("underwater_physical_revised", device="cpu", degradation=Foreign(), **OKW)
+    cond3 = CM.get_conditioning_method("osmosis", op3, M.get_noise("clean"), gradient_x_prev=True)
+    assert not cond3._has_kernels() and cond3._degradation() is None
+    assert float((op3.observe(x) - op3.forward(x)).abs().max()) == 0.0
+
+
+def _cfg(degradation, tiling=None):
+    op = dict(OKW, name="underwater_physical_revised", optimizer="sgd", degradation=degradation)
+    cfg = {"measurement": {"operator": op, "noise": {"name": "clean"}},
+           "conditioning": {"method": "osmosis", "params": dict(loss_function="norm", loss_weight="depth", weight_function="gamma,1.4,1.4,1",
+                                                                scale="7,7,7,0.9", gradient_x_prev=True, gradient_clip="True,0.005")},
+           "diffusion": dict(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon", model_var_type="learned_range",
+                             dynamic_threshold=False, clip_denoised=True, rescale_timesteps=False, timestep_respacing="10"),
+           "sample_pattern": dict(pattern="pcgs", update_start=0.7, update_end=0, global_N=1, local_M=1, s_start=1, s_end=0, n_iter=20,
+                                  start_guidance=1, stop_guidance=0),
+           "aux_loss": {"aux_loss": AUX}, "unet_model": {"pretrain_model": "osmosis"}, "manual_seed": 0, "rgb_guidance": False}
+    if tiling is not None:
+        cfg["tiling"] = tiling
+    return cfg
+
+
+class HalfPool:
+    """A linear degradation the package does not know (2 x 2 mean with gain 0.5): the autograd route's case."""
+    def forward(self, data, **kw):
+        return 0.5 * torch.nn.functional.avg_pool2d(data, 2)
+
+    def out_shape(self, H, W):
+        return H // 2, W // 2
+
+
+@pytest.mark.parametrize("loss_function", ["norm", "mse"])
+@pytest.mark.parametrize("loss_weight", ["none", "depth"])
+def test_autograd_route_of_a_foreign_degradation_is_the_composed_loss(loss_function, loss_weight):
+    """A degradation object that is no `GRID_OPERATORS` instance has no kernels: `_loss_autograd` evaluates the same contract on
+    torch tensors (through `operator.observe`, the weight plane through the degradation, the mask on the measurement's grid, mse
+    over the measurement's 3 h w).  Against the oracle with the same A, in float32 on both sides: loss and d loss / d x0."""
+    H, W = 12, 10
+    g = torch.Generator().manual_seed(11)
+    x0 = (0.6 * torch.randn(1, 4, H, W, generator=g)).clamp(-1.0, 1.0)
+    y = torch.rand(1, 3, H // 2, W // 2, generator=g) * 1.6 - 0.8
+    mask = torch.rand(1, 3, H // 2, W // 2, generator=g)
+    deg = HalfPool()
+    op = M.get_operator("underwater_physical_revised", device="cpu", degradation=deg, **OKW)
+    cond = CM.get_conditioning_method("osmosis", op, M.get_noise("clean"), gradient_x_prev=True, loss_function=loss_function,
+                                      loss_weight=loss_weight, weight_function="gamma,1.4,1.4,1")
+    assert not cond._has_kernels()
+    cond.set_measurement_mask(mask, batch=1)
+    xa = x0.clone().requires_grad_(True)
+    sep, loss, image = cond._loss_autograd(xa, y)
+    assert image.shape == (1, 3, H // 2, W // 2) and torch.equal(image, op.observe(x0))
+    (ga,) = torch.autograd.grad(loss, xa)
+    rop = D.PhysOperator("underwater_physical_revised", batch_size=1, **OKW)
+    guide = LinGuidance(rop, n_iter=1, loss_function=loss_function, loss_weight=loss_weight)
+    guide.A, guide.mask = (lambda t: deg.forward(t.double())), mask
+    xb = x0.clone().requires_grad_(True)
+    want_sep, want = guide.loss(xb, y)
+    (gb,) = torch.autograd.grad(want, xb)
+    assert abs(float(loss) - float(want)) <= 1e-5 * abs(float(want)) and abs(float(sep[0]) - float(want_sep[0])) <= 1e-5 * float(want_sep[0])
+    assert float((ga - gb).abs().max()) <= 1e-5 * float(gb.abs().max())
+    if loss_function == "mse":      # the denominator is the measurement's size
+        w = 1.0 if loss_weight == "none" else deg.forward(D.convert_depth(x0[:, 3:4], "gamma", np.array([1.4, 1.4, 1.0])))
+        diff = (y - (2 * op.observe(x0) - 1)) * w * mask
+        assert float(loss) == pytest.approx(float((diff ** 2).sum()) / (3 * (H // 2) * (W // 2)), rel=1e-5)
+
+
+def test_postprocess_each_takes_every_images_observed():
+    """The batched driver path: `postprocess_each` hands row b of `observed` to image b (the photo lives on the degradation's grid,
+    so without it nothing can be compared) and refuses a composed config that comes without."""
+    from osmosis_diffusion_code_amd import sampling
+    op_cfg = _cfg(DEGRADATIONS["sr2_bicubic"])["measurement"]["operator"]
+    op = M.get_operator(device="cpu", batch_size=2, **op_cfg)
+    g = torch.Generator().manual_seed(6)
+    x0 = torch.rand(2, 4, 32, 32, generator=g) * 2 - 1
+    photo = torch.rand(2, 3, 16, 16, generator=g) * 2 - 1
+    obs = torch.rand(2, 3, 16, 16, generator=g) * 2 - 1
+    outs = sampling.postprocess_each(x0, op.variables(), photo, op_cfg, observed=obs)
+    assert len(outs) == 2
+    for b, post in enumerate(outs):
+        one = sampling.postprocess(x0[b:b + 1], {k: v[b:b + 1] for k, v in op.variables().items()}, photo[b:b + 1], op_cfg, observed=obs[b])
+        assert torch.equal(post["observed"], obs[b]) and post["norm_loss_final"] == one["norm_loss_final"] and "rgb_recon" not in post
+        assert post["norm_loss_final"] == float(np.round(torch.linalg.norm(obs[b] - photo[b]).numpy(), decimals=3))
+    assert outs[0]["norm_loss_final"] != outs[1]["norm_loss_final"]
+    with pytest.raises(ValueError, match="observed"):
+        sampling.postprocess_each(x0, op.variables(), photo, op_cfg)
+    with pytest.raises(ValueError, match="one row per image"):
+        sampling.postprocess_each(x0, op.variables(), photo, op_cfg, observed=obs[0:1])
+    with pytest.raises(ValueError, match="grid of its own"):
+        sampling.measurement_grid(dict(op_cfg, degradation={"name": "haze_physical"}), (16, 16))
+
+
+class _Net:
+    image_size = 32
+
+
+def test_restore_image_config_errors_without_a_gpu():
+    """An unknown degradation name, a photo that is not on the degradation's grid for the network's image, tiling, and
+    full-resolution reconstruction: each raises before anything is launched."""
+    from osmosis_diffusion_code_amd import sampling
+    photo = torch.zeros(1, 3, 16, 16)
+    with pytest.raises(NameError, match="no_such_blur"):
+        sampling.restore_image(_Net(), photo, _cfg({"name": "no_such_blur"}), device="cpu")
+    with pytest.raises(ValueError, match=r"expected \(16, 16\).*got \(32, 32\)"):
+        sampling.restore_image(_Net(), torch.zeros(1, 3, 32, 32), _cfg(DEGRADATIONS["sr2_bicubic"]), device="cpu")
+    with pytest.raises(ValueError, match=r"expected \(32, 32\).*got \(16, 16\)"):
+        sampling.restore_image(_Net(), photo, _cfg(DEGRADATIONS["gaussian_blur"]), device="cpu")
+    with pytest.raises(NotImplementedError, match="tiling: a degradation inside the physical operator is not tiled"):
+        sampling.restore_image(_Net(), photo, _cfg(DEGRADATIONS["sr2_bicubic"], tiling={"tile": 16, "stride": 8}), device="cpu")
+    with pytest.raises(NotImplementedError, match="degradation"):
+        sampling.restore_images(_Net(), [photo], _cfg(DEGRADATIONS["sr2_bicubic"]), device="cpu", originals=[torch.zeros(3, 64, 64)],
+                                geometries=[None])
+
+
+def test_tiled_loop_refuses_a_degradation():
+    from osmosis_diffusion_code_amd.guided_diffusion import gaussian_diffusion as gd
+    op = M.get_operator("underwater_physical_revised", device="cpu", degradation=DEGRADATIONS["gaussian_blur"], **OKW)
+    cond = CM.get_conditioning_method("osmosis", op, M.get_noise("clean"), gradient_x_prev=True)
+    sampler = gd.get_sampler("ddpm")(use_timesteps=range(0, 100, 10), betas=gd.get_named_beta_schedule("linear", 1000),
+                                     model_mean_type="epsilon", model_var_type="learned_range", dynamic_threshold=False,
+                                     clip_denoised=False, rescale_timesteps=False)
+    with pytest.raises(NotImplementedError, match="tiling: a degradation inside the physical operator is not tiled"):
+        sampler.p_sample_loop(model=_Net(), x_start=torch.zeros(1, 4, 32, 32), measurement=torch.zeros(1, 3, 32, 32),
+                              measurement_cond_fn=cond.conditioning, record=False, save_root=None, pretrain_model="osmosis",
+                              rgb_guidance=False, sample_pattern=None, tiling={"tile": 16, "stride": 8})
+
+
+def test_measurement_grid_and_postprocess_of_a_composed_config():
+    """The photo is the measurement: `measurement_grid` is the photo's own grid (where the mask lives), the operator's
+    `out_shape` maps the network's grid onto it; `postprocess` reports `observed` on that grid, takes norm_loss_final against it
+    and has `rgb_recon` only when the photo has the image's size."""
+    from osmosis_diffusion_code_amd import sampling
+    op_cfg = _cfg(DEGRADATIONS["sr2_bicubic"])["measurement"]["operator"]
+    assert sampling.measurement_grid(op_cfg, (16, 16)) == (16, 16)
+    with pytest.raises(NameError):
+        sampling.measurement_grid(dict(op_cfg, degradation={"name": "nope"}), (16, 16))
+    op = M.get_operator(device="cpu", **op_cfg)
+    assert op.out_shape(32, 32) == (16, 16)
+    g = torch.Generator().manual_seed(5)
+    x0 = torch.rand(1, 4, 32, 32, generator=g) * 2 - 1
+    photo = torch.rand(1, 3, 16, 16, generator=g) * 2 - 1
+    obs = torch.rand(3, 16, 16, generator=g) * 2 - 1
+    post = sampling.postprocess(x0, op.variables(), photo, op_cfg, observed=obs)
+    assert torch.equal(post["observed"], obs) and "rgb_recon" not in post and post["forward_predicted"].shape == (3, 32, 32)
+    assert post["norm_loss_final"] == float(np.round(torch.linalg.norm(obs - photo[0]).numpy(), decimals=3))
+    with pytest.raises(ValueError, match="observed"):
+        sampling.postprocess(x0, op.variables(), photo, op_cfg, observed=torch.zeros(3, 32, 32))
+    same = sampling.postprocess(x0, op.variables(), torch.zeros(1, 3, 32, 32), op_cfg, observed=torch.zeros(3, 32, 32))
+    assert "rgb_recon" in same and "observed" in same
+    plain = sampling.postprocess(x0, op.variables(), torch.zeros(1, 3, 32, 32), op_cfg)
+    assert "rgb_recon" in plain and "observed" not in plain
+    # a smaller measurement beside its sample in the grid image
+    imgs = sampling.output_images(post, photo)
+    assert imgs["input"].shape == (16, 16, 3) and imgs["rgb"].shape == (32, 32, 3)
+
+
+def test_physlin_entries_are_exported_declared_in_their_own_header_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_physlin.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = set(re.findall(r"\bint\s+(osm_[a-z0-9_]+)\s*\(", body))
+    assert declared == set(_lib.EXPORTS_PHYSLIN) == {"osm_phys_forward", "osm_phys_resid", "osm_phys_reduce_lin",
+                                                      "osm_phys_finalize_lin", "osm_phys_grad_lin", "osm_phys_optimize_lin"}
+    for name in declared:
+        args = re.search(name + r"\s*\(([^)]*)\)", body).group(1)
+        assert len(args.split(",")) == len(_lib._SIGS_PHYSLIN[name]), name
+    fields = re.search(r"typedef struct osm_lin_desc \{(.*?)\} osm_lin_desc;", body, flags=re.S).group(1)
+    names = [n.strip(" *") for decl in fields.split(";") if decl.strip() for n in decl.strip().split(None, 1)[1].replace("int*", "").replace(
+        "float*", "").replace("const", "").split(",")]
+    assert names == [f[0] for f in _lib.LinDesc._fields_], names
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in declared:
+        assert hasattr(lib, name) and getattr(_lib.load(), name).argtypes == _lib._SIGS_PHYSLIN[name]
+    mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
+    assert "osmosis_physlin.h" in mk
+    from osmosis_diffusion_code_amd import torch_ops
+    assert "phys_loss_grad_lin" in torch_ops.OPS and "phys_loss_grad_lin" not in torch_ops.OPS_C
+    schema = str(torch.ops.osmosis.phys_loss_grad_lin.default._schema)
+    assert schema.startswith("osmosis::phys_loss_grad_lin(Tensor x0, Tensor y, Tensor? mask, Tensor phi, SymInt[] icfg, float[] fcfg, "
+                             "SymInt n_inner, bool freeze_phi, SymInt family, Tensor[] tables, SymInt[] dims)"), schema
+
+
+def test_physlin_entries_validate_their_arguments_without_a_gpu():
+    """Null pointers, the identity kind, a bad family, grids that disagree with the descriptor's HW, a PSF that changes the grid:
+    a non-zero status with a message, nothing launched (the checks come before the launch)."""
+    lib = _lib.load()
+    p = 4096                                                                              # never dereferenced on the host
+    d = _lib.PhysDesc()
+    d.kind, d.B, d.HW = 0, 1, 8 * 12
+    lin = _lib.LinDesc()
+    lin.family, lin.H, lin.W, lin.h, lin.w = 1, 8, 12, 8, 12
+    lin.dy = lin.dx = lin.tap_w = p
+    lin.T, lin.Ry, lin.Rx = 3, 1, 1
+
+    def optimize(dd=d, ll=lin, x0=p, n_inner=1, freeze=0):
+        return lib.osm_phys_optimize_lin(ctypes.byref(dd), ctypes.byref(ll), x0, p, None, p, p, p, p, p, p, p, p, p, p, n_inner, freeze,
+                                         None, None)
+
+    def fails(word, **kw):
+        assert optimize(**kw) != 0
+        msg = lib.osm_last_error().decode()
+        assert msg.startswith("osm_phys_optimize_lin") and word in msg, msg
+    fails("null pointer", x0=None)
+    fails("n_inner", n_inner=0)
+    fails("freeze_phi", n_inner=2, freeze=1)
+    d3 = _lib.PhysDesc()
+    d3.kind, d3.B, d3.HW = 3, 1, 96
+    fails("identity", dd=d3)
+    for field, val, word in (("family", 2, "family"), ("H", 9, "HW"), ("h", 4, "psf operator keeps"), ("dy", None, "tap list")):
+        bad = _lib.LinDesc.from_buffer_copy(lin)
+        setattr(bad, field, val)
+        fails(word, ll=bad)
+    for field, val, word in (("T", 0, "tap count"), ("Ry", 8, "Ry"), ("Rx", -1, "Rx")):      # caught before the first launch
+        bad = _lib.LinDesc.from_buffer_copy(lin)
+        setattr(bad, field, val)
+        fails(word, ll=bad)
+    sep = _lib.LinDesc.from_buffer_copy(lin)
+    sep.family = 0
+    fails("band tables", ll=sep)
+    sep.start_h = sep.wt_h = sep.start_w = sep.wt_w = sep.tstart_h = sep.twt_h = sep.tstart_w = sep.twt_w = p
+    fails("band widths", ll=sep)
+    dad = _lib.PhysDesc()
+    dad.kind, dad.B, dad.HW, dad.optimizer = 0, 1, 96, 1
+    fails("opt_state", dd=dad)                                                            # adam without its state
+    assert lib.osm_phys_forward(ctypes.byref(d), p, None, p, None) != 0 and b"null" in lib.osm_last_error()
+    assert lib.osm_phys_resid(ctypes.byref(d), 0, p, p, None, p, p, None) != 0 and b"hw" in lib.osm_last_error()
+    assert lib.osm_phys_finalize_lin(ctypes.byref(d), 96, p, None, p, p, 0, p, None, 0, None) != 0
+    d.optimizer = 1
+    assert lib.osm_phys_finalize_lin(ctypes.byref(d), 96, p, p, p, p, 1, p, None, 0, None) != 0 and b"opt_state" in lib.osm_last_error()
+
+
+@pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
+def test_physlin_header_is_strict_c99(tmp_path):
+    src = tmp_path / "use.c"
+    src.write_text('#include "osmosis_physlin.h"\nint main(void) {\n  osm_lin_desc l;\n'
+                   '  int (*f)(const osm_phys_desc*, const float*, const float*, float*, void*) = osm_phys_forward;\n'
+                   '  l.family = 0;\n  return l.family + (f ? 0 : 1);\n}\n')
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Werror", "-Wall", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                    str(tmp_path / "use.o")], check=True)
