@@ -73,6 +73,27 @@ class LinDesc(C.Structure):
                 ("dy", C.c_void_p), ("dx", C.c_void_p), ("tap_w", C.c_void_p), ("T", C.c_int), ("Ry", C.c_int), ("Rx", C.c_int)]
 
 
+class GroupDesc(C.Structure):
+    """osm_group_desc (include/osmosis_physgroup.h): G contiguous groups of a batch that share one phi row each; `off` is a HOST
+    array of G + 1 ints, read when the entry point is called (`GroupDesc.of` keeps it alive with the descriptor)."""
+    _fields_ = [("G", C.c_int), ("off", C.POINTER(C.c_int)), ("reduce", C.c_int)]
+
+    @staticmethod
+    def of(group_sizes, reduce="mean") -> "GroupDesc":
+        sizes = [int(n) for n in group_sizes]
+        if reduce not in ("mean", "sum"):
+            raise ValueError(f"phi_reduce must be 'mean' or 'sum', got {reduce!r}")
+        if not sizes or any(n < 1 for n in sizes):
+            raise ValueError(f"group sizes must be positive ints, got {group_sizes!r}")
+        d = GroupDesc()
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        d._offs = (C.c_int * len(offs))(*offs)
+        d.G, d.off, d.reduce = len(sizes), C.cast(d._offs, C.POINTER(C.c_int)), 1 if reduce == "mean" else 0
+        return d
+
+
 class ReconDesc(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("guide", C.c_void_p), ("image", C.c_void_p),
                 ("phi_a", C.c_void_p), ("phi_b", C.c_void_p), ("phi_inf", C.c_void_p),
@@ -194,6 +215,15 @@ _SIGS_PHYSLIN = {
     "osm_phys_optimize_lin": [C.POINTER(PhysDesc), C.POINTER(LinDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
 }
 EXPORTS_PHYSLIN = sorted(_SIGS_PHYSLIN)
+# the entry points of the fifth header, include/osmosis_physgroup.h (one phi step per group of images: shared water parameters)
+_SIGS_PHYSGROUP = {
+    "osm_phys_finalize_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _P, _P, _P, _I, _P, _P, _I, _P],
+    "osm_phys_finalize_lin_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _I, _P, _P, _P, _P, _I, _P, _P, _I, _P],
+    "osm_phys_optimize_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "osm_phys_optimize_lin_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), C.POINTER(LinDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _P, _P, _I, _I, _P, _P],
+}
+EXPORTS_PHYSGROUP = sorted(_SIGS_PHYSGROUP)
 
 _lib = None
 _lock = threading.Lock()
@@ -212,7 +242,8 @@ def load():
                     "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
-            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()):
+            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
+                    list(_SIGS_PHYSGROUP.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

@@ -12,6 +12,7 @@
 #include "../../include/osmosis_linop.h"
 #include "../../include/osmosis_psf.h"
 #include "../../include/osmosis_physlin.h"
+#include "../../include/osmosis_physgroup.h"
 
 namespace {
 
@@ -154,6 +155,130 @@ __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, cons
 
 __device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
+// The learning rate of every phi slot and the live mask of `kind` (bit i: phi[i] is a parameter of this operator).
+__device__ __forceinline__ int phys_param_lr(const osm_phys_desc& ds, float* lr) {
+  for (int i = 0; i < 9; ++i) lr[i] = 0.f;
+  int live;
+  if (ds.kind == 0) {
+    for (int c = 0; c < 3; ++c) { lr[c] = ds.eta[0]; lr[3 + c] = ds.eta[1]; }
+    live = 0x3f;
+  } else if (ds.kind == 1) {
+    for (int c = 0; c < 3; ++c) lr[c] = ds.eta[0];
+    live = 0x7;
+  } else {
+    lr[0] = ds.eta[0];
+    live = 0x1;
+  }
+  for (int c = 0; c < 3; ++c) lr[6 + c] = ds.eta[2];
+  return live | 0x1c0;
+}
+
+// One image's gradient of every live parameter (as the reference's autograd leaves have it) from its reduced sums, in fp64: the
+// plain finalize casts it to fp32 as it is, the grouped one sums it over the members of a group first.
+__device__ __forceinline__ void phys_param_grad(const osm_phys_desc& ds, const double* tot, double gscale, double* dg) {
+  for (int i = 0; i < 9; ++i) dg[i] = 0.0;
+  if (ds.kind == 0) {
+    for (int c = 0; c < 3; ++c) {
+      dg[c] = tot[1 + c] * gscale;
+      dg[3 + c] = tot[4 + c] * gscale;
+    }
+  } else if (ds.kind == 1) {
+    for (int c = 0; c < 3; ++c) dg[c] = (tot[1 + c] + tot[4 + c]) * gscale;
+  } else {
+    double gs = 0.0;
+    for (int c = 0; c < 3; ++c) gs += tot[1 + c] + tot[4 + c];
+    dg[0] = gs * gscale;
+  }
+  for (int c = 0; c < 3; ++c) dg[6 + c] = tot[7 + c] * gscale;
+}
+
+// One optimizer step of one phi row ph [9] with its state row st [20] (NULL for sgd): shared by the per-image and the grouped
+// finalize kernels.
+__device__ __forceinline__ void phys_opt_step(const osm_phys_desc& ds, const float* g, const float* lr, int live, float* ph, float* st) {
+  // torch.optim with its DEFAULT hyper-parameters (utils.py:494-524 passes none), single-tensor path, fp32 state, one parameter
+  // group per phi with lr = eta (measurements.py:132-136, 244-249).  st: [B][20] floats, layout per optimizer below.  A parameter
+  // with learn_flag False has no gradient: the optimizer skips it (its state stays untouched).
+  if (ds.optimizer == 1 || ds.optimizer == 2) {          // Adam | AdamW (weight_decay 0.01, decoupled): exp_avg[9] | exp_avg_sq[9] | step
+    const float step = st[18] + 1.f;
+    st[18] = step;
+    const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      if (ds.optimizer == 2) ph[i] *= (float)(1.0 - (double)lr[i] * 0.01);      // param.mul_(1 - lr * weight_decay)
+      const float m = st[i] + (g[i] - st[i]) * (float)(1.0 - b1);             // exp_avg.lerp_(grad, 1 - beta1)
+      const float v = st[9 + i] * (float)b2 + (float)(1.0 - b2) * g[i] * g[i];  // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+      st[i] = m; st[9 + i] = v;
+      const float denom = sqrtf(v) / bc2_sqrt + (float)eps;
+      ph[i] += (float)(-(double)lr[i] / bc1) * (m / denom);                   // param.addcdiv_(exp_avg, denom, value=-step_size)
+    }
+  } else if (ds.optimizer == 3) {   // Adamax (betas 0.9 / 0.999, eps 1e-8): exp_avg[9] | exp_inf[9] | step
+    const float step = st[18] + 1.f;
+    st[18] = step;
+    const double bc = 1.0 - pow(0.9, (double)step);
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      const float m = st[i] + (g[i] - st[i]) * (float)(1.0 - 0.9);            // exp_avg.lerp_(grad, 1 - beta1)
+      const float u = fmaxf(st[9 + i] * (float)0.999, fabsf(g[i]) + (float)1e-8);   // max(exp_inf * beta2, |grad| + eps)
+      st[i] = m; st[9 + i] = u;
+      ph[i] += (float)(-(double)lr[i] / bc) * (m / u);                         // param.addcdiv_(exp_avg, exp_inf, value=-clr)
+    }
+  } else if (ds.optimizer == 4) {   // RMSprop (alpha 0.99, eps 1e-8, no momentum, not centered): square_avg[9]
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      const float sq = st[i] * (float)0.99 + (float)(1.0 - 0.99) * g[i] * g[i];
+      st[i] = sq;
+      ph[i] += -lr[i] * (g[i] / (sqrtf(sq) + (float)1e-8));
+    }
+  } else if (ds.optimizer == 5) {   // Adagrad (lr_decay 0, initial accumulator 0, eps 1e-10): sum[9]
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      const float sm = st[i] + g[i] * g[i];
+      st[i] = sm;
+      ph[i] += -lr[i] * (g[i] / (sqrtf(sm) + (float)1e-10));
+    }
+  } else if (ds.optimizer == 6) {   // Adadelta (rho 0.9, eps 1e-6; lr = eta): square_avg[9] | acc_delta[9]
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      const float sq = st[i] * (float)0.9 + (float)(1.0 - 0.9) * g[i] * g[i];
+      const float sd = sqrtf(sq + (float)1e-6);
+      const float dl = sqrtf(st[9 + i] + (float)1e-6) / sd * g[i];
+      st[i] = sq;
+      st[9 + i] = st[9 + i] * (float)0.9 + (float)(1.0 - 0.9) * dl * dl;
+      ph[i] += -lr[i] * dl;
+    }
+  } else if (ds.optimizer == 7) {   // ASGD (lambd 1e-4, alpha 0.75, t0 1e6): eta[9] | - | step (19); eta starts at lr (0 = not yet set)
+    const float step = st[19] + 1.f;
+    st[19] = step;
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      const float eta = step == 1.f ? lr[i] : st[i];
+      ph[i] *= (float)(1.0 - 1e-4 * (double)eta);                             // param.mul_(1 - lambd * eta)
+      ph[i] += -eta * g[i];                                                    // param.add_(grad, alpha=-eta)
+      st[i] = (float)((double)lr[i] / pow(1.0 + 1e-4 * (double)lr[i] * (double)step, 0.75));
+    }                                                                          // (the averaged iterate `ax` is not what the operator reads)
+  } else if (ds.optimizer == 8) {   // Rprop (etas 0.5 / 1.2, step sizes 1e-6 .. 50): prev[9] | step_size[9] | step
+    const float step = st[18] + 1.f;
+    st[18] = step;
+    for (int i = 0; i < 9; ++i) {
+      if (!((live >> i) & 1) || lr[i] == 0.f) continue;
+      float ss = step == 1.f ? lr[i] : st[9 + i];
+      const float pr = g[i] * st[i];
+      float gi = g[i];
+      ss *= pr > 0.f ? 1.2f : (pr < 0.f ? 0.5f : 1.f);
+      ss = fminf(fmaxf(ss, 1e-6f), 50.f);
+      if (pr < 0.f) gi = 0.f;
+      ph[i] += -(sgn(gi) * ss);
+      st[i] = gi; st[9 + i] = ss;
+    }
+  } else {
+    for (int i = 0; i < 9; ++i)
+      if ((live >> i) & 1) ph[i] -= lr[i] * g[i];
+  }
+  if (ds.kind == 2) ph[1] = ph[2] = ph[0];
+}
+
 // LIN (the composed path): component 0, the sum of squared residuals, comes from lin.part_r [B][lin.nblk_r] -- the residual lives
 // on the measurement's grid of lin.hw pixels -- and the losses normalise by that grid.  The `false` instantiation carries no such
 // argument and is the code it always was.
@@ -203,111 +328,116 @@ __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__
     }
     if (loss_out) loss_out[b] = (float)L;
     if (do_update) {
-      float* ph = phi + b * 9;
-      // gradient of every live parameter (as the reference's autograd leaves have it), then the optimizer step
-      float g[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      float lr[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      int live = 0;                      // bit i: phi[i] is a parameter of this operator
-      if (ds.kind == 0) {
-        for (int c = 0; c < 3; ++c) {
-          g[c] = (float)(tot[1 + c] * gscale); lr[c] = ds.eta[0];
-          g[3 + c] = (float)(tot[4 + c] * gscale); lr[3 + c] = ds.eta[1];
+      double dg[9];
+      float g[9], lr[9];
+      const int live = phys_param_lr(ds, lr);
+      phys_param_grad(ds, tot, gscale, dg);
+      for (int i = 0; i < 9; ++i) g[i] = (float)dg[i];
+      phys_opt_step(ds, g, lr, live, phi + b * 9, opt_state ? opt_state + b * 20 : nullptr);
+    }
+  }
+}
+
+// The grouped finalize (include/osmosis_physgroup.h): the images off[g] .. off[g + 1] - 1 share ONE phi row and ONE optimizer state
+// row.  One workgroup per group, its members dealt to the GWAVES waves round by round; a wave does for its member what the plain
+// kernel's single wave does (the same four-lane partial walk, fp64, two shuffle folds: red[b] and loss_out[b] are the plain
+// kernel's bits), lane 0 forms the member's fp64 parameter gradient (phys_param_grad) into shared memory, and thread 0 adds the
+// members up in ascending order -- fixed order, no atomics; the addends come out of shared memory, so no multiply is contracted into
+// the sum and a + a is exact.  Then one optimizer step on the group's first row with omega * sum (omega = 1 / n for `mean`, 1 for
+// `sum`), and every other member row receives the new phi and state.  A member that is zero-guarded adds nothing; a group whose
+// members are all guarded takes no step.  With n = 1 this is phys_finalize_kernel bit for bit (0 + d = d, omega = 1).
+struct GroupOff { int off[OSM_MAX_GROUPS + 1]; };
+constexpr int GWAVES = 4;
+
+template <bool LIN>
+__global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_phys_desc ds, const float* __restrict__ part,
+                                                                          float* __restrict__ red, float* phi, int do_update,
+                                                                          float* __restrict__ loss_out, float* opt_state, int nblk,
+                                                                          int zero_guard, int reduce_mean, const GroupOff go,
+                                                                          const FinLin<LIN> lin) {
+  __shared__ double tot[GWAVES][NRED];
+  __shared__ double dsh[GWAVES][9];
+  __shared__ int live_sh[GWAVES];
+  __shared__ float row[9 + 20];
+  __shared__ int stepped;
+  const int b0 = go.off[blockIdx.x], n = go.off[blockIdx.x + 1] - b0;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // thread 0: the group's sum
+  int any = 0;                                                       // thread 0: a member that is not zero-guarded
+  for (int r0 = 0; r0 < n; r0 += GWAVES) {
+    const int m = r0 + wv;                // this wave's member of the round (wave-uniform)
+    const int b = b0 + m;
+    if (m < n) {
+      const int comp = lane >> 2, sub = lane & 3;
+      double a = 0.0;
+#pragma unroll 4
+      for (int k = sub; k < nblk; k += 4) a += (double)part[((long long)b * nblk + k) * NRED + comp];
+      if constexpr (LIN) {
+        if (comp == 0) {
+          a = 0.0;
+          for (int k = sub; k < lin.nblk_r; k += 4) a += (double)lin.part_r[(long long)b * lin.nblk_r + k];
         }
-        live = 0x3f;
-      } else if (ds.kind == 1) {
-        for (int c = 0; c < 3; ++c) { g[c] = (float)((tot[1 + c] + tot[4 + c]) * gscale); lr[c] = ds.eta[0]; }
-        live = 0x7;
-      } else {
-        double gs = 0.0;
-        for (int c = 0; c < 3; ++c) gs += tot[1 + c] + tot[4 + c];
-        g[0] = (float)(gs * gscale); lr[0] = ds.eta[0];
-        live = 0x1;
       }
-      for (int c = 0; c < 3; ++c) { g[6 + c] = (float)(tot[7 + c] * gscale); lr[6 + c] = ds.eta[2]; }
-      live |= 0x1c0;
-      // torch.optim with its DEFAULT hyper-parameters (utils.py:494-524 passes none), single-tensor path, fp32 state, one parameter
-      // group per phi with lr = eta (measurements.py:132-136, 244-249).  st: [B][20] floats, layout per optimizer below.  A parameter
-      // with learn_flag False has no gradient: the optimizer skips it (its state stays untouched).
-      float* st = opt_state ? opt_state + b * 20 : nullptr;
-      if (ds.optimizer == 1 || ds.optimizer == 2) {          // Adam | AdamW (weight_decay 0.01, decoupled): exp_avg[9] | exp_avg_sq[9] | step
-        const float step = st[18] + 1.f;
-        st[18] = step;
-        const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
-        const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-        const float bc2_sqrt = (float)sqrt(bc2);
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          if (ds.optimizer == 2) ph[i] *= (float)(1.0 - (double)lr[i] * 0.01);      // param.mul_(1 - lr * weight_decay)
-          const float m = st[i] + (g[i] - st[i]) * (float)(1.0 - b1);             // exp_avg.lerp_(grad, 1 - beta1)
-          const float v = st[9 + i] * (float)b2 + (float)(1.0 - b2) * g[i] * g[i];  // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
-          st[i] = m; st[9 + i] = v;
-          const float denom = sqrtf(v) / bc2_sqrt + (float)eps;
-          ph[i] += (float)(-(double)lr[i] / bc1) * (m / denom);                   // param.addcdiv_(exp_avg, denom, value=-step_size)
-        }
-      } else if (ds.optimizer == 3) {   // Adamax (betas 0.9 / 0.999, eps 1e-8): exp_avg[9] | exp_inf[9] | step
-        const float step = st[18] + 1.f;
-        st[18] = step;
-        const double bc = 1.0 - pow(0.9, (double)step);
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          const float m = st[i] + (g[i] - st[i]) * (float)(1.0 - 0.9);            // exp_avg.lerp_(grad, 1 - beta1)
-          const float u = fmaxf(st[9 + i] * (float)0.999, fabsf(g[i]) + (float)1e-8);   // max(exp_inf * beta2, |grad| + eps)
-          st[i] = m; st[9 + i] = u;
-          ph[i] += (float)(-(double)lr[i] / bc) * (m / u);                         // param.addcdiv_(exp_avg, exp_inf, value=-clr)
-        }
-      } else if (ds.optimizer == 4) {   // RMSprop (alpha 0.99, eps 1e-8, no momentum, not centered): square_avg[9]
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          const float sq = st[i] * (float)0.99 + (float)(1.0 - 0.99) * g[i] * g[i];
-          st[i] = sq;
-          ph[i] += -lr[i] * (g[i] / (sqrtf(sq) + (float)1e-8));
-        }
-      } else if (ds.optimizer == 5) {   // Adagrad (lr_decay 0, initial accumulator 0, eps 1e-10): sum[9]
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          const float sm = st[i] + g[i] * g[i];
-          st[i] = sm;
-          ph[i] += -lr[i] * (g[i] / (sqrtf(sm) + (float)1e-10));
-        }
-      } else if (ds.optimizer == 6) {   // Adadelta (rho 0.9, eps 1e-6; lr = eta): square_avg[9] | acc_delta[9]
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          const float sq = st[i] * (float)0.9 + (float)(1.0 - 0.9) * g[i] * g[i];
-          const float sd = sqrtf(sq + (float)1e-6);
-          const float dl = sqrtf(st[9 + i] + (float)1e-6) / sd * g[i];
-          st[i] = sq;
-          st[9 + i] = st[9 + i] * (float)0.9 + (float)(1.0 - 0.9) * dl * dl;
-          ph[i] += -lr[i] * dl;
-        }
-      } else if (ds.optimizer == 7) {   // ASGD (lambd 1e-4, alpha 0.75, t0 1e6): eta[9] | - | step (19); eta starts at lr (0 = not yet set)
-        const float step = st[19] + 1.f;
-        st[19] = step;
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          const float eta = step == 1.f ? lr[i] : st[i];
-          ph[i] *= (float)(1.0 - 1e-4 * (double)eta);                             // param.mul_(1 - lambd * eta)
-          ph[i] += -eta * g[i];                                                    // param.add_(grad, alpha=-eta)
-          st[i] = (float)((double)lr[i] / pow(1.0 + 1e-4 * (double)lr[i] * (double)step, 0.75));
-        }                                                                          // (the averaged iterate `ax` is not what the operator reads)
-      } else if (ds.optimizer == 8) {   // Rprop (etas 0.5 / 1.2, step sizes 1e-6 .. 50): prev[9] | step_size[9] | step
-        const float step = st[18] + 1.f;
-        st[18] = step;
-        for (int i = 0; i < 9; ++i) {
-          if (!((live >> i) & 1) || lr[i] == 0.f) continue;
-          float ss = step == 1.f ? lr[i] : st[9 + i];
-          const float pr = g[i] * st[i];
-          float gi = g[i];
-          ss *= pr > 0.f ? 1.2f : (pr < 0.f ? 0.5f : 1.f);
-          ss = fminf(fmaxf(ss, 1e-6f), 50.f);
-          if (pr < 0.f) gi = 0.f;
-          ph[i] += -(sgn(gi) * ss);
-          st[i] = gi; st[9 + i] = ss;
-        }
-      } else {
-        for (int i = 0; i < 9; ++i)
-          if ((live >> i) & 1) ph[i] -= lr[i] * g[i];
+      a += __shfl_xor(a, 1, 64);
+      a += __shfl_xor(a, 2, 64);
+      if (sub == 0) {
+        tot[wv][comp] = a;
+        red[b * NRED + comp] = (float)a;
       }
-      if (ds.kind == 2) ph[1] = ph[2] = ph[0];
+    }
+    __syncthreads();
+    if (m < n && lane == 0) {
+      double nn = 3.0 * (double)ds.HW;
+      if constexpr (LIN) nn = 3.0 * (double)lin.hw;
+      double L, gscale;
+      int guarded = 0;
+      if (ds.loss_type == 0) {
+        L = sqrt(tot[wv][0]);
+        gscale = 1.0 / L;
+        if (zero_guard && tot[wv][0] == 0.0) { gscale = 0.0; guarded = 1; }
+      } else {
+        L = tot[wv][0] / nn;
+        gscale = 2.0 / nn;
+      }
+      if (loss_out) loss_out[b] = (float)L;
+      if (do_update) {
+        double dg[9];
+        phys_param_grad(ds, tot[wv], gscale, dg);
+        for (int i = 0; i < 9; ++i) dsh[wv][i] = dg[i];
+        live_sh[wv] = !guarded;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && do_update) {
+      const int cnt = min(GWAVES, n - r0);
+      for (int w = 0; w < cnt; ++w) {
+        for (int i = 0; i < 9; ++i) acc[i] += dsh[w][i];
+        any |= live_sh[w];
+      }
+    }
+    // (the next round writes tot / dsh only after its own barriers, which thread 0 reaches after this sum)
+  }
+  if (threadIdx.x == 0) {
+    stepped = 0;
+    if (do_update && any) {
+      const double omega = reduce_mean ? 1.0 / (double)n : 1.0;
+      float g[9], lr[9];
+      const int live = phys_param_lr(ds, lr);
+      for (int i = 0; i < 9; ++i) g[i] = (float)(acc[i] * omega);
+      float* ph = phi + b0 * 9;
+      float* st = opt_state ? opt_state + b0 * 20 : nullptr;
+      phys_opt_step(ds, g, lr, live, ph, st);
+      for (int i = 0; i < 9; ++i) row[i] = ph[i];
+      for (int i = 0; i < 20; ++i) row[9 + i] = st ? st[i] : 0.f;
+      stepped = 1;
+    }
+  }
+  __syncthreads();
+  if (stepped) {      // every other member row receives the group's new phi and state
+    for (int idx = threadIdx.x; idx < (n - 1) * 29; idx += 64 * GWAVES) {
+      const int b = b0 + 1 + idx / 29, k = idx % 29;
+      if (k < 9) phi[b * 9 + k] = row[k];
+      else if (opt_state) opt_state[b * 20 + (k - 9)] = row[k];
     }
   }
 }
@@ -817,14 +947,39 @@ int phys_reduce_launch(const char* who, const osm_phys_desc* d, const float* x0,
   return osm::check_launch("phys_reduce_kernel");
 }
 
+// The offsets of a group descriptor, validated and copied by value (they travel in the kernel's arguments).
+struct GroupArgs { GroupOff go; int G, reduce; };
+
+int check_group(const osm_phys_desc* d, const osm_group_desc* grp, GroupArgs* ga, const char* who) {
+  OSM_REQUIRE(grp, "%s: null group descriptor", who);
+  OSM_REQUIRE(grp->G >= 1 && grp->G <= OSM_MAX_GROUPS, "%s: G = %d groups, must be 1 .. %d", who, grp->G, OSM_MAX_GROUPS);
+  OSM_REQUIRE(grp->off, "%s: null pointer (group offsets)", who);
+  OSM_REQUIRE(grp->reduce == 0 || grp->reduce == 1, "%s: reduce must be 0 (sum) or 1 (mean), got %d", who, grp->reduce);
+  OSM_REQUIRE(grp->off[0] == 0, "%s: off[0] must be 0, got %d", who, grp->off[0]);
+  for (int j = 0; j < grp->G; ++j)
+    OSM_REQUIRE(grp->off[j + 1] > grp->off[j], "%s: group offsets must be strictly increasing (off[%d] = %d, off[%d] = %d)", who, j,
+                grp->off[j], j + 1, grp->off[j + 1]);
+  OSM_REQUIRE(grp->off[grp->G] == d->B, "%s: off[G] = %d must be the batch B = %d", who, grp->off[grp->G], d->B);
+  for (int j = 0; j <= grp->G; ++j) ga->go.off[j] = grp->off[j];
+  ga->G = grp->G;
+  ga->reduce = grp->reduce;
+  return OSM_OK;
+}
+
+// ga == nullptr: the per-image finalize; else one phi step per group
 int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
-                         float* loss_out, float* opt_state, int zero_guard, void* stream) {
+                         float* loss_out, float* opt_state, int zero_guard, void* stream, const GroupArgs* ga = nullptr) {
   int rc = check_desc(d, who);
   if (rc) return rc;
   OSM_REQUIRE(part && red && phi, "%s: null pointer", who);
   OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
   OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
   OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
+  if (ga) {
+    hipLaunchKernelGGL(phys_finalize_group_kernel<false>, dim3(ga->G), dim3(64 * GWAVES), 0, (hipStream_t)stream, *d, part, red, phi,
+                       do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard, ga->reduce, ga->go, FinLin<false>{});
+    return osm::check_launch("phys_finalize_group_kernel");
+  }
   hipLaunchKernelGGL(phys_finalize_kernel<false>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
                      do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard, FinLin<false>{});
   return osm::check_launch("phys_finalize_kernel");
@@ -847,20 +1002,25 @@ int phys_grad_launch(const char* who, const osm_phys_desc* d, const float* x0, c
 // n_inner x { reduce; finalize (+ phi step) } + the x0-gradient: the launches of osm_phys_optimize, with or without a mask
 int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi,
                          float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
-                         void* stream) {
+                         void* stream, const GroupArgs* ga = nullptr) {
   int rc = check_desc(d, who);
   if (rc) return rc;
   OSM_REQUIRE(x0 && y && phi && part && red && loss_out && g, "%s: null pointer", who);
   OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
   OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
+  if (ga) {   // (before the first launch: a failure of a later finalize would leave phi half-stepped)
+    OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+    OSM_REQUIRE(d->optimizer == 0 || freeze_phi || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+    OSM_REQUIRE(!(d->kind == 3 && !freeze_phi), "%s: the identity operator (kind 3) has no parameters to step", who);
+  }
   const int zg = mask != nullptr;
   for (int it = 0; it < n_inner; ++it) {
     if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream))) return rc;
     if (it == n_inner - 1) {
-      if ((rc = phys_finalize_launch(who, d, part, red, phi, 0, loss_out, nullptr, zg, stream))) return rc;
+      if ((rc = phys_finalize_launch(who, d, part, red, phi, 0, loss_out, nullptr, zg, stream, ga))) return rc;
       if ((rc = phys_grad_launch(who, d, x0, y, mask, phi, red, g, stream))) return rc;
-      if (!freeze_phi && (rc = phys_finalize_launch(who, d, part, red, phi, 1, nullptr, opt_state, zg, stream))) return rc;
-    } else if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream))) {
+      if (!freeze_phi && (rc = phys_finalize_launch(who, d, part, red, phi, 1, nullptr, opt_state, zg, stream, ga))) return rc;
+    } else if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream, ga))) {
       return rc;
     }
   }
@@ -996,18 +1156,31 @@ extern "C" int osm_phys_reduce_lin(const osm_phys_desc* d, const float* x0, cons
   return osm::check_launch("phys_reduce_lin_kernel");
 }
 
-extern "C" int osm_phys_finalize_lin(const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red, float* phi,
-                                     int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
-  const char* who = "osm_phys_finalize_lin";
+namespace {
+int phys_finalize_lin_launch(const char* who, const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red,
+                             float* phi, int do_update, float* loss_out, float* opt_state, int masked, void* stream,
+                             const GroupArgs* ga = nullptr) {
   int rc = check_lin_desc(d, who);
   if (rc) return rc;
   OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
   OSM_REQUIRE(part && part_r && red && phi, "%s: null pointer", who);
   OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
   OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+  if (ga) {
+    hipLaunchKernelGGL(phys_finalize_group_kernel<true>, dim3(ga->G), dim3(64 * GWAVES), 0, (hipStream_t)stream, *d, part, red, phi,
+                       do_update, loss_out, opt_state, osm_phys_nblk(d->HW), masked != 0, ga->reduce, ga->go,
+                       FinLin<true>{part_r, osm_phys_nblk(hw), hw});
+    return osm::check_launch("phys_finalize_group_kernel<lin>");
+  }
   hipLaunchKernelGGL(phys_finalize_kernel<true>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi, do_update,
                      loss_out, opt_state, osm_phys_nblk(d->HW), masked != 0, FinLin<true>{part_r, osm_phys_nblk(hw), hw});
   return osm::check_launch("phys_finalize_kernel<lin>");
+}
+}  // namespace
+
+extern "C" int osm_phys_finalize_lin(const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red, float* phi,
+                                     int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
+  return phys_finalize_lin_launch("osm_phys_finalize_lin", d, hw, part, part_r, red, phi, do_update, loss_out, opt_state, masked, stream);
 }
 
 extern "C" int osm_phys_grad_lin(const osm_phys_desc* d, int hw, const float* x0, const float* phi, const float* v, const float* red,
@@ -1022,10 +1195,12 @@ extern "C" int osm_phys_grad_lin(const osm_phys_desc* d, int hw, const float* x0
   return osm::check_launch("phys_grad_lin_kernel");
 }
 
-extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y, const float* mask,
-                                     float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part, float* red,
-                                     float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
-  const char* who = "osm_phys_optimize_lin";
+namespace {
+// ga == nullptr: osm_phys_optimize_lin; else the grouped finalize in the place of the plain one
+int phys_optimize_lin_launch(const char* who, const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y,
+                             const float* mask, float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part,
+                             float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream,
+                             const GroupArgs* ga) {
   int rc = check_lin_desc(d, who);
   if (rc) return rc;
   if ((rc = check_lin(d, lin, who))) return rc;
@@ -1044,14 +1219,72 @@ extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc*
     if ((rc = lin_apply(lin, u, v, d->B, 3, 1, stream))) return rc;
     if ((rc = osm_phys_reduce_lin(d, x0, phi, v, part, stream))) return rc;
     if (it == n_inner - 1) {
-      if ((rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 0, loss_out, nullptr, zg, stream))) return rc;
+      if ((rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 0, loss_out, nullptr, zg, stream, ga)))
+        return rc;
       if ((rc = osm_phys_grad_lin(d, hw, x0, phi, v, red, g, zg, stream))) return rc;
-      if (!freeze_phi && (rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 1, nullptr, opt_state, zg, stream))) return rc;
-    } else if ((rc = osm_phys_finalize_lin(d, hw, part, part_r, red, phi, 1, loss_out, opt_state, zg, stream))) {
+      if (!freeze_phi &&
+          (rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 1, nullptr, opt_state, zg, stream, ga)))
+        return rc;
+    } else if ((rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 1, loss_out, opt_state, zg,
+                                              stream, ga))) {
       return rc;
     }
   }
   return OSM_OK;
+}
+}  // namespace
+
+extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y, const float* mask,
+                                     float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part, float* red,
+                                     float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
+  return phys_optimize_lin_launch("osm_phys_optimize_lin", d, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, n_inner,
+                                  freeze_phi, opt_state, stream, nullptr);
+}
+
+// ---------------------------------------------------------------- shared water parameters (include/osmosis_physgroup.h)
+extern "C" int osm_phys_finalize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* part, float* red, float* phi,
+                                   int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
+  const char* who = "osm_phys_finalize_g";
+  GroupArgs ga;
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &ga, who))) return rc;
+  return phys_finalize_launch(who, d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream, &ga);
+}
+
+extern "C" int osm_phys_finalize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, int hw, const float* part, const float* part_r,
+                                       float* red, float* phi, int do_update, float* loss_out, float* opt_state, int masked,
+                                       void* stream) {
+  const char* who = "osm_phys_finalize_lin_g";
+  GroupArgs ga;
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &ga, who))) return rc;
+  return phys_finalize_lin_launch(who, d, hw, part, part_r, red, phi, do_update, loss_out, opt_state, masked, stream, &ga);
+}
+
+extern "C" int osm_phys_optimize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* x0, const float* y, const float* mask,
+                                   float* phi, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
+                                   float* opt_state, void* stream) {
+  const char* who = "osm_phys_optimize_g";
+  GroupArgs ga;
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &ga, who))) return rc;
+  return phys_optimize_launch(who, d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state, stream, &ga);
+}
+
+extern "C" int osm_phys_optimize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, const osm_lin_desc* lin, const float* x0,
+                                       const float* y, const float* mask, float* phi, float* F, float* AF, float* u, float* v,
+                                       float* part_r, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
+                                       float* opt_state, void* stream) {
+  const char* who = "osm_phys_optimize_lin_g";
+  GroupArgs ga;
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &ga, who))) return rc;
+  return phys_optimize_lin_launch(who, d, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                                  stream, &ga);
 }
 
 extern "C" int osm_posterior_typed(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,

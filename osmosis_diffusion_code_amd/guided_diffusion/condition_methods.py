@@ -243,17 +243,35 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         self._state = st
         return st
 
+    def _group(self, phi):
+        """The group descriptor of an operator with shared water parameters (`phi_groups`), None without.  A group's members are
+        pooled inside ONE launch, so the phi rows in hand must be the operator's whole batch."""
+        sizes = getattr(self.operator, "group_sizes", None)
+        if sizes is None:
+            return None
+        full = self.operator.phi
+        if phi.data_ptr() != full.data_ptr() or phi.shape[0] != full.shape[0]:
+            raise ValueError(f"phi_groups: a water group spans chunks -- the data term got {phi.shape[0]} phi rows of the operator's "
+                             f"{full.shape[0]}; a grouped batch takes ONE call over all its images")
+        key = (sizes, self.operator.phi_reduce)
+        if getattr(self, "_grp_key", None) != key:
+            self._grp, self._grp_key = ops.group_desc(sizes, self.operator.phi_reduce), key
+        return self._grp
+
     def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
         """Inner phi-optimisation + dL/dx0.  x0 [B,4,H,W], y [B,3,H,W] contiguous device fp32.
         Returns (g [B,4,H,W] view of an internal buffer (or g_out), per-image data loss [B] (device)).
         `phi` / `loss_out` / `mask`: rows of the operator's [B][9] state / of a [B] loss vector / of the [B,3,HW] mask when the
         caller walks a batch in chunks of independent images (default: the operator's whole state, the mask of
-        `set_measurement_mask`)."""
+        `set_measurement_mask`).
+        An operator with `phi_groups`: the same launches with ONE phi step per group and inner iteration (osm_phys_optimize_g); loss
+        and g stay per image, and the call must cover the operator's whole batch."""
         if getattr(self.operator, "degradation", None) is not None:
             return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] != 4:
             raise ValueError("expected x0 [B,4,H,W] and measurement [B,3,H,W]")
+        grp = self._group(self.operator.phi if phi is None else phi)        # (refuses a chunk of a grouped batch before anything else)
         st = self._prepare(B, HW, x0.device)
         d, part, red, loss = st["desc"], st["part"], st["red"], st["loss"]
         opt = self._opt if d.optimizer != 0 else None       # read at call time: _prepare may have re-allocated it
@@ -267,6 +285,21 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         if mask is None:
             mask = self.measurement_mask(B, HW, x0.device)
         n_inner = 1 if freeze_phi else self.n_iter
+        if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
+            rows, masked = self._opt_rows(opt, phi), mask is not None
+            if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+                ops.phys_optimize_g(d, grp, x0c, yc, mask, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=rows)
+                return g.view(x0.shape), loss
+            for it in range(n_inner):
+                ops.phys_reduce_m(d, x0c, yc, mask, phi, part)
+                if it == n_inner - 1:
+                    ops.phys_finalize_g(d, grp, part, red, phi, False, loss, masked=masked)
+                    ops.phys_grad_m(d, x0c, yc, mask, phi, red, g)
+                    if not freeze_phi:
+                        ops.phys_finalize_g(d, grp, part, red, phi, True, None, opt_state=rows, masked=masked)
+                else:
+                    ops.phys_finalize_g(d, grp, part, red, phi, True, loss, opt_state=rows, masked=masked)
+            return g.view(x0.shape), loss
         if mask is not None:        # the same launches with the mask in the residual (osm_phys_*_m)
             if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
                 ops.phys_optimize_m(d, x0c, yc, mask, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=self._opt_rows(opt, phi))
@@ -313,6 +346,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         if tuple(y.shape) != (B, 3, h, w):
             raise ValueError(f"expected the measurement [{B},3,{h},{w}] (the degradation's grid for a {H} x {W} image), got {tuple(y.shape)}")
         HW, hw = H * W, h * w
+        grp = self._group(self.operator.phi if phi is None else phi)
         st = self._prepare(B, HW, x0.device, grid=(H, W))
         d, lin, part, red, loss = st["desc"], st["lin"], st["part"], st["red"], st["loss"]
         F, AF, u, v, part_r = st["F"], st["AF"], st["u"], st["v"], st["part_r"]
@@ -333,7 +367,16 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError(f"expected mask rows [{B},3,{hw}] (the measurement's grid {h} x {w}), got {tuple(mask.shape)}")
         n_inner = 1 if freeze_phi else self.n_iter
         rows = self._opt_rows(opt, phi)
+
+        def finalize(do_update, loss_out, opt_state=None, masked=False):
+            if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
+                return ops.phys_finalize_lin_g(d, grp, hw, part, part_r, red, phi, do_update, loss_out, opt_state=opt_state, masked=masked)
+            return ops.phys_finalize_lin(d, hw, part, part_r, red, phi, do_update, loss_out, opt_state=opt_state, masked=masked)
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            if grp is not None:
+                ops.phys_optimize_lin_g(d, grp, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g, n_inner, freeze_phi,
+                                        opt_state=rows)
+                return g.view(x0.shape), loss
             ops.phys_optimize_lin(d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g, n_inner, freeze_phi, opt_state=rows)
             return g.view(x0.shape), loss
         P, masked = ops.phys_lin_planes(d), mask is not None
@@ -344,12 +387,12 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             ops.phys_lin_apply(lin, u, v, B, 3, adjoint=True)
             ops.phys_reduce_lin(d, x0c, phi, v, part)
             if it == n_inner - 1:
-                ops.phys_finalize_lin(d, hw, part, part_r, red, phi, False, loss, masked=masked)
+                finalize(False, loss, masked=masked)
                 ops.phys_grad_lin(d, hw, x0c, phi, v, red, g, masked=masked)
                 if not freeze_phi:
-                    ops.phys_finalize_lin(d, hw, part, part_r, red, phi, True, None, opt_state=rows, masked=masked)
+                    finalize(True, None, opt_state=rows, masked=masked)
             else:
-                ops.phys_finalize_lin(d, hw, part, part_r, red, phi, True, loss, opt_state=rows, masked=masked)
+                finalize(True, loss, opt_state=rows, masked=masked)
         return g.view(x0.shape), loss
 
     def _opt_rows(self, opt, phi):
@@ -412,7 +455,12 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         if m is not None:           # (mse below keeps its 3 HW denominator: a mask of ones is the unmasked loss)
             diff = diff * m
         if self.loss_function == "norm":
-            return torch.norm(diff.detach().cpu(), p=2, dim=[1, 2, 3]).numpy(), torch.linalg.norm(diff), image.detach()
+            sep = torch.norm(diff.detach().cpu(), p=2, dim=[1, 2, 3]).numpy()
+            if getattr(self.operator, "group_sizes", None) is not None:
+                # shared water parameters: a group's objective is the SUM of its members' per-image norms (what the kernels pool),
+                # not the norm over the batch
+                return sep, torch.linalg.vector_norm(diff, dim=(1, 2, 3)).sum(), image.detach()
+            return sep, torch.linalg.norm(diff), image.detach()
         if self.loss_function == "mse":
             mse = (diff ** 2).mean(dim=(1, 2, 3))
             return mse.detach().cpu().numpy(), mse.sum(), image.detach()

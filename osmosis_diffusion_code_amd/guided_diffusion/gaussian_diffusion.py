@@ -394,7 +394,12 @@ class GaussianDiffusion:
         mean_only: the mean-only 'ps' step (:235-238, :298-306): x_next = mean - scale grad at every index, no noise drawn or added
         (`noise="aten"` with reference_rng_order draws q_sample's only; noise_fn is not called).
         Channels: x_start [B,C,H,W] with the network's C; (C, Cout) = (4, 8) runs the [B,4,HW] entry points, anything else the
-        channel-generic ones (osm_*_c)."""
+        channel-generic ones (osm_*_c).
+        Shared water parameters (the operator's `phi_groups`): the images of a group are no longer independent in phi, so a guided
+        sub-step runs every chunk's forward + posterior, then ONE data term over the whole batch (one phi step per group and inner
+        iteration, osm_phys_optimize_g), then every chunk's backward + update.  With one chunk that is the ungrouped launch order
+        with the grouped call in the data term's place; with more, each chunk's forward is re-run before its backward (the engine
+        keeps one pass's activations): ONE EXTRA FORWARD per chunk per guided sub-step.  Ungrouped chains keep their launch sequence."""
         import os
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
@@ -457,6 +462,7 @@ class GaussianDiffusion:
         mask = cond.measurement_mask(B, y.shape[2] * y.shape[3] if y.dim() == 4 else HW, dev)
         phi = None if ps else cond.operator.phi
         single = len(chunks) == 1
+        grouped = not ps and getattr(cond.operator, "group_sizes", None) is not None
         x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
         x_state.copy_(x_start.detach())
         noise_fn = kwargs.get("noise_fn", None)           # (k, shape) -> tensor : injected noise (parity runs)
@@ -520,34 +526,54 @@ class GaussianDiffusion:
                     rec = {"idx": idx, "sub": sub, "x_in": x_state.clone()}
                     grad_all = torch.empty_like(g) if guided else None
                     model_out = torch.empty(B, eng.out.shape[1], H, W, **f32)
-                for c0, c1 in chunks:
-                    ce, Bc = engs[c1 - c0], c1 - c0        # this chunk's engine (`eng` stays the first one)
-                    if not single:
-                        ce.x_in.copy_(x_state[c0:c1])
-                    ce.run_forward()
-                    mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
-                    if dyn and rgbd:
-                        ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
-                                             mk, vk, DYNAMIC_THRESHOLD_S)
-                    elif dyn:
-                        ops.posterior_dynthr_c(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, C, Cout, HW,
-                                               mk, vk, DYNAMIC_THRESHOLD_S)
-                    elif rgbd:
-                        ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW, mk, vk,
-                                      None if x0_raw is None else x0_raw[c0:c1])
-                    else:
-                        ops.posterior_c(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, C, Cout, HW, mk, vk,
-                                        None if x0_raw is None else x0_raw[c0:c1])
-                    if trace is not None:
-                        model_out[c0:c1].copy_(ce.out)
-                    gg = dxu = grad_out = None
-                    if guided:
+                # what this sub-step does, in launch order.  Independent chains: chunk by chunk forward -> data term -> backward -> update.
+                # Shared water parameters (the operator's `phi_groups`): a group's phi step pools its members, so (a) every chunk's forward
+                # + posterior into the [B]-sized x0 / mean / logvar, (b) ONE data term over the whole batch, (c) per chunk backward +
+                # update -- with more than one chunk after re-running its forward (the engine's activations are the last chunk's by then)
+                if grouped and guided:
+                    walk = [("fwd", c) for c in chunks] + [("data", (0, B))]
+                    for c in chunks:
+                        walk += ([] if single else [("refwd", c)]) + [("upd", c)]
+                else:
+                    walk = []
+                    for c in chunks:
+                        walk += [("fwd", c)] + ([("data", c)] if guided else []) + [("upd", c)]
+                for act, (c0, c1) in walk:
+                    if act == "data":
                         if ps:
                             cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
                         else:
                             cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
                                               loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
                         have_loss = True
+                        continue
+                    ce, Bc = engs[c1 - c0], c1 - c0        # this chunk's engine (`eng` stays the first one)
+                    if act == "refwd":
+                        ce.x_in.copy_(x_state[c0:c1])
+                        ce.run_forward()
+                        continue
+                    if act == "fwd":
+                        if not single:
+                            ce.x_in.copy_(x_state[c0:c1])
+                        ce.run_forward()
+                        mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
+                        if dyn and rgbd:
+                            ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
+                                                 mk, vk, DYNAMIC_THRESHOLD_S)
+                        elif dyn:
+                            ops.posterior_dynthr_c(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, C, Cout, HW,
+                                                   mk, vk, DYNAMIC_THRESHOLD_S)
+                        elif rgbd:
+                            ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW, mk, vk,
+                                          None if x0_raw is None else x0_raw[c0:c1])
+                        else:
+                            ops.posterior_c(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, C, Cout, HW, mk, vk,
+                                            None if x0_raw is None else x0_raw[c0:c1])
+                        if trace is not None:
+                            model_out[c0:c1].copy_(ce.out)
+                        continue
+                    gg = dxu = grad_out = None
+                    if guided:
                         if dyn:                           # (a clip_denoised clamp after it masks nothing more)
                             ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
                         elif x0_raw is not None:
@@ -622,6 +648,9 @@ class GaussianDiffusion:
             raise NotImplementedError("tiling: rgb_guidance (the 'ps' branch) is not tiled")
         if getattr(getattr(getattr(cond_fn, "__self__", None), "operator", None), "degradation", None) is not None:
             raise NotImplementedError("tiling: a degradation inside the physical operator is not tiled")
+        if getattr(getattr(getattr(cond_fn, "__self__", None), "operator", None), "group_sizes", None) not in (None, (1,)):
+            raise NotImplementedError("tiling: phi_groups (water parameters shared across photos) is not tiled -- a tiled chain is one "
+                                      "canvas with its one phi")
         if pretrain_model != "osmosis":
             raise NotImplementedError(f"tiling: pretrain_model={pretrain_model!r} (the mean-only branch) is not tiled")
         if getattr(type(self), "p_sample", None) is DDIM.p_sample:

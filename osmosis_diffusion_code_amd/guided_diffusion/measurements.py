@@ -496,12 +496,32 @@ def build_degradation(degradation, device, batch_size=1):
     return get_operator(name, device=device, batch_size=batch_size, **cfg)
 
 
+def parse_phi_groups(phi_groups, batch_size):
+    """`phi_groups` of a physical operator -> the tuple of group sizes, or None (every image its own phi): None; "all" / True, one
+    group of `batch_size`; a list of positive ints summing to `batch_size`.  Anything else raises ValueError."""
+    if phi_groups is None or phi_groups is False:
+        return None
+    if phi_groups is True or (isinstance(phi_groups, str) and phi_groups == "all"):
+        return (int(batch_size),)
+    if isinstance(phi_groups, (list, tuple)) and len(phi_groups) > 0 and \
+            all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and n >= 1 for n in phi_groups):
+        sizes = tuple(int(n) for n in phi_groups)
+        if sum(sizes) != int(batch_size):
+            raise ValueError(f"phi_groups {list(sizes)} sums to {sum(sizes)}, the operator has batch_size = {batch_size}")
+        return sizes
+    raise ValueError(f"phi_groups must be None, 'all' / True or a list of positive ints summing to batch_size, got {phi_groups!r}")
+
+
 class _PhysicalOperator(LearnableOperator):
     """Shared machinery of the three image-formation models
     I = 0.5(rgb+1) exp(-phi_a d) + phi_inf (1 - exp(-phi_b d)),  d = convert_depth(x[:,3]).
     `degradation=` (a `GRID_OPERATORS` instance or its config dict, `build_degradation`; default None) puts a linear operator A
     between the model and the photo: the photo in [0, 1] is A I on A's grid `out_shape(H, W)`.  `forward` stays the water / haze
-    image on the image grid; `observe` is A of it."""
+    image on the image grid; `observe` is A of it.
+    `phi_groups=` (`parse_phi_groups`; default None) partitions the batch into contiguous groups of photos of ONE water body: a
+    group's rows of `phi` (and of the optimizer state) are equal and stay equal, stepped once with the members' pooled gradient,
+    `phi_reduce=` "mean" (default: the eta of the configs were chosen for one image's gradient) or "sum".  Attributes
+    `group_sizes` (None: ungrouped), `group_offsets`, `phi_reduce`."""
     KIND = -1
     VARS = ()
 
@@ -514,6 +534,11 @@ class _PhysicalOperator(LearnableOperator):
         self.optimizer = _check_optimizer(kwargs.get("optimizer", None))
         self._requires_grad = {v: False for v in self.VARS}
         self.degradation = build_degradation(kwargs.get("degradation", None), self.device, batch_size)
+        self.group_sizes = parse_phi_groups(kwargs.get("phi_groups", None), batch_size)
+        self.phi_reduce = kwargs.get("phi_reduce", None) or "mean"
+        if self.phi_reduce not in ("mean", "sum"):
+            raise ValueError(f"phi_reduce must be 'mean' or 'sum', got {self.phi_reduce!r}")
+        self.group_offsets = None if self.group_sizes is None else tuple(int(v) for v in np.cumsum((0,) + self.group_sizes))
 
     # -- state ------------------------------------------------------------------------------
     def _init_phi(self, a, b, inf):
@@ -575,6 +600,15 @@ class _PhysicalOperator(LearnableOperator):
         gets the reference's step here: plain gradient descent phi -= eta * grad for 'GD' / 'sgd' / '', else the torch optimizer of
         `optimizer:` over one parameter group per variable (lr = eta), then the gradients are zeroed."""
         if not kwargs.get("freeze_phi", False) and any(v.grad is not None for v in self._leaves.values()):
+            if self.group_sizes is not None:
+                # shared water parameters: the rows of a group are one parameter, so its gradient is the members' pooled one (sum or
+                # mean), handed to every row -- the same optimizer code below then keeps the rows equal
+                with torch.no_grad():
+                    for v in self._leaves.values():
+                        if v.grad is not None:
+                            for lo, hi in zip(self.group_offsets[:-1], self.group_offsets[1:]):
+                                pooled = v.grad[lo:hi].sum(dim=0, keepdim=True)
+                                v.grad[lo:hi] = pooled / (hi - lo) if self.phi_reduce == "mean" else pooled
             etas = dict(zip(("phi_a", "phi_b", "phi_inf"), self.eta3()))
             etas["phi_ab"] = etas["phi_a"]
             if OPTIMIZER_CODES[self.optimizer] == 0:

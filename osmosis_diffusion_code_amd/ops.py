@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, GemmDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
+from ._lib import AttnDesc, ConvDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
 
 
 @dataclass
@@ -816,3 +816,52 @@ def phys_optimize_lin(desc: PhysDesc, lin: LinDesc, x0, y, mask, phi, F, AF, u, 
     call("osm_phys_optimize_lin", C.byref(desc), C.byref(lin), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(F), ptr(AF), ptr(u), ptr(v),
          ptr(part_r), ptr(part), ptr(red), ptr(loss_out), ptr(g), int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(),
          keep=(desc, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, opt_state) + tuple(lin._keep))
+
+
+# ----------------------------------------------------------------------------- shared water parameters (include/osmosis_physgroup.h)
+def group_desc(group_sizes, reduce="mean") -> GroupDesc:
+    """The group descriptor of a batch partitioned into contiguous groups of `group_sizes` images (a Python tuple: the offsets stay
+    on the host and travel in the kernel's arguments, nothing is allocated on the device)."""
+    return GroupDesc.of(group_sizes, reduce)
+
+
+def _check_group(name, desc: PhysDesc, grp: GroupDesc):
+    if grp.G < 1 or grp.off[grp.G] != desc.B:
+        raise ValueError(f"{name}: the groups cover {grp.off[grp.G] if grp.G >= 1 else 0} images, the descriptor has B = {desc.B}")
+
+
+def phys_finalize_g(desc: PhysDesc, grp: GroupDesc, part, red, phi, do_update, loss_out, opt_state=None, masked=False):
+    """`phys_finalize_m` with ONE phi step per group: the members' gradients pooled (fp64, ascending order; sum or mean), every member
+    row receives the new phi and optimizer state."""
+    _check_group("phys_finalize_g", desc, grp)
+    call("osm_phys_finalize_g", C.byref(desc), C.byref(grp), ptr(part), ptr(red), ptr(phi), int(do_update), ptr(loss_out), ptr(opt_state),
+         int(bool(masked)), _s(), keep=(desc, grp, part, red, phi, loss_out, opt_state))
+
+
+def phys_finalize_lin_g(desc: PhysDesc, grp: GroupDesc, hw, part, part_r, red, phi, do_update, loss_out, opt_state=None, masked=False):
+    _check_group("phys_finalize_lin_g", desc, grp)
+    _check_lin_ws("phys_finalize_lin_g", desc, hw, part=part, part_r=part_r, red=red, phi=phi)
+    call("osm_phys_finalize_lin_g", C.byref(desc), C.byref(grp), int(hw), ptr(part), ptr(part_r), ptr(red), ptr(phi), int(do_update),
+         ptr(loss_out), ptr(opt_state), int(bool(masked)), _s(), keep=(desc, grp, part, part_r, red, phi, loss_out, opt_state))
+
+
+def phys_optimize_g(desc: PhysDesc, grp: GroupDesc, x0, y, mask, phi, part, red, loss_out, g, n_inner: int, freeze_phi: bool, opt_state=None):
+    """`phys_optimize_m` (mask None: `phys_optimize`) with the grouped finalize in the place of the plain one."""
+    _check_group("phys_optimize_g", desc, grp)
+    _check_mask(mask, y)
+    call("osm_phys_optimize_g", C.byref(desc), C.byref(grp), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(part), ptr(red), ptr(loss_out),
+         ptr(g), int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(),
+         keep=(desc, grp, x0, y, mask, phi, part, red, loss_out, g, opt_state))
+
+
+def phys_optimize_lin_g(desc: PhysDesc, grp: GroupDesc, lin: LinDesc, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g,
+                        n_inner: int, freeze_phi: bool, opt_state=None):
+    """`phys_optimize_lin` with the grouped finalize in the place of the plain one."""
+    _check_group("phys_optimize_lin_g", desc, grp)
+    if lin.H * lin.W != desc.HW:
+        raise ValueError(f"phys_optimize_lin_g: the operator's image grid {lin.H} x {lin.W} does not have HW = {desc.HW} pixels")
+    _check_lin_ws("phys_optimize_lin_g", desc, lin.h * lin.w, x0=x0, y=y, mask=mask, phi=phi, F=F, AF=AF, u=u, v=v, part_r=part_r,
+                  part=part, red=red, g=g)
+    call("osm_phys_optimize_lin_g", C.byref(desc), C.byref(grp), C.byref(lin), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(F), ptr(AF),
+         ptr(u), ptr(v), ptr(part_r), ptr(part), ptr(red), ptr(loss_out), ptr(g), int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(),
+         keep=(desc, grp, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, opt_state) + tuple(lin._keep))

@@ -504,7 +504,7 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
-                   geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, **loop_kwargs):
+                   geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -515,7 +515,19 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     `originals` (list of `to_tensor` photos [3,H0,W0]) with `geometries` (their `data.Geometry`) attaches
     `reconstruct_full_resolution(..., upsample=full_res_upsample)` to every result that carries phi, under `full_res`.
 
-    `tiling` goes to `restore_image` as it is (one canvas per call: `batch_size` stays 1 with it)."""
+    `tiling` goes to `restore_image` as it is (one canvas per call: `batch_size` stays 1 with it).
+
+    `shared_water=True`: the photos were taken in ONE water body (a burst, a clip, a survey transect), so every batch this call
+    forms (`batch_size` images of this rank) is one water group -- `phi_groups="all"` on a copy of the operator config of that
+    batch: one phi estimated from all its images (`_PhysicalOperator(phi_groups=)`; `measurement.operator.phi_reduce` chooses
+    "mean" or "sum").  A batch of one stays ungrouped.  Every result carries `water_group`, the image indices that shared its phi;
+    everything downstream reads the per-image phi rows as before.  Not with `tiling`, nor with a `ps` / rgb-guidance config (no
+    phi there)."""
+    if shared_water:
+        if tiling is not None or cfg.get("tiling") is not None:
+            raise NotImplementedError("shared_water: tiling is one canvas per call, water parameters are not shared across canvases")
+        if cfg.get("rgb_guidance", False) or cfg.get("conditioning", {}).get("method") == "ps":
+            raise ValueError("shared_water: the rgb-guidance ('ps') chain has no water parameters to share")
     if tiling is not None:
         loop_kwargs = dict(loop_kwargs, tiling=tiling)
     if (originals is None) != (geometries is None):
@@ -546,7 +558,10 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
                                  **loop_kwargs)[-1]]
         else:
             ref = torch.cat([images[i] for i in idxs], 0)
-            full = restore_image(model, ref, cfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
+            bcfg = cfg
+            if shared_water:        # this batch is one water group (a copy: the caller's config stays as it is)
+                bcfg = dict(cfg, measurement=dict(cfg["measurement"], operator=dict(cfg["measurement"]["operator"], phi_groups="all")))
+            full = restore_image(model, ref, bcfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
                                  postprocess_batch=False, mask=batch_mask(idxs), **loop_kwargs)[-1]
             if "pred_xstart" in full:
                 res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"],
@@ -560,6 +575,8 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
                 for b, r in enumerate(res):
                     r["mask"] = full["mask"][b:b + 1]
         for i, r in zip(idxs, res):
+            if shared_water:
+                r["water_group"] = list(idxs)
             if gt_rgb is not None:
                 r["psnr"] = float(utilso.psnr(r["rgb_01_clip"], gt_rgb[i]))
             if originals is not None and "phi" in r:

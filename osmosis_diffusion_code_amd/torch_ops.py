@@ -20,6 +20,7 @@ registered for the "cuda" device type only, which is HIP on ROCm).
                                                            condition_methods.py:186-221 update rule + the noise add of :262-271
     osmosis::phys_loss_grad(x0, y, phi, icfg, fcfg, n_inner, freeze_phi) -> (loss, grad_x0, phi_new)
     osmosis::phys_loss_grad_lin(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, family, tables, dims) -> (loss, grad_x0, phi_new)
+    osmosis::phys_loss_grad_g(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, group_sizes, reduce) -> (loss, grad_x0, phi_new)
                                                            measurements.py forward models + the inner phi optimisation
                                                            (cm.py:141-184), functional (phi is returned, not updated in place)
     osmosis::recon_fullres(depth, guide, image, phi_a, phi_b, phi_inf, depth_type, dval, amap, mode, radius, sigma_s, sigma_r)
@@ -294,7 +295,7 @@ def _mask_rows(name, mask, y):
     return mask.expand(y.shape).contiguous()
 
 
-def _phys_loss_grad_impl(name, x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi):
+def _phys_loss_grad_impl(name, x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, grp=None):
     B, HW = _chw(x0)
     if len(icfg) != len(PHYS_ICFG) or len(fcfg) != len(PHYS_FCFG):
         raise OsmosisHipError(f"{name}: icfg / fcfg must come from torch_ops.phys_config(desc)")
@@ -315,7 +316,10 @@ def _phys_loss_grad_impl(name, x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi
     red = torch.zeros(B * 16, device=dev, dtype=torch.float32)
     loss = torch.zeros(B, device=dev, dtype=torch.float32)
     g = torch.empty_like(x0)
-    if mask is None:
+    if grp is not None:
+        ops.phys_optimize_g(d, grp, x0, y.contiguous(), None if mask is None else _mask_rows(name, mask, y), phi_new, part, red, loss, g,
+                            1 if freeze_phi else n_inner, freeze_phi)
+    elif mask is None:
         ops.phys_optimize(d, x0, y.contiguous(), phi_new, part, red, loss, g, 1 if freeze_phi else n_inner, freeze_phi)
     else:
         ops.phys_optimize_m(d, x0, y.contiguous(), _mask_rows(name, mask, y), phi_new, part, red, loss, g,
@@ -338,6 +342,26 @@ def phys_loss_grad_m(x0: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, phi:
 
 @phys_loss_grad_m.register_fake
 def _phys_loss_grad_m_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
+
+
+@torch.library.custom_op("osmosis::phys_loss_grad_g", mutates_args=(), device_types="cuda")
+def phys_loss_grad_g(x0: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], phi: torch.Tensor, icfg: List[int],
+                     fcfg: List[float], n_inner: int, freeze_phi: bool, group_sizes: List[int],
+                     reduce: str) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """osmosis::phys_loss_grad / _m (mask None / a mask) with shared water parameters: the batch is partitioned into contiguous
+    groups of `group_sizes` images, each with ONE phi (its rows of `phi` equal on entry, equal on return), stepped once per inner
+    iteration with the members' pooled gradient (`reduce`: "mean" or "sum"; osm_phys_optimize_g).  Loss and grad_x0 stay per image."""
+    name = "osmosis::phys_loss_grad_g"
+    if reduce not in ("mean", "sum") or not group_sizes or any(int(n) < 1 for n in group_sizes) or \
+            sum(int(n) for n in group_sizes) != x0.shape[0]:
+        raise OsmosisHipError(f"{name}: group_sizes must be positive ints summing to the batch {x0.shape[0]} and reduce 'mean' or 'sum', "
+                              f"got {list(group_sizes)} and {reduce!r}")
+    return _phys_loss_grad_impl(name, x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, grp=ops.group_desc(group_sizes, reduce))
+
+
+@phys_loss_grad_g.register_fake
+def _phys_loss_grad_g_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, group_sizes, reduce):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
 
 
@@ -802,4 +826,5 @@ def _phys_loss_grad_lin_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, 
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
-       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin") + OPS_C
+       "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
+       "phys_loss_grad_g") + OPS_C
