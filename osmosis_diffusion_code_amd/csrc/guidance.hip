@@ -8,6 +8,11 @@
 // 20-iteration phi loop runs with no host synchronisation (the reference syncs 4+20 times a step).
 // Batch semantics: every reduction is PER IMAGE (equal to B=1 reference runs image by image,
 // SURVEY.md F1/F2).
+// One kernel per job.  The step kernels (posterior, posterior_bwd, guide_update(_rng), ddim_update) take the state's C and the
+// network output's Cout as launch arguments: the RGBD entry points pass (4, 8), the `_c` ones the RGB family's (3, 6) / (3, 3).
+// The physics kernels are templates over what a route adds -- phys_reduce_kernel / phys_grad_kernel<MASKED, LIN> (a validity
+// mask; a linear operator between the model and the residual), phys_finalize(_group)_kernel<LIN> over one shared device body --
+// and ONE host function, phys_optimize_launch, enqueues the inner loop of the plain, masked, grouped and composed entry points.
 #include "osm_common.h"
 #include "../../include/osmosis_linop.h"
 #include "../../include/osmosis_psf.h"
@@ -109,12 +114,16 @@ __device__ __forceinline__ void eval_pixel(const osm_phys_desc& ds, const float*
   }
 }
 
-template <bool MASKED>
+// LIN (the composed data term, a linear operator A between the model and the residual; include/osmosis_physlin.h): k2 is read from
+// v = A^T u [B,3,HW] where the plain instantiations form -2 w r inline, no measurement is read (y and mask are null), and slot 0 of `part`
+// is written as 0 (the finalize takes the squared residual from part_r, on the measurement's grid).
+template <bool MASKED, bool LIN>
 __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, const float* __restrict__ x0,
                                                            const float* __restrict__ y,
                                                            const float* __restrict__ mask,
-                                                           const float* __restrict__ phi,
+                                                           const float* __restrict__ phi, const float* __restrict__ v,
                                                            float* __restrict__ part, int nblk) {
+  static_assert(!(MASKED && LIN), "the composed route's mask acts on the measurement's grid (phys_resid_kernel)");
   __shared__ float red[4][NRED];
   const int b = blockIdx.y, blk = blockIdx.x;
   float s[NRED];
@@ -124,14 +133,19 @@ __global__ __launch_bounds__(256) void phys_reduce_kernel(osm_phys_desc ds, cons
   const float* ph = phi + b * 9;
   for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
     Pix<MASKED> q;
-    eval_pixel<MASKED>(ds, x0, y, mask, phi, b, p, q);
+    eval_pixel<MASKED, false, LIN>(ds, x0, y, mask, phi, b, p, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float pinf = ph[6 + c];
-      float wc = q.w;
-      if constexpr (MASKED) wc = q.wm[c];
-      const float k2 = -2.0f * wc * q.r[c];                  // r_c * d r_c / d I_c
-      s[0] += q.r[c] * q.r[c];
+      float k2;                                              // r_c * d r_c / d I_c
+      if constexpr (LIN) {
+        k2 = v[((long long)b * 3 + c) * ds.HW + p];
+      } else {
+        float wc = q.w;
+        if constexpr (MASKED) wc = q.wm[c];
+        k2 = -2.0f * wc * q.r[c];
+        s[0] += q.r[c] * q.r[c];
+      }
       s[1 + c] += k2 * (-q.d * q.J[c] * q.Ea[c]);            // d I / d phi_a
       s[4 + c] += k2 * (pinf * q.d * q.Eb[c]);               // d I / d phi_b
       s[7 + c] += k2 * (1.0f - q.Eb[c]);                     // d I / d phi_inf
@@ -279,82 +293,104 @@ __device__ __forceinline__ void phys_opt_step(const osm_phys_desc& ds, const flo
   if (ds.kind == 2) ph[1] = ph[2] = ph[0];
 }
 
+// The finalize of one reduce: per image the NRED sums (red) and the loss, then one optimizer step of phi.  Its three parts exist
+// once, as device functions; two thin kernels call them (ONE kernel with the per-image launch as its identity grouping measured
+// 6.2 us per launch against 4.4 - 4.7 us on the per-image path, which runs 21 times a step: it paid the group kernel's shared-memory
+// round trip and two more barriers).
 // LIN (the composed path): component 0, the sum of squared residuals, comes from lin.part_r [B][lin.nblk_r] -- the residual lives
 // on the measurement's grid of lin.hw pixels -- and the losses normalise by that grid.  The `false` instantiation carries no such
-// argument and is the code it always was.
+// argument.
 template <bool LIN> struct FinLin { const float* part_r; int nblk_r, hw; };
 template <> struct FinLin<false> {};
 
+// One wave walks image b's nblk partials into tot [NRED] (shared) and red[b]: component lane >> 2, four lanes share its partials
+// (fixed order: deterministic), fp64, two shuffle folds (a single lane per component walked 64 dependent loads: 10.6 us per
+// launch, 21 launches per step)
+template <bool LIN>
+__device__ __forceinline__ void fin_walk(const float* __restrict__ part, float* __restrict__ red, int nblk, const FinLin<LIN>& lin,
+                                         int b, int lane, double* tot) {
+  static_assert(NRED * 4 == 64, "one wave covers the components");
+  const int comp = lane >> 2, sub = lane & 3;
+  double a = 0.0;
+#pragma unroll 4
+  for (int k = sub; k < nblk; k += 4) a += (double)part[((long long)b * nblk + k) * NRED + comp];
+  if constexpr (LIN) {
+    if (comp == 0) {
+      a = 0.0;
+      for (int k = sub; k < lin.nblk_r; k += 4) a += (double)lin.part_r[(long long)b * lin.nblk_r + k];
+    }
+  }
+  a += __shfl_xor(a, 1, 64);
+  a += __shfl_xor(a, 2, 64);
+  if (sub == 0) {
+    tot[comp] = a;
+    red[b * NRED + comp] = (float)a;
+  }
+}
+
+// One lane, after the walk's barrier: image b's loss and, for a step, its fp64 parameter gradient dg [9].  Returns whether the
+// image steps: not on the masked path (zero_guard) with every pixel masked out -- the data term has no gradient there
+// (torch.linalg.norm's backward at 0; dg is 0) and does not step phi (no optimizer state moves either).
+template <bool LIN>
+__device__ __forceinline__ bool fin_member(const osm_phys_desc& ds, const double* tot, const FinLin<LIN>& lin, int zero_guard, int b,
+                                           float* __restrict__ loss_out, int do_update, double* dg) {
+  double n = 3.0 * (double)ds.HW;
+  if constexpr (LIN) n = 3.0 * (double)lin.hw;
+  double L, gscale;
+  bool live = true;
+  if (ds.loss_type == 0) {
+    L = sqrt(tot[0]);
+    gscale = 1.0 / L;
+    if (zero_guard && tot[0] == 0.0) { gscale = 0.0; live = false; }
+  } else {
+    L = tot[0] / n;
+    gscale = 2.0 / n;
+  }
+  if (loss_out) loss_out[b] = (float)L;
+  if (do_update) phys_param_grad(ds, tot, gscale, dg);
+  return live;
+}
+
+// One lane: the optimizer step of the row ph (state row st, NULL for sgd) with the fp64 gradient omega dg
+__device__ __forceinline__ void fin_step(const osm_phys_desc& ds, const double* dg, double omega, float* ph, float* st) {
+  float g[9], lr[9];
+  const int live = phys_param_lr(ds, lr);
+  for (int i = 0; i < 9; ++i) g[i] = (float)(dg[i] * omega);
+  phys_opt_step(ds, g, lr, live, ph, st);
+}
+
+// Per image: one wave per image, grid B
 template <bool LIN>
 __global__ void phys_finalize_kernel(osm_phys_desc ds, const float* __restrict__ part, float* __restrict__ red,
                                      float* __restrict__ phi, int do_update, float* __restrict__ loss_out,
                                      float* __restrict__ opt_state, int nblk, int zero_guard, const FinLin<LIN> lin) {
   __shared__ double tot[NRED];
   const int b = blockIdx.x;
-  {   // one wave: component lane >> 2, four lanes share its nblk partials (fixed order: deterministic), fp64, two shuffle folds
-    //  (a single lane per component walked 64 dependent loads: 10.6 us per launch, 21 launches per step)
-    static_assert(NRED * 4 == 64, "one wave covers the components");
-    const int comp = threadIdx.x >> 2, sub = threadIdx.x & 3;
-    double a = 0.0;
-#pragma unroll 4
-    for (int k = sub; k < nblk; k += 4) a += (double)part[((long long)b * nblk + k) * NRED + comp];
-    if constexpr (LIN) {
-      if (comp == 0) {
-        a = 0.0;
-        for (int k = sub; k < lin.nblk_r; k += 4) a += (double)lin.part_r[(long long)b * lin.nblk_r + k];
-      }
-    }
-    a += __shfl_xor(a, 1, 64);
-    a += __shfl_xor(a, 2, 64);
-    if (sub == 0) {
-      tot[comp] = a;
-      red[b * NRED + comp] = (float)a;
-    }
-  }
+  fin_walk(part, red, nblk, lin, b, threadIdx.x, tot);
   __syncthreads();
   if (threadIdx.x == 0) {
-    double n = 3.0 * (double)ds.HW;
-    if constexpr (LIN) n = 3.0 * (double)lin.hw;
-    double L, gscale;
-    if (ds.loss_type == 0) {
-      L = sqrt(tot[0]);
-      gscale = 1.0 / L;
-      // masked path, every pixel of the image masked out: the data term has no gradient (torch.linalg.norm's backward at 0) and
-      // does not step phi (no optimizer state moves either)
-      if (zero_guard && tot[0] == 0.0) { gscale = 0.0; do_update = 0; }
-    } else {
-      L = tot[0] / n;
-      gscale = 2.0 / n;
-    }
-    if (loss_out) loss_out[b] = (float)L;
-    if (do_update) {
-      double dg[9];
-      float g[9], lr[9];
-      const int live = phys_param_lr(ds, lr);
-      phys_param_grad(ds, tot, gscale, dg);
-      for (int i = 0; i < 9; ++i) g[i] = (float)dg[i];
-      phys_opt_step(ds, g, lr, live, phi + b * 9, opt_state ? opt_state + b * 20 : nullptr);
-    }
+    double dg[9];
+    if (fin_member(ds, tot, lin, zero_guard, b, loss_out, do_update, dg) && do_update)
+      fin_step(ds, dg, 1.0, phi + b * 9, opt_state ? opt_state + b * 20 : nullptr);
   }
 }
 
-// The grouped finalize (include/osmosis_physgroup.h): the images off[g] .. off[g + 1] - 1 share ONE phi row and ONE optimizer state
-// row.  One workgroup per group, its members dealt to the GWAVES waves round by round; a wave does for its member what the plain
-// kernel's single wave does (the same four-lane partial walk, fp64, two shuffle folds: red[b] and loss_out[b] are the plain
-// kernel's bits), lane 0 forms the member's fp64 parameter gradient (phys_param_grad) into shared memory, and thread 0 adds the
-// members up in ascending order -- fixed order, no atomics; the addends come out of shared memory, so no multiply is contracted into
-// the sum and a + a is exact.  Then one optimizer step on the group's first row with omega * sum (omega = 1 / n for `mean`, 1 for
-// `sum`), and every other member row receives the new phi and state.  A member that is zero-guarded adds nothing; a group whose
-// members are all guarded takes no step.  With n = 1 this is phys_finalize_kernel bit for bit (0 + d = d, omega = 1).
-struct GroupOff { int off[OSM_MAX_GROUPS + 1]; };
+// Per group (include/osmosis_physgroup.h): the images off[g] .. off[g + 1] - 1 share ONE phi row and ONE optimizer state row.  One
+// workgroup per group, its members dealt to the GWAVES waves round by round; a wave does for its member what the per-image
+// kernel's single wave does (red[b] and loss_out[b] are its bits), lane 0 leaves the member's gradient in shared memory, and thread
+// 0 adds the members up in ascending order, starting FROM the first member's -- fixed order, no atomics; the addends come out of
+// shared memory, so no multiply is contracted into the sum and a + a is exact.  Then one optimizer step on the group's first row
+// with omega * sum (omega = 1 / n for `mean`, 1 for `sum`), and every other member row receives the new phi and state.  A member
+// that is zero-guarded adds zeros; a group whose members are all guarded takes no step.  With n = 1 the sum is the member's own
+// gradient and omega = 1: phys_finalize_kernel bit for bit, signed zeros included.
+struct GroupOff { int G, reduce_mean, off[OSM_MAX_GROUPS + 1]; };
 constexpr int GWAVES = 4;
 
 template <bool LIN>
 __global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_phys_desc ds, const float* __restrict__ part,
                                                                           float* __restrict__ red, float* phi, int do_update,
                                                                           float* __restrict__ loss_out, float* opt_state, int nblk,
-                                                                          int zero_guard, int reduce_mean, const GroupOff go,
-                                                                          const FinLin<LIN> lin) {
+                                                                          int zero_guard, const GroupOff go, const FinLin<LIN> lin) {
   __shared__ double tot[GWAVES][NRED];
   __shared__ double dsh[GWAVES][9];
   __shared__ int live_sh[GWAVES];
@@ -362,56 +398,18 @@ __global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_ph
   __shared__ int stepped;
   const int b0 = go.off[blockIdx.x], n = go.off[blockIdx.x + 1] - b0;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // thread 0: the group's sum
+  double acc[9];                                                     // thread 0: the group's sum
   int any = 0;                                                       // thread 0: a member that is not zero-guarded
   for (int r0 = 0; r0 < n; r0 += GWAVES) {
     const int m = r0 + wv;                // this wave's member of the round (wave-uniform)
-    const int b = b0 + m;
-    if (m < n) {
-      const int comp = lane >> 2, sub = lane & 3;
-      double a = 0.0;
-#pragma unroll 4
-      for (int k = sub; k < nblk; k += 4) a += (double)part[((long long)b * nblk + k) * NRED + comp];
-      if constexpr (LIN) {
-        if (comp == 0) {
-          a = 0.0;
-          for (int k = sub; k < lin.nblk_r; k += 4) a += (double)lin.part_r[(long long)b * lin.nblk_r + k];
-        }
-      }
-      a += __shfl_xor(a, 1, 64);
-      a += __shfl_xor(a, 2, 64);
-      if (sub == 0) {
-        tot[wv][comp] = a;
-        red[b * NRED + comp] = (float)a;
-      }
-    }
+    if (m < n) fin_walk(part, red, nblk, lin, b0 + m, lane, tot[wv]);
     __syncthreads();
-    if (m < n && lane == 0) {
-      double nn = 3.0 * (double)ds.HW;
-      if constexpr (LIN) nn = 3.0 * (double)lin.hw;
-      double L, gscale;
-      int guarded = 0;
-      if (ds.loss_type == 0) {
-        L = sqrt(tot[wv][0]);
-        gscale = 1.0 / L;
-        if (zero_guard && tot[wv][0] == 0.0) { gscale = 0.0; guarded = 1; }
-      } else {
-        L = tot[wv][0] / nn;
-        gscale = 2.0 / nn;
-      }
-      if (loss_out) loss_out[b] = (float)L;
-      if (do_update) {
-        double dg[9];
-        phys_param_grad(ds, tot[wv], gscale, dg);
-        for (int i = 0; i < 9; ++i) dsh[wv][i] = dg[i];
-        live_sh[wv] = !guarded;
-      }
-    }
+    if (m < n && lane == 0) live_sh[wv] = fin_member(ds, tot[wv], lin, zero_guard, b0 + m, loss_out, do_update, dsh[wv]);
     __syncthreads();
     if (threadIdx.x == 0 && do_update) {
       const int cnt = min(GWAVES, n - r0);
       for (int w = 0; w < cnt; ++w) {
-        for (int i = 0; i < 9; ++i) acc[i] += dsh[w][i];
+        for (int i = 0; i < 9; ++i) acc[i] = r0 + w == 0 ? dsh[w][i] : acc[i] + dsh[w][i];
         any |= live_sh[w];
       }
     }
@@ -420,13 +418,9 @@ __global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_ph
   if (threadIdx.x == 0) {
     stepped = 0;
     if (do_update && any) {
-      const double omega = reduce_mean ? 1.0 / (double)n : 1.0;
-      float g[9], lr[9];
-      const int live = phys_param_lr(ds, lr);
-      for (int i = 0; i < 9; ++i) g[i] = (float)(acc[i] * omega);
       float* ph = phi + b0 * 9;
       float* st = opt_state ? opt_state + b0 * 20 : nullptr;
-      phys_opt_step(ds, g, lr, live, ph, st);
+      fin_step(ds, acc, go.reduce_mean ? 1.0 / (double)n : 1.0, ph, st);
       for (int i = 0; i < 9; ++i) row[i] = ph[i];
       for (int i = 0; i < 20; ++i) row[9 + i] = st ? st[i] : 0.f;
       stepped = 1;
@@ -442,43 +436,54 @@ __global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_ph
   }
 }
 
-template <bool MASKED>
+// LIN: dL/dI_c = v_c gscale with v = A^T u where the plain instantiations form -2 w r gscale inline; mse normalises by the measurement's
+// 3 hw (the auxiliary losses by the image's 3 HW), and the zero guard of a fully masked image is the launch's flag (the mask lives
+// on the measurement's grid, in phys_resid_kernel).
+template <bool MASKED, bool LIN>
 __global__ __launch_bounds__(256) void phys_grad_kernel(osm_phys_desc ds, const float* __restrict__ x0,
                                                          const float* __restrict__ y,
                                                          const float* __restrict__ mask,
-                                                         const float* __restrict__ phi,
-                                                         const float* __restrict__ red, float* __restrict__ g) {
+                                                         const float* __restrict__ phi, const float* __restrict__ v,
+                                                         const float* __restrict__ red, float* __restrict__ g, int hw,
+                                                         int zero_guard) {
+  static_assert(!(MASKED && LIN), "the composed route's mask acts on the measurement's grid (phys_resid_kernel)");
   const int b = blockIdx.y;
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= ds.HW) return;
   Pix<MASKED> q;
-  eval_pixel<MASKED, MASKED>(ds, x0, y, mask, phi, b, p, q);
+  eval_pixel<MASKED, MASKED, LIN>(ds, x0, y, mask, phi, b, p, q);
   const float* rd = red + b * NRED;
   const float n = 3.0f * (float)ds.HW;
-  float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / n;
-  if constexpr (MASKED) {   // a fully masked image: no data-term gradient (the auxiliary losses, which act on the prediction, remain)
-    if (ds.loss_type == 0 && rd[0] == 0.f) gscale = 0.f;
-  }
+  float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / (LIN ? 3.0f * (float)hw : n);
+  // a fully masked image: no data-term gradient (the auxiliary losses, which act on the prediction, remain)
+  if ((MASKED || (LIN && zero_guard)) && ds.loss_type == 0 && rd[0] == 0.f) gscale = 0.f;
   const float* ph = phi + b * 9;
   float gD = 0.f;
   const long long base = (long long)b * 4 * ds.HW + p;
-  if (ds.kind == 3) {   // d ||y - x0[:, 0:3]|| / d x0 = -(y - x0) / ||.|| on the colour channels, nothing on depth
+  if constexpr (!LIN) {   // (kind 3 has no model to compose with: the host refuses it on the composed route)
+    if (ds.kind == 3) {   // d ||y - x0[:, 0:3]|| / d x0 = -(y - x0) / ||.|| on the colour channels, nothing on depth
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if constexpr (MASKED) g[base + (long long)c * ds.HW] = -(q.wm[c] * (q.r[c] * gscale));
-      else g[base + (long long)c * ds.HW] = -(q.r[c] * gscale);
+      for (int c = 0; c < 3; ++c) {
+        if constexpr (MASKED) g[base + (long long)c * ds.HW] = -(q.wm[c] * (q.r[c] * gscale));
+        else g[base + (long long)c * ds.HW] = -(q.r[c] * gscale);
+      }
+      g[base + 3LL * ds.HW] = 0.f;
+      return;
     }
-    g[base + 3LL * ds.HW] = 0.f;
-    return;
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float pa = ds.kind == 2 ? ph[0] : ph[c];
     const float pb = ds.kind == 0 ? ph[3 + c] : pa;
     const float pinf = ph[6 + c];
-    float wc = q.w;
-    if constexpr (MASKED) wc = q.wm[c];
-    const float dLdI = -2.0f * wc * (q.r[c] * gscale);
+    float dLdI;
+    if constexpr (LIN) {
+      dLdI = v[((long long)b * 3 + c) * ds.HW + p] * gscale;
+    } else {
+      float wc = q.w;
+      if constexpr (MASKED) wc = q.wm[c];
+      dLdI = -2.0f * wc * (q.r[c] * gscale);
+    }
     float grgb = dLdI * 0.5f * q.Ea[c];
     if (ds.gamma_avrg != 0.f) grgb += ds.gamma_avrg * sgn(rd[10 + c]) / (float)ds.HW;
     if (ds.gamma_val != 0.f) {
@@ -494,7 +499,7 @@ __global__ __launch_bounds__(256) void phys_grad_kernel(osm_phys_desc ds, const 
 // ---------------------------------------------------------------- the data term through a linear operator A (blur, super-resolution)
 // y = A I on A's own grid [h,w]: the image is materialised (forward), A applied (osm_linop_apply / osm_psf_apply), the residual taken on
 // the measurement's grid (resid), A^T brings u = d S / d (A I) back (v), and the phi / x0 gradients read v where the kernels above form
-// k2 = -2 w r inline.  Reductions: fixed order through per-workgroup partial slots, no atomics.
+// k2 = -2 w r inline (their LIN instantiations).  Reductions: fixed order through per-workgroup partial slots, no atomics.
 
 // F [B,P,HW]: planes 0..2 the image I_c, plane 3 (P = 4, weight_type 1) the depth weight w
 __global__ __launch_bounds__(256) void phys_forward_kernel(osm_phys_desc ds, const float* __restrict__ x0,
@@ -535,140 +540,50 @@ __global__ __launch_bounds__(256) void phys_resid_kernel(const float* __restrict
   if (threadIdx.x == 0) part_r[(long long)b * nblk + blk] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// phys_reduce_kernel with v = A^T u [B,3,HW] read in the place of k2; slot 0 of `part` is written as 0 (the finalize takes it from part_r)
-__global__ __launch_bounds__(256) void phys_reduce_lin_kernel(osm_phys_desc ds, const float* __restrict__ x0,
-                                                               const float* __restrict__ phi, const float* __restrict__ v,
-                                                               float* __restrict__ part, int nblk) {
-  __shared__ float red[4][NRED];
-  const int b = blockIdx.y, blk = blockIdx.x;
-  float s[NRED];
-#pragma unroll
-  for (int k = 0; k < NRED; ++k) s[k] = 0.f;
-  const int pend = min(ds.HW, (blk + 1) * PPB);
-  const float* ph = phi + b * 9;
-  for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
-    Pix<false> q;
-    eval_pixel<false, false, true>(ds, x0, nullptr, nullptr, phi, b, p, q);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float pinf = ph[6 + c];
-      const float k2 = v[((long long)b * 3 + c) * ds.HW + p];
-      s[1 + c] += k2 * (-q.d * q.J[c] * q.Ea[c]);            // d I / d phi_a
-      s[4 + c] += k2 * (pinf * q.d * q.Eb[c]);               // d I / d phi_b
-      s[7 + c] += k2 * (1.0f - q.Eb[c]);                     // d I / d phi_inf
-      s[10 + c] += q.rgb[c];
-      const float e = fmaxf(fabsf(q.rgb[c]) - 0.7f, 0.0f);
-      s[13] += e * e;
-    }
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NRED; ++k) {
-    const float t = osm::wave_sum(s[k]);
-    if (lane == 0) red[wv][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < NRED) {
-    const int k = threadIdx.x;
-    part[((long long)b * nblk + blk) * NRED + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-  }
-}
-
-// phys_grad_kernel with dL/dI_c = v_c gscale; mse normalises by the measurement's 3 h w, the auxiliary losses by the image's 3 HW
-__global__ __launch_bounds__(256) void phys_grad_lin_kernel(osm_phys_desc ds, const float* __restrict__ x0,
-                                                             const float* __restrict__ phi, const float* __restrict__ v,
-                                                             const float* __restrict__ red, float* __restrict__ g, int hw,
-                                                             int zero_guard) {
-  const int b = blockIdx.y;
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= ds.HW) return;
-  Pix<false> q;
-  eval_pixel<false, false, true>(ds, x0, nullptr, nullptr, phi, b, p, q);
-  const float* rd = red + b * NRED;
-  const float n = 3.0f * (float)ds.HW;
-  float gscale = ds.loss_type == 0 ? 1.0f / sqrtf(rd[0]) : 2.0f / (3.0f * (float)hw);
-  if (zero_guard && ds.loss_type == 0 && rd[0] == 0.f) gscale = 0.f;   // a fully masked image: the auxiliary terms only
-  const float* ph = phi + b * 9;
-  float gD = 0.f;
-  const long long base = (long long)b * 4 * ds.HW + p;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float pa = ds.kind == 2 ? ph[0] : ph[c];
-    const float pb = ds.kind == 0 ? ph[3 + c] : pa;
-    const float pinf = ph[6 + c];
-    const float dLdI = v[((long long)b * 3 + c) * ds.HW + p] * gscale;
-    float grgb = dLdI * 0.5f * q.Ea[c];
-    if (ds.gamma_avrg != 0.f) grgb += ds.gamma_avrg * sgn(rd[10 + c]) / (float)ds.HW;
-    if (ds.gamma_val != 0.f) {
-      const float e = fmaxf(fabsf(q.rgb[c]) - 0.7f, 0.0f);
-      grgb += ds.gamma_val * 2.0f * e * sgn(q.rgb[c]) / n;
-    }
-    g[base + (long long)c * ds.HW] = grgb;
-    gD += dLdI * (-pa * q.J[c] * q.Ea[c] + pinf * pb * q.Eb[c]) * q.dd;
-  }
-  g[base + 3LL * ds.HW] = gD;
-}
-
 // ---------------------------------------------------------------- posterior
+// [B,C,HW] state, [B,Cout,HW] network output: the RGBD model (4, 8), the RGB model family (create_model with pretrain_model !=
+// "osmosis": 3 -> 6, or 3 -> 3 without learn_sigma) and any C -> C model with a fixed variance.  Cout == C: the network has no
+// variance half and the variance processor reads model_out itself (reference gaussian_diffusion.py:349-355, model_var_values =
+// model_output).
 // MK: mean processor (0 epsilon / start_x / previous_x through ONE form, x0 = c0 x - c1 out: the row holds
 //     c0 = d x0 / d x and c1 = -d x0 / d out, which is also what posterior_bwd_kernel and the update kernels read;
 //     1 start_x, x0 = out exactly; 2 previous_x, mean = out exactly).  VK: variance processor (0 learned_range,
 //     1 fixed_small / fixed_large: the row's value, 2 learned: the network's second half).
 // x0_raw != nullptr: clip_denoised (process_xstart, posterior_mean_variance.py:43-50): the unclamped prediction goes to x0_raw
 // (clamp_bwd_kernel masks the guidance gradient with it), x0 = clamp(x0_raw, -1, 1) and the mean is formed from the clamped x0.
-template <int MK, int VK>
+// RAW: the first pass of dynamic_threshold: the prediction to x0_raw, logvar, and the previous_x mean (= out); x0 and the other
+// means wait for the batch-wide quantile (dynthr_apply_kernel).
+template <int MK, int VK, bool RAW>
 __global__ __launch_bounds__(256) void posterior_kernel(const float* __restrict__ mo, const float* __restrict__ x,
-                                                         const float* __restrict__ coef, float* __restrict__ x0_raw,
-                                                         float* __restrict__ x0, float* __restrict__ mean,
-                                                         float* __restrict__ logvar, int B, int HW) {
-  const long long total = (long long)B * 4 * HW;
+                                                           const float* __restrict__ coef, float* __restrict__ x0_raw,
+                                                           float* __restrict__ x0, float* __restrict__ mean,
+                                                           float* __restrict__ logvar, int B, int C, int Cout, int HW) {
+  const long long n = (long long)C * HW, no = (long long)Cout * HW;
+  const long long total = (long long)B * n;
+  const long long voff = Cout == C ? 0 : n;
   const float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], mn = coef[4], mxl = coef[5];
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / (4LL * HW);
-    const long long rem = i - b * 4LL * HW;
-    const float eps = mo[b * 8LL * HW + rem];
+    const long long b = i / n;
+    const long long rem = i - b * n;
+    const float eps = mo[b * no + rem];
     const float xv = x[i];
     float xs = MK == 1 ? eps : c0 * xv - c1 * eps;
-    if (x0_raw) {
+    if (RAW) {
       x0_raw[i] = xs;
-      xs = (xs != xs) ? xs : fminf(fmaxf(xs, -1.0f), 1.0f);          // torch.clamp keeps NaN
-    }
-    x0[i] = xs;
-    mean[i] = MK == 2 ? eps : c2 * xs + c3 * xv;
-    if (VK == 1) {
-      logvar[i] = mn;
+      if (MK == 2) mean[i] = eps;
     } else {
-      const float v = mo[b * 8LL * HW + 4LL * HW + rem];
-      if (VK == 2) {
-        logvar[i] = v;
-      } else {
-        const float frac = (v + 1.0f) / 2.0f;
-        logvar[i] = frac * mxl + (1.0f - frac) * mn;
+      if (x0_raw) {
+        x0_raw[i] = xs;
+        xs = (xs != xs) ? xs : fminf(fmaxf(xs, -1.0f), 1.0f);          // torch.clamp keeps NaN
       }
+      x0[i] = xs;
+      mean[i] = MK == 2 ? eps : c2 * xs + c3 * xv;
     }
-  }
-}
-
-// posterior_kernel's raw pass for dynamic_threshold: the prediction to x0_raw, logvar, and the previous_x mean (= out); x0 and the
-// other means wait for the batch-wide quantile (dynthr_apply_kernel).
-template <int MK, int VK>
-__global__ __launch_bounds__(256) void posterior_raw_kernel(const float* __restrict__ mo, const float* __restrict__ x,
-                                                             const float* __restrict__ coef, float* __restrict__ x0_raw,
-                                                             float* __restrict__ mean, float* __restrict__ logvar, int B, int HW) {
-  const long long total = (long long)B * 4 * HW;
-  const float c0 = coef[0], c1 = coef[1], mn = coef[4], mxl = coef[5];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / (4LL * HW);
-    const long long rem = i - b * 4LL * HW;
-    const float eps = mo[b * 8LL * HW + rem];
-    x0_raw[i] = MK == 1 ? eps : c0 * x[i] - c1 * eps;
-    if (MK == 2) mean[i] = eps;
     if (VK == 1) {
       logvar[i] = mn;
     } else {
-      const float v = mo[b * 8LL * HW + 4LL * HW + rem];
+      const float v = mo[b * no + voff + rem];
       if (VK == 2) {
         logvar[i] = v;
       } else {
@@ -708,39 +623,37 @@ __global__ __launch_bounds__(256) void clamp_bwd_kernel(float* __restrict__ g, c
   }
 }
 
-__global__ __launch_bounds__(256) void posterior_bwd_kernel(const float* __restrict__ g,
-                                                             const float* __restrict__ coef,
-                                                             float* __restrict__ d_out, int B, int HW) {
-  const long long total = (long long)B * 8 * HW;
+// d_out[:, :C] = -c1 g, d_out[:, C:] = 0: exactly B * Cout * HW floats
+__global__ __launch_bounds__(256) void posterior_bwd_kernel(const float* __restrict__ g, const float* __restrict__ coef,
+                                                               float* __restrict__ d_out, int B, int C, int Cout, int HW) {
+  const long long n = (long long)C * HW, no = (long long)Cout * HW;
+  const long long total = (long long)B * no;
   const float c1 = coef[1];
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / (8LL * HW);
-    const long long rem = i - b * 8LL * HW;
-    d_out[i] = rem < 4LL * HW ? -c1 * g[b * 4LL * HW + rem] : 0.f;
+    const long long b = i / no;
+    const long long rem = i - b * no;
+    d_out[i] = rem < n ? -c1 * g[b * n + rem] : 0.f;
   }
 }
 
-__global__ __launch_bounds__(256) void guide_update_kernel(const float* __restrict__ mean,
-                                                            const float* __restrict__ logvar,
-                                                            const float* __restrict__ g,
-                                                            const float* __restrict__ dxu,
-                                                            const float* __restrict__ noise,
-                                                            const float* __restrict__ coef,
-                                                            const float* __restrict__ scale4, float clip,
-                                                            float* __restrict__ x_next,
-                                                            float* __restrict__ grad_out, int B, int HW) {
-  const long long total = (long long)B * 4 * HW;
+__global__ __launch_bounds__(256) void guide_update_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
+                                                              const float* __restrict__ g, const float* __restrict__ dxu,
+                                                              const float* __restrict__ noise, const float* __restrict__ coef,
+                                                              const float* __restrict__ scale, float clip,
+                                                              float* __restrict__ x_next, float* __restrict__ grad_out, int B, int C,
+                                                              int HW) {
+  const long long total = (long long)B * C * HW;
   const float c0 = coef[0], noise_on = coef[6];
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i / HW) % 4);
+    const int c = (int)((i / HW) % C);
     float grad = 0.f;
     if (g) grad = c0 * g[i] + (dxu ? dxu[i] : 0.f);
     if (grad_out) grad_out[i] = grad;
     float gc = grad;
-    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);   // torch.clamp keeps NaN (fminf/fmaxf would drop it)
-    float xt = mean[i] - (g ? scale4[c] * gc : 0.f);
+    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);   // torch.clamp keeps NaN
+    float xt = mean[i] - (g ? scale[c] * gc : 0.f);
     if (noise_on != 0.f && noise) xt += expf(0.5f * logvar[i]) * noise[i];
     x_next[i] = xt;
   }
@@ -826,740 +739,9 @@ __global__ __launch_bounds__(256) void randn_kernel(float* __restrict__ out, int
   }
 }
 
-// guide_update with the noise drawn in the kernel: four consecutive elements of one image per thread (4 HW % 4 == 0)
+// guide_update with the noise drawn in the kernel: counter word 0 = element / 4 within the image's C HW elements (HW % 4 == 0: a
+// quad never straddles two channels) -- osm_randn(_sub) with n = C HW draws the same
 __global__ __launch_bounds__(256) void guide_update_rng_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
-                                                                const float* __restrict__ g, const float* __restrict__ dxu,
-                                                                const float* __restrict__ coef, const float* __restrict__ scale4,
-                                                                float clip, float* __restrict__ x_next, float* __restrict__ grad_out,
-                                                                float* __restrict__ noise_out, int B, int HW, unsigned k0, unsigned k1,
-                                                                const int* __restrict__ step_dev, int step_offset, unsigned sub,
-                                                                int img0, int img_stride) {
-  const long long nq = (long long)HW;             // 4 HW elements per image = HW quads
-  const long long total = (long long)B * nq;
-  const float c0 = coef[0], noise_on = coef[6];
-  const unsigned step = step_word((unsigned)(*step_dev + step_offset), sub);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / nq, q = i - b * nq;
-    const long long e0 = b * 4LL * HW + 4 * q;
-    const int c = (int)((4 * q) / HW);            // HW % 4 == 0: a quad never straddles two channels
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (noise_on != 0.f) normal4(philox4x32_10((unsigned)q, (unsigned)(img0 + (int)b * img_stride), step, OSM_RNG_STREAM_STEP_NOISE, k0, k1), z);
-    const float4 m = *reinterpret_cast<const float4*>(mean + e0);
-    const float4 lv = *reinterpret_cast<const float4*>(logvar + e0);
-    float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), du = gv;
-    if (g) gv = *reinterpret_cast<const float4*>(g + e0);
-    if (g && dxu) du = *reinterpret_cast<const float4*>(dxu + e0);
-    const float mm[4] = {m.x, m.y, m.z, m.w}, ll[4] = {lv.x, lv.y, lv.z, lv.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w},
-                dd[4] = {du.x, du.y, du.z, du.w};
-    float xo[4], go[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float grad = g ? c0 * gg[e] + dd[e] : 0.f;
-      go[e] = grad;
-      float gc = grad;
-      if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);
-      float xt = mm[e] - (g ? scale4[c] * gc : 0.f);
-      if (noise_on != 0.f) xt += expf(0.5f * ll[e]) * z[e];
-      xo[e] = xt;
-    }
-    *reinterpret_cast<float4*>(x_next + e0) = make_float4(xo[0], xo[1], xo[2], xo[3]);
-    if (grad_out) *reinterpret_cast<float4*>(grad_out + e0) = make_float4(go[0], go[1], go[2], go[3]);
-    if (noise_out) *reinterpret_cast<float4*>(noise_out + e0) = make_float4(z[0], z[1], z[2], z[3]);
-  }
-}
-
-// DDIM step + guidance (gaussian_diffusion.py:505-535, condition_methods.py:247-251), in the reference's operation order:
-//   eps = (r0 x - x0) / r1 ; sigma = eta sqrt((1 - abp) / (1 - ab)) sqrt(1 - ab / abp) ;
-//   x_next = x0 sqrt(abp) + sqrt(1 - abp - sigma^2) eps + [t != 0] sigma noise - scale[c] clamp(grad) ; grad = c0 g + dx_unet
-// coef = the posterior row (c0 = d x0 / d x of the mean processor), dcoef = {alpha_bar, alpha_bar_prev, eta, noise_on,
-// r0 = sqrt_recip_ac, r1 = sqrt_recipm1_ac}: predict_eps_from_x_start (:533-536) uses the SAMPLER's tables whatever the mean
-// processor is (for `epsilon` r0 = c0 and r1 = c1).
-// x_next may alias x (each element is read, then written, by one thread).
-__global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restrict__ x0, const float* x, const float* __restrict__ g,
-                                                           const float* __restrict__ dxu, const float* __restrict__ noise,
-                                                           const float* __restrict__ coef, const float* __restrict__ dcoef,
-                                                           const float* __restrict__ scale4, float clip, float* x_next,
-                                                           float* __restrict__ grad_out, int B, int HW) {
-  const long long total = (long long)B * 4 * HW;
-  const float c0 = coef[0];
-  const float ab = dcoef[0], abp = dcoef[1], eta = dcoef[2], noise_on = dcoef[3], r0 = dcoef[4], r1 = dcoef[5];
-  const float sigma = eta * sqrtf((1.0f - abp) / (1.0f - ab)) * sqrtf(1.0f - ab / abp);
-  const float sa = sqrtf(abp), sb = sqrtf(1.0f - abp - sigma * sigma);
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i / HW) % 4);
-    const float xs = x0[i];
-    const float eps = (r0 * x[i] - xs) / r1;
-    float xt = xs * sa + sb * eps;
-    if (noise_on != 0.f && noise) xt += sigma * noise[i];
-    float grad = 0.f;
-    if (g) grad = c0 * g[i] + (dxu ? dxu[i] : 0.f);
-    if (grad_out) grad_out[i] = grad;
-    float gc = grad;
-    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);
-    x_next[i] = xt - (g ? scale4[c] * gc : 0.f);
-  }
-}
-
-__global__ void fetch_coefs_kernel(const float* __restrict__ table, int* __restrict__ step, int delta,
-                                   float* __restrict__ coef_out, float* __restrict__ t_out, int B, int n_rows) {
-  const int s = min(max(*step, 0), n_rows - 1);   // a counter that ran off the table re-reads its last row
-  if (threadIdx.x < 8) coef_out[threadIdx.x] = table[s * 8 + threadIdx.x];
-  if (threadIdx.x < B) t_out[threadIdx.x] = table[s * 8 + 7];
-  __syncthreads();
-  if (threadIdx.x == 0) *step = s + delta;
-}
-
-inline int grid_for(long long total) {
-  long long b = (total + 255) / 256;
-  if (b > 2048) b = 2048;
-  return (int)(b < 1 ? 1 : b);
-}
-
-int check_desc(const osm_phys_desc* d, const char* who) {
-  OSM_REQUIRE(d, "%s: null descriptor", who);
-  OSM_REQUIRE(d->kind >= 0 && d->kind <= 3, "%s: unknown operator kind %d", who, d->kind);
-  OSM_REQUIRE(d->kind != 3 || (d->loss_type == 0 && d->weight_type == 0 && d->gamma_avrg == 0.f && d->gamma_val == 0.f),
-              "%s: the identity operator (kind 3) is the plain norm loss: no weight, no auxiliary losses", who);
-  OSM_REQUIRE(d->depth_type >= 0 && d->depth_type <= 2, "%s: unknown depth_type %d", who, d->depth_type);
-  OSM_REQUIRE(d->loss_type == 0 || d->loss_type == 1, "%s: unknown loss_type %d", who, d->loss_type);
-  OSM_REQUIRE(d->B > 0 && d->HW > 0, "%s: bad shape", who);
-  return OSM_OK;
-}
-
-}  // namespace
-
-extern "C" int osm_phys_nblk(int HW) { return (HW + PPB - 1) / PPB; }
-
-namespace {
-int phys_reduce_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
-                       float* part, void* stream) {
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && part, "%s: null pointer", who);
-  const int nblk = osm_phys_nblk(d->HW);
-  if (mask) {
-    hipLaunchKernelGGL(phys_reduce_kernel<true>, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, y, mask, phi, part,
-                       nblk);
-  } else {
-    hipLaunchKernelGGL(phys_reduce_kernel<false>, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, y, nullptr, phi,
-                       part, nblk);
-  }
-  return osm::check_launch("phys_reduce_kernel");
-}
-
-// The offsets of a group descriptor, validated and copied by value (they travel in the kernel's arguments).
-struct GroupArgs { GroupOff go; int G, reduce; };
-
-int check_group(const osm_phys_desc* d, const osm_group_desc* grp, GroupArgs* ga, const char* who) {
-  OSM_REQUIRE(grp, "%s: null group descriptor", who);
-  OSM_REQUIRE(grp->G >= 1 && grp->G <= OSM_MAX_GROUPS, "%s: G = %d groups, must be 1 .. %d", who, grp->G, OSM_MAX_GROUPS);
-  OSM_REQUIRE(grp->off, "%s: null pointer (group offsets)", who);
-  OSM_REQUIRE(grp->reduce == 0 || grp->reduce == 1, "%s: reduce must be 0 (sum) or 1 (mean), got %d", who, grp->reduce);
-  OSM_REQUIRE(grp->off[0] == 0, "%s: off[0] must be 0, got %d", who, grp->off[0]);
-  for (int j = 0; j < grp->G; ++j)
-    OSM_REQUIRE(grp->off[j + 1] > grp->off[j], "%s: group offsets must be strictly increasing (off[%d] = %d, off[%d] = %d)", who, j,
-                grp->off[j], j + 1, grp->off[j + 1]);
-  OSM_REQUIRE(grp->off[grp->G] == d->B, "%s: off[G] = %d must be the batch B = %d", who, grp->off[grp->G], d->B);
-  for (int j = 0; j <= grp->G; ++j) ga->go.off[j] = grp->off[j];
-  ga->G = grp->G;
-  ga->reduce = grp->reduce;
-  return OSM_OK;
-}
-
-// ga == nullptr: the per-image finalize; else one phi step per group
-int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
-                         float* loss_out, float* opt_state, int zero_guard, void* stream, const GroupArgs* ga = nullptr) {
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(part && red && phi, "%s: null pointer", who);
-  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
-  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
-  OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
-  if (ga) {
-    hipLaunchKernelGGL(phys_finalize_group_kernel<false>, dim3(ga->G), dim3(64 * GWAVES), 0, (hipStream_t)stream, *d, part, red, phi,
-                       do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard, ga->reduce, ga->go, FinLin<false>{});
-    return osm::check_launch("phys_finalize_group_kernel");
-  }
-  hipLaunchKernelGGL(phys_finalize_kernel<false>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi,
-                     do_update, loss_out, opt_state, osm_phys_nblk(d->HW), zero_guard, FinLin<false>{});
-  return osm::check_launch("phys_finalize_kernel");
-}
-
-int phys_grad_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
-                     const float* red, float* g, void* stream) {
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && red && g, "%s: null pointer", who);
-  const dim3 grid((d->HW + 255) / 256, d->B);
-  if (mask) {
-    hipLaunchKernelGGL(phys_grad_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, *d, x0, y, mask, phi, red, g);
-  } else {
-    hipLaunchKernelGGL(phys_grad_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, *d, x0, y, nullptr, phi, red, g);
-  }
-  return osm::check_launch("phys_grad_kernel");
-}
-
-// n_inner x { reduce; finalize (+ phi step) } + the x0-gradient: the launches of osm_phys_optimize, with or without a mask
-int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi,
-                         float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
-                         void* stream, const GroupArgs* ga = nullptr) {
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && y && phi && part && red && loss_out && g, "%s: null pointer", who);
-  OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
-  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
-  if (ga) {   // (before the first launch: a failure of a later finalize would leave phi half-stepped)
-    OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
-    OSM_REQUIRE(d->optimizer == 0 || freeze_phi || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
-    OSM_REQUIRE(!(d->kind == 3 && !freeze_phi), "%s: the identity operator (kind 3) has no parameters to step", who);
-  }
-  const int zg = mask != nullptr;
-  for (int it = 0; it < n_inner; ++it) {
-    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream))) return rc;
-    if (it == n_inner - 1) {
-      if ((rc = phys_finalize_launch(who, d, part, red, phi, 0, loss_out, nullptr, zg, stream, ga))) return rc;
-      if ((rc = phys_grad_launch(who, d, x0, y, mask, phi, red, g, stream))) return rc;
-      if (!freeze_phi && (rc = phys_finalize_launch(who, d, part, red, phi, 1, nullptr, opt_state, zg, stream, ga))) return rc;
-    } else if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream, ga))) {
-      return rc;
-    }
-  }
-  return OSM_OK;
-}
-}  // namespace
-
-extern "C" int osm_phys_reduce(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
-                               float* part, void* stream) {
-  return phys_reduce_launch("osm_phys_reduce", d, x0, y, nullptr, phi, part, stream);
-}
-
-// The masked entry points (`_m`): mask [B,3,HW] in [0, 1], laid out like y; mask == NULL is the plain entry point, launch for launch.
-extern "C" int osm_phys_reduce_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
-                                 float* part, void* stream) {
-  return phys_reduce_launch("osm_phys_reduce_m", d, x0, y, mask, phi, part, stream);
-}
-
-extern "C" int osm_phys_finalize_m(const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
-                                   float* loss_out, float* opt_state, int masked, void* stream) {
-  return phys_finalize_launch("osm_phys_finalize_m", d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream);
-}
-
-extern "C" int osm_phys_grad_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
-                               const float* red, float* g, void* stream) {
-  return phys_grad_launch("osm_phys_grad_m", d, x0, y, mask, phi, red, g, stream);
-}
-
-extern "C" int osm_phys_optimize_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi, float* part,
-                                   float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
-                                   void* stream) {
-  return phys_optimize_launch("osm_phys_optimize_m", d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
-                              stream);
-}
-
-extern "C" int osm_phys_finalize(const osm_phys_desc* d, const float* part, float* red, float* phi,
-                                 int do_update, float* loss_out, float* opt_state, void* stream) {
-  return phys_finalize_launch("osm_phys_finalize", d, part, red, phi, do_update, loss_out, opt_state, 0, stream);
-}
-
-extern "C" int osm_phys_grad(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
-                             const float* red, float* g, void* stream) {
-  return phys_grad_launch("osm_phys_grad", d, x0, y, nullptr, phi, red, g, stream);
-}
-
-// The inner phi optimisation + dL/dx0 of one guided step, enqueued by ONE call (measurements.py:266-303, condition_methods.py:109-144):
-//   n_inner x { reduce; finalize (+ phi step) }, with the loss and the x0-gradient taken at the phi of the LAST iteration, which is
-//   stepped afterwards (unless freeze_phi: then n_inner = 1 and phi stays).  The same launches as the three entry points above in the
-//   same order -- from C the 2 n_inner + 2 launches cost the host ~2 us each instead of a Python call each (measured: the GPU idled
-//   0.24 ms per step between them).
-extern "C" int osm_phys_optimize(const osm_phys_desc* d, const float* x0, const float* y, float* phi, float* part, float* red,
-                                 float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
-  return phys_optimize_launch("osm_phys_optimize", d, x0, y, nullptr, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
-                              stream);
-}
-
-// ---------------------------------------------------------------- the composed data term (include/osmosis_physlin.h)
-namespace {
-int check_lin_desc(const osm_phys_desc* d, const char* who) {
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(d->kind != 3, "%s: the identity operator (kind 3) has no image-formation model to compose with", who);
-  return OSM_OK;
-}
-
-int check_lin(const osm_phys_desc* d, const osm_lin_desc* l, const char* who) {
-  OSM_REQUIRE(l, "%s: null operator descriptor", who);
-  OSM_REQUIRE(l->family == 0 || l->family == 1, "%s: unknown operator family %d (0 separable, 1 psf)", who, l->family);
-  OSM_REQUIRE(l->H >= 1 && l->W >= 1 && l->h >= 1 && l->w >= 1, "%s: bad operator grids %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
-  OSM_REQUIRE((long long)l->H * l->W == (long long)d->HW, "%s: the operator's image grid %d x %d does not have the descriptor's HW = %d pixels",
-              who, l->H, l->W, d->HW);
-  OSM_REQUIRE((long long)l->h * l->w < (1LL << 29), "%s: measurement grid %d x %d too large", who, l->h, l->w);
-  if (l->family == 0) {
-    OSM_REQUIRE(l->start_h && l->wt_h && l->start_w && l->wt_w && l->tstart_h && l->twt_h && l->tstart_w && l->twt_w,
-                "%s: a separable operator needs its forward and transposed band tables", who);
-    OSM_REQUIRE(l->Kh >= 1 && l->Kw >= 1 && l->tKh >= 1 && l->tKw >= 1, "%s: bad band widths Kh %d, Kw %d, tKh %d, tKw %d", who, l->Kh, l->Kw,
-                l->tKh, l->tKw);
-  } else {
-    OSM_REQUIRE(l->h == l->H && l->w == l->W, "%s: a psf operator keeps the image's grid, got %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
-    OSM_REQUIRE(l->dy && l->dx && l->tap_w, "%s: a psf operator needs its tap list", who);
-    OSM_REQUIRE(l->T >= 1, "%s: bad tap count T %d", who, l->T);
-    OSM_REQUIRE(l->Ry >= 0 && l->Rx >= 0 && l->Ry < l->H && l->Rx < l->W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d",
-                who, l->Ry, l->H, l->Rx, l->W);
-  }
-  return OSM_OK;
-}
-
-inline int lin_planes(const osm_phys_desc* d) { return d->weight_type == 1 ? 4 : 3; }
-
-// out [B,P,h w] = A x [B,P,H W] (adjoint = 0) or out [B,P,H W] = A^T x [B,P,h w] (adjoint = 1), P planes, densely packed images
-int lin_apply(const osm_lin_desc* l, const float* x, float* out, int B, int P, int adjoint, void* stream) {
-  const long long HW = (long long)l->H * l->W, hw = (long long)l->h * l->w;
-  if (l->family == 1) return osm_psf_apply(x, out, l->dy, l->dx, l->tap_w, l->T, l->Ry, l->Rx, B, P, P * HW, P * HW, l->H, l->W, adjoint, 0, stream);
-  if (adjoint)
-    return osm_linop_apply(x, out, l->tstart_h, l->twt_h, l->tstart_w, l->twt_w, B, P, P * hw, P * HW, l->h, l->w, l->H, l->W, l->tKh,
-                           l->tKw, 0, stream);
-  return osm_linop_apply(x, out, l->start_h, l->wt_h, l->start_w, l->wt_w, B, P, P * HW, P * hw, l->H, l->W, l->h, l->w, l->Kh, l->Kw, 0,
-                         stream);
-}
-}  // namespace
-
-extern "C" int osm_phys_forward(const osm_phys_desc* d, const float* x0, const float* phi, float* F, void* stream) {
-  const char* who = "osm_phys_forward";
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && phi && F, "%s: null pointer", who);
-  hipLaunchKernelGGL(phys_forward_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, F,
-                     lin_planes(d));
-  return osm::check_launch("phys_forward_kernel");
-}
-
-extern "C" int osm_phys_resid(const osm_phys_desc* d, int hw, const float* AF, const float* y, const float* mask, float* u,
-                              float* part_r, void* stream) {
-  const char* who = "osm_phys_resid";
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
-  OSM_REQUIRE(AF && y && u && part_r, "%s: null pointer", who);
-  const int nblk = osm_phys_nblk(hw);
-  hipLaunchKernelGGL(phys_resid_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, AF, y, mask, u, part_r, lin_planes(d), hw,
-                     nblk);
-  return osm::check_launch("phys_resid_kernel");
-}
-
-extern "C" int osm_phys_reduce_lin(const osm_phys_desc* d, const float* x0, const float* phi, const float* v, float* part,
-                                   void* stream) {
-  const char* who = "osm_phys_reduce_lin";
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(x0 && phi && v && part, "%s: null pointer", who);
-  const int nblk = osm_phys_nblk(d->HW);
-  hipLaunchKernelGGL(phys_reduce_lin_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, v, part, nblk);
-  return osm::check_launch("phys_reduce_lin_kernel");
-}
-
-namespace {
-int phys_finalize_lin_launch(const char* who, const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red,
-                             float* phi, int do_update, float* loss_out, float* opt_state, int masked, void* stream,
-                             const GroupArgs* ga = nullptr) {
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
-  OSM_REQUIRE(part && part_r && red && phi, "%s: null pointer", who);
-  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
-  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
-  if (ga) {
-    hipLaunchKernelGGL(phys_finalize_group_kernel<true>, dim3(ga->G), dim3(64 * GWAVES), 0, (hipStream_t)stream, *d, part, red, phi,
-                       do_update, loss_out, opt_state, osm_phys_nblk(d->HW), masked != 0, ga->reduce, ga->go,
-                       FinLin<true>{part_r, osm_phys_nblk(hw), hw});
-    return osm::check_launch("phys_finalize_group_kernel<lin>");
-  }
-  hipLaunchKernelGGL(phys_finalize_kernel<true>, dim3(d->B), dim3(64), 0, (hipStream_t)stream, *d, part, red, phi, do_update,
-                     loss_out, opt_state, osm_phys_nblk(d->HW), masked != 0, FinLin<true>{part_r, osm_phys_nblk(hw), hw});
-  return osm::check_launch("phys_finalize_kernel<lin>");
-}
-}  // namespace
-
-extern "C" int osm_phys_finalize_lin(const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red, float* phi,
-                                     int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
-  return phys_finalize_lin_launch("osm_phys_finalize_lin", d, hw, part, part_r, red, phi, do_update, loss_out, opt_state, masked, stream);
-}
-
-extern "C" int osm_phys_grad_lin(const osm_phys_desc* d, int hw, const float* x0, const float* phi, const float* v, const float* red,
-                                 float* g, int masked, void* stream) {
-  const char* who = "osm_phys_grad_lin";
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
-  OSM_REQUIRE(x0 && phi && v && red && g, "%s: null pointer", who);
-  hipLaunchKernelGGL(phys_grad_lin_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, v, red, g,
-                     hw, masked != 0);
-  return osm::check_launch("phys_grad_lin_kernel");
-}
-
-namespace {
-// ga == nullptr: osm_phys_optimize_lin; else the grouped finalize in the place of the plain one
-int phys_optimize_lin_launch(const char* who, const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y,
-                             const float* mask, float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part,
-                             float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream,
-                             const GroupArgs* ga) {
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  if ((rc = check_lin(d, lin, who))) return rc;
-  OSM_REQUIRE(x0 && y && phi && F && AF && u && v && part_r && part && red && loss_out && g, "%s: null pointer", who);
-  OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
-  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
-  // (before the first launch: a failure of a later entry point would leave the workspaces half-written)
-  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
-  OSM_REQUIRE(d->optimizer == 0 || freeze_phi || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
-  OSM_REQUIRE((long long)d->B * 4 <= 65535, "%s: batch %d is too large for one launch of the operator", who, d->B);
-  const int zg = mask != nullptr, hw = lin->h * lin->w, P = lin_planes(d);
-  for (int it = 0; it < n_inner; ++it) {
-    if ((rc = osm_phys_forward(d, x0, phi, F, stream))) return rc;
-    if ((rc = lin_apply(lin, F, AF, d->B, P, 0, stream))) return rc;
-    if ((rc = osm_phys_resid(d, hw, AF, y, mask, u, part_r, stream))) return rc;
-    if ((rc = lin_apply(lin, u, v, d->B, 3, 1, stream))) return rc;
-    if ((rc = osm_phys_reduce_lin(d, x0, phi, v, part, stream))) return rc;
-    if (it == n_inner - 1) {
-      if ((rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 0, loss_out, nullptr, zg, stream, ga)))
-        return rc;
-      if ((rc = osm_phys_grad_lin(d, hw, x0, phi, v, red, g, zg, stream))) return rc;
-      if (!freeze_phi &&
-          (rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 1, nullptr, opt_state, zg, stream, ga)))
-        return rc;
-    } else if ((rc = phys_finalize_lin_launch(ga ? who : "osm_phys_finalize_lin", d, hw, part, part_r, red, phi, 1, loss_out, opt_state, zg,
-                                              stream, ga))) {
-      return rc;
-    }
-  }
-  return OSM_OK;
-}
-}  // namespace
-
-extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y, const float* mask,
-                                     float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part, float* red,
-                                     float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
-  return phys_optimize_lin_launch("osm_phys_optimize_lin", d, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, n_inner,
-                                  freeze_phi, opt_state, stream, nullptr);
-}
-
-// ---------------------------------------------------------------- shared water parameters (include/osmosis_physgroup.h)
-extern "C" int osm_phys_finalize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* part, float* red, float* phi,
-                                   int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
-  const char* who = "osm_phys_finalize_g";
-  GroupArgs ga;
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  if ((rc = check_group(d, grp, &ga, who))) return rc;
-  return phys_finalize_launch(who, d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream, &ga);
-}
-
-extern "C" int osm_phys_finalize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, int hw, const float* part, const float* part_r,
-                                       float* red, float* phi, int do_update, float* loss_out, float* opt_state, int masked,
-                                       void* stream) {
-  const char* who = "osm_phys_finalize_lin_g";
-  GroupArgs ga;
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  if ((rc = check_group(d, grp, &ga, who))) return rc;
-  return phys_finalize_lin_launch(who, d, hw, part, part_r, red, phi, do_update, loss_out, opt_state, masked, stream, &ga);
-}
-
-extern "C" int osm_phys_optimize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* x0, const float* y, const float* mask,
-                                   float* phi, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
-                                   float* opt_state, void* stream) {
-  const char* who = "osm_phys_optimize_g";
-  GroupArgs ga;
-  int rc = check_desc(d, who);
-  if (rc) return rc;
-  if ((rc = check_group(d, grp, &ga, who))) return rc;
-  return phys_optimize_launch(who, d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state, stream, &ga);
-}
-
-extern "C" int osm_phys_optimize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, const osm_lin_desc* lin, const float* x0,
-                                       const float* y, const float* mask, float* phi, float* F, float* AF, float* u, float* v,
-                                       float* part_r, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
-                                       float* opt_state, void* stream) {
-  const char* who = "osm_phys_optimize_lin_g";
-  GroupArgs ga;
-  int rc = check_lin_desc(d, who);
-  if (rc) return rc;
-  if ((rc = check_group(d, grp, &ga, who))) return rc;
-  return phys_optimize_lin_launch(who, d, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
-                                  stream, &ga);
-}
-
-extern "C" int osm_posterior_typed(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
-                                   int clip_denoised, float* x0_raw, float* x0, float* mean, float* logvar, int B, int HW,
-                                   void* stream) {
-  OSM_REQUIRE(model_out && x && coef && x0 && mean && logvar && B > 0 && HW > 0, "osm_posterior_typed: bad argument");
-  OSM_REQUIRE(!clip_denoised || x0_raw, "osm_posterior_typed: clip_denoised needs x0_raw (the unclamped prediction, read by osm_clamp_bwd)");
-  if (!clip_denoised) x0_raw = nullptr;
-  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "osm_posterior_typed: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)");
-  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "osm_posterior_typed: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)");
-  const dim3 grid(grid_for((long long)B * 4 * HW)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define OSM_POST(MK, VK) \
-  hipLaunchKernelGGL((posterior_kernel<MK, VK>), grid, block, 0, st, model_out, x, coef, x0_raw, x0, mean, logvar, B, HW)
-  switch (mean_kind * 3 + var_kind) {
-    case 0: OSM_POST(0, 0); break;
-    case 1: OSM_POST(0, 1); break;
-    case 2: OSM_POST(0, 2); break;
-    case 3: OSM_POST(1, 0); break;
-    case 4: OSM_POST(1, 1); break;
-    case 5: OSM_POST(1, 2); break;
-    case 6: OSM_POST(2, 0); break;
-    case 7: OSM_POST(2, 1); break;
-    default: OSM_POST(2, 2); break;
-  }
-#undef OSM_POST
-  return osm::check_launch("posterior_kernel");
-}
-
-extern "C" int osm_posterior_dynthr(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
-                                    float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int HW,
-                                    void* stream) {
-  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && HW > 0,
-              "osm_posterior_dynthr: bad argument");
-  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "osm_posterior_dynthr: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)");
-  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "osm_posterior_dynthr: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)");
-  const long long total = (long long)B * 4 * HW;
-  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr: quantile() input tensor is too large (%lld elements > 2^24)", total);
-  const dim3 grid(grid_for(total)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define OSM_POST(MK, VK) \
-  hipLaunchKernelGGL((posterior_raw_kernel<MK, VK>), grid, block, 0, st, model_out, x, coef, x0_raw, mean, logvar, B, HW)
-  switch (mean_kind * 3 + var_kind) {
-    case 0: OSM_POST(0, 0); break;
-    case 1: OSM_POST(0, 1); break;
-    case 2: OSM_POST(0, 2); break;
-    case 3: OSM_POST(1, 0); break;
-    case 4: OSM_POST(1, 1); break;
-    case 5: OSM_POST(1, 2); break;
-    case 6: OSM_POST(2, 0); break;
-    case 7: OSM_POST(2, 1); break;
-    default: OSM_POST(2, 2); break;
-  }
-#undef OSM_POST
-  int rc = osm::check_launch("posterior_raw_kernel");
-  if (rc) return rc;
-  if ((rc = osm_quantile_abs(x0_raw, total, s, q, idx, ws, stream))) return rc;
-  if (mean_kind == 2) {
-    hipLaunchKernelGGL(dynthr_apply_kernel<2>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
-  } else {
-    hipLaunchKernelGGL(dynthr_apply_kernel<0>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
-  }
-  return osm::check_launch("dynthr_apply_kernel");
-}
-
-extern "C" int osm_posterior(const float* model_out, const float* x, const float* coef, float* x0, float* mean,
-                             float* logvar, int B, int HW, void* stream) {
-  return osm_posterior_typed(model_out, x, coef, 0, 0, 0, nullptr, x0, mean, logvar, B, HW, stream);
-}
-
-extern "C" int osm_clamp_bwd(float* g, const float* x_raw, float lo, float hi, long long n, void* stream) {
-  OSM_REQUIRE(g && x_raw && n > 0 && lo <= hi, "osm_clamp_bwd: bad argument");
-  hipLaunchKernelGGL(clamp_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, x_raw, lo, hi, n);
-  return osm::check_launch("clamp_bwd_kernel");
-}
-
-extern "C" int osm_posterior_bwd(const float* g, const float* coef, float* d_out, int B, int HW, void* stream) {
-  OSM_REQUIRE(g && coef && d_out && B > 0 && HW > 0, "osm_posterior_bwd: bad argument");
-  hipLaunchKernelGGL(posterior_bwd_kernel, dim3(grid_for((long long)B * 8 * HW)), dim3(256), 0,
-                     (hipStream_t)stream, g, coef, d_out, B, HW);
-  return osm::check_launch("posterior_bwd_kernel");
-}
-
-extern "C" int osm_guide_update(const float* mean, const float* logvar, const float* g, const float* dx_unet,
-                                const float* noise, const float* coef, const float* scale4, float clip,
-                                float* x_next, float* grad_out, int B, int HW, void* stream) {
-  OSM_REQUIRE(mean && logvar && coef && x_next && B > 0 && HW > 0, "osm_guide_update: bad argument");
-  OSM_REQUIRE(!g || scale4, "osm_guide_update: guidance needs the per-channel scale");
-  hipLaunchKernelGGL(guide_update_kernel, dim3(grid_for((long long)B * 4 * HW)), dim3(256), 0,
-                     (hipStream_t)stream, mean, logvar, g, dx_unet, noise, coef, scale4, clip, x_next, grad_out, B,
-                     HW);
-  return osm::check_launch("guide_update_kernel");
-}
-
-
-namespace {
-int guide_update_rng_launch(const char* name, const float* mean, const float* logvar, const float* g, const float* dx_unet,
-                            const float* coef, const float* scale4, float clip, float* x_next, float* grad_out, float* noise_out,
-                            int B, int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
-                            int img_stride, void* stream) {
-  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && HW > 0, "%s: bad argument", name);
-  OSM_REQUIRE(!g || scale4, "%s: guidance needs the per-channel scale", name);
-  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
-  OSM_REQUIRE(HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements)", name);
-  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
-                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
-                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "%s: tensors must be 16-byte aligned", name);
-  hipLaunchKernelGGL(guide_update_rng_kernel, dim3(grid_for((long long)B * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
-                     g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out, B, HW, (unsigned)(seed & 0xffffffffull),
-                     (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
-  return osm::check_launch("guide_update_rng_kernel");
-}
-
-int randn_launch(const char* name, float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const,
-                 int sub, int img0, int img_stride, void* stream) {
-  OSM_REQUIRE(out && B > 0 && n > 0, "%s: bad argument", name);
-  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
-  OSM_REQUIRE(sub == 0 || step_dev || (step_const >= 0 && step_const < 65536),
-              "%s: with sub != 0 the step must be in [0, 65536), got %d", name, step_const);
-  OSM_REQUIRE((reinterpret_cast<size_t>(out) & 15) == 0, "%s: out must be 16-byte aligned", name);
-  OSM_REQUIRE(n % 4 == 0 || B == 1, "%s: a batch needs n %% 4 == 0 (every image's row starts 16-byte aligned)", name);
-  hipLaunchKernelGGL(randn_kernel, dim3(grid_for((long long)B * ((n + 3) / 4))), dim3(256), 0, (hipStream_t)stream, out, B, n,
-                     (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step_dev, step_const, (unsigned)sub, img0, img_stride);
-  return osm::check_launch("randn_kernel");
-}
-}  // namespace
-
-extern "C" int osm_guide_update_rng(const float* mean, const float* logvar, const float* g, const float* dx_unet,
-                                    const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
-                                    float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
-                                    int img0, int img_stride, void* stream) {
-  return guide_update_rng_launch("osm_guide_update_rng", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out,
-                                 B, HW, seed, step, step_offset, 0, img0, img_stride, stream);
-}
-
-extern "C" int osm_guide_update_rng_sub(const float* mean, const float* logvar, const float* g, const float* dx_unet,
-                                        const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
-                                        float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
-                                        int sub, int img0, int img_stride, void* stream) {
-  return guide_update_rng_launch("osm_guide_update_rng_sub", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out,
-                                 noise_out, B, HW, seed, step, step_offset, sub, img0, img_stride, stream);
-}
-
-extern "C" int osm_randn(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int img0,
-                         int img_stride, void* stream) {
-  return randn_launch("osm_randn", out, B, n, seed, step_dev, step_const, 0, img0, img_stride, stream);
-}
-
-extern "C" int osm_randn_sub(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int sub,
-                             int img0, int img_stride, void* stream) {
-  return randn_launch("osm_randn_sub", out, B, n, seed, step_dev, step_const, sub, img0, img_stride, stream);
-}
-
-extern "C" int osm_philox_raw(unsigned* out, long long n4, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                              void* stream) {
-  OSM_REQUIRE(out && n4 > 0, "osm_philox_raw: bad argument");
-  hipLaunchKernelGGL(philox_raw_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, out, n4, c1, c2, c3, k0, k1);
-  return osm::check_launch("philox_raw_kernel");
-}
-
-extern "C" int osm_ddim_update(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
-                               const float* coef, const float* dcoef, const float* scale4, float clip, float* x_next,
-                               float* grad_out, int B, int HW, void* stream) {
-  OSM_REQUIRE(x0 && x && coef && dcoef && x_next && B > 0 && HW > 0, "osm_ddim_update: bad argument");
-  OSM_REQUIRE(!g || scale4, "osm_ddim_update: guidance needs the per-channel scale");
-  hipLaunchKernelGGL(ddim_update_kernel, dim3(grid_for((long long)B * 4 * HW)), dim3(256), 0, (hipStream_t)stream, x0, x, g,
-                     dx_unet, noise, coef, dcoef, scale4, clip, x_next, grad_out, B, HW);
-  return osm::check_launch("ddim_update_kernel");
-}
-
-extern "C" int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out,
-                               int B, void* stream) {
-  OSM_REQUIRE(table && step && coef_out && t_out && B > 0 && B <= 256 && n_rows > 0, "osm_fetch_coefs: bad argument");
-  hipLaunchKernelGGL(fetch_coefs_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, table, step, delta, coef_out,
-                     t_out, B, n_rows);
-  return osm::check_launch("fetch_coefs_kernel");
-}
-
-extern "C" int osm_ancestral_step(const float* model_out, const float* x, const float* z, const float* coef,
-                                  float* x_next, float* x0, int B, int C, int Cout, int HW, void* stream) {
-  OSM_REQUIRE(model_out && x && coef && x_next && B > 0 && C > 0 && Cout >= C && HW > 0, "osm_ancestral_step: bad argument");
-  hipLaunchKernelGGL(ancestral_step_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream,
-                     model_out, x, z, coef, x_next, x0, B, C, Cout, HW);
-  return osm::check_launch("ancestral_step_kernel");
-}
-
-
-// ================================================================ channel-generic step ([B,C,HW] state, [B,Cout,HW] network output)
-// The RGB model family (create_model with pretrain_model != "osmosis": 3 -> 6, or 3 -> 3 without learn_sigma) and any C -> C model
-// with a fixed variance.  Same arithmetic, element by element and in the same operation order, as the [B,4,HW] / [B,8,HW] kernels
-// above (which keep their compile-time shapes); C and Cout are launch arguments.  Cout == C: the network has no variance half and
-// the variance processor reads model_out itself (reference gaussian_diffusion.py:349-355, model_var_values = model_output).
-namespace {
-
-// RAW: posterior_raw_kernel's pass for dynamic_threshold (x0_raw, logvar, the previous_x mean); else posterior_kernel's.
-template <int MK, int VK, bool RAW>
-__global__ __launch_bounds__(256) void posterior_c_kernel(const float* __restrict__ mo, const float* __restrict__ x,
-                                                           const float* __restrict__ coef, float* __restrict__ x0_raw,
-                                                           float* __restrict__ x0, float* __restrict__ mean,
-                                                           float* __restrict__ logvar, int B, int C, int Cout, int HW) {
-  const long long n = (long long)C * HW, no = (long long)Cout * HW;
-  const long long total = (long long)B * n;
-  const long long voff = Cout == C ? 0 : n;
-  const float c0 = coef[0], c1 = coef[1], c2 = coef[2], c3 = coef[3], mn = coef[4], mxl = coef[5];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / n;
-    const long long rem = i - b * n;
-    const float eps = mo[b * no + rem];
-    const float xv = x[i];
-    float xs = MK == 1 ? eps : c0 * xv - c1 * eps;
-    if (RAW) {
-      x0_raw[i] = xs;
-      if (MK == 2) mean[i] = eps;
-    } else {
-      if (x0_raw) {
-        x0_raw[i] = xs;
-        xs = (xs != xs) ? xs : fminf(fmaxf(xs, -1.0f), 1.0f);          // torch.clamp keeps NaN
-      }
-      x0[i] = xs;
-      mean[i] = MK == 2 ? eps : c2 * xs + c3 * xv;
-    }
-    if (VK == 1) {
-      logvar[i] = mn;
-    } else {
-      const float v = mo[b * no + voff + rem];
-      if (VK == 2) {
-        logvar[i] = v;
-      } else {
-        const float frac = (v + 1.0f) / 2.0f;
-        logvar[i] = frac * mxl + (1.0f - frac) * mn;
-      }
-    }
-  }
-}
-
-// d_out[:, :C] = -c1 g, d_out[:, C:] = 0: exactly B * Cout * HW floats
-__global__ __launch_bounds__(256) void posterior_bwd_c_kernel(const float* __restrict__ g, const float* __restrict__ coef,
-                                                               float* __restrict__ d_out, int B, int C, int Cout, int HW) {
-  const long long n = (long long)C * HW, no = (long long)Cout * HW;
-  const long long total = (long long)B * no;
-  const float c1 = coef[1];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const long long b = i / no;
-    const long long rem = i - b * no;
-    d_out[i] = rem < n ? -c1 * g[b * n + rem] : 0.f;
-  }
-}
-
-__global__ __launch_bounds__(256) void guide_update_c_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
-                                                              const float* __restrict__ g, const float* __restrict__ dxu,
-                                                              const float* __restrict__ noise, const float* __restrict__ coef,
-                                                              const float* __restrict__ scale, float clip,
-                                                              float* __restrict__ x_next, float* __restrict__ grad_out, int B, int C,
-                                                              int HW) {
-  const long long total = (long long)B * C * HW;
-  const float c0 = coef[0], noise_on = coef[6];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)((i / HW) % C);
-    float grad = 0.f;
-    if (g) grad = c0 * g[i] + (dxu ? dxu[i] : 0.f);
-    if (grad_out) grad_out[i] = grad;
-    float gc = grad;
-    if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);   // torch.clamp keeps NaN
-    float xt = mean[i] - (g ? scale[c] * gc : 0.f);
-    if (noise_on != 0.f && noise) xt += expf(0.5f * logvar[i]) * noise[i];
-    x_next[i] = xt;
-  }
-}
-
-// guide_update_c with the noise drawn in the kernel: counter word 0 = element / 4 within the image's C HW elements (HW % 4 == 0: a
-// quad never straddles two channels), the other words as guide_update_rng_kernel's -- osm_randn(_sub) with n = C HW draws the same
-__global__ __launch_bounds__(256) void guide_update_rng_c_kernel(const float* __restrict__ mean, const float* __restrict__ logvar,
                                                                   const float* __restrict__ g, const float* __restrict__ dxu,
                                                                   const float* __restrict__ coef, const float* __restrict__ scale,
                                                                   float clip, float* __restrict__ x_next, float* __restrict__ grad_out,
@@ -1600,8 +782,14 @@ __global__ __launch_bounds__(256) void guide_update_rng_c_kernel(const float* __
   }
 }
 
+// DDIM step + guidance (gaussian_diffusion.py:505-535, condition_methods.py:247-251), in the reference's operation order:
+//   eps = (r0 x - x0) / r1 ; sigma = eta sqrt((1 - abp) / (1 - ab)) sqrt(1 - ab / abp) ;
+//   x_next = x0 sqrt(abp) + sqrt(1 - abp - sigma^2) eps + [t != 0] sigma noise - scale[c] clamp(grad) ; grad = c0 g + dx_unet
+// coef = the posterior row (c0 = d x0 / d x of the mean processor), dcoef = {alpha_bar, alpha_bar_prev, eta, noise_on,
+// r0 = sqrt_recip_ac, r1 = sqrt_recipm1_ac}: predict_eps_from_x_start (:533-536) uses the SAMPLER's tables whatever the mean
+// processor is (for `epsilon` r0 = c0 and r1 = c1).
 // x_next may alias x (each element is read, then written, by one thread)
-__global__ __launch_bounds__(256) void ddim_update_c_kernel(const float* __restrict__ x0, const float* x, const float* __restrict__ g,
+__global__ __launch_bounds__(256) void ddim_update_kernel(const float* __restrict__ x0, const float* x, const float* __restrict__ g,
                                                              const float* __restrict__ dxu, const float* __restrict__ noise,
                                                              const float* __restrict__ coef, const float* __restrict__ dcoef,
                                                              const float* __restrict__ scale, float clip, float* x_next,
@@ -1625,6 +813,624 @@ __global__ __launch_bounds__(256) void ddim_update_c_kernel(const float* __restr
     x_next[i] = xt - (g ? scale[c] * gc : 0.f);
   }
 }
+
+__global__ void fetch_coefs_kernel(const float* __restrict__ table, int* __restrict__ step, int delta,
+                                   float* __restrict__ coef_out, float* __restrict__ t_out, int B, int n_rows) {
+  const int s = min(max(*step, 0), n_rows - 1);   // a counter that ran off the table re-reads its last row
+  if (threadIdx.x < 8) coef_out[threadIdx.x] = table[s * 8 + threadIdx.x];
+  if (threadIdx.x < B) t_out[threadIdx.x] = table[s * 8 + 7];
+  __syncthreads();
+  if (threadIdx.x == 0) *step = s + delta;
+}
+
+inline int grid_for(long long total) {
+  long long b = (total + 255) / 256;
+  if (b > 2048) b = 2048;
+  return (int)(b < 1 ? 1 : b);
+}
+
+int check_desc(const osm_phys_desc* d, const char* who) {
+  OSM_REQUIRE(d, "%s: null descriptor", who);
+  OSM_REQUIRE(d->kind >= 0 && d->kind <= 3, "%s: unknown operator kind %d", who, d->kind);
+  OSM_REQUIRE(d->kind != 3 || (d->loss_type == 0 && d->weight_type == 0 && d->gamma_avrg == 0.f && d->gamma_val == 0.f),
+              "%s: the identity operator (kind 3) is the plain norm loss: no weight, no auxiliary losses", who);
+  OSM_REQUIRE(d->depth_type >= 0 && d->depth_type <= 2, "%s: unknown depth_type %d", who, d->depth_type);
+  OSM_REQUIRE(d->loss_type == 0 || d->loss_type == 1, "%s: unknown loss_type %d", who, d->loss_type);
+  OSM_REQUIRE(d->B > 0 && d->HW > 0, "%s: bad shape", who);
+  return OSM_OK;
+}
+
+}  // namespace
+
+extern "C" int osm_phys_nblk(int HW) { return (HW + PPB - 1) / PPB; }
+
+namespace {
+int check_lin_desc(const osm_phys_desc* d, const char* who) {
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(d->kind != 3, "%s: the identity operator (kind 3) has no image-formation model to compose with", who);
+  return OSM_OK;
+}
+
+// What a phi step needs.  The schedules ask before their first launch: a failure of a later finalize would leave phi half-stepped.
+int check_phi_step(const char* who, const osm_phys_desc* d, int do_update, const float* opt_state) {
+  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+  OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
+  OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
+  return OSM_OK;
+}
+
+// The composed route's arguments (include/osmosis_physlin.h): the measurement's size, v = A^T u and the residual's partial sums.  A
+// launcher that is handed one runs its kernel's LIN instantiation; each checks the members it reads.
+struct LinArgs { int hw; const float* v; const float* part_r; };
+
+int phys_reduce_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                       float* part, void* stream, const LinArgs* la = nullptr) {
+  int rc = la ? check_lin_desc(d, who) : check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && phi && part && (la ? la->v != nullptr : y != nullptr), "%s: null pointer", who);
+  const int nblk = osm_phys_nblk(d->HW);
+  const dim3 grid(nblk, d->B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (la) hipLaunchKernelGGL((phys_reduce_kernel<false, true>), grid, block, 0, st, *d, x0, nullptr, nullptr, phi, la->v, part, nblk);
+  else if (mask) hipLaunchKernelGGL((phys_reduce_kernel<true, false>), grid, block, 0, st, *d, x0, y, mask, phi, nullptr, part, nblk);
+  else hipLaunchKernelGGL((phys_reduce_kernel<false, false>), grid, block, 0, st, *d, x0, y, nullptr, phi, nullptr, part, nblk);
+  return osm::check_launch("phys_reduce_kernel");
+}
+
+// The offsets of a group descriptor, validated and copied by value (they travel in the kernel's arguments).
+int check_group(const osm_phys_desc* d, const osm_group_desc* grp, GroupOff* go, const char* who) {
+  OSM_REQUIRE(grp, "%s: null group descriptor", who);
+  OSM_REQUIRE(grp->G >= 1 && grp->G <= OSM_MAX_GROUPS, "%s: G = %d groups, must be 1 .. %d", who, grp->G, OSM_MAX_GROUPS);
+  OSM_REQUIRE(grp->off, "%s: null pointer (group offsets)", who);
+  OSM_REQUIRE(grp->reduce == 0 || grp->reduce == 1, "%s: reduce must be 0 (sum) or 1 (mean), got %d", who, grp->reduce);
+  OSM_REQUIRE(grp->off[0] == 0, "%s: off[0] must be 0, got %d", who, grp->off[0]);
+  for (int j = 0; j < grp->G; ++j)
+    OSM_REQUIRE(grp->off[j + 1] > grp->off[j], "%s: group offsets must be strictly increasing (off[%d] = %d, off[%d] = %d)", who, j,
+                grp->off[j], j + 1, grp->off[j + 1]);
+  OSM_REQUIRE(grp->off[grp->G] == d->B, "%s: off[G] = %d must be the batch B = %d", who, grp->off[grp->G], d->B);
+  for (int j = 0; j <= grp->G; ++j) go->off[j] = grp->off[j];
+  go->G = grp->G;
+  go->reduce_mean = grp->reduce;
+  return OSM_OK;
+}
+
+// go == nullptr: the per-image finalize; else one phi step per group
+int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
+                         float* loss_out, float* opt_state, int zero_guard, void* stream, const GroupOff* go = nullptr,
+                         const LinArgs* la = nullptr) {
+  int rc = la ? check_lin_desc(d, who) : check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(!la || (la->hw >= 1 && la->hw < (1 << 29)), "%s: bad measurement size hw = %d", who, la->hw);
+  OSM_REQUIRE(part && red && phi && (!la || la->part_r), "%s: null pointer", who);
+  if ((rc = check_phi_step(who, d, do_update, opt_state))) return rc;
+  const int nblk = osm_phys_nblk(d->HW);
+  const dim3 grid(go ? go->G : d->B), block(go ? 64 * GWAVES : 64);
+  hipStream_t st = (hipStream_t)stream;
+  if (go && la) {
+    hipLaunchKernelGGL(phys_finalize_group_kernel<true>, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk,
+                       zero_guard, *go, FinLin<true>{la->part_r, osm_phys_nblk(la->hw), la->hw});
+  } else if (go) {
+    hipLaunchKernelGGL(phys_finalize_group_kernel<false>, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk,
+                       zero_guard, *go, FinLin<false>{});
+  } else if (la) {
+    hipLaunchKernelGGL(phys_finalize_kernel<true>, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk,
+                       zero_guard, FinLin<true>{la->part_r, osm_phys_nblk(la->hw), la->hw});
+  } else {
+    hipLaunchKernelGGL(phys_finalize_kernel<false>, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk,
+                       zero_guard, FinLin<false>{});
+  }
+  return osm::check_launch("phys_finalize_kernel");
+}
+
+int phys_grad_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                     const float* red, float* g, void* stream, const LinArgs* la = nullptr, int zero_guard = 0) {
+  int rc = la ? check_lin_desc(d, who) : check_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(!la || (la->hw >= 1 && la->hw < (1 << 29)), "%s: bad measurement size hw = %d", who, la->hw);
+  OSM_REQUIRE(x0 && phi && red && g && (la ? la->v != nullptr : y != nullptr), "%s: null pointer", who);
+  const dim3 grid((d->HW + 255) / 256, d->B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (la) {
+    hipLaunchKernelGGL((phys_grad_kernel<false, true>), grid, block, 0, st, *d, x0, nullptr, nullptr, phi, la->v, red, g, la->hw,
+                       zero_guard);
+  } else if (mask) {
+    hipLaunchKernelGGL((phys_grad_kernel<true, false>), grid, block, 0, st, *d, x0, y, mask, phi, nullptr, red, g, 0, 0);
+  } else {
+    hipLaunchKernelGGL((phys_grad_kernel<false, false>), grid, block, 0, st, *d, x0, y, nullptr, phi, nullptr, red, g, 0, 0);
+  }
+  return osm::check_launch("phys_grad_kernel");
+}
+
+int check_lin(const osm_phys_desc* d, const osm_lin_desc* l, const char* who) {
+  OSM_REQUIRE(l, "%s: null operator descriptor", who);
+  OSM_REQUIRE(l->family == 0 || l->family == 1, "%s: unknown operator family %d (0 separable, 1 psf)", who, l->family);
+  OSM_REQUIRE(l->H >= 1 && l->W >= 1 && l->h >= 1 && l->w >= 1, "%s: bad operator grids %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
+  OSM_REQUIRE((long long)l->H * l->W == (long long)d->HW, "%s: the operator's image grid %d x %d does not have the descriptor's HW = %d pixels",
+              who, l->H, l->W, d->HW);
+  OSM_REQUIRE((long long)l->h * l->w < (1LL << 29), "%s: measurement grid %d x %d too large", who, l->h, l->w);
+  if (l->family == 0) {
+    OSM_REQUIRE(l->start_h && l->wt_h && l->start_w && l->wt_w && l->tstart_h && l->twt_h && l->tstart_w && l->twt_w,
+                "%s: a separable operator needs its forward and transposed band tables", who);
+    OSM_REQUIRE(l->Kh >= 1 && l->Kw >= 1 && l->tKh >= 1 && l->tKw >= 1, "%s: bad band widths Kh %d, Kw %d, tKh %d, tKw %d", who, l->Kh, l->Kw,
+                l->tKh, l->tKw);
+  } else {
+    OSM_REQUIRE(l->h == l->H && l->w == l->W, "%s: a psf operator keeps the image's grid, got %d x %d -> %d x %d", who, l->H, l->W, l->h, l->w);
+    OSM_REQUIRE(l->dy && l->dx && l->tap_w, "%s: a psf operator needs its tap list", who);
+    OSM_REQUIRE(l->T >= 1, "%s: bad tap count T %d", who, l->T);
+    OSM_REQUIRE(l->Ry >= 0 && l->Rx >= 0 && l->Ry < l->H && l->Rx < l->W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d",
+                who, l->Ry, l->H, l->Rx, l->W);
+  }
+  return OSM_OK;
+}
+
+inline int lin_planes(const osm_phys_desc* d) { return d->weight_type == 1 ? 4 : 3; }
+
+// out [B,P,h w] = A x [B,P,H W] (adjoint = 0) or out [B,P,H W] = A^T x [B,P,h w] (adjoint = 1), P planes, densely packed images
+int lin_apply(const osm_lin_desc* l, const float* x, float* out, int B, int P, int adjoint, void* stream) {
+  const long long HW = (long long)l->H * l->W, hw = (long long)l->h * l->w;
+  if (l->family == 1) return osm_psf_apply(x, out, l->dy, l->dx, l->tap_w, l->T, l->Ry, l->Rx, B, P, P * HW, P * HW, l->H, l->W, adjoint, 0, stream);
+  if (adjoint)
+    return osm_linop_apply(x, out, l->tstart_h, l->twt_h, l->tstart_w, l->twt_w, B, P, P * hw, P * HW, l->h, l->w, l->H, l->W, l->tKh,
+                           l->tKw, 0, stream);
+  return osm_linop_apply(x, out, l->start_h, l->wt_h, l->start_w, l->wt_w, B, P, P * HW, P * hw, l->H, l->W, l->h, l->w, l->Kh, l->Kw, 0,
+                         stream);
+}
+}  // namespace
+
+extern "C" int osm_phys_reduce(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
+                               float* part, void* stream) {
+  return phys_reduce_launch("osm_phys_reduce", d, x0, y, nullptr, phi, part, stream);
+}
+
+extern "C" int osm_phys_finalize(const osm_phys_desc* d, const float* part, float* red, float* phi,
+                                 int do_update, float* loss_out, float* opt_state, void* stream) {
+  return phys_finalize_launch("osm_phys_finalize", d, part, red, phi, do_update, loss_out, opt_state, 0, stream);
+}
+
+extern "C" int osm_phys_grad(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
+                             const float* red, float* g, void* stream) {
+  return phys_grad_launch("osm_phys_grad", d, x0, y, nullptr, phi, red, g, stream);
+}
+
+// The masked entry points (`_m`): mask [B,3,HW] in [0, 1], laid out like y; mask == NULL is the plain entry point, launch for launch.
+extern "C" int osm_phys_reduce_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                                 float* part, void* stream) {
+  return phys_reduce_launch("osm_phys_reduce_m", d, x0, y, mask, phi, part, stream);
+}
+
+extern "C" int osm_phys_finalize_m(const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
+                                   float* loss_out, float* opt_state, int masked, void* stream) {
+  return phys_finalize_launch("osm_phys_finalize_m", d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream);
+}
+
+extern "C" int osm_phys_grad_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
+                               const float* red, float* g, void* stream) {
+  return phys_grad_launch("osm_phys_grad_m", d, x0, y, mask, phi, red, g, stream);
+}
+
+// ---------------------------------------------------------------- the composed data term (include/osmosis_physlin.h)
+extern "C" int osm_phys_forward(const osm_phys_desc* d, const float* x0, const float* phi, float* F, void* stream) {
+  const char* who = "osm_phys_forward";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(x0 && phi && F, "%s: null pointer", who);
+  hipLaunchKernelGGL(phys_forward_kernel, dim3((d->HW + 255) / 256, d->B), dim3(256), 0, (hipStream_t)stream, *d, x0, phi, F,
+                     lin_planes(d));
+  return osm::check_launch("phys_forward_kernel");
+}
+
+extern "C" int osm_phys_resid(const osm_phys_desc* d, int hw, const float* AF, const float* y, const float* mask, float* u,
+                              float* part_r, void* stream) {
+  const char* who = "osm_phys_resid";
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  OSM_REQUIRE(hw >= 1 && hw < (1 << 29), "%s: bad measurement size hw = %d", who, hw);
+  OSM_REQUIRE(AF && y && u && part_r, "%s: null pointer", who);
+  const int nblk = osm_phys_nblk(hw);
+  hipLaunchKernelGGL(phys_resid_kernel, dim3(nblk, d->B), dim3(256), 0, (hipStream_t)stream, AF, y, mask, u, part_r, lin_planes(d), hw,
+                     nblk);
+  return osm::check_launch("phys_resid_kernel");
+}
+
+extern "C" int osm_phys_reduce_lin(const osm_phys_desc* d, const float* x0, const float* phi, const float* v, float* part,
+                                   void* stream) {
+  const LinArgs la{0, v, nullptr};
+  return phys_reduce_launch("osm_phys_reduce_lin", d, x0, nullptr, nullptr, phi, part, stream, &la);
+}
+
+extern "C" int osm_phys_finalize_lin(const osm_phys_desc* d, int hw, const float* part, const float* part_r, float* red, float* phi,
+                                     int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
+  const LinArgs la{hw, nullptr, part_r};
+  return phys_finalize_launch("osm_phys_finalize_lin", d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream, nullptr,
+                              &la);
+}
+
+extern "C" int osm_phys_grad_lin(const osm_phys_desc* d, int hw, const float* x0, const float* phi, const float* v, const float* red,
+                                 float* g, int masked, void* stream) {
+  const LinArgs la{hw, v, nullptr};
+  return phys_grad_launch("osm_phys_grad_lin", d, x0, nullptr, nullptr, phi, red, g, stream, &la, masked != 0);
+}
+
+// ---------------------------------------------------------------- the inner loop of one guided step, enqueued by ONE call
+namespace {
+// The composed route's operator and workspaces; a null pointer to one is the plain route.
+struct LinWs { const osm_lin_desc* lin; float *F, *AF, *u, *v, *part_r; };
+
+// The inner phi optimisation + dL/dx0 (measurements.py:266-303, condition_methods.py:109-144):
+//   n_inner x { reduce; finalize (+ phi step) }, with the loss and the x0-gradient taken at the phi of the LAST iteration, which is
+//   stepped afterwards (unless freeze_phi: then n_inner = 1 and phi stays).  The composed route runs forward, A, resid, A^T in front
+//   of every reduce; `go` puts the grouped finalize in the place of the per-image one.  The same launches as the single entry points
+//   in the same order -- from C the 2 n_inner + 2 launches cost the host ~2 us each instead of a Python call each (measured: the GPU
+//   idled 0.24 ms per step between them).  Every argument is checked before the first launch.
+int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi,
+                         float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
+                         void* stream, const GroupOff* go = nullptr, const LinWs* lw = nullptr) {
+  int rc = lw ? check_lin_desc(d, who) : check_desc(d, who);
+  if (rc) return rc;
+  if (lw && (rc = check_lin(d, lw->lin, who))) return rc;
+  OSM_REQUIRE(x0 && y && phi && part && red && loss_out && g && (!lw || (lw->F && lw->AF && lw->u && lw->v && lw->part_r)),
+              "%s: null pointer", who);
+  OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
+  OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
+  if ((rc = check_phi_step(who, d, !freeze_phi, opt_state))) return rc;
+  OSM_REQUIRE(!lw || (long long)d->B * 4 <= 65535, "%s: batch %d is too large for one launch of the operator", who, d->B);
+  const int zg = mask != nullptr, hw = lw ? lw->lin->h * lw->lin->w : 0, P = lin_planes(d);
+  const LinArgs la_{hw, lw ? lw->v : nullptr, lw ? lw->part_r : nullptr}, *la = lw ? &la_ : nullptr;
+  for (int it = 0; it < n_inner; ++it) {
+    if (lw) {
+      if ((rc = osm_phys_forward(d, x0, phi, lw->F, stream))) return rc;
+      if ((rc = lin_apply(lw->lin, lw->F, lw->AF, d->B, P, 0, stream))) return rc;
+      if ((rc = osm_phys_resid(d, hw, lw->AF, y, mask, lw->u, lw->part_r, stream))) return rc;
+      if ((rc = lin_apply(lw->lin, lw->u, lw->v, d->B, 3, 1, stream))) return rc;
+    }
+    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream, la))) return rc;
+    if (it < n_inner - 1) {
+      if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream, go, la))) return rc;
+      continue;
+    }
+    if ((rc = phys_finalize_launch(who, d, part, red, phi, 0, loss_out, nullptr, zg, stream, go, la))) return rc;
+    if ((rc = phys_grad_launch(who, d, x0, y, mask, phi, red, g, stream, la, zg))) return rc;
+    if (!freeze_phi && (rc = phys_finalize_launch(who, d, part, red, phi, 1, nullptr, opt_state, zg, stream, go, la))) return rc;
+  }
+  return OSM_OK;
+}
+}  // namespace
+
+extern "C" int osm_phys_optimize(const osm_phys_desc* d, const float* x0, const float* y, float* phi, float* part, float* red,
+                                 float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
+  return phys_optimize_launch("osm_phys_optimize", d, x0, y, nullptr, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                              stream);
+}
+
+extern "C" int osm_phys_optimize_m(const osm_phys_desc* d, const float* x0, const float* y, const float* mask, float* phi, float* part,
+                                   float* red, float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state,
+                                   void* stream) {
+  return phys_optimize_launch("osm_phys_optimize_m", d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                              stream);
+}
+
+extern "C" int osm_phys_optimize_lin(const osm_phys_desc* d, const osm_lin_desc* lin, const float* x0, const float* y, const float* mask,
+                                     float* phi, float* F, float* AF, float* u, float* v, float* part_r, float* part, float* red,
+                                     float* loss_out, float* g, int n_inner, int freeze_phi, float* opt_state, void* stream) {
+  const LinWs lw{lin, F, AF, u, v, part_r};
+  return phys_optimize_launch("osm_phys_optimize_lin", d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state,
+                              stream, nullptr, &lw);
+}
+
+// ---------------------------------------------------------------- shared water parameters (include/osmosis_physgroup.h)
+extern "C" int osm_phys_finalize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* part, float* red, float* phi,
+                                   int do_update, float* loss_out, float* opt_state, int masked, void* stream) {
+  const char* who = "osm_phys_finalize_g";
+  GroupOff go;
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &go, who))) return rc;
+  return phys_finalize_launch(who, d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream, &go);
+}
+
+extern "C" int osm_phys_finalize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, int hw, const float* part, const float* part_r,
+                                       float* red, float* phi, int do_update, float* loss_out, float* opt_state, int masked,
+                                       void* stream) {
+  const char* who = "osm_phys_finalize_lin_g";
+  GroupOff go;
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &go, who))) return rc;
+  const LinArgs la{hw, nullptr, part_r};
+  return phys_finalize_launch(who, d, part, red, phi, do_update, loss_out, opt_state, masked != 0, stream, &go, &la);
+}
+
+extern "C" int osm_phys_optimize_g(const osm_phys_desc* d, const osm_group_desc* grp, const float* x0, const float* y, const float* mask,
+                                   float* phi, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
+                                   float* opt_state, void* stream) {
+  const char* who = "osm_phys_optimize_g";
+  GroupOff go;
+  int rc = check_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &go, who))) return rc;
+  return phys_optimize_launch(who, d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state, stream, &go);
+}
+
+extern "C" int osm_phys_optimize_lin_g(const osm_phys_desc* d, const osm_group_desc* grp, const osm_lin_desc* lin, const float* x0,
+                                       const float* y, const float* mask, float* phi, float* F, float* AF, float* u, float* v,
+                                       float* part_r, float* part, float* red, float* loss_out, float* g, int n_inner, int freeze_phi,
+                                       float* opt_state, void* stream) {
+  const char* who = "osm_phys_optimize_lin_g";
+  GroupOff go;
+  int rc = check_lin_desc(d, who);
+  if (rc) return rc;
+  if ((rc = check_group(d, grp, &go, who))) return rc;
+  const LinWs lw{lin, F, AF, u, v, part_r};
+  return phys_optimize_launch(who, d, x0, y, mask, phi, part, red, loss_out, g, n_inner, freeze_phi, opt_state, stream, &go, &lw);
+}
+
+// ---------------------------------------------------------------- the step kernels' entry points
+// The fixed-shape entry points are the channel-generic ones (`_c`) at (C, Cout) = (4, 8): one launch helper per kernel, which takes
+// its caller's name for the messages.
+namespace {
+int check_kinds(const char* name, int mean_kind, int var_kind) {
+  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "%s: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)", name);
+  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "%s: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)", name);
+  return OSM_OK;
+}
+
+int check_cout(const char* name, int C, int Cout) {
+  OSM_REQUIRE(C > 0 && (Cout == C || Cout == 2 * C), "%s: Cout must be C or 2 C, got C = %d, Cout = %d", name, C, Cout);
+  return OSM_OK;
+}
+
+// (mean_kind and var_kind in range: check_kinds)
+int posterior_launch(bool raw, const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float* x0_raw,
+                     float* x0, float* mean, float* logvar, int B, int C, int Cout, int HW, hipStream_t st) {
+  const dim3 grid(grid_for((long long)B * C * HW)), block(256);
+#define OSM_POST1(MK, VK, RAW) \
+  hipLaunchKernelGGL((posterior_kernel<MK, VK, RAW>), grid, block, 0, st, model_out, x, coef, x0_raw, x0, mean, logvar, B, C, Cout, HW)
+#define OSM_POST(MK, VK) do { if (raw) OSM_POST1(MK, VK, true); else OSM_POST1(MK, VK, false); } while (0)
+  switch (mean_kind * 3 + var_kind) {
+    case 0: OSM_POST(0, 0); break;
+    case 1: OSM_POST(0, 1); break;
+    case 2: OSM_POST(0, 2); break;
+    case 3: OSM_POST(1, 0); break;
+    case 4: OSM_POST(1, 1); break;
+    case 5: OSM_POST(1, 2); break;
+    case 6: OSM_POST(2, 0); break;
+    case 7: OSM_POST(2, 1); break;
+    default: OSM_POST(2, 2); break;
+  }
+#undef OSM_POST
+#undef OSM_POST1
+  return osm::check_launch("posterior_kernel");
+}
+
+// dynamic_threshold: the raw pass, the batch-wide quantile of |x0_raw|, then x0 and the mean
+int posterior_dynthr_launch(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                            float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int C, int Cout,
+                            int HW, void* stream) {
+  const long long total = (long long)B * C * HW;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = posterior_launch(true, model_out, x, coef, mean_kind, var_kind, x0_raw, x0, mean, logvar, B, C, Cout, HW, st);
+  if (rc) return rc;
+  if ((rc = osm_quantile_abs(x0_raw, total, s, q, idx, ws, stream))) return rc;
+  const dim3 grid(grid_for(total)), block(256);
+  if (mean_kind == 2) {
+    hipLaunchKernelGGL(dynthr_apply_kernel<2>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  } else {
+    hipLaunchKernelGGL(dynthr_apply_kernel<0>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
+  }
+  return osm::check_launch("dynthr_apply_kernel");
+}
+
+int posterior_bwd_launch(const char* name, const float* g, const float* coef, float* d_out, int B, int C, int Cout, int HW,
+                         void* stream) {
+  OSM_REQUIRE(g && coef && d_out && B > 0 && HW > 0, "%s: bad argument", name);
+  int rc = check_cout(name, C, Cout);
+  if (rc) return rc;
+  hipLaunchKernelGGL(posterior_bwd_kernel, dim3(grid_for((long long)B * Cout * HW)), dim3(256), 0, (hipStream_t)stream, g, coef,
+                     d_out, B, C, Cout, HW);
+  return osm::check_launch("posterior_bwd_kernel");
+}
+
+int guide_update_launch(const char* name, const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                        const float* noise, const float* coef, const float* scale, float clip, float* x_next, float* grad_out, int B,
+                        int C, int HW, void* stream) {
+  OSM_REQUIRE(mean && logvar && coef && x_next && B > 0 && C > 0 && HW > 0, "%s: bad argument", name);
+  OSM_REQUIRE(!g || scale, "%s: guidance needs the per-channel scale", name);
+  hipLaunchKernelGGL(guide_update_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
+                     g, dx_unet, noise, coef, scale, clip, x_next, grad_out, B, C, HW);
+  return osm::check_launch("guide_update_kernel");
+}
+
+int guide_update_rng_launch(const char* name, const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                            const float* coef, const float* scale, float clip, float* x_next, float* grad_out, float* noise_out,
+                            int B, int C, int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
+                            int img_stride, void* stream) {
+  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && C > 0 && HW > 0, "%s: bad argument", name);
+  OSM_REQUIRE(!g || scale, "%s: guidance needs the per-channel scale", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements of one channel)", name);
+  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
+                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
+                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "%s: tensors must be 16-byte aligned", name);
+  hipLaunchKernelGGL(guide_update_rng_kernel, dim3(grid_for((long long)B * C * (HW / 4))), dim3(256), 0, (hipStream_t)stream, mean,
+                     logvar, g, dx_unet, coef, scale, clip, x_next, grad_out, noise_out, B, C, HW, (unsigned)(seed & 0xffffffffull),
+                     (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("guide_update_rng_kernel");
+}
+
+int ddim_update_launch(const char* name, const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
+                       const float* coef, const float* dcoef, const float* scale, float clip, float* x_next, float* grad_out, int B,
+                       int C, int HW, void* stream) {
+  OSM_REQUIRE(x0 && x && coef && dcoef && x_next && B > 0 && C > 0 && HW > 0, "%s: bad argument", name);
+  OSM_REQUIRE(!g || scale, "%s: guidance needs the per-channel scale", name);
+  hipLaunchKernelGGL(ddim_update_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, x0, x, g,
+                     dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, C, HW);
+  return osm::check_launch("ddim_update_kernel");
+}
+
+int randn_launch(const char* name, float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const,
+                 int sub, int img0, int img_stride, void* stream) {
+  OSM_REQUIRE(out && B > 0 && n > 0, "%s: bad argument", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(sub == 0 || step_dev || (step_const >= 0 && step_const < 65536),
+              "%s: with sub != 0 the step must be in [0, 65536), got %d", name, step_const);
+  OSM_REQUIRE((reinterpret_cast<size_t>(out) & 15) == 0, "%s: out must be 16-byte aligned", name);
+  OSM_REQUIRE(n % 4 == 0 || B == 1, "%s: a batch needs n %% 4 == 0 (every image's row starts 16-byte aligned)", name);
+  hipLaunchKernelGGL(randn_kernel, dim3(grid_for((long long)B * ((n + 3) / 4))), dim3(256), 0, (hipStream_t)stream, out, B, n,
+                     (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step_dev, step_const, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("randn_kernel");
+}
+}  // namespace
+
+extern "C" int osm_posterior_typed(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
+                                   int clip_denoised, float* x0_raw, float* x0, float* mean, float* logvar, int B, int HW,
+                                   void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0 && mean && logvar && B > 0 && HW > 0, "osm_posterior_typed: bad argument");
+  OSM_REQUIRE(!clip_denoised || x0_raw, "osm_posterior_typed: clip_denoised needs x0_raw (the unclamped prediction, read by osm_clamp_bwd)");
+  int rc = check_kinds("osm_posterior_typed", mean_kind, var_kind);
+  if (rc) return rc;
+  return posterior_launch(false, model_out, x, coef, mean_kind, var_kind, clip_denoised ? x0_raw : nullptr, x0, mean, logvar, B, 4, 8,
+                          HW, (hipStream_t)stream);
+}
+
+extern "C" int osm_posterior_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
+                               int clip_denoised, float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout,
+                               int HW, void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0 && mean && logvar && B > 0 && HW > 0, "osm_posterior_c: bad argument");
+  OSM_REQUIRE(!clip_denoised || x0_raw, "osm_posterior_c: clip_denoised needs x0_raw (the unclamped prediction, read by osm_clamp_bwd)");
+  int rc = check_kinds("osm_posterior_c", mean_kind, var_kind);
+  if (rc || (rc = check_cout("osm_posterior_c", C, Cout))) return rc;
+  return posterior_launch(false, model_out, x, coef, mean_kind, var_kind, clip_denoised ? x0_raw : nullptr, x0, mean, logvar, B, C,
+                          Cout, HW, (hipStream_t)stream);
+}
+
+extern "C" int osm_posterior(const float* model_out, const float* x, const float* coef, float* x0, float* mean,
+                             float* logvar, int B, int HW, void* stream) {
+  return osm_posterior_typed(model_out, x, coef, 0, 0, 0, nullptr, x0, mean, logvar, B, HW, stream);
+}
+
+extern "C" int osm_posterior_dynthr(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                                    float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int HW,
+                                    void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && HW > 0,
+              "osm_posterior_dynthr: bad argument");
+  int rc = check_kinds("osm_posterior_dynthr", mean_kind, var_kind);
+  if (rc) return rc;
+  const long long total = (long long)B * 4 * HW;
+  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr: quantile() input tensor is too large (%lld elements > 2^24)", total);
+  return posterior_dynthr_launch(model_out, x, coef, mean_kind, var_kind, s, x0_raw, x0, mean, logvar, q, idx, ws, B, 4, 8, HW, stream);
+}
+
+extern "C" int osm_posterior_dynthr_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
+                                      float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int C,
+                                      int Cout, int HW, void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && C > 0 && HW > 0,
+              "osm_posterior_dynthr_c: bad argument");
+  const long long total = (long long)B * C * HW;
+  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr_c: quantile() input tensor is too large (%lld elements > 2^24)", total);
+  int rc = check_kinds("osm_posterior_dynthr_c", mean_kind, var_kind);
+  if (rc || (rc = check_cout("osm_posterior_dynthr_c", C, Cout))) return rc;
+  return posterior_dynthr_launch(model_out, x, coef, mean_kind, var_kind, s, x0_raw, x0, mean, logvar, q, idx, ws, B, C, Cout, HW,
+                                 stream);
+}
+
+extern "C" int osm_clamp_bwd(float* g, const float* x_raw, float lo, float hi, long long n, void* stream) {
+  OSM_REQUIRE(g && x_raw && n > 0 && lo <= hi, "osm_clamp_bwd: bad argument");
+  hipLaunchKernelGGL(clamp_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, g, x_raw, lo, hi, n);
+  return osm::check_launch("clamp_bwd_kernel");
+}
+
+extern "C" int osm_posterior_bwd(const float* g, const float* coef, float* d_out, int B, int HW, void* stream) {
+  return posterior_bwd_launch("osm_posterior_bwd", g, coef, d_out, B, 4, 8, HW, stream);
+}
+
+extern "C" int osm_posterior_bwd_c(const float* g, const float* coef, float* d_out, int B, int C, int Cout, int HW, void* stream) {
+  return posterior_bwd_launch("osm_posterior_bwd_c", g, coef, d_out, B, C, Cout, HW, stream);
+}
+
+extern "C" int osm_guide_update(const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                                const float* noise, const float* coef, const float* scale4, float clip,
+                                float* x_next, float* grad_out, int B, int HW, void* stream) {
+  return guide_update_launch("osm_guide_update", mean, logvar, g, dx_unet, noise, coef, scale4, clip, x_next, grad_out, B, 4, HW, stream);
+}
+
+extern "C" int osm_guide_update_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* noise,
+                                  const float* coef, const float* scale, float clip, float* x_next, float* grad_out, int B, int C,
+                                  int HW, void* stream) {
+  return guide_update_launch("osm_guide_update_c", mean, logvar, g, dx_unet, noise, coef, scale, clip, x_next, grad_out, B, C, HW, stream);
+}
+
+extern "C" int osm_guide_update_rng(const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                                    const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
+                                    float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
+                                    int img0, int img_stride, void* stream) {
+  return guide_update_rng_launch("osm_guide_update_rng", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out, noise_out,
+                                 B, 4, HW, seed, step, step_offset, 0, img0, img_stride, stream);
+}
+
+extern "C" int osm_guide_update_rng_sub(const float* mean, const float* logvar, const float* g, const float* dx_unet,
+                                        const float* coef, const float* scale4, float clip, float* x_next, float* grad_out,
+                                        float* noise_out, int B, int HW, unsigned long long seed, const int* step, int step_offset,
+                                        int sub, int img0, int img_stride, void* stream) {
+  return guide_update_rng_launch("osm_guide_update_rng_sub", mean, logvar, g, dx_unet, coef, scale4, clip, x_next, grad_out,
+                                 noise_out, B, 4, HW, seed, step, step_offset, sub, img0, img_stride, stream);
+}
+
+extern "C" int osm_guide_update_rng_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
+                                      const float* scale, float clip, float* x_next, float* grad_out, float* noise_out, int B, int C,
+                                      int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
+                                      int img_stride, void* stream) {
+  return guide_update_rng_launch("osm_guide_update_rng_c", mean, logvar, g, dx_unet, coef, scale, clip, x_next, grad_out, noise_out, B,
+                                 C, HW, seed, step, step_offset, sub, img0, img_stride, stream);
+}
+
+extern "C" int osm_randn(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int img0,
+                         int img_stride, void* stream) {
+  return randn_launch("osm_randn", out, B, n, seed, step_dev, step_const, 0, img0, img_stride, stream);
+}
+
+extern "C" int osm_randn_sub(float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const, int sub,
+                             int img0, int img_stride, void* stream) {
+  return randn_launch("osm_randn_sub", out, B, n, seed, step_dev, step_const, sub, img0, img_stride, stream);
+}
+
+extern "C" int osm_philox_raw(unsigned* out, long long n4, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                              void* stream) {
+  OSM_REQUIRE(out && n4 > 0, "osm_philox_raw: bad argument");
+  hipLaunchKernelGGL(philox_raw_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, out, n4, c1, c2, c3, k0, k1);
+  return osm::check_launch("philox_raw_kernel");
+}
+
+extern "C" int osm_ddim_update(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
+                               const float* coef, const float* dcoef, const float* scale4, float clip, float* x_next,
+                               float* grad_out, int B, int HW, void* stream) {
+  return ddim_update_launch("osm_ddim_update", x0, x, g, dx_unet, noise, coef, dcoef, scale4, clip, x_next, grad_out, B, 4, HW, stream);
+}
+
+extern "C" int osm_ddim_update_c(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
+                                 const float* coef, const float* dcoef, const float* scale, float clip, float* x_next,
+                                 float* grad_out, int B, int C, int HW, void* stream) {
+  return ddim_update_launch("osm_ddim_update_c", x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, C, HW, stream);
+}
+
+extern "C" int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out,
+                               int B, void* stream) {
+  OSM_REQUIRE(table && step && coef_out && t_out && B > 0 && B <= 256 && n_rows > 0, "osm_fetch_coefs: bad argument");
+  hipLaunchKernelGGL(fetch_coefs_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, table, step, delta, coef_out,
+                     t_out, B, n_rows);
+  return osm::check_launch("fetch_coefs_kernel");
+}
+
+extern "C" int osm_ancestral_step(const float* model_out, const float* x, const float* z, const float* coef,
+                                  float* x_next, float* x0, int B, int C, int Cout, int HW, void* stream) {
+  OSM_REQUIRE(model_out && x && coef && x_next && B > 0 && C > 0 && Cout >= C && HW > 0, "osm_ancestral_step: bad argument");
+  hipLaunchKernelGGL(ancestral_step_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                     model_out, x, z, coef, x_next, x0, B, C, Cout, HW);
+  return osm::check_launch("ancestral_step_kernel");
+}
+
+// ---------------------------------------------------------------- the 'ps' data term and the exposure mask
+namespace {
 
 // 'ps' data term on a C-channel x0 (condition_methods.py:35-41): per image, the partial sums of (y - x0[0:3])^2 in the order of
 // phys_reduce_kernel (PPB pixels per workgroup, wave sums, the four waves pairwise): deterministic
@@ -1718,111 +1524,7 @@ __global__ __launch_bounds__(256) void exposure_mask_kernel(const float* __restr
     for (int c = 0; c < 3; ++c) mask[base + (long long)c * HW] = m[c];
   }
 }
-
-int posterior_c_launch(const char* name, bool raw, const float* model_out, const float* x, const float* coef, int mean_kind,
-                       int var_kind, float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout, int HW,
-                       hipStream_t st) {
-  OSM_REQUIRE(mean_kind >= 0 && mean_kind <= 2, "%s: mean_kind must be 0 (epsilon), 1 (start_x) or 2 (previous_x)", name);
-  OSM_REQUIRE(var_kind >= 0 && var_kind <= 2, "%s: var_kind must be 0 (learned_range), 1 (fixed) or 2 (learned)", name);
-  OSM_REQUIRE(C > 0 && (Cout == C || Cout == 2 * C), "%s: Cout must be C or 2 C, got C = %d, Cout = %d", name, C, Cout);
-  const dim3 grid(grid_for((long long)B * C * HW)), block(256);
-#define OSM_POST1(MK, VK, RAW) \
-  hipLaunchKernelGGL((posterior_c_kernel<MK, VK, RAW>), grid, block, 0, st, model_out, x, coef, x0_raw, x0, mean, logvar, B, C, Cout, HW)
-#define OSM_POST(MK, VK) do { if (raw) OSM_POST1(MK, VK, true); else OSM_POST1(MK, VK, false); } while (0)
-  switch (mean_kind * 3 + var_kind) {
-    case 0: OSM_POST(0, 0); break;
-    case 1: OSM_POST(0, 1); break;
-    case 2: OSM_POST(0, 2); break;
-    case 3: OSM_POST(1, 0); break;
-    case 4: OSM_POST(1, 1); break;
-    case 5: OSM_POST(1, 2); break;
-    case 6: OSM_POST(2, 0); break;
-    case 7: OSM_POST(2, 1); break;
-    default: OSM_POST(2, 2); break;
-  }
-#undef OSM_POST
-#undef OSM_POST1
-  return osm::check_launch("posterior_c_kernel");
-}
-
 }  // namespace
-
-extern "C" int osm_posterior_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind,
-                               int clip_denoised, float* x0_raw, float* x0, float* mean, float* logvar, int B, int C, int Cout,
-                               int HW, void* stream) {
-  OSM_REQUIRE(model_out && x && coef && x0 && mean && logvar && B > 0 && HW > 0, "osm_posterior_c: bad argument");
-  OSM_REQUIRE(!clip_denoised || x0_raw, "osm_posterior_c: clip_denoised needs x0_raw (the unclamped prediction, read by osm_clamp_bwd)");
-  if (!clip_denoised) x0_raw = nullptr;
-  return posterior_c_launch("osm_posterior_c", false, model_out, x, coef, mean_kind, var_kind, x0_raw, x0, mean, logvar, B, C, Cout,
-                            HW, (hipStream_t)stream);
-}
-
-extern "C" int osm_posterior_dynthr_c(const float* model_out, const float* x, const float* coef, int mean_kind, int var_kind, float s,
-                                      float* x0_raw, float* x0, float* mean, float* logvar, float* q, int* idx, void* ws, int B, int C,
-                                      int Cout, int HW, void* stream) {
-  OSM_REQUIRE(model_out && x && coef && x0_raw && x0 && mean && logvar && q && idx && ws && B > 0 && C > 0 && HW > 0,
-              "osm_posterior_dynthr_c: bad argument");
-  const long long total = (long long)B * C * HW;
-  OSM_REQUIRE(total <= (1LL << 24), "osm_posterior_dynthr_c: quantile() input tensor is too large (%lld elements > 2^24)", total);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = posterior_c_launch("osm_posterior_dynthr_c", true, model_out, x, coef, mean_kind, var_kind, x0_raw, x0, mean, logvar, B, C,
-                              Cout, HW, st);
-  if (rc) return rc;
-  if ((rc = osm_quantile_abs(x0_raw, total, s, q, idx, ws, stream))) return rc;
-  const dim3 grid(grid_for(total)), block(256);
-  if (mean_kind == 2) {
-    hipLaunchKernelGGL(dynthr_apply_kernel<2>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
-  } else {
-    hipLaunchKernelGGL(dynthr_apply_kernel<0>, grid, block, 0, st, x0_raw, x, coef, q, x0, mean, total);
-  }
-  return osm::check_launch("dynthr_apply_kernel");
-}
-
-extern "C" int osm_posterior_bwd_c(const float* g, const float* coef, float* d_out, int B, int C, int Cout, int HW, void* stream) {
-  OSM_REQUIRE(g && coef && d_out && B > 0 && HW > 0, "osm_posterior_bwd_c: bad argument");
-  OSM_REQUIRE(C > 0 && (Cout == C || Cout == 2 * C), "osm_posterior_bwd_c: Cout must be C or 2 C, got C = %d, Cout = %d", C, Cout);
-  hipLaunchKernelGGL(posterior_bwd_c_kernel, dim3(grid_for((long long)B * Cout * HW)), dim3(256), 0, (hipStream_t)stream, g, coef,
-                     d_out, B, C, Cout, HW);
-  return osm::check_launch("posterior_bwd_c_kernel");
-}
-
-extern "C" int osm_guide_update_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* noise,
-                                  const float* coef, const float* scale, float clip, float* x_next, float* grad_out, int B, int C,
-                                  int HW, void* stream) {
-  OSM_REQUIRE(mean && logvar && coef && x_next && B > 0 && C > 0 && HW > 0, "osm_guide_update_c: bad argument");
-  OSM_REQUIRE(!g || scale, "osm_guide_update_c: guidance needs the per-channel scale");
-  hipLaunchKernelGGL(guide_update_c_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, mean, logvar,
-                     g, dx_unet, noise, coef, scale, clip, x_next, grad_out, B, C, HW);
-  return osm::check_launch("guide_update_c_kernel");
-}
-
-extern "C" int osm_guide_update_rng_c(const float* mean, const float* logvar, const float* g, const float* dx_unet, const float* coef,
-                                      const float* scale, float clip, float* x_next, float* grad_out, float* noise_out, int B, int C,
-                                      int HW, unsigned long long seed, const int* step, int step_offset, int sub, int img0,
-                                      int img_stride, void* stream) {
-  const char* name = "osm_guide_update_rng_c";
-  OSM_REQUIRE(mean && logvar && coef && x_next && step && B > 0 && C > 0 && HW > 0, "%s: bad argument", name);
-  OSM_REQUIRE(!g || scale, "%s: guidance needs the per-channel scale", name);
-  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
-  OSM_REQUIRE(HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements of one channel)", name);
-  OSM_REQUIRE(((reinterpret_cast<size_t>(mean) | reinterpret_cast<size_t>(logvar) | reinterpret_cast<size_t>(g) |
-                reinterpret_cast<size_t>(dx_unet) | reinterpret_cast<size_t>(x_next) | reinterpret_cast<size_t>(grad_out) |
-                reinterpret_cast<size_t>(noise_out)) & 15) == 0, "%s: tensors must be 16-byte aligned", name);
-  hipLaunchKernelGGL(guide_update_rng_c_kernel, dim3(grid_for((long long)B * C * (HW / 4))), dim3(256), 0, (hipStream_t)stream, mean,
-                     logvar, g, dx_unet, coef, scale, clip, x_next, grad_out, noise_out, B, C, HW, (unsigned)(seed & 0xffffffffull),
-                     (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
-  return osm::check_launch("guide_update_rng_c_kernel");
-}
-
-extern "C" int osm_ddim_update_c(const float* x0, const float* x, const float* g, const float* dx_unet, const float* noise,
-                                 const float* coef, const float* dcoef, const float* scale, float clip, float* x_next,
-                                 float* grad_out, int B, int C, int HW, void* stream) {
-  OSM_REQUIRE(x0 && x && coef && dcoef && x_next && B > 0 && C > 0 && HW > 0, "osm_ddim_update_c: bad argument");
-  OSM_REQUIRE(!g || scale, "osm_ddim_update_c: guidance needs the per-channel scale");
-  hipLaunchKernelGGL(ddim_update_c_kernel, dim3(grid_for((long long)B * C * HW)), dim3(256), 0, (hipStream_t)stream, x0, x, g,
-                     dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, C, HW);
-  return osm::check_launch("ddim_update_c_kernel");
-}
 
 namespace {
 int ps_loss_grad_launch(const char* who, const float* x0, const float* y, const float* mask, float* part, float* loss, float* g, int B,

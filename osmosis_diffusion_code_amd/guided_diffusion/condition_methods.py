@@ -17,6 +17,7 @@ Two ways in:
     5-tuple; works with any autograd graph from x_prev to x_0_hat (our UNet is an autograd.Function).
 """
 from abc import ABC, abstractmethod
+from functools import partial
 
 import os
 import torch
@@ -284,51 +285,43 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         x0c, yc = x0.contiguous(), y.contiguous()
         if mask is None:
             mask = self.measurement_mask(B, HW, x0.device)
-        n_inner = 1 if freeze_phi else self.n_iter
+        # the route's four calls: reduce, finalize, grad, optimize (the schedule: _inner_loop)
         if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
-            rows, masked = self._opt_rows(opt, phi), mask is not None
-            if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
-                ops.phys_optimize_g(d, grp, x0c, yc, mask, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=rows)
-                return g.view(x0.shape), loss
-            for it in range(n_inner):
-                ops.phys_reduce_m(d, x0c, yc, mask, phi, part)
-                if it == n_inner - 1:
-                    ops.phys_finalize_g(d, grp, part, red, phi, False, loss, masked=masked)
-                    ops.phys_grad_m(d, x0c, yc, mask, phi, red, g)
-                    if not freeze_phi:
-                        ops.phys_finalize_g(d, grp, part, red, phi, True, None, opt_state=rows, masked=masked)
-                else:
-                    ops.phys_finalize_g(d, grp, part, red, phi, True, loss, opt_state=rows, masked=masked)
-            return g.view(x0.shape), loss
-        if mask is not None:        # the same launches with the mask in the residual (osm_phys_*_m)
-            if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
-                ops.phys_optimize_m(d, x0c, yc, mask, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=self._opt_rows(opt, phi))
-                return g.view(x0.shape), loss
-            for it in range(n_inner):
-                ops.phys_reduce_m(d, x0c, yc, mask, phi, part)
-                if it == n_inner - 1:
-                    ops.phys_finalize_m(d, part, red, phi, False, loss)
-                    ops.phys_grad_m(d, x0c, yc, mask, phi, red, g)
-                    if not freeze_phi:
-                        ops.phys_finalize_m(d, part, red, phi, True, None, opt_state=self._opt_rows(opt, phi))
-                else:
-                    ops.phys_finalize_m(d, part, red, phi, True, loss, opt_state=self._opt_rows(opt, phi))
-            return g.view(x0.shape), loss
-        # n_inner x { reduce; finalize + phi step }; loss and dL/dx0 use the phi of the LAST iteration, which is stepped afterwards:
-        # one C call enqueues the 2 n_inner + 2 launches (one Python call per launch left the GPU idle between them)
-        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
-            ops.phys_optimize(d, x0c, yc, phi, part, red, loss, g, n_inner, freeze_phi, opt_state=self._opt_rows(opt, phi))
-            return g.view(x0.shape), loss
-        for it in range(n_inner):          # the same launches, one Python call each (A/B measurements, tests of the entry points)
-            ops.phys_reduce(d, x0c, yc, phi, part)
-            if it == n_inner - 1:
-                ops.phys_finalize(d, part, red, phi, False, loss)
-                ops.phys_grad(d, x0c, yc, phi, red, g)
-                if not freeze_phi:
-                    ops.phys_finalize(d, part, red, phi, True, None, opt_state=self._opt_rows(opt, phi))
-            else:
-                ops.phys_finalize(d, part, red, phi, True, loss, opt_state=self._opt_rows(opt, phi))
+            route = (partial(ops.phys_reduce_m, d, x0c, yc, mask, phi, part),
+                     partial(ops.phys_finalize_g, d, grp, part, red, phi, masked=mask is not None),
+                     partial(ops.phys_grad_m, d, x0c, yc, mask, phi, red, g),
+                     partial(ops.phys_optimize_g, d, grp, x0c, yc, mask, phi, part, red, loss, g))
+        elif mask is not None:      # the same launches with the mask in the residual (osm_phys_*_m)
+            route = (partial(ops.phys_reduce_m, d, x0c, yc, mask, phi, part), partial(ops.phys_finalize_m, d, part, red, phi),
+                     partial(ops.phys_grad_m, d, x0c, yc, mask, phi, red, g),
+                     partial(ops.phys_optimize_m, d, x0c, yc, mask, phi, part, red, loss, g))
+        else:
+            route = (partial(ops.phys_reduce, d, x0c, yc, phi, part), partial(ops.phys_finalize, d, part, red, phi),
+                     partial(ops.phys_grad, d, x0c, yc, phi, red, g),
+                     partial(ops.phys_optimize, d, x0c, yc, phi, part, red, loss, g))
+        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
         return g.view(x0.shape), loss
+
+    @staticmethod
+    def _inner_loop(route, n_inner, freeze_phi, loss, rows):
+        """The inner-loop schedule of every data-term route: n_inner x { reduce; finalize + phi step }; loss and dL/dx0 use the phi of
+        the LAST iteration, which is stepped afterwards.  `route`: its four calls (reduce, finalize, grad, optimize); `optimize` is
+        the ONE C call that enqueues all 2 n_inner + 2 launches (one Python call per launch left the GPU idle between them).
+        OSM_PHYS_PY_LOOP=1 walks the same launches through the single-launch entry points instead (A/B measurements, tests of the
+        entry points)."""
+        reduce, finalize, grad, optimize = route
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            optimize(n_inner, freeze_phi, opt_state=rows)
+            return
+        for it in range(n_inner):
+            reduce()
+            if it < n_inner - 1:
+                finalize(True, loss, opt_state=rows)
+                continue
+            finalize(False, loss)
+            grad()
+            if not freeze_phi:
+                finalize(True, None, opt_state=rows)
 
     def _loss_grad_x0_lin(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
         """`loss_grad_x0` with the operator's `degradation` A between the image-formation model and the photo: y and the mask live on
@@ -365,34 +358,22 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             mask = self.measurement_mask(B, hw, x0.device)
         elif mask.numel() != B * 3 * hw:
             raise ValueError(f"expected mask rows [{B},3,{hw}] (the measurement's grid {h} x {w}), got {tuple(mask.shape)}")
-        n_inner = 1 if freeze_phi else self.n_iter
-        rows = self._opt_rows(opt, phi)
-
-        def finalize(do_update, loss_out, opt_state=None, masked=False):
-            if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
-                return ops.phys_finalize_lin_g(d, grp, hw, part, part_r, red, phi, do_update, loss_out, opt_state=opt_state, masked=masked)
-            return ops.phys_finalize_lin(d, hw, part, part_r, red, phi, do_update, loss_out, opt_state=opt_state, masked=masked)
-        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
-            if grp is not None:
-                ops.phys_optimize_lin_g(d, grp, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g, n_inner, freeze_phi,
-                                        opt_state=rows)
-                return g.view(x0.shape), loss
-            ops.phys_optimize_lin(d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g, n_inner, freeze_phi, opt_state=rows)
-            return g.view(x0.shape), loss
         P, masked = ops.phys_lin_planes(d), mask is not None
-        for it in range(n_inner):
+
+        def reduce():
             ops.phys_forward(d, x0c, phi, F)
             ops.phys_lin_apply(lin, F, AF, B, P)
             ops.phys_resid(d, hw, AF, yc, mask, u, part_r)
             ops.phys_lin_apply(lin, u, v, B, 3, adjoint=True)
             ops.phys_reduce_lin(d, x0c, phi, v, part)
-            if it == n_inner - 1:
-                finalize(False, loss, masked=masked)
-                ops.phys_grad_lin(d, hw, x0c, phi, v, red, g, masked=masked)
-                if not freeze_phi:
-                    finalize(True, None, opt_state=rows, masked=masked)
-            else:
-                finalize(True, loss, opt_state=rows, masked=masked)
+        grad = partial(ops.phys_grad_lin, d, hw, x0c, phi, v, red, g, masked=masked)
+        if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
+            route = (reduce, partial(ops.phys_finalize_lin_g, d, grp, hw, part, part_r, red, phi, masked=masked), grad,
+                     partial(ops.phys_optimize_lin_g, d, grp, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g))
+        else:
+            route = (reduce, partial(ops.phys_finalize_lin, d, hw, part, part_r, red, phi, masked=masked), grad,
+                     partial(ops.phys_optimize_lin, d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g))
+        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
         return g.view(x0.shape), loss
 
     def _opt_rows(self, opt, phi):

@@ -2,7 +2,8 @@
 
 Kernel level: `loss_grad_x0` of a grouped operator against the oracle of a group (tests/physgroup_oracle.py), bit-equalities
 (all-singleton groups against the ungrouped entry points, one C call against the single launches, repeats, two identical images as
-one `mean` group, the independence of groups, freeze_phi), fully masked members, torch.library.opcheck.
+one `mean` group, the independence of groups, freeze_phi, an ungrouped batch past the group limit), fully masked members,
+torch.library.opcheck.
 Chain level (the tiny 4 -> 8 network in f32, a 16 x 24 image, a 10-index respaced chain, injected noise, `_generic_loop` patched to
 raise): B = 3 as groups [2, 1] against the oracle's own loop driven per group, a group walked in chunks, fused against
 `_generic_loop`, `restore_images(shared_water=True)`."""
@@ -128,9 +129,9 @@ HW0 = (36, 34)
 
 
 def route_run(pkg, route, groups, reduce="mean", optimizer="sgd", B=3, sl=None, py_loop=False, calls=1, seed=400, n_iter=5, freeze=False,
-              monkeypatch=None, edit=None, eta=None, mask_edit=None):
+              monkeypatch=None, edit=None, eta=None, mask_edit=None, grid=HW0):
     degname, mkind, lw = ROUTES[route]
-    H, W = HW0
+    H, W = grid
     cond = gcond(pkg, "underwater_physical_revised", B if sl is None else sl.stop - sl.start, groups, reduce, optimizer, n_iter, AUX, "norm",
                  lw, None if degname is None else DEGRADATIONS[degname], eta=eta)
     h, w = cond.operator.out_shape(H, W)
@@ -206,6 +207,34 @@ def test_freeze_phi_is_the_ungrouped_call(pkg, route):
     got = route_run(pkg, route, (2, 1), "sum", "adam", freeze=True)[0]
     same(got, want, (route, "freeze_phi"))
     assert torch.equal(got["phi"], gcond(pkg, "underwater_physical_revised", 3, None).operator.phi)
+
+
+# B = 65: one image more than a group table holds (OSM_MAX_GROUPS = 64).  36 x 36 = 1296 pixels: two reduce workgroups, the second
+# one partial, and no multiple of the gradient kernel's 256.
+PAST_LIMIT = dict(B=65, grid=(36, 36), n_iter=3)
+
+
+@pytest.mark.parametrize("route", ["plain", "masked", "blur_P4"])
+def test_ungrouped_finalize_past_the_group_limit(pkg, route):
+    """The per-image finalize shares its body with the grouped one but takes no group table: a batch of 65 runs (adam, 3 inner
+    iterations, auxiliary losses), and phi, loss, g, red and the optimizer rows of images 0, 63 and 64 equal their own B = 1 runs
+    bit for bit."""
+    got = route_run(pkg, route, None, optimizer="adam", **PAST_LIMIT)[0]
+    assert all(bool(torch.isfinite(t).all()) for t in got.values())
+    for b in (0, 63, 64):
+        one = route_run(pkg, route, None, optimizer="adam", sl=slice(b, b + 1), **PAST_LIMIT)[0]
+        same(got, one, (route, f"image {b}"), rows=(slice(b, b + 1), slice(0, 1)))
+
+
+def test_a_full_group_table_entry_beside_a_singleton(pkg):
+    """The same batch as groups [64, 1] under `mean`: the singleton's rows equal the ungrouped B = 1 run of image 64 bit for bit (a
+    group's sum starts from its first member), and the 64 members of the other group hold one phi row and one optimizer row."""
+    got = route_run(pkg, "plain", (64, 1), "mean", "adam", **PAST_LIMIT)[0]
+    one = route_run(pkg, "plain", None, optimizer="adam", sl=slice(64, 65), **PAST_LIMIT)[0]
+    same(got, one, "the singleton", rows=(slice(64, 65), slice(0, 1)))
+    for name in ("phi", "opt"):
+        assert bool((got[name][0:64] == got[name][0:1]).all()), name
+    assert not torch.equal(got["phi"][0], got["phi"][64]) and bool(torch.isfinite(got["phi"]).all())
 
 
 # ------------------------------------------------------------------------------------------------------------ 3: masks
