@@ -7,17 +7,17 @@
 gradient_x_prev, any registered mean / variance processor pair, clip_denoised or not) every step runs as
 ONE device-resident sequence with no host synchronisation:
 
-    fetch_coefs -> UNet forward plan -> osm_posterior_typed -> [osm_phys_reduce/finalize x n_iter ->
-    osm_phys_grad] -> [osm_clamp_bwd] -> osm_posterior_bwd -> UNet data-gradient plan -> osm_guide_update
+    fetch_coefs -> UNet forward plan -> osm_posterior_c -> [osm_phys_reduce/finalize x n_iter ->
+    osm_phys_grad] -> [osm_clamp_bwd] -> osm_posterior_bwd_c -> UNet data-gradient plan -> osm_guide_update_c
 
 (the reference performs 4 + n_iter device->host copies per step: gaussian_diffusion.py:216,276,288,
 condition_methods.py:130,224).  Per-timestep coefficients live in a device table indexed by a
 device-side step counter, so the whole step can be replayed from a hipGraph.  The rgb-guidance
 configuration (`rgb_guidance=True`: DDPM / DDIM `p_sample` + 'ps' conditioning on an identity operator,
 gaussian noiser) runs through the same loop: osm_phys_* with the identity operator (kind 3) for
-||y - x0[:, 0:3]|| and its gradient, osm_guide_update(_rng) or osm_ddim_update for the step.  The per-step
+||y - x0[:, 0:3]|| and its gradient, osm_guide_update(_rng)_c or osm_ddim_update_c for the step.  The per-step
 noise is drawn inside the update kernel (Philox-4x32-10) unless `noise="aten"` asks for torch's stream.
-`dynamic_threshold` runs there too (osm_posterior_dynthr / osm_dynthr_bwd: an on-device exact quantile of the whole batch) when the
+`dynamic_threshold` runs there too (osm_posterior_dynthr_c / osm_dynthr_bwd: an on-device exact quantile of the whole batch) when the
 batch is one engine pass.  The PCGS inner alternation (`local_M > 1`: the step repeated at the same t inside [s_end, s_start],
 :225-309) runs there as `alternate_len` sub-steps per index (`pcgs_schedule`).  Any other combination (third-party conditioners /
 operators / processors, a chunked batch with dynamic_threshold) falls back to a generic loop that follows the reference control flow on
@@ -205,6 +205,126 @@ def extract_and_expand(array, time, target):
     return a.expand_as(target)
 
 
+class _Chain:
+    """What `_fused_loop` and `_tiled_loop` do alike for one chain: the host-only plan (`__init__`), then on the device (`open`) the
+    chunks and engines of the network's inputs, the coefficient table with its device step counter and the library-noise seed, and
+    per sub-step the coefficient fetch, the state update of a row block and the trace record; at the end the snapshots and the
+    returned values.  What a loop does on its own (which noise it draws when, the tiles, the grouped walk) stays in the loop."""
+
+    def __init__(self, diffusion, sample_pattern, kwargs, HW, record, record_every, ddim=False, mean_only=False):
+        """The host-only plan of a chain over images of HW pixels.  It touches no device and draws nothing: everything it refuses
+        is refused before an engine is built, a seed drawn or a kernel launched."""
+        import os
+        self.diffusion, self.kwargs, self.record, self.record_every, self.ddim = diffusion, kwargs, record, record_every, ddim
+        T = diffusion.num_timesteps
+        # optional sub-range of the chain (benchmarks / resumed chains): idx = first .. last, descending
+        self.first, self.last = kwargs.get("index_range", (T - 1, 0))
+        if not (0 <= self.last <= self.first <= T - 1):
+            raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({self.first}, {self.last})")
+        self.sched = pcgs_schedule(sample_pattern, T)     # (an invalid pattern raises here)
+        if T > 1 << 16 and max(a for _, _, a in self.sched) > 1:
+            raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
+        self.noise_fn = kwargs.get("noise_fn", None)      # (k, shape) -> tensor : injected noise (parity runs)
+        source = "fn" if self.noise_fn is not None else str(kwargs.get("noise", os.environ.get("OSM_STEP_NOISE", "library"))).lower()
+        if source not in ("fn", "library", "aten"):
+            raise ValueError(f"noise must be 'library' or 'aten', got {source!r}")
+        if source == "library" and HW % 4 != 0:
+            source = "aten"                               # (one Philox counter covers four consecutive elements of an image)
+        self.source = source
+        # q_sample's unused draw (reference :241) and, for 'ps', p_sample's draw before it: only meaningful on torch's generator
+        self.draw_measurement_noise = kwargs.get("reference_rng_order", source == "aten") and source == "aten"
+        # the update kernel draws the step noise itself (DDIM at eta = 0 adds none and osm_ddim_update_c takes a tensor for eta > 0;
+        # the mean-only step adds none)
+        self.lib_rng = source == "library" and not ddim and not mean_only
+        self.trace = kwargs.get("trace", None)            # list collecting per-step tensors (tests)
+        self.records = kwargs.get("record_out", [] if record else None)   # (idx, pred_xstart cpu) snapshots
+        self.have_loss = False
+
+    def open(self, model, n, h, w, dev, scale, clip):
+        """The device side, for n network inputs of h x w (independent chains, SURVEY.md F1/F2: a batch whose kept activations would
+        not fit the device -- ~8 GB per 256 x 256 image in fp32 -- is walked in chunks per step, contiguous row blocks).  scale, clip:
+        the conditioner's per-channel guidance scale [C] and gradient clip, used at the guided indices."""
+        sizes = self.diffusion.chunk_sizes(n, model.images_in_flight(n, h, w))
+        self.chunks, c0 = [], 0
+        for sz in sizes:
+            self.chunks.append((c0, c0 + sz))
+            c0 += sz
+        self.engs = {}
+        for sz in sorted(set(sizes), reverse=True):       # at most two sizes; the second call keeps the first engine alive
+            self.engs[sz] = model.engine(sz, h, w, keep=tuple(self.engs.values()))
+        self.eng = self.engs[sizes[0]]
+        self.single = len(self.chunks) == 1
+        self.scale, self.clip = scale, clip
+        self.table = torch.from_numpy(self.diffusion.coef_table()).to(dev)
+        self.step = torch.tensor([self.first], device=dev, dtype=torch.int32)
+        self.coef = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.dtable = self.dcoef = None
+        if self.ddim:
+            self.dtable = torch.from_numpy(self.diffusion.ddim_table(float(self.kwargs.get("eta", 0.0)))).to(dev)
+            self.dcoef = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.seed = 0
+        if self.source == "library":
+            self.seed = self.kwargs.get("noise_seed")
+            if self.seed is None:  # one draw per CHAIN from the device's generator (what torch.manual_seed seeds, and only device ops consume)
+                self.seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev).item())
+
+    def fetch(self, final):
+        """The coefficients of this sub-step.  Every engine's timestep vector is filled from the SAME step counter; the counter moves
+        once per index, in the last fetch of its last sub-step, which always goes through the first engine (stream order: the delta-0
+        fetches read it before it moves)."""
+        eng = self.eng
+        for e2 in self.engs.values():
+            if e2 is not eng:
+                ops.fetch_coefs(self.table, self.step, 0, self.coef, e2.t_dev, e2.B)
+        if self.ddim:
+            ops.fetch_coefs(self.dtable, self.step, 0, self.dcoef, eng.t_dev, eng.B)
+        ops.fetch_coefs(self.table, self.step, -1 if final else 0, self.coef, eng.t_dev, eng.B)
+
+    def update(self, a, b, g, dxu, noise, x_next, grad_out, noise_out, sub, final, img0, img_stride):
+        """x_next [Bc,C,H,W] = the state of one row block after this sub-step, from (a, b) = its (mean, log variance) -- for DDIM its
+        (pred_xstart, x_t).  g, dxu: the data term's gradient and the network's dx, None at an unguided index (no scale, no clip);
+        noise: the step noise as a tensor, or None (drawn in the kernel into noise_out if given; the mean-only step: none added)."""
+        Bc, C, H, W = x_next.shape
+        HW = H * W
+        sc, cl = (None, -1.0) if g is None else (self.scale, self.clip)
+        if self.ddim:
+            ops.ddim_update_c(a, b, g, dxu, noise, self.coef, self.dcoef, sc, cl, x_next, grad_out, Bc, C, HW)
+        elif self.lib_rng:                                # (+1 after the last sub-step's fetch: it moved the counter)
+            ops.guide_update_rng_c(a, b, g, dxu, self.coef, sc, cl, x_next, grad_out, noise_out, Bc, C, HW, self.seed, self.step,
+                                   step_offset=1 if final else 0, sub=sub, img0=img0, img_stride=img_stride)
+        else:
+            ops.guide_update_c(a, b, g, dxu, noise, self.coef, sc, cl, x_next, grad_out, Bc, C, HW)
+
+    def trace_record(self, idx, sub, x_in, x0, mean, x_out, model_out, loss_all, phi, noise=None, q=None, grad=None):
+        """One sub-step's entry of `trace=`; x_in: the state's clone from before the sub-step, model_out / grad: tensors of its own."""
+        rec = dict(idx=idx, sub=sub, x_in=x_in, x0=x0.clone(), mean=mean.clone(), x_out=x_out.clone(), model_out=model_out,
+                   loss=loss_all.clone() if self.have_loss else None, phi=None if phi is None else phi.clone(),
+                   step=self.step.clone())                # (the device step counter after this sub-step)
+        for key, v in (("noise", noise), ("q", q)):
+            if v is not None:
+                rec[key] = v.clone()
+        if grad is not None:
+            rec["grad"] = grad
+        self.trace.append(rec)
+
+    def snapshot(self, idx, x0):
+        """pred_xstart during the chain (reference :308-327): same steps, one D2H copy each, after the index's last sub-step."""
+        if self.records is not None and ((idx % self.record_every == 0) or idx == 0 or idx == 999):
+            self.records.append((idx, x0.detach().cpu()))
+
+    def finish(self, x_state, x0, loss_all, operator):
+        """What the loop returns: the sample -- and with an operator (the Osmosis configuration) its variables, the last losses and
+        pred_xstart; the rgb-guidance branch returns the sample only (:339-340)."""
+        img = x_state.clone()
+        if self.record and self.records:
+            self.diffusion._save_process_grid(self.records, self.kwargs.get("save_grids_path"), self.kwargs.get("original_file_name"))
+        if operator is None:
+            return img
+        variables = operator.optimize(freeze_phi=True)
+        loss_np = loss_all.detach().cpu().numpy() if self.have_loss else None
+        return img, variables, loss_np, x0.detach().cpu()
+
+
 class GaussianDiffusion:
     def __init__(self, betas, model_mean_type, model_var_type, dynamic_threshold, clip_denoised,
                  rescale_timesteps, **kwargs):
@@ -383,7 +503,7 @@ class GaussianDiffusion:
     def _fused_loop(self, model, cond, x_start, measurement, sample_pattern, kwargs, record=False, record_every=150,
                     mean_only=False):
         """One device-resident step per index, for the Osmosis configuration and for the rgb-guidance ('ps') one (`_fast_path_ok`).
-        Per-step noise (gaussian_diffusion.py:266-268 / :497 / :522): by default drawn INSIDE osm_guide_update_rng from the
+        Per-step noise (gaussian_diffusion.py:266-268 / :497 / :522): by default drawn INSIDE osm_guide_update_rng_c from the
         library's Philox-4x32-10 stream (seed: `noise_seed=`, else one draw per chain from the device's torch generator, so
         `torch.manual_seed` still fixes the chain); `noise="aten"` (or OSM_STEP_NOISE=aten) draws it with torch on the device in the reference's
         call order instead (the reference's own realisation for the same seed); `noise_fn=` injects it (parity runs).
@@ -393,14 +513,13 @@ class GaussianDiffusion:
         phi, x0) are those after the index's last sub-step (:274, :309).
         mean_only: the mean-only 'ps' step (:235-238, :298-306): x_next = mean - scale grad at every index, no noise drawn or added
         (`noise="aten"` with reference_rng_order draws q_sample's only; noise_fn is not called).
-        Channels: x_start [B,C,H,W] with the network's C; (C, Cout) = (4, 8) runs the [B,4,HW] entry points, anything else the
-        channel-generic ones (osm_*_c).
+        Channels: x_start [B,C,H,W] with the network's C; every step kernel is called through its channel-generic entry point
+        (osm_*_c) with the chain's own (C, Cout) -- at (4, 8) bit-identical to the [B,4,HW] entry points, which remain for C callers.
         Shared water parameters (the operator's `phi_groups`): the images of a group are no longer independent in phi, so a guided
         sub-step runs every chunk's forward + posterior, then ONE data term over the whole batch (one phi step per group and inner
         iteration, osm_phys_optimize_g), then every chunk's backward + update.  With one chunk that is the ungrouped launch order
         with the grouped call in the data term's place; with more, each chunk's forward is re-run before its backward (the engine
         keeps one pass's activations): ONE EXTRA FORWARD per chunk per guided sub-step.  Ungrouped chains keep their launch sequence."""
-        import os
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
         ddim = ps and not mean_only and getattr(type(self), "p_sample", None) is DDIM.p_sample
@@ -409,121 +528,75 @@ class GaussianDiffusion:
         Cout = model.out_channels
         if C != model.in_channels:
             raise ValueError(f"expected x_start [B,{model.in_channels},H,W], got {tuple(x_start.shape)}")
-        rgbd = (C, Cout) == (4, 8)                        # the compile-time [B,4,HW] / [B,8,HW] kernels
         HW = H * W
         T = self.num_timesteps
         # the loop drives the engine's plans directly and calls the network as model(x, t) (gaussian_diffusion.py:243): a
         # class-conditional network has no labels here -- the reference's forward asserts (unet.py:713-716); so does this path,
         # instead of replaying the plans with zero / stale label rows
         assert getattr(model, "num_classes", None) is None, "must specify y if and only if the model is class-conditional"
-        # optional sub-range of the chain (benchmarks / resumed chains): idx = first .. last, descending
-        first, last = kwargs.get("index_range", (T - 1, 0))
-        if not (0 <= last <= first <= T - 1):
-            raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({first}, {last})")
-        sched = pcgs_schedule(sample_pattern, T)          # (before anything launches: an invalid pattern raises here)
-        if T > 1 << 16 and max(a for _, _, a in sched) > 1:
-            raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
-        # Images are independent chains: a batch whose kept activations would not fit the device
-        # (~8 GB per 256 x 256 image in fp32) is walked in chunks per step; per-image state (x_t, phi, losses) stays in
-        # [B]-sized tensors, the chunks are contiguous row blocks.
-        sizes = self.chunk_sizes(B, model.images_in_flight(B, H, W))
-        chunks, c0 = [], 0
-        for sz in sizes:
-            chunks.append((c0, c0 + sz))
-            c0 += sz
-        engs = {}
-        for sz in sorted(set(sizes), reverse=True):       # at most two sizes; the second call keeps the first engine alive
-            engs[sz] = model.engine(sz, H, W, keep=tuple(engs.values()))
-        eng = engs[sizes[0]]
+        ch = _Chain(self, sample_pattern, kwargs, HW, record, record_every, ddim=ddim, mean_only=mean_only)
+        # ---- everything above is host-side; from here on the device is used
+        ch.open(model, B, H, W, dev, cond.scale4(dev, C) if ps else cond.scale4(dev), -1.0 if ps else cond.clip_value)
+        chunks, engs, eng, single, coef = ch.chunks, ch.engs, ch.eng, ch.single, ch.coef
+        source, lib_rng, noise_fn, trace = ch.source, ch.lib_rng, ch.noise_fn, ch.trace
         f32 = dict(device=dev, dtype=torch.float32)
-        table = torch.from_numpy(self.coef_table()).to(dev)
-        step = torch.tensor([first], device=dev, dtype=torch.int32)
-        coef = torch.zeros(8, **f32)
-        dtable = torch.from_numpy(self.ddim_table(float(kwargs.get("eta", 0.0)))).to(dev) if ddim else None
-        dcoef = torch.zeros(8, **f32) if ddim else None
         x0, mean, logvar = (torch.empty(B, C, H, W, **f32) for _ in range(3))
         # `clip_denoised: True` (configs/rgb_guidance_sample_config.yaml; posterior_mean_variance.py:43-50): x0 is clamped inside
-        # osm_posterior_typed, the unclamped prediction is kept for the clamp's backward (osm_clamp_bwd masks d loss / d x0)
+        # osm_posterior_c, the unclamped prediction is kept for the clamp's backward (osm_clamp_bwd masks d loss / d x0)
         # `dynamic_threshold: True` (util/img_utils.py:8-15): x0 = clip(x0_raw * quantile(|x0_raw|, 0.98), -1, 1) over the whole batch
-        # (osm_posterior_dynthr; q and its order statistics stay on the device for osm_dynthr_bwd); `_fast_path_ok` guarantees one chunk
+        # (osm_posterior_dynthr_c; q and its order statistics stay on the device for osm_dynthr_bwd); `_fast_path_ok` guarantees one chunk
         dyn = bool(self.mean_processor.dynamic_threshold)
         x0_raw = torch.empty(B, C, H, W, **f32) if (self.mean_processor.clip_denoised or dyn) else None
+        q_dev = None
         if dyn:
-            assert len(chunks) == 1, "dynamic_threshold couples every image: the fused loop takes it in one engine pass only"
+            assert single, "dynamic_threshold couples every image: the fused loop takes it in one engine pass only"
             q_dev, q_idx = torch.zeros(1, **f32), torch.zeros(2, device=dev, dtype=torch.int32)
             q_ws = ops.quantile_workspace(B * C * HW, dev)
         g = torch.empty(B, C, H, W, **f32)
         loss_all = torch.zeros(B, **f32)
-        scale4 = cond.scale4(dev, C) if ps else cond.scale4(dev)
-        clip = -1.0 if ps else cond.clip_value
         y = measurement.detach().to(dev, torch.float32).contiguous()
         # [B,3,hw] rows like y, or None (`measurement_mask=`): the mask lives on the measurement's grid (the image's, except for a
         # downsampling operator of the 'ps' branch)
         mask = cond.measurement_mask(B, y.shape[2] * y.shape[3] if y.dim() == 4 else HW, dev)
         phi = None if ps else cond.operator.phi
-        single = len(chunks) == 1
         grouped = not ps and getattr(cond.operator, "group_sizes", None) is not None
         x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
         x_state.copy_(x_start.detach())
-        noise_fn = kwargs.get("noise_fn", None)           # (k, shape) -> tensor : injected noise (parity runs)
-        trace = kwargs.get("trace", None)                 # list collecting per-step tensors (tests)
-        records = kwargs.get("record_out", [] if record else None)   # (idx, pred_xstart cpu) snapshots
         shared = bool(kwargs.get("shared_noise", False)) and B > 1   # every image receives the SAME noise (separately seeded batch-1 runs)
-        source = "fn" if noise_fn is not None else str(kwargs.get("noise", os.environ.get("OSM_STEP_NOISE", "library"))).lower()
-        if source not in ("fn", "library", "aten"):
-            raise ValueError(f"noise must be 'library' or 'aten', got {source!r}")
-        if source == "library" and (HW % 4 != 0):
-            source = "aten"                               # (one Philox counter covers four consecutive elements of an image)
-        # q_sample's unused draw (reference :241) and, for 'ps', p_sample's draw before it: only meaningful on torch's generator
-        draw_measurement_noise = kwargs.get("reference_rng_order", source == "aten") and source == "aten"
-        lib_rng = source == "library" and not ddim and not mean_only        # (DDIM at eta = 0 adds no noise; osm_ddim_update takes a tensor for eta > 0)
-        seed = 0
-        if source == "library":
-            seed = kwargs.get("noise_seed")
-            if seed is None:      # one draw per CHAIN from the device's generator (what torch.manual_seed seeds, and only device ops consume)
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev).item())
         img_base, img_stride = int(kwargs.get("image_index0", 0)), 0 if shared else 1
         noise = None if (lib_rng or mean_only) else torch.zeros(B, C, H, W, **f32)
         noise1 = torch.zeros(1, C, H, W, **f32) if (shared and source == "aten" and not mean_only) else None
         noise_used = torch.empty(B, C, H, W, **f32) if (lib_rng and trace is not None) else None
-        have_loss = False
         # (no mask: the call as it always was -- a conditioner subclass whose loss_grad_x0 predates the kwarg keeps working)
         mk_rows = (lambda a, b: {}) if mask is None else (lambda a, b: {"mask": mask[a:b]})
+        mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
         k = 0                                             # sub-step count (noise_fn's k)
-        for idx in range(first, last - 1, -1):
-            guided, freeze, alt = sched[T - 1 - idx]
+        for idx in range(ch.first, ch.last - 1, -1):
+            guided, freeze, alt = ch.sched[T - 1 - idx]
             if ps:
                 guided, freeze = True, False
             for sub in range(alt):
                 final = sub == alt - 1
                 if mean_only:                             # no step noise; the reference's only draw per call is q_sample's (:241)
-                    if draw_measurement_noise:
+                    if ch.draw_measurement_noise:
                         torch.randn_like(y[:1] if shared else y)
                 elif source == "fn":
                     noise.copy_(noise_fn(k, noise.shape))
                 elif source == "aten":
                     if ps:                                # DDPM / DDIM.p_sample draw first (:497, :522), then q_sample (:241)
                         noise1.normal_() if noise1 is not None else noise.normal_()
-                    if draw_measurement_noise:
+                    if ch.draw_measurement_noise:
                         torch.randn_like(y[:1] if noise1 is not None else y)
                     if not ps:
                         noise1.normal_() if noise1 is not None else noise.normal_()
                     if noise1 is not None:
                         noise.copy_(noise1.expand_as(noise))
                 elif not lib_rng:                         # library stream, DDIM: as a tensor (used only for eta > 0)
-                    ops.randn_sub(noise, B, C * HW, seed, step=step, sub=sub, img0=img_base,
+                    ops.randn_sub(noise, B, C * HW, ch.seed, step=ch.step, sub=sub, img0=img_base,
                                   img_stride=img_stride)  # (before the fetch: counter = idx)
-                # every engine's timestep vector is filled from the SAME step counter; the counter moves once per index, in the last
-                # fetch of its last sub-step, which always goes through the first engine (stream order: the delta-0 fetches read it
-                # before it moves)
-                for e2 in engs.values():
-                    if e2 is not eng:
-                        ops.fetch_coefs(table, step, 0, coef, e2.t_dev, e2.B)
-                if ddim:
-                    ops.fetch_coefs(dtable, step, 0, dcoef, eng.t_dev, eng.B)
-                ops.fetch_coefs(table, step, -1 if final else 0, coef, eng.t_dev, eng.B)
+                ch.fetch(final)
                 if trace is not None:
-                    rec = {"idx": idx, "sub": sub, "x_in": x_state.clone()}
+                    x_in = x_state.clone()
                     grad_all = torch.empty_like(g) if guided else None
                     model_out = torch.empty(B, eng.out.shape[1], H, W, **f32)
                 # what this sub-step does, in launch order.  Independent chains: chunk by chunk forward -> data term -> backward -> update.
@@ -545,7 +618,7 @@ class GaussianDiffusion:
                         else:
                             cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
                                               loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
-                        have_loss = True
+                        ch.have_loss = True
                         continue
                     ce, Bc = engs[c1 - c0], c1 - c0        # this chunk's engine (`eng` stays the first one)
                     if act == "refwd":
@@ -556,16 +629,9 @@ class GaussianDiffusion:
                         if not single:
                             ce.x_in.copy_(x_state[c0:c1])
                         ce.run_forward()
-                        mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
-                        if dyn and rgbd:
-                            ops.posterior_dynthr(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, HW,
-                                                 mk, vk, DYNAMIC_THRESHOLD_S)
-                        elif dyn:
+                        if dyn:
                             ops.posterior_dynthr_c(ce.out, ce.x_in, coef, x0, mean, logvar, x0_raw, q_dev, q_idx, q_ws, Bc, C, Cout, HW,
                                                    mk, vk, DYNAMIC_THRESHOLD_S)
-                        elif rgbd:
-                            ops.posterior(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, HW, mk, vk,
-                                          None if x0_raw is None else x0_raw[c0:c1])
                         else:
                             ops.posterior_c(ce.out, ce.x_in, coef, x0[c0:c1], mean[c0:c1], logvar[c0:c1], Bc, C, Cout, HW, mk, vk,
                                             None if x0_raw is None else x0_raw[c0:c1])
@@ -578,55 +644,19 @@ class GaussianDiffusion:
                             ops.dynthr_bwd(g, x0_raw, q_dev, q_idx, q_ws, DYNAMIC_THRESHOLD_S)
                         elif x0_raw is not None:
                             ops.clamp_bwd(g[c0:c1], x0_raw[c0:c1])
-                        if rgbd:
-                            ops.posterior_bwd(g[c0:c1], coef, ce.d_out, Bc, HW)
-                        else:
-                            ops.posterior_bwd_c(g[c0:c1], coef, ce.d_out, Bc, C, Cout, HW)
+                        ops.posterior_bwd_c(g[c0:c1], coef, ce.d_out, Bc, C, Cout, HW)
                         ce.run_backward()
                         gg, dxu = g[c0:c1], ce.dx
                         grad_out = grad_all[c0:c1] if trace is not None else None
-                    nz = None if noise is None else noise[c0:c1]
-                    sc, cl = (scale4, clip) if guided else (None, -1.0)
-                    nu = None if noise_used is None else noise_used[c0:c1]
-                    if ddim and rgbd:
-                        ops.ddim_update(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
-                    elif ddim:
-                        ops.ddim_update_c(x0[c0:c1], ce.x_in, gg, dxu, nz, coef, dcoef, sc, cl, x_state[c0:c1], grad_out, Bc, C, HW)
-                    elif lib_rng and rgbd:                # (+1 after the last sub-step's fetch: it moved the counter)
-                        ops.guide_update_rng_sub(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
-                                                 nu, Bc, HW, seed, step, step_offset=1 if final else 0, sub=sub,
-                                                 img0=img_base + (0 if shared else c0), img_stride=img_stride)
-                    elif lib_rng:
-                        ops.guide_update_rng_c(mean[c0:c1], logvar[c0:c1], gg, dxu, coef, sc, cl, x_state[c0:c1], grad_out,
-                                               nu, Bc, C, HW, seed, step, step_offset=1 if final else 0, sub=sub,
-                                               img0=img_base + (0 if shared else c0), img_stride=img_stride)
-                    elif rgbd:
-                        ops.guide_update(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, HW)
-                    else:                                 # (mean_only: nz is None -> the kernel adds no noise at any index)
-                        ops.guide_update_c(mean[c0:c1], logvar[c0:c1], gg, dxu, nz, coef, sc, cl, x_state[c0:c1], grad_out, Bc, C, HW)
+                    a, b = (x0[c0:c1], ce.x_in) if ddim else (mean[c0:c1], logvar[c0:c1])
+                    ch.update(a, b, gg, dxu, None if noise is None else noise[c0:c1], x_state[c0:c1], grad_out,
+                              None if noise_used is None else noise_used[c0:c1], sub, final,
+                              img_base + (0 if shared else c0), img_stride)
                 if trace is not None:
-                    rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out,
-                               loss=loss_all.clone() if have_loss else None, phi=None if phi is None else phi.clone(),
-                               step=step.clone())         # (the device step counter after this sub-step)
-                    if noise_used is not None:
-                        rec["noise"] = noise_used.clone()
-                    if dyn:
-                        rec["q"] = q_dev.clone()
-                    if guided:
-                        rec["grad"] = grad_all
-                    trace.append(rec)
+                    ch.trace_record(idx, sub, x_in, x0, mean, x_state, model_out, loss_all, phi, noise_used, q_dev, grad_all)
                 k += 1
-            # snapshots of pred_xstart during the chain (reference :308-327): same steps, one D2H copy each, after the last sub-step
-            if records is not None and ((idx % record_every == 0) or idx == 0 or idx == 999):
-                records.append((idx, x0.detach().cpu()))
-        img = x_state.clone()
-        if record and records:
-            self._save_process_grid(records, kwargs.get("save_grids_path"), kwargs.get("original_file_name"))
-        if ps:                                            # the rgb-guidance branch returns the sample only (:339-340)
-            return img
-        variables = cond.operator.optimize(freeze_phi=True)
-        loss_np = loss_all.detach().cpu().numpy() if have_loss else None
-        return img, variables, loss_np, x0.detach().cpu()
+            ch.snapshot(idx, x0)
+        return ch.finish(x_state, x0, loss_all, None if ps else cond.operator)
 
     def _tiled_loop(self, model, cond_fn, x_start, measurement, pretrain_model, rgb_guidance, sample_pattern, kwargs, tiling,
                     record=False, record_every=150):
@@ -640,7 +670,6 @@ class GaussianDiffusion:
         more than one chunk the forward of a chunk is re-run before its data-gradient pass.
         Never `_generic_loop` (the network on the whole canvas is another computation): what this loop does not carry raises
         NotImplementedError naming the option; a bad tiling raises ValueError before anything launches."""
-        import os
         from .condition_methods import PosteriorSamplingOsmosis
         from .unet import UNetModel
         th, tw, sy, sx, window = parse_tiling(tiling)
@@ -676,97 +705,61 @@ class GaussianDiffusion:
         assert getattr(model, "num_classes", None) is None, "must specify y if and only if the model is class-conditional"
         dev = x_start.device
         HW, T, n = Hc * Wc, self.num_timesteps, origins.shape[0]
-        first, last = kwargs.get("index_range", (T - 1, 0))
-        if not (0 <= last <= first <= T - 1):
-            raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({first}, {last})")
-        sched = pcgs_schedule(sample_pattern, T)
-        if T > 1 << 16 and max(a for _, _, a in sched) > 1:
-            raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
-        noise_fn = kwargs.get("noise_fn", None)
-        source = "fn" if noise_fn is not None else str(kwargs.get("noise", os.environ.get("OSM_STEP_NOISE", "library"))).lower()
-        if source not in ("fn", "library", "aten"):
-            raise ValueError(f"noise must be 'library' or 'aten', got {source!r}")
-        if source == "library" and HW % 4 != 0:
-            source = "aten"
+        ch = _Chain(self, sample_pattern, kwargs, HW, record, record_every)
         # ---- everything above is host-side; from here on the device is used
-        sizes = self.chunk_sizes(n, model.images_in_flight(n, th, tw))
-        chunks, c0 = [], 0
-        for sz in sizes:
-            chunks.append((c0, c0 + sz))
-            c0 += sz
-        engs = {}
-        for sz in sorted(set(sizes), reverse=True):
-            engs[sz] = model.engine(sz, th, tw, keep=tuple(engs.values()))
-        eng = engs[sizes[0]]
-        single = len(chunks) == 1
+        ch.open(model, n, th, tw, dev, cond.scale4(dev), cond.clip_value)
+        chunks, engs, eng, single, coef, trace = ch.chunks, ch.engs, ch.eng, ch.single, ch.coef, ch.trace
         f32 = dict(device=dev, dtype=torch.float32)
         org, wy, wx, inv_norm = origins.to(dev), wy.to(dev), wx.to(dev), inv_norm.to(dev).contiguous()
         weights = (wy, wx, inv_norm)
-        table = torch.from_numpy(self.coef_table()).to(dev)
-        step = torch.tensor([first], device=dev, dtype=torch.int32)
-        coef = torch.zeros(8, **f32)
         x_state = x_start.detach().to(**f32).clone().contiguous()
         x0, mean, logvar, g, dx = (torch.empty(1, 4, Hc, Wc, **f32) for _ in range(5))
         model_out = torch.empty(1, 8, Hc, Wc, **f32)
-        d_out = torch.zeros(1, 8, Hc, Wc, **f32)          # (osm_posterior_bwd fills the mean half; the variance half stays 0)
+        d_out = torch.empty(1, 8, Hc, Wc, **f32)
         out_tiles = None if single else torch.empty(n, 8, th, tw, **f32)
         dx_tiles = None if single else torch.empty(n, 4, th, tw, **f32)
         x0_raw = torch.empty(1, 4, Hc, Wc, **f32) if self.mean_processor.clip_denoised else None
         loss_all = torch.zeros(1, **f32)
-        scale4, clip = cond.scale4(dev), cond.clip_value
         y = measurement.detach().to(dev, torch.float32).contiguous()
         mask = cond.measurement_mask(1, HW, dev)
         mk_rows = {} if mask is None else {"mask": mask}
         phi = cond.operator.phi
-        trace = kwargs.get("trace", None)
-        records = kwargs.get("record_out", [] if record else None)
-        draw_measurement_noise = kwargs.get("reference_rng_order", source == "aten") and source == "aten"
-        lib_rng = source == "library"
-        seed = 0
-        if lib_rng:
-            seed = kwargs.get("noise_seed")
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=dev).item())
         img_base = int(kwargs.get("image_index0", 0))
-        noise = None if lib_rng else torch.zeros(1, 4, Hc, Wc, **f32)      # the noise belongs to the canvas
-        noise_used = torch.empty(1, 4, Hc, Wc, **f32) if (lib_rng and trace is not None) else None
+        noise = None if ch.lib_rng else torch.zeros(1, 4, Hc, Wc, **f32)      # the noise belongs to the canvas
+        noise_used = torch.empty(1, 4, Hc, Wc, **f32) if (ch.lib_rng and trace is not None) else None
         mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
-        have_loss = False
 
         def forward_chunk(ce, a, b):
             ops.tile_gather(x_state, ce.x_in, org[a:b])
             ce.run_forward()
         k = 0
-        for idx in range(first, last - 1, -1):
-            guided, freeze, alt = sched[T - 1 - idx]
+        for idx in range(ch.first, ch.last - 1, -1):
+            guided, freeze, alt = ch.sched[T - 1 - idx]
             for sub in range(alt):
                 final = sub == alt - 1
-                if source == "fn":
-                    noise.copy_(noise_fn(k, noise.shape))
-                elif source == "aten":
-                    if draw_measurement_noise:
+                if ch.source == "fn":
+                    noise.copy_(ch.noise_fn(k, noise.shape))
+                elif ch.source == "aten":
+                    if ch.draw_measurement_noise:
                         torch.randn_like(y)
                     noise.normal_()
-                for e2 in engs.values():                  # (every engine's timestep vector from the same step counter: `_fused_loop`)
-                    if e2 is not eng:
-                        ops.fetch_coefs(table, step, 0, coef, e2.t_dev, e2.B)
-                ops.fetch_coefs(table, step, -1 if final else 0, coef, eng.t_dev, eng.B)
+                ch.fetch(final)
                 if trace is not None:
-                    rec = {"idx": idx, "sub": sub, "x_in": x_state.clone()}
+                    x_in = x_state.clone()
                 for a, b in chunks:
                     ce = engs[b - a]
                     forward_chunk(ce, a, b)
                     if not single:
                         out_tiles[a:b].copy_(ce.out)
                 ops.tile_blend(eng.out if single else out_tiles, model_out, org, *weights)
-                ops.posterior(model_out, x_state, coef, x0, mean, logvar, 1, HW, mk, vk, x0_raw)
+                ops.posterior_c(model_out, x_state, coef, x0, mean, logvar, 1, 4, 8, HW, mk, vk, x0_raw)
                 gg = dxu = grad_out = None
                 if guided:
                     cond.loss_grad_x0(x0, y, freeze_phi=freeze, g_out=g, phi=phi, loss_out=loss_all, **mk_rows)
-                    have_loss = True
+                    ch.have_loss = True
                     if x0_raw is not None:
                         ops.clamp_bwd(g, x0_raw)
-                    ops.posterior_bwd(g, coef, d_out, 1, HW)
+                    ops.posterior_bwd_c(g, coef, d_out, 1, 4, 8, HW)
                     for a, b in chunks:
                         ce = engs[b - a]
                         if not single:                    # this engine's activations are another chunk's by now
@@ -778,29 +771,12 @@ class GaussianDiffusion:
                     ops.tile_blend(eng.dx if single else dx_tiles, dx, org)
                     gg, dxu = g, dx
                     grad_out = torch.empty_like(g) if trace is not None else None
-                sc, cl = (scale4, clip) if guided else (None, -1.0)
-                if lib_rng:
-                    ops.guide_update_rng_sub(mean, logvar, gg, dxu, coef, sc, cl, x_state, grad_out, noise_used, 1, HW, seed, step,
-                                             step_offset=1 if final else 0, sub=sub, img0=img_base, img_stride=1)
-                else:
-                    ops.guide_update(mean, logvar, gg, dxu, noise, coef, sc, cl, x_state, grad_out, 1, HW)
+                ch.update(mean, logvar, gg, dxu, noise, x_state, grad_out, noise_used, sub, final, img_base, 1)
                 if trace is not None:
-                    rec.update(x0=x0.clone(), mean=mean.clone(), x_out=x_state.clone(), model_out=model_out.clone(),
-                               loss=loss_all.clone() if have_loss else None, phi=phi.clone(), step=step.clone())
-                    if noise_used is not None:
-                        rec["noise"] = noise_used.clone()
-                    if guided:
-                        rec["grad"] = grad_out
-                    trace.append(rec)
+                    ch.trace_record(idx, sub, x_in, x0, mean, x_state, model_out.clone(), loss_all, phi, noise_used, grad=grad_out)
                 k += 1
-            if records is not None and ((idx % record_every == 0) or idx == 0 or idx == 999):
-                records.append((idx, x0.detach().cpu()))
-        img = x_state.clone()
-        if record and records:
-            self._save_process_grid(records, kwargs.get("save_grids_path"), kwargs.get("original_file_name"))
-        variables = cond.operator.optimize(freeze_phi=True)
-        loss_np = loss_all.detach().cpu().numpy() if have_loss else None
-        return img, variables, loss_np, x0.detach().cpu()
+            ch.snapshot(idx, x0)
+        return ch.finish(x_state, x0, loss_all, cond.operator)
 
     @staticmethod
     def _save_process_grid(records, save_grids_path, original_file_name):
@@ -959,7 +935,7 @@ class _WrappedModel:
 
 @register_sampler(name="ddpm")
 class DDPM(SpacedDiffusion):
-    """Ancestral step (reference :492-502).  In the fused loop it IS osm_guide_update / osm_guide_update_rng (the row's
+    """Ancestral step (reference :492-502).  In the fused loop it IS osm_guide_update_c / osm_guide_update_rng_c (the row's
     `noise_on` switches the noise off at index 0); `p_sample` is the same row applied to torch tensors, for conditioners the
     fused loop has no kernels for (`_generic_loop`, autograd through `pred_xstart`)."""
 
@@ -973,7 +949,7 @@ class DDPM(SpacedDiffusion):
 
 @register_sampler(name="ddim")
 class DDIM(SpacedDiffusion):
-    """DDIM step (reference :505-535, Song et al. eq. 12).  In the fused loop it IS osm_ddim_update fed by `ddim_table`;
+    """DDIM step (reference :505-535, Song et al. eq. 12).  In the fused loop it IS osm_ddim_update_c fed by `ddim_table`;
     `p_sample` applies the same fp32 row scalars to torch tensors (`_generic_loop`)."""
 
     def step_scalars(self, idx: int, eta: float = 0.0):

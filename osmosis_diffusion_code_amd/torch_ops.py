@@ -18,6 +18,11 @@ registered for the "cuda" device type only, which is HIP on ROCm).
     osmosis::posterior_bwd(g, coef) -> d_model_out         d(pred_xstart)/d(model_out)^T g  (the chain rule into the UNet)
     osmosis::guide_update(mean, log_variance, g, dx_unet, noise, coef, scale4, clip) -> (x_next, grad)
                                                            condition_methods.py:186-221 update rule + the noise add of :262-271
+    The step operators (posterior, posterior_clip, posterior_dynthr, posterior_bwd, guide_update, guide_update_rng, ddim_update) take a
+    [B,C,H,W] state of any channel count with a network output of C or 2 C channels and a scale of C entries: (C, Cout) is read off
+    the tensors and the channel-generic entry points (osm_*_c) are called, for every pair; a mismatch raises before anything
+    launches.  Each has a `_c` twin (OPS_C) with the same implementation.  The [B,4,HW] C entry points remain for C callers and
+    are bit-identical at (4, 8).
     osmosis::phys_loss_grad(x0, y, phi, icfg, fcfg, n_inner, freeze_phi) -> (loss, grad_x0, phi_new)
     osmosis::phys_loss_grad_lin(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, family, tables, dims) -> (loss, grad_x0, phi_new)
     osmosis::phys_loss_grad_g(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, group_sizes, reduce) -> (loss, grad_x0, phi_new)
@@ -115,36 +120,98 @@ def _chw(x):
     return x.shape[0], x.shape[2] * x.shape[3]
 
 
-@torch.library.custom_op("osmosis::posterior", mutates_args=(), device_types="cuda")
-def posterior(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
-              var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """coef: the 8 fp32 coefficients of the step (GaussianDiffusion.coef_table row, fetched by osm_fetch_coefs); mean_kind / var_kind:
-    the processors' `kernel_kind` (osm_posterior_typed; 0, 0 = epsilon / learned_range)."""
+# One plain implementation per step job, serving the [B,4,HW]-era operator name and its `_c` twin alike: (C, Cout) comes from the
+# tensors, and what does not fit them is refused before anything launches.  Twins with one schema are one function under two names.
+def _step_ops(fn, fake, *names):
+    out = []
+    for name in names:
+        out.append(torch.library.custom_op(f"osmosis::{name}", fn, mutates_args=(), device_types="cuda"))
+        out[-1].register_fake(fake)
+    return out
+
+
+def _cc(model_out, x):
+    if model_out.dim() != 4 or model_out.shape[1] not in (x.shape[1], 2 * x.shape[1]):
+        raise OsmosisHipError("osmosis:: the network output must have C or 2 C channels")
+    if model_out.shape[0] != x.shape[0] or model_out.shape[2:] != x.shape[2:]:
+        raise OsmosisHipError("osmosis:: the network output must have the state's batch and grid")
+    return x.shape[1], model_out.shape[1]
+
+
+def _channel_scale(name, scale, x):
+    if scale.numel() != x.shape[1]:
+        raise OsmosisHipError(f"{name}: scale must have one entry per channel")
+    return x.shape[1]
+
+
+def _posterior_impl(model_out, x, coef, mean_kind, var_kind, clip):
     B, HW = _chw(x)
+    Cc, Cout = _cc(model_out, x)
     x0, mean, logvar = (torch.empty_like(x) for _ in range(3))
-    ops.posterior(model_out.contiguous(), x, coef, x0, mean, logvar, B, HW, mean_kind, var_kind)
-    return x0, mean, logvar
+    raw = torch.empty_like(x) if clip else None
+    ops.posterior_c(model_out.contiguous(), x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind, var_kind, x0_raw=raw)
+    return (x0, mean, logvar, raw) if clip else (x0, mean, logvar)
 
 
-@posterior.register_fake
+def _posterior_bwd_impl(g, coef, cout):
+    B, HW = _chw(g)
+    d_out = torch.empty(B, cout, g.shape[2], g.shape[3], device=g.device, dtype=torch.float32)
+    ops.posterior_bwd_c(g, coef, d_out, B, g.shape[1], cout, HW)
+    return d_out
+
+
+def _guide_update_impl(name, mean, log_variance, g, dx_unet, noise, coef, scale, clip):
+    B, HW = _chw(mean)
+    Cc = _channel_scale(name, scale, mean)
+    x_next, grad = torch.empty_like(mean), torch.empty_like(mean)
+    ops.guide_update_c(mean, log_variance, g, dx_unet, noise, coef, scale, clip, x_next, grad, B, Cc, HW)
+    return x_next, grad
+
+
+def _guide_update_rng_impl(name, mean, log_variance, g, dx_unet, coef, scale, clip, seed, step, step_offset, img0, img_stride, sub):
+    B, HW = _chw(mean)
+    Cc = _channel_scale(name, scale, mean)
+    x_next, grad, noise = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
+    ops.guide_update_rng_c(mean, log_variance, g, dx_unet, coef, scale, clip, x_next, grad, noise, B, Cc, HW, seed, step,
+                           step_offset=step_offset, sub=sub, img0=img0, img_stride=img_stride)
+    return x_next, grad, noise
+
+
+def _ddim_update_impl(name, x0, x, g, dx_unet, noise, coef, dcoef, scale, clip):
+    B, HW = _chw(x0)
+    Cc = _channel_scale(name, scale, x0)
+    x_next, grad = torch.empty_like(x0), torch.empty_like(x0)
+    ops.ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad, B, Cc, HW)
+    return x_next, grad
+
+
+def _posterior(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
+               var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """coef: the 8 fp32 coefficients of the step (GaussianDiffusion.coef_table row, fetched by osm_fetch_coefs); mean_kind / var_kind:
+    the processors' `kernel_kind` (osm_posterior_c; 0, 0 = epsilon / learned_range).  x [B,C,H,W], model_out with 2 C channels or
+    with C (no variance half: the variance processor reads model_out itself)."""
+    return _posterior_impl(model_out, x, coef, mean_kind, var_kind, clip=False)
+
+
 def _posterior_fake(model_out, x, coef, mean_kind=0, var_kind=0):
     return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
 
 
-@torch.library.custom_op("osmosis::posterior_clip", mutates_args=(), device_types="cuda")
-def posterior_clip(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
-                   var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+posterior, posterior_c = _step_ops(_posterior, _posterior_fake, "posterior", "posterior_c")
+
+
+def _posterior_clip(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
+                    var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """osmosis::posterior with `clip_denoised` (process_xstart, posterior_mean_variance.py:43-50; configs/rgb_guidance_sample_config.yaml):
     (pred_xstart clamped to [-1, 1], mean formed from it, log_variance, the unclamped prediction for osmosis::clamp_bwd)."""
-    B, HW = _chw(x)
-    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
-    ops.posterior(model_out.contiguous(), x, coef, x0, mean, logvar, B, HW, mean_kind, var_kind, x0_raw=raw)
-    return x0, mean, logvar, raw
+    return _posterior_impl(model_out, x, coef, mean_kind, var_kind, clip=True)
 
 
-@posterior_clip.register_fake
 def _posterior_clip_fake(model_out, x, coef, mean_kind=0, var_kind=0):
     return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+
+
+posterior_clip, posterior_clip_c = _step_ops(_posterior_clip, _posterior_clip_fake, "posterior_clip", "posterior_clip_c")
 
 
 @torch.library.custom_op("osmosis::clamp_bwd", mutates_args=(), device_types="cuda")
@@ -176,24 +243,26 @@ def _quantile_abs_fake(x, s):
     return x.new_empty((1,)), x.new_empty((2,), dtype=torch.int32)
 
 
-@torch.library.custom_op("osmosis::posterior_dynthr", mutates_args=(), device_types="cuda")
-def posterior_dynthr(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0, var_kind: int = 0,
-                     s: float = 0.98) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+def _posterior_dynthr(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0, var_kind: int = 0,
+                      s: float = 0.98) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """osmosis::posterior with `dynamic_threshold` (process_xstart, posterior_mean_variance.py:43-50): (pred_xstart = clip(raw *
-    quantile(|raw|, s), -1, 1) over the whole batch, mean formed from it, log_variance, the raw prediction, q [1], idx [2]) -- the last
-    three are what osmosis::dynthr_bwd takes."""
+    quantile(|raw|, s), -1, 1) over all B C H W elements, mean formed from it, log_variance, the raw prediction, q [1], idx [2]) -- the
+    last three are what osmosis::dynthr_bwd takes."""
     B, HW = _chw(x)
+    Cc, Cout = _cc(model_out, x)
     x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
     q, idx = torch.empty(1, device=x.device, dtype=torch.float32), torch.empty(2, device=x.device, dtype=torch.int32)
-    ops.posterior_dynthr(model_out.contiguous(), x, coef, x0, mean, logvar, raw, q, idx, ops.quantile_workspace(x.numel(), x.device),
-                         B, HW, mean_kind, var_kind, s)
+    ops.posterior_dynthr_c(model_out.contiguous(), x, coef, x0, mean, logvar, raw, q, idx,
+                           ops.quantile_workspace(x.numel(), x.device), B, Cc, Cout, HW, mean_kind, var_kind, s)
     return x0, mean, logvar, raw, q, idx
 
 
-@posterior_dynthr.register_fake
 def _posterior_dynthr_fake(model_out, x, coef, mean_kind=0, var_kind=0, s=0.98):
     return (torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), x.new_empty((1,)),
             x.new_empty((2,), dtype=torch.int32))
+
+
+posterior_dynthr, posterior_dynthr_c = _step_ops(_posterior_dynthr, _posterior_dynthr_fake, "posterior_dynthr", "posterior_dynthr_c")
 
 
 @torch.library.custom_op("osmosis::dynthr_bwd", mutates_args=(), device_types="cuda")
@@ -211,10 +280,8 @@ def _dynthr_bwd_fake(g, x_raw, q, idx, s=0.98):
 
 @torch.library.custom_op("osmosis::posterior_bwd", mutates_args=(), device_types="cuda")
 def posterior_bwd(g: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
-    B, HW = _chw(g)
-    d_out = torch.zeros(B, 2 * g.shape[1], g.shape[2], g.shape[3], device=g.device, dtype=torch.float32)
-    ops.posterior_bwd(g, coef, d_out, B, HW)
-    return d_out
+    """d loss / d model_out for a network output of 2 C channels (the variance half is zero); C channels: osmosis::posterior_bwd_c."""
+    return _posterior_bwd_impl(g, coef, 2 * g.shape[1])
 
 
 @posterior_bwd.register_fake
@@ -225,10 +292,7 @@ def _posterior_bwd_fake(g, coef):
 @torch.library.custom_op("osmosis::guide_update", mutates_args=(), device_types="cuda")
 def guide_update(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor,
                  coef: torch.Tensor, scale4: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    B, HW = _chw(mean)
-    x_next, grad = torch.empty_like(mean), torch.empty_like(mean)
-    ops.guide_update(mean, log_variance, g, dx_unet, noise, coef, scale4, clip, x_next, grad, B, HW)
-    return x_next, grad
+    return _guide_update_impl("osmosis::guide_update", mean, log_variance, g, dx_unet, noise, coef, scale4, clip)
 
 
 @guide_update.register_fake
@@ -243,11 +307,8 @@ def guide_update_rng(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Te
     """osmosis::guide_update with the step noise drawn in the kernel (Philox-4x32-10: key = seed, counter = (element / 4,
     img0 + b * img_stride, (step[0] + step_offset) | sub << 16)); a pure function of its inputs.  sub: the sub-step of a step
     repeated at the same t (PCGS local_M; 0 = the plain step).  Returns (x_next, grad, the noise drawn)."""
-    B, HW = _chw(mean)
-    x_next, grad, noise = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    ops.guide_update_rng_sub(mean, log_variance, g, dx_unet, coef, scale4, clip, x_next, grad, noise, B, HW, seed, step,
-                             step_offset=step_offset, sub=sub, img0=img0, img_stride=img_stride)
-    return x_next, grad, noise
+    return _guide_update_rng_impl("osmosis::guide_update_rng", mean, log_variance, g, dx_unet, coef, scale4, clip, seed, step,
+                                  step_offset, img0, img_stride, sub)
 
 
 @guide_update_rng.register_fake
@@ -259,10 +320,7 @@ def _guide_update_rng_fake(mean, log_variance, g, dx_unet, coef, scale4, clip, s
 def ddim_update(x0: torch.Tensor, x: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor,
                 dcoef: torch.Tensor, scale4: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """DDIM step + guidance (osm_ddim_update): coef = the posterior row, dcoef = row of GaussianDiffusion.ddim_table()."""
-    B, HW = _chw(x0)
-    x_next, grad = torch.empty_like(x0), torch.empty_like(x0)
-    ops.ddim_update(x0, x, g, dx_unet, noise, coef, dcoef, scale4, clip, x_next, grad, B, HW)
-    return x_next, grad
+    return _ddim_update_impl("osmosis::ddim_update", x0, x, g, dx_unet, noise, coef, dcoef, scale4, clip)
 
 
 @ddim_update.register_fake
@@ -381,71 +439,11 @@ def _exposure_mask_fake(y, low, high, soft=0.0, per_pixel=False):
     return y.new_empty(y.shape)
 
 
-# ---- channel-generic step (the RGB model family: [B,C,H,W] state, [B,Cout,H,W] network output with Cout = C or 2 C)
-def _cc(model_out, x):
-    if model_out.dim() != 4 or model_out.shape[1] not in (x.shape[1], 2 * x.shape[1]):
-        raise OsmosisHipError("osmosis:: the network output must have C or 2 C channels")
-    return x.shape[1], model_out.shape[1]
-
-
-@torch.library.custom_op("osmosis::posterior_c", mutates_args=(), device_types="cuda")
-def posterior_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
-                var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """osmosis::posterior for any channel count (osm_posterior_c); model_out with C channels: the variance processor reads it too."""
-    B, HW = _chw(x)
-    Cc, Cout = _cc(model_out, x)
-    x0, mean, logvar = (torch.empty_like(x) for _ in range(3))
-    ops.posterior_c(model_out.contiguous(), x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind, var_kind)
-    return x0, mean, logvar
-
-
-@posterior_c.register_fake
-def _posterior_c_fake(model_out, x, coef, mean_kind=0, var_kind=0):
-    return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-
-
-@torch.library.custom_op("osmosis::posterior_clip_c", mutates_args=(), device_types="cuda")
-def posterior_clip_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0,
-                     var_kind: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """osmosis::posterior_clip for any channel count."""
-    B, HW = _chw(x)
-    Cc, Cout = _cc(model_out, x)
-    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
-    ops.posterior_c(model_out.contiguous(), x, coef, x0, mean, logvar, B, Cc, Cout, HW, mean_kind, var_kind, x0_raw=raw)
-    return x0, mean, logvar, raw
-
-
-@posterior_clip_c.register_fake
-def _posterior_clip_c_fake(model_out, x, coef, mean_kind=0, var_kind=0):
-    return torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-
-
-@torch.library.custom_op("osmosis::posterior_dynthr_c", mutates_args=(), device_types="cuda")
-def posterior_dynthr_c(model_out: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, mean_kind: int = 0, var_kind: int = 0,
-                       s: float = 0.98) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """osmosis::posterior_dynthr for any channel count (the quantile over all B C H W elements)."""
-    B, HW = _chw(x)
-    Cc, Cout = _cc(model_out, x)
-    x0, mean, logvar, raw = (torch.empty_like(x) for _ in range(4))
-    q, idx = torch.empty(1, device=x.device, dtype=torch.float32), torch.empty(2, device=x.device, dtype=torch.int32)
-    ops.posterior_dynthr_c(model_out.contiguous(), x, coef, x0, mean, logvar, raw, q, idx,
-                           ops.quantile_workspace(x.numel(), x.device), B, Cc, Cout, HW, mean_kind, var_kind, s)
-    return x0, mean, logvar, raw, q, idx
-
-
-@posterior_dynthr_c.register_fake
-def _posterior_dynthr_c_fake(model_out, x, coef, mean_kind=0, var_kind=0, s=0.98):
-    return (torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), x.new_empty((1,)),
-            x.new_empty((2,), dtype=torch.int32))
-
-
+# ---- the `_c` names of the step operators whose schema differs from their twin's (`cout`; `scale` for `scale4`): same implementations
 @torch.library.custom_op("osmosis::posterior_bwd_c", mutates_args=(), device_types="cuda")
 def posterior_bwd_c(g: torch.Tensor, coef: torch.Tensor, cout: int) -> torch.Tensor:
     """d loss / d model_out [B,cout,H,W] from g = d loss / d x0 [B,C,H,W] (osm_posterior_bwd_c); cout = C or 2 C."""
-    B, HW = _chw(g)
-    d_out = torch.empty(B, cout, g.shape[2], g.shape[3], device=g.device, dtype=torch.float32)
-    ops.posterior_bwd_c(g, coef, d_out, B, g.shape[1], cout, HW)
-    return d_out
+    return _posterior_bwd_impl(g, coef, cout)
 
 
 @posterior_bwd_c.register_fake
@@ -456,13 +454,8 @@ def _posterior_bwd_c_fake(g, coef, cout):
 @torch.library.custom_op("osmosis::guide_update_c", mutates_args=(), device_types="cuda")
 def guide_update_c(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor,
                    coef: torch.Tensor, scale: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    """osmosis::guide_update for any channel count; scale: [C]."""
-    B, HW = _chw(mean)
-    if scale.numel() != mean.shape[1]:
-        raise OsmosisHipError("osmosis::guide_update_c: scale must have one entry per channel")
-    x_next, grad = torch.empty_like(mean), torch.empty_like(mean)
-    ops.guide_update_c(mean, log_variance, g, dx_unet, noise, coef, scale, clip, x_next, grad, B, mean.shape[1], HW)
-    return x_next, grad
+    """osmosis::guide_update under its `_c` name; scale: [C]."""
+    return _guide_update_impl("osmosis::guide_update_c", mean, log_variance, g, dx_unet, noise, coef, scale, clip)
 
 
 @guide_update_c.register_fake
@@ -474,14 +467,9 @@ def _guide_update_c_fake(mean, log_variance, g, dx_unet, noise, coef, scale, cli
 def guide_update_rng_c(mean: torch.Tensor, log_variance: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, coef: torch.Tensor,
                        scale: torch.Tensor, clip: float, seed: int, step: torch.Tensor, step_offset: int, img0: int,
                        img_stride: int, sub: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """osmosis::guide_update_rng for any channel count (counter word 0 = element / 4 within the image's C H W elements)."""
-    B, HW = _chw(mean)
-    if scale.numel() != mean.shape[1]:
-        raise OsmosisHipError("osmosis::guide_update_rng_c: scale must have one entry per channel")
-    x_next, grad, noise = torch.empty_like(mean), torch.empty_like(mean), torch.empty_like(mean)
-    ops.guide_update_rng_c(mean, log_variance, g, dx_unet, coef, scale, clip, x_next, grad, noise, B, mean.shape[1], HW, seed, step,
-                           step_offset=step_offset, sub=sub, img0=img0, img_stride=img_stride)
-    return x_next, grad, noise
+    """osmosis::guide_update_rng under its `_c` name (counter word 0 = element / 4 within the image's C H W elements)."""
+    return _guide_update_rng_impl("osmosis::guide_update_rng_c", mean, log_variance, g, dx_unet, coef, scale, clip, seed, step,
+                                  step_offset, img0, img_stride, sub)
 
 
 @guide_update_rng_c.register_fake
@@ -492,13 +480,8 @@ def _guide_update_rng_c_fake(mean, log_variance, g, dx_unet, coef, scale, clip, 
 @torch.library.custom_op("osmosis::ddim_update_c", mutates_args=(), device_types="cuda")
 def ddim_update_c(x0: torch.Tensor, x: torch.Tensor, g: torch.Tensor, dx_unet: torch.Tensor, noise: torch.Tensor, coef: torch.Tensor,
                   dcoef: torch.Tensor, scale: torch.Tensor, clip: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    """osmosis::ddim_update for any channel count; scale: [C]."""
-    B, HW = _chw(x0)
-    if scale.numel() != x0.shape[1]:
-        raise OsmosisHipError("osmosis::ddim_update_c: scale must have one entry per channel")
-    x_next, grad = torch.empty_like(x0), torch.empty_like(x0)
-    ops.ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad, B, x0.shape[1], HW)
-    return x_next, grad
+    """osmosis::ddim_update under its `_c` name; scale: [C]."""
+    return _ddim_update_impl("osmosis::ddim_update_c", x0, x, g, dx_unet, noise, coef, dcoef, scale, clip)
 
 
 @ddim_update_c.register_fake
