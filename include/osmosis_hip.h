@@ -187,7 +187,9 @@ typedef struct osm_attn_desc {
  * logits / probabilities stay in registers, fp32 operands are split into 3 bf16 planes (6 MFMAs per product, fp32-class),
  * softmax in fp32.  Forward writes `out` and lse[B*heads][T] (max + log-sum of the scaled logits of each query row);
  * backward takes that lse and the forward output (for delta = rowsum(d(out) * out), scratch `delta` [B*heads][T]),
- * recomputes P and writes dq | dk | dv into dqkv. */
+ * recomputes P and writes dq | dk | dv into dqkv.  Refused: other shapes, q / k / v columns, ldqkv or (when dout is given)
+ * lddout that are no multiple of 4 floats, and a row stride of the forward output (d->ldout forward, `ldout` backward)
+ * below heads * 64. */
 int osm_attn_flash_supported(int T, int ch);
 int osm_attn_flash_fwd(const osm_attn_desc* d, float* lse, void* stream);
 int osm_attn_flash_bwd(const osm_attn_desc* d, const float* out, long long ldout, const float* lse, float* delta,

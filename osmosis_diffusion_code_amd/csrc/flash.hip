@@ -910,7 +910,8 @@ int max_waves() {
 }
 int nw_of(int T) { return T >= 256 && T % 256 == 0 && max_waves() == 8 ? 8 : (T >= 128 ? 4 : (T >= 64 ? 2 : 1)); }
 
-int check(const osm_attn_desc* d, const char* who) {
+// ldout: row stride of the forward output (forward: the one it writes; backward: the one it reads for delta)
+int check(const osm_attn_desc* d, long long ldout, const char* who) {
   OSM_REQUIRE(d && d->qkv, "%s: null pointer", who);
   OSM_REQUIRE(d->ch == DH && d->T >= 64 && d->T % (32 * nw_of(d->T)) == 0,
               "%s: needs 64-wide heads and T a multiple of 64 (of 128 from T = 128) (got ch %d, T %d)", who, d->ch, d->T);
@@ -918,6 +919,8 @@ int check(const osm_attn_desc* d, const char* who) {
   OSM_REQUIRE(d->arith >= 0 && d->arith <= 2, "%s: arith must be 0 (bf16x6), 1 (fp16) or 2 (f16x3)", who);
   OSM_REQUIRE(d->ldqkv % 4 == 0 && d->q_off % 4 == 0 && d->k_off % 4 == 0 && d->v_off % 4 == 0 && d->head_stride % 4 == 0 &&
               osm::aligned16(d->qkv), "%s: qkv columns must be 16-byte aligned", who);
+  OSM_REQUIRE(ldout >= (long long)d->heads * DH, "%s: bad output (ld %lld < heads * 64)", who, ldout);   // as attention.hip's check
+  OSM_REQUIRE(!d->dout || (d->lddout % 4 == 0 && osm::aligned16(d->dout)), "%s: dout must be 16-byte aligned", who);
   return OSM_OK;
 }
 
@@ -935,7 +938,7 @@ FlashArgs to_args(const osm_attn_desc* d) {
 extern "C" int osm_attn_flash_supported(int T, int ch) { return ch == DH && T >= 64 && T % (32 * nw_of(T)) == 0; }
 
 extern "C" int osm_attn_flash_fwd(const osm_attn_desc* d, float* lse, void* stream) {
-  int rc = check(d, "osm_attn_flash_fwd");
+  int rc = check(d, d ? d->ldout : 0, "osm_attn_flash_fwd");
   if (rc) return rc;
   OSM_REQUIRE(d->out && lse, "osm_attn_flash_fwd: null pointer");
   FlashArgs a = to_args(d);
@@ -965,7 +968,7 @@ extern "C" int osm_attn_flash_fwd(const osm_attn_desc* d, float* lse, void* stre
 
 extern "C" int osm_attn_flash_bwd(const osm_attn_desc* d, const float* out, long long ldout, const float* lse, float* delta,
                                   void* stream) {
-  int rc = check(d, "osm_attn_flash_bwd");
+  int rc = check(d, ldout, "osm_attn_flash_bwd");
   if (rc) return rc;
   OSM_REQUIRE(d->dout && d->dqkv && out && lse && delta, "osm_attn_flash_bwd: null pointer");
   OSM_REQUIRE(d->lddout % 4 == 0 && osm::aligned16(d->dout), "osm_attn_flash_bwd: dout must be 16-byte aligned");
