@@ -1,5 +1,5 @@
-"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h and
-include/osmosis_physlin.h).
+"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
+include/osmosis_physlin.h, include/osmosis_physgroup.h and include/osmosis_blind.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -224,6 +224,14 @@ _SIGS_PHYSGROUP = {
                                 _P, _P, _I, _I, _P, _P],
 }
 EXPORTS_PHYSGROUP = sorted(_SIGS_PHYSGROUP)
+# the entry points of the sixth header, include/osmosis_blind.h (blind deblurring: the tap gradient of a PSF and its projected step)
+_D = C.c_double
+_SIGS_BLIND = {
+    "osm_psf_tap_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _I, _I, _P, _P],
+    "osm_psf_tap_step": [_P, _P, _P, _I, _I, _I, _LL, _D, _D, _P],
+    "osm_ps_blind_optimize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
+}
+EXPORTS_BLIND = sorted(_SIGS_BLIND)
 
 _lib = None
 _lock = threading.Lock()
@@ -243,7 +251,7 @@ def load():
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
-                    list(_SIGS_PHYSGROUP.items()):
+                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

@@ -518,8 +518,15 @@ class PosteriorSampling(ConditioningMethod):
         self.scale = _parse_scale(kwargs.get("scale", 1.0))
         self._states = {}
 
+    def _blind(self):
+        """The operator when it is a `blind_blur` that learns its PSF (its data term steps the weights and couples the batch), else None."""
+        from .measurements import BlindBlurOperator
+        return self.operator if isinstance(self.operator, BlindBlurOperator) and self.operator.learn else None
+
     def hip_ok(self, channels: int = 4) -> bool:
         from .measurements import GRID_OPERATORS, _IdentityOperator
+        if self._blind() is not None and getattr(self.noiser, "__name__", None) == "poisson":
+            raise NotImplementedError("blind_blur learns its PSF on the gaussian data term only: the poisson noiser is not supported")
         return isinstance(self.operator, (_IdentityOperator,) + GRID_OPERATORS) and \
             getattr(self.noiser, "__name__", None) == "gaussian" and self.scale.numel() in (1, channels)
 
@@ -539,6 +546,8 @@ class PosteriorSampling(ConditioningMethod):
         loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`); a `PSFOperator` (motion blur, a
         measured point-spread function) goes the same way with its own kernel."""
         from .measurements import GRID_OPERATORS
+        if self._blind() is not None:
+            return self._loss_grad_x0_blind(x0, y, g_out, loss_out, mask)
         if isinstance(self.operator, GRID_OPERATORS):
             return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask)
         B, C, HW = x0.shape[0], x0.shape[1], x0.shape[2] * x0.shape[3]
@@ -617,7 +626,64 @@ class PosteriorSampling(ConditioningMethod):
             ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)
         return g.view(x0.shape), loss
 
+    def _loss_grad_x0_blind(self, x0, y, g_out=None, loss_out=None, mask=None):
+        """The data term through a `blind_blur` operator that learns its PSF: ONE call over the whole batch (the PSF is shared), the
+        operator's n_iter inner iterations of  Ax = A(w) x0[:, 0:3];  loss, r = d loss / d Ax;  the tap gradient c = corr(r, x0);
+        on the last iteration g[:, 0:3] = A(w)^T r;  the projected step of w  -- enqueued by one C call (osm_ps_blind_optimize,
+        5 n_iter + 1 launches, no host sync); OSM_PHYS_PY_LOOP=1 walks the single-launch entry points.  loss and g are those before
+        the last step of w, as the Osmosis conditioner treats phi."""
+        op = self.operator
+        B, C, H, W = x0.shape
+        op.out_shape(H, W)
+        if C not in (3, 4) or tuple(y.shape) != (B, 3, H, W):
+            raise ValueError(f"expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,{H},{W}], got {tuple(x0.shape)} and {tuple(y.shape)}")
+        HW = H * W
+        dy, dx, w = op.taps(x0.device)
+        Ry, Rx = op.radius()
+        T, nparts = int(w.numel()), ops.tap_grad_nparts(3, H, W)
+        key = ("blind", B, H, W, str(x0.device), C)
+        st = self._states.get(key)
+        if st is None or st["tpart"].numel() < B * nparts * T:
+            f32 = dict(device=x0.device, dtype=torch.float32)
+            st = {"part": torch.empty(B * ops.phys_nblk(HW), **f32), "loss": torch.zeros(B, **f32), "g": torch.empty(B, C, HW, **f32),
+                  "Ax": torch.empty(B, 3, HW, **f32), "r": torch.empty(B, 3, HW, **f32), "tpart": torch.empty(B * nparts * T, **f32)}
+            self._states.pop(key, None)
+            while len(self._states) >= 4:
+                self._states.pop(next(iter(self._states)))
+            self._states[key] = st
+        g = g_out if g_out is not None else st["g"]
+        loss = loss_out if loss_out is not None else st["loss"]
+        if mask is None:
+            mask = self.measurement_mask(B, HW, x0.device)
+        x0, y = x0.contiguous(), y.contiguous()
+        Ax, r, tpart = st["Ax"], st["r"], st["tpart"]
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            ops.ps_blind_optimize(x0, y, mask, dy, dx, w, Ry, Rx, B, C, H, W, Ax, r, st["part"], tpart, loss, g, op.n_iter, op.eta, op.l1)
+            return g.view(x0.shape), loss
+        for it in range(op.n_iter):
+            ops.psf_apply(x0, Ax, dy, dx, w, Ry, Rx, B, 3, C * HW, 3 * HW, H, W)
+            if mask is not None:
+                ops.ps_loss_grad_mc(Ax, y, mask, st["part"], loss, r, B, 3, HW)
+            else:
+                ops.ps_loss_grad_c(Ax, y, st["part"], loss, r, B, 3, HW)
+            ops.psf_tap_grad(x0, r, dy, dx, Ry, Rx, B, 3, C * HW, 3 * HW, H, W, tpart)
+            if it == op.n_iter - 1:
+                ops.psf_apply(r, g, dy, dx, w, Ry, Rx, B, 3, 3 * HW, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+            ops.psf_tap_step(w, tpart, loss, B, nparts, 3 * HW, op.eta, op.l1)
+        return g.view(x0.shape), loss
+
     def conditioning(self, x_prev, x_t, x_0_hat, measurement, **kwargs):
+        if self._blind() is not None:
+            # the PSF is stepped by kernels, not by autograd: the data term's x0-gradient from `loss_grad_x0`, pulled back through
+            # the network by autograd (the form the Osmosis conditioner uses)
+            self.hip_ok(x_0_hat.shape[1])
+            g, loss = self.loss_grad_x0(x_0_hat.detach(), measurement)
+            if x_prev.grad is not None:
+                x_prev.grad = None
+            x_0_hat.backward(gradient=g.clone(), inputs=[x_prev])
+            with torch.no_grad():
+                x_t -= x_prev.grad * self.scale[None, ..., None, None].to(x_prev.device)
+            return x_t, loss.detach().clone()
         norm_grad, norm = self.grad_and_value(x_prev=x_prev, x_0_hat=x_0_hat, measurement=measurement, **kwargs)
         with torch.no_grad():
             x_t -= norm_grad * self.scale[None, ..., None, None].to(x_prev.device)

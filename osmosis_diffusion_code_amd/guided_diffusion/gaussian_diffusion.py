@@ -519,7 +519,9 @@ class GaussianDiffusion:
         sub-step runs every chunk's forward + posterior, then ONE data term over the whole batch (one phi step per group and inner
         iteration, osm_phys_optimize_g), then every chunk's backward + update.  With one chunk that is the ungrouped launch order
         with the grouped call in the data term's place; with more, each chunk's forward is re-run before its backward (the engine
-        keeps one pass's activations): ONE EXTRA FORWARD per chunk per guided sub-step.  Ungrouped chains keep their launch sequence."""
+        keeps one pass's activations): ONE EXTRA FORWARD per chunk per guided sub-step.  Ungrouped chains keep their launch sequence.
+        The 'ps' branch takes the same walk for an operator with `couples_batch` (`blind_blur`: the learnt PSF is shared by the batch,
+        so its step pools every image's tap gradient -- ONE `loss_grad_x0` over [0, B))."""
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
         ddim = ps and not mean_only and getattr(type(self), "p_sample", None) is DDIM.p_sample
@@ -559,7 +561,10 @@ class GaussianDiffusion:
         # downsampling operator of the 'ps' branch)
         mask = cond.measurement_mask(B, y.shape[2] * y.shape[3] if y.dim() == 4 else HW, dev)
         phi = None if ps else cond.operator.phi
-        grouped = not ps and getattr(cond.operator, "group_sizes", None) is not None
+        # a data term that couples the images of the batch: shared water parameters, or on the 'ps' branch an operator with
+        # `couples_batch` (`blind_blur`: one learnt PSF for all images)
+        grouped = (not ps and getattr(cond.operator, "group_sizes", None) is not None) or \
+            (ps and bool(getattr(cond.operator, "couples_batch", False)))
         x_state = eng.x_in if single else torch.empty(B, C, H, W, **f32)
         x_state.copy_(x_start.detach())
         shared = bool(kwargs.get("shared_noise", False)) and B > 1   # every image receives the SAME noise (separately seeded batch-1 runs)

@@ -17,6 +17,7 @@ Device state: `phi` is ONE fp32 device tensor [B][9] = phi_a[3] | phi_b[3] | phi
 replicated).  It is read and updated in place by osm_phys_* kernels (csrc/guidance.hip); the
 Python object never syncs with the device unless the caller asks for values.
 """
+import os
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -332,8 +333,11 @@ class PSFOperator(LinearOperator):
         device = torch.device(device if device is not None else self.device)
         t = self._dev.get(str(device))
         if t is None:
-            t = self._dev[str(device)] = tuple(torch.from_numpy(a).to(device).contiguous() for a in self.host_taps())
+            t = self._dev[str(device)] = tuple(self._to_device(a, device) for a in self.host_taps())
         return t
+
+    def _to_device(self, a, device):
+        return torch.from_numpy(a).to(device).contiguous()
 
     def out_shape(self, H, W):
         Ry, Rx = self.radius()
@@ -446,6 +450,130 @@ class PSFBlurOperator(PSFOperator):
         return self._kernel
 
 
+BLIND_MAX_KERNEL = 61      # the largest side of a learnt PSF (the window a workgroup of osm_psf_tap_grad stages: halo <= 32 per side)
+
+
+def blind_init_kernel(kernel_size=31, init="gaussian", init_sigma=None):
+    """The starting point of a learnt PSF, float64 [k, k], non-negative, summing to 1: `init` is 'gaussian' (standard deviation
+    `init_sigma`, default k / 6, sampled at the pixel centres), 'delta' (the identity), 'uniform', or a kernel of the user's -- a
+    2-D array, a nested list or the path of a .npy file (`check_kernel2d`; no side larger than k; centred in the k x k support)."""
+    k = kernel_size
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k % 2 == 0:
+        raise ValueError(f"blind_blur: kernel_size must be a positive odd integer, got {kernel_size!r}")
+    k = int(k)
+    if k > BLIND_MAX_KERNEL:
+        raise ValueError(f"blind_blur: kernel_size {k} is larger than {BLIND_MAX_KERNEL}, the largest support the tap-gradient kernel stages")
+    if isinstance(init, str) and init in ("gaussian", "delta", "uniform"):
+        if init == "gaussian":
+            sigma = k / 6.0 if init_sigma is None else float(init_sigma)
+            if not (np.isfinite(sigma) and sigma > 0):
+                raise ValueError(f"blind_blur: init_sigma must be a positive number, got {init_sigma!r}")
+            a = np.arange(k, dtype=np.float64) - k // 2
+            ker = np.exp(-(a[:, None] ** 2 + a[None, :] ** 2) / (2.0 * sigma * sigma))
+        elif init == "delta":
+            ker = np.zeros((k, k), dtype=np.float64)
+            ker[k // 2, k // 2] = 1.0
+        else:
+            ker = np.ones((k, k), dtype=np.float64)
+    else:
+        if isinstance(init, (str, bytes)) or hasattr(init, "__fspath__"):
+            if not str(os.fspath(init) if hasattr(init, "__fspath__") else init).endswith(".npy"):
+                raise ValueError(f"blind_blur: init must be 'gaussian', 'delta', 'uniform', a 2-D array or the path of a .npy file, got {init!r}")
+            init = np.load(init, allow_pickle=False)
+        if isinstance(init, torch.Tensor):
+            init = init.detach().cpu().numpy()
+        given = check_kernel2d(init, "blind_blur")
+        if (given < 0).any():
+            raise ValueError("blind_blur: the init kernel must be non-negative (the estimate lives on the simplex)")
+        kh, kw = given.shape
+        if kh > k or kw > k:
+            raise ValueError(f"blind_blur: the init kernel {kh} x {kw} is larger than kernel_size {k}")
+        ker = np.zeros((k, k), dtype=np.float64)
+        ker[(k - kh) // 2:(k - kh) // 2 + kh, (k - kw) // 2:(k - kw) // 2 + kw] = given
+    return ker / ker.sum()
+
+
+@register_operator(name="blind_blur")
+class BlindBlurOperator(PSFOperator):
+    """Blind deblurring: blur with ONE unknown 2-D point-spread function on the dense support kernel_size x kernel_size (T = k^2 taps
+    in row-major order, Ry = Rx = k // 2) whose weights are LEARNT during sampling: they live in a device tensor `w` fp32 [T] that
+    the step kernel overwrites between the network's forward and backward, with no host sync (osm_ps_blind_optimize,
+    include/osmosis_blind.h: a projected gradient step on Q(w) = sum_b ||M (y_b - A(w) x0_b)||^2 / (2 * 3 h w) per inner iteration).
+    The PSF is shared by the batch (`couples_batch`): a batch is photos through one optical system, a single shaken photo is B = 1 --
+    `restore_images(batch_size > 1)` over photos with unrelated shakes is the wrong model (one kernel would be fitted to all).
+    Config keys: kernel_size (odd, <= 61, default 31); init ('gaussian' with init_sigma default kernel_size / 6, 'delta', 'uniform',
+    or a kernel: array / nested list / .npy path, non-negative, normalised to sum 1 in float64); eta (step size, 0.1), n_iter (inner
+    iterations per guided sub-step, 1), l1 (sparsity shrinkage, 0.0); learn (True).  The defaults are parameters, not tuned values.
+    `learn: False` IS `psf_blur` with the init kernel (its non-zero taps, the three-launch data term, nothing stepped); the driver
+    still treats it by its name: `simulate: True` needs `simulate_with`, so that switching `learn` does not change the measurement.
+    An unknown config key raises ValueError.
+    `taps(device)` returns (dy, dx, w_live); `forward` / `transpose` apply the current estimate; `kernel2d()` copies it from the
+    device on demand only; `reset()` puts the initial weights back (same tensors: recorded launches stay valid)."""
+
+    couples_batch = True
+
+    DRIVER_KEYS = ("simulate", "simulate_with")       # read by `sampling.restore_image`, not by the operator
+
+    def __init__(self, device, kernel_size=31, init="gaussian", init_sigma=None, eta=0.1, n_iter=1, l1=0.0, learn=True, batch_size=1,
+                 **kwargs):
+        unknown = sorted(set(kwargs) - set(self.DRIVER_KEYS))
+        if unknown:                                   # (a mistyped `n_iters` would otherwise run with the default, silently)
+            raise ValueError(f"blind_blur: unknown config key(s) {unknown} (known: kernel_size, init, init_sigma, eta, n_iter, l1, learn, "
+                             f"simulate, simulate_with)")
+        super().__init__(device, batch_size, **kwargs)
+        self._init = blind_init_kernel(kernel_size, init, init_sigma)
+        self.kernel_size = int(kernel_size)
+        self.eta, self.l1 = float(eta), float(l1)
+        if not (np.isfinite(self.eta) and self.eta >= 0.0):
+            raise ValueError(f"blind_blur: eta must be a finite number >= 0, got {eta!r}")
+        if not (np.isfinite(self.l1) and self.l1 >= 0.0):
+            raise ValueError(f"blind_blur: l1 must be a finite number >= 0, got {l1!r}")
+        if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 1:
+            raise ValueError(f"blind_blur: n_iter must be an integer >= 1, got {n_iter!r}")
+        self.n_iter = int(n_iter)
+        self.learn = bool(learn)
+        self.couples_batch = self.learn          # (a fixed kernel leaves the images of a batch independent)
+
+    def host_taps(self):
+        if not self.learn:
+            return super().host_taps()           # the init kernel's non-zeros: psf_blur
+        if self._host is None:
+            k = self.kernel_size
+            iy, ix = np.divmod(np.arange(k * k), k)
+            self._host = ((iy - k // 2).astype(np.int32), (ix - k // 2).astype(np.int32), self._init.reshape(-1).astype(np.float32))
+        return self._host
+
+    def radius(self):
+        if not self.learn:
+            return super().radius()
+        return self.kernel_size // 2, self.kernel_size // 2
+
+    def _to_device(self, a, device):
+        # the live weights are a copy of their own: on the CPU `from_numpy` would alias the host's init, which `reset()` reads
+        return super()._to_device(a.copy() if self.learn else a, device)
+
+    def kernel2d(self):
+        """The current estimate, float64 [k, k] (one device-to-host copy, made here and nowhere else); not learning: the init.
+        The weights are read from where the data term stepped them: the tensors `taps(device)` made for the operator's own device
+        ('cuda' and 'cuda:0' are different keys there: an index-less device finds them all the same), else the ones made last."""
+        if not self.learn:
+            return self._init.copy()
+        t = self._dev.get(str(self.device))
+        if t is None and self._dev:
+            same = [v for v in self._dev.values() if v[2].device.type == self.device.type]
+            t = (same or list(self._dev.values()))[-1]
+        if t is None:
+            return self.host_taps()[2].astype(np.float64).reshape(self._init.shape)
+        return t[2].detach().cpu().numpy().astype(np.float64).reshape(self._init.shape)
+
+    def reset(self):
+        """Put the initial weights back on every device the operator lives on, in place."""
+        if self.learn:
+            for dev, (_, _, w) in self._dev.items():
+                w.copy_(torch.from_numpy(self.host_taps()[2]))
+        return self
+
+
 class LearnableOperator(ABC):
     @abstractmethod
     def forward(self, data, **kwargs):
@@ -481,11 +609,15 @@ def _check_optimizer(name):
 def build_degradation(degradation, device, batch_size=1):
     """The linear operator between a physical image-formation model and the photo (`_PhysicalOperator(degradation=)`): None, an
     operator instance (handed through as it is), or a dict {name: <a registered blur / super-resolution / PSF operator>, ...its
-    keys} built here.  NameError for a name nobody registered, ValueError for one that is no `GRID_OPERATORS` class."""
+    keys} built here.  NameError for a name nobody registered, ValueError for one that is no `GRID_OPERATORS` class and for
+    'blind_blur' (by name: it is a `PSFOperator`, but a learnt PSF inside the water / haze model is out of scope)."""
     if degradation is None or not isinstance(degradation, dict):
         return degradation
     cfg = dict(degradation)
     name = cfg.pop("name", None)
+    if name == "blind_blur":
+        raise ValueError("degradation: 'blind_blur' (a learnt PSF) inside a physical image-formation model is not supported -- its "
+                         "weights and the water / haze parameters would have to be stepped together; give a fixed 'psf_blur' kernel")
     cls = __OPERATOR__.get(name)
     grid = sorted(n for n, c in __OPERATOR__.items() if issubclass(c, GRID_OPERATORS))
     if cls is None:

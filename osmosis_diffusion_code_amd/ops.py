@@ -720,6 +720,74 @@ def psf_apply(x, out, dy, dx, w, Ry, Rx, B, P, x_img_stride, out_img_stride, H, 
          int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(), keep=(x, out, dy, dx, w))
 
 
+# ----------------------------------------------------------------------------- blind deblurring (include/osmosis_blind.h)
+BLIND_MAX_TAPS = 4225
+BLIND_MAX_RADIUS = 32
+
+
+def tap_grad_nparts(P, H, W):
+    """Partials per image osm_psf_tap_grad writes for P planes of H x W: one per 32 x 32 tile and plane."""
+    return int(P) * (-(-int(H) // 32)) * (-(-int(W) // 32))
+
+
+def _check_tap_lists(name, dy, dx, w=None):
+    for d in (dy, dx):
+        if d.dtype != torch.int32 or not d.is_contiguous() or d.dim() != 1 or d.shape[0] != dy.shape[0]:
+            raise _lib.OsmosisHipError(f"{name}: a tap list is dy, dx int32 [T], got {tuple(d.shape)} {d.dtype}")
+    if w is not None and (w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 1 or w.shape[0] != dy.shape[0]):
+        raise _lib.OsmosisHipError(f"{name}: the weights are fp32 [T = {dy.shape[0]}], got {tuple(w.shape)} {w.dtype}")
+
+
+def psf_tap_grad(x, r, dy, dx, Ry, Rx, B, P, x_img_stride, r_img_stride, H, W, part):
+    """part[b][q][t] = the tile partials of c_b[t] = sum_p sum_ij r[b,p,i,j] x[b,p,refl(i+dy[t]),refl(j+dx[t])] (osm_psf_tap_grad,
+    include/osmosis_blind.h): q = p ntiles + tile, `tap_grad_nparts(P, H, W)` per image; c is their sum (fp64 in `psf_tap_step`).
+    x / r: contiguous fp32 with image strides in elements; part fp32 with at least B nparts T elements, every one written.
+    Deterministic (gather form, no atomics)."""
+    for t in (x, r, part):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_tap_grad takes contiguous fp32 tensors")
+    _check_tap_lists("psf_tap_grad", dy, dx)
+    B, P, H, W, T = int(B), int(P), int(H), int(W), int(dy.shape[0])
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * H * W or r.numel() < (B - 1) * int(r_img_stride) + P * H * W
+                   or part.numel() < B * tap_grad_nparts(P, H, W) * T):
+        raise _lib.OsmosisHipError(f"psf_tap_grad: x ({x.numel()} elements) / r ({r.numel()}) / part ({part.numel()}) are smaller than "
+                                   f"{B} images of {P} x {H} x {W} at strides {x_img_stride} / {r_img_stride} with {T} taps")
+    call("osm_psf_tap_grad", ptr(x), ptr(r), ptr(dy), ptr(dx), T, int(Ry), int(Rx), B, P, int(x_img_stride), int(r_img_stride), H, W,
+         ptr(part), _s(), keep=(x, r, dy, dx, part))
+
+
+def psf_tap_step(w, part, loss, B, nparts, hw3, eta, l1=0.0):
+    """One projected step of the PSF weights w fp32 [T], in place (osm_psf_tap_step): fp64 throughout, g = sum_b loss[b] c_b / hw3,
+    u = max(w - eta (g - mean g) - eta l1, 0), w = u / sum u -- left untouched when the sum is 0 or not finite."""
+    for t in (w, part, loss):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_tap_step takes contiguous fp32 tensors")
+    B, nparts, T = int(B), int(nparts), int(w.numel())
+    if B >= 1 and (part.numel() < B * nparts * T or loss.numel() < B):
+        raise _lib.OsmosisHipError(f"psf_tap_step: part ({part.numel()} elements) / loss ({loss.numel()}) are smaller than {B} x {nparts} x {T} / {B}")
+    call("osm_psf_tap_step", ptr(w), ptr(part), ptr(loss), B, nparts, T, int(hw3), float(eta), float(l1), _s(), keep=(w, part, loss))
+
+
+def ps_blind_optimize(x0, y, mask, dy, dx, w, Ry, Rx, B, Cc, H, W, Ax, r, lpart, tpart, loss, g, n_iter, eta, l1=0.0):
+    """One guided sub-step of the 'ps' data term through a PSF whose weights are learnt, enqueued by one call
+    (osm_ps_blind_optimize): n_iter x (A, loss / r, tap gradient, step of w), loss and g = A^T r those before the last step."""
+    B, Cc, H, W, T = int(B), int(Cc), int(H), int(W), int(dy.shape[0])
+    HW = H * W
+    _check_tap_lists("ps_blind_optimize", dy, dx, w)
+    need = dict(x0=B * Cc * HW, y=B * 3 * HW, Ax=B * 3 * HW, r=B * 3 * HW, lpart=B * phys_nblk(HW), tpart=B * tap_grad_nparts(3, H, W) * T,
+                loss=B, g=B * Cc * HW)
+    if mask is not None:
+        need["mask"] = B * 3 * HW
+    have = dict(x0=x0, y=y, Ax=Ax, r=r, lpart=lpart, tpart=tpart, loss=loss, g=g, mask=mask)
+    for k, n in need.items():
+        t = have[k]
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise _lib.OsmosisHipError(f"ps_blind_optimize: {k} must be contiguous fp32 with at least {n} elements, got {tuple(t.shape)} {t.dtype}")
+    call("osm_ps_blind_optimize", ptr(x0), ptr(y), ptr(mask), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), B, Cc, H, W, ptr(Ax), ptr(r),
+         ptr(lpart), ptr(tpart), ptr(loss), ptr(g), int(n_iter), float(eta), float(l1), _s(),
+         keep=(x0, y, mask, dy, dx, w, Ax, r, lpart, tpart, loss, g))
+
+
 # ----------------------------------------------------------------------------- the water / haze data term through a linear operator
 def lin_desc(operator, H, W, device) -> LinDesc:
     """The osm_lin_desc of a `measurements.GRID_OPERATORS` instance at the image grid H x W (include/osmosis_physlin.h).  The device

@@ -217,6 +217,11 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         os.makedirs(d, exist_ok=True)
         paths["mask"] = os.path.join(d, f"{name}_mask.png")
         Image.fromarray(_to_pil_u8(post["mask"][0].clamp(0, 1)), mode="RGB").save(paths["mask"])
+    if save_singles and post.get("kernel") is not None:     # only a `blind_blur` chain: the learnt PSF
+        d = os.path.join(out_dir, "single_images", "kernel")
+        os.makedirs(d, exist_ok=True)
+        paths["kernel"] = os.path.join(d, f"{name}_kernel.png")
+        Image.fromarray(kernel_image_u8(post["kernel"]), mode="L").save(paths["kernel"])
     if save_grids:
         d = os.path.join(out_dir, "grid_results")
         os.makedirs(d, exist_ok=True)
@@ -230,6 +235,17 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         paths["depth_full"] = os.path.join(d, f"{name}_depth_full.png")
         Image.fromarray(full_depth_color_u8(full_res), mode="RGB").save(paths["depth_full"])
     return paths
+
+
+def kernel_image_u8(kernel, side=128):
+    """uint8 [k z, k z] picture of a PSF [k, k]: the kernel over its maximum (negative values clamped to 0), every tap replicated to a
+    z x z block of pixels, z = max(1, side // k) -- no interpolation, a tap stays a square."""
+    k = torch.as_tensor(kernel, dtype=torch.float32).clamp(min=0)
+    top = float(k.max())
+    k = k / top if top > 0 else k
+    z = max(1, int(side) // int(max(k.shape)))
+    u8 = (k * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
+    return u8.repeat_interleave(z, dim=0).repeat_interleave(z, dim=1).contiguous().numpy()
 
 
 def full_depth_color_u8(full_res):
@@ -395,7 +411,12 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     `tiling` (or the optional top-level config key `tiling`; the argument wins): `{tile, stride, window}` (`parse_tiling`; unknown
     keys raise) for ONE image larger than the network's grid, e.g. the 512-class grid of `data.fit_transform(size=512)`: the
     network sees overlapping tiles of side `tile`, everything else acts on the whole image (`p_sample_loop(tiling=)`).  Every
-    result then carries `tiling` = {tile, stride, window, origins int32 [n,2]}; without it nothing is passed and there is no such key."""
+    result then carries `tiling` = {tile, stride, window, origins int32 [n,2]}; without it nothing is passed and there is no such key.
+
+    Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
+    carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
+    `simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` -- the blur that makes y = noiser(A* ref); it must keep the
+    image's size.  ONE PSF serves the whole batch: B > 1 means photos through one optical system, not unrelated shakes."""
     tiling = tiling if tiling is not None else cfg.get("tiling")
     tiling_info = None
     if tiling is not None:
@@ -419,10 +440,27 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     pretrain = cfg["unet_model"]["pretrain_model"]
     shape = list(ref_img.shape)
     y_clean = ref_img
+    is_blind = op_cfg.get("name") == "blind_blur"
     if isinstance(operator, GRID_OPERATORS):
         # a blur / super-resolution operator: the measurement is simulated from the clean image, y = noiser(A ref), as the DPS driver
         # does; `measurement.operator.simulate: False` takes ref_img as the measurement itself, on the operator's own grid
-        if op_cfg.get("simulate", True):
+        if op_cfg.get("simulate", True) and is_blind:
+            # the PSF is what the chain looks for, so the operator cannot simulate its own measurement: another grid operator stands
+            # for the unknown optics, y = noiser(A* ref)
+            sim_cfg = op_cfg.get("simulate_with")
+            if not isinstance(sim_cfg, dict) or sim_cfg.get("name") is None:
+                raise ValueError("blind_blur: `simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` (the blur that produces "
+                                 "the measurement); `simulate: False` takes the photo as it is")
+            sim_cfg = dict(sim_cfg)
+            sim_cfg["batch_size"] = ref_img.shape[0]
+            truth = get_operator(device=device, **sim_cfg)
+            if not isinstance(truth, GRID_OPERATORS):
+                raise ValueError(f"blind_blur: simulate_with {sim_cfg['name']!r} is not a linear operator with a grid of its own")
+            if tuple(truth.out_shape(*ref_img.shape[-2:])) != tuple(ref_img.shape[-2:]):
+                raise ValueError(f"blind_blur: simulate_with {sim_cfg['name']!r} changes the image's size {tuple(ref_img.shape[-2:])} -> "
+                                 f"{tuple(truth.out_shape(*ref_img.shape[-2:]))}; a PSF keeps it")
+            y_clean = truth.forward(ref_img[:, 0:3].to(torch.float32).contiguous())
+        elif op_cfg.get("simulate", True):
             y_clean = operator.forward(ref_img[:, 0:3].to(torch.float32).contiguous())
         else:
             grid = model_grid(model, ref_img)
@@ -449,6 +487,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
         torch.manual_seed(cfg.get("manual_seed", 0))
+        if is_blind:
+            operator.reset()        # every global iteration learns the PSF from its initial weights
         if same_seed_per_image and shape[0] > 1:
             x_start = torch.randn([1] + shape[1:], device=device).repeat(shape[0], 1, 1, 1)
             loop_kwargs = dict(loop_kwargs, shared_noise=True)
@@ -468,6 +508,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             results.append(rgb_guidance_result(ret.detach().cpu(), y_n.detach().cpu()))
             if m_dev is not None:
                 results[-1]["mask"] = m_dev.detach().cpu()
+            if is_blind:
+                results[-1]["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
             continue
         sample, variable_dict, loss, out_xstart = ret
         if postprocess_batch:
@@ -483,6 +525,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             post["mask"] = m_dev.detach().cpu()
         if tiling_info is not None:
             post["tiling"] = tiling_info
+        if is_blind:
+            post["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
         results.append(post)
     return results
 
@@ -574,6 +618,9 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
             if full.get("mask") is not None:
                 for b, r in enumerate(res):
                     r["mask"] = full["mask"][b:b + 1]
+            if full.get("kernel") is not None:      # `blind_blur`: ONE PSF was learnt for the batch (photos through one optical system)
+                for r in res:
+                    r["kernel"] = full["kernel"]
         for i, r in zip(idxs, res):
             if shared_water:
                 r["water_group"] = list(idxs)

@@ -806,8 +806,37 @@ def _phys_loss_grad_lin_fake(x0, y, mask, phi, icfg, fcfg, n_inner, freeze_phi, 
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0), torch.empty_like(phi)
 
 
+# ---- blind deblurring: the 'ps' data term through a PSF whose weights are learnt; the only operator here that mutates an argument
+@torch.library.custom_op("osmosis::ps_blind_loss_grad", mutates_args=("w",), device_types="cuda")
+def ps_blind_loss_grad(x0: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor,
+                       Ry: int, Rx: int, n_iter: int, eta: float, l1: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One guided sub-step of a `blind_blur` data term (osm_ps_blind_optimize, include/osmosis_blind.h): x0 [B,C,H,W] (C >= 3),
+    y [B,3,H,W], the optional mask ([B,3,H,W] / [B,1,H,W]), the tap list dy, dx int32 [T] and the weights w fp32 [T], which are
+    STEPPED IN PLACE n_iter times (one PSF for the batch).  Returns (loss [B], g = A(w)^T d loss / d (A x0) on the colour planes, 0
+    beyond), both for the weights before the last step."""
+    name = "osmosis::ps_blind_loss_grad"
+    B, HW = _chw(x0)
+    C, H, W = x0.shape[1], x0.shape[2], x0.shape[3]
+    if C < 3 or tuple(y.shape) != (B, 3, H, W):
+        raise OsmosisHipError(f"{name}: expected x0 [B,C>=3,H,W] and y [B,3,H,W], got {tuple(x0.shape)} and {tuple(y.shape)}")
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape) or tuple(w.shape) != tuple(dy.shape) or not w.is_contiguous():
+        raise OsmosisHipError(f"{name}: expected dy [T], dx [T] and a contiguous w [T], got {tuple(dy.shape)}, {tuple(dx.shape)}, {tuple(w.shape)}")
+    f32 = dict(device=x0.device, dtype=torch.float32)
+    loss, g = torch.zeros(B, **f32), torch.empty_like(x0)
+    ops.ps_blind_optimize(x0.contiguous(), y.contiguous(), None if mask is None else _mask_rows(name, mask, y), dy.contiguous(),
+                          dx.contiguous(), w, Ry, Rx, B, C, H, W, torch.empty(B, 3, HW, **f32), torch.empty(B, 3, HW, **f32),
+                          torch.empty(B * ops.phys_nblk(HW), **f32), torch.empty(B * ops.tap_grad_nparts(3, H, W) * w.numel(), **f32),
+                          loss, g, n_iter, eta, l1)
+    return loss, g
+
+
+@ps_blind_loss_grad.register_fake
+def _ps_blind_loss_grad_fake(x0, y, mask, dy, dx, w, Ry, Rx, n_iter, eta, l1):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad") + OPS_C

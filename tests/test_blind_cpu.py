@@ -1,0 +1,245 @@
+"""Blind deblurring without a GPU: the `blind_blur` operator (registry, validation, init kernels, the refusal inside a physical
+model), the sixth header against `_lib.EXPORTS_BLIND`, the argument checks of the three entry points (they return before a launch),
+and the oracle of tests/blind_oracle.py against itself: its tap correlation against the definition, the linearity identity, and the
+recovery of a known kernel on a convex problem (the image is known, only the PSF is not)."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import blind_oracle as BO
+from osmosis_diffusion_code_amd import _lib
+from osmosis_diffusion_code_amd.guided_diffusion import measurements as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"osm_psf_tap_grad", "osm_psf_tap_step", "osm_ps_blind_optimize"}
+
+
+def blind(**kw):
+    return M.get_operator("blind_blur", device="cpu", **kw)
+
+
+def test_operator_is_registered_a_psf_operator_and_couples_the_batch():
+    op = blind()
+    assert isinstance(op, M.PSFOperator) and isinstance(op, M.GRID_OPERATORS) and op.__name__ == "blind_blur"
+    assert M.GRID_OPERATORS == (M.SeparableOperator, M.PSFOperator)
+    assert op.couples_batch is True and M.BlindBlurOperator.couples_batch is True
+    assert (op.kernel_size, op.eta, op.n_iter, op.l1, op.learn) == (31, 0.1, 1, 0.0, True)
+    assert op.radius() == (15, 15) and op.out_shape(40, 50) == (40, 50)
+    dy, dx, w = op.taps("cpu")
+    assert dy.dtype == dx.dtype == torch.int32 and w.dtype == torch.float32 and dy.shape == dx.shape == w.shape == (31 * 31,)
+    # dense, row-major
+    assert dy[:32].tolist() == [-15] * 31 + [-14] and dx[:32].tolist() == list(range(-15, 16)) + [-15]
+    with pytest.raises(ValueError, match="reflection"):
+        op.out_shape(15, 64)
+    # a fixed kernel leaves the images independent and IS psf_blur with the init kernel (its non-zero taps)
+    fixed = blind(kernel_size=5, init="delta", learn=False)
+    assert fixed.couples_batch is False and fixed.radius() == (0, 0) and fixed.host_taps()[2].tolist() == [1.0]
+    init = M.blind_init_kernel(9, "gaussian", 1.5)
+    a, b = blind(kernel_size=9, init_sigma=1.5, learn=False), M.get_operator("psf_blur", device="cpu", kernel=init, normalize=False)
+    for s, t in zip(a.host_taps(), b.host_taps()):
+        assert np.array_equal(s, t)
+    assert a.radius() == b.radius()
+
+
+def test_init_kernels_and_reset():
+    for name in ("gaussian", "delta", "uniform"):
+        k = M.blind_init_kernel(7, name)
+        assert k.shape == (7, 7) and k.dtype == np.float64 and (k >= 0).all() and abs(k.sum() - 1.0) < 1e-15
+    a = np.arange(7) - 3.0
+    want = np.exp(-(a[:, None] ** 2 + a[None, :] ** 2) / (2 * (7 / 6.0) ** 2))
+    assert np.allclose(M.blind_init_kernel(7), want / want.sum(), rtol=0, atol=1e-16)
+    assert M.blind_init_kernel(5, "delta")[2, 2] == 1.0 and np.all(M.blind_init_kernel(5, "uniform") == 1.0 / 25)
+    # a kernel of the user's: normalised in float64, centred in the support
+    k = M.blind_init_kernel(5, [[0.0, 2.0, 0.0], [1.0, 4.0, 1.0], [0.0, 0.0, 0.0]])
+    assert k.shape == (5, 5) and k[2, 2] == 0.5 and k[1, 2] == 0.25 and k[0].sum() == 0 and abs(k.sum() - 1) < 1e-15
+    assert np.array_equal(M.blind_init_kernel(3, torch.ones(3, 3)), np.full((3, 3), 1.0 / 9))
+    # the live weights: kernel2d reads them, reset puts the init back into the SAME tensor
+    op = blind(kernel_size=5)
+    w = op.taps("cpu")[2]
+    first = op.kernel2d()
+    assert first.dtype == np.float64 and first.shape == (5, 5) and np.array_equal(first.reshape(-1), op.host_taps()[2].astype(np.float64))
+    w.fill_(0.04)
+    assert np.all(op.kernel2d() == np.float64(np.float32(0.04)))
+    assert op.reset() is op and op.taps("cpu")[2] is w and np.array_equal(op.kernel2d(), first)
+    assert np.array_equal(op.host_taps()[2].astype(np.float64).reshape(5, 5), first)       # (the host copy was never aliased)
+
+
+def test_validation_errors(tmp_path):
+    for bad in (8, 0, -3, 2.5, "9", True):
+        with pytest.raises(ValueError, match="odd"):
+            blind(kernel_size=bad)
+    with pytest.raises(ValueError, match="61"):
+        blind(kernel_size=63)
+    assert blind(kernel_size=61).radius() == (30, 30)
+    with pytest.raises(ValueError, match="init_sigma"):
+        blind(init_sigma=0.0)
+    with pytest.raises(ValueError, match="init"):
+        blind(init="box")
+    with pytest.raises(ValueError, match="non-negative"):
+        blind(kernel_size=3, init=[[0.0, 1.0, 0.0], [0.0, -0.1, 0.0], [0.0, 1.0, 0.0]])
+    with pytest.raises(ValueError, match="odd"):
+        blind(kernel_size=5, init=np.ones((4, 3)))
+    with pytest.raises(ValueError, match="larger"):
+        blind(kernel_size=3, init=np.ones((5, 5)))
+    with pytest.raises(ValueError, match="zero"):
+        blind(kernel_size=3, init=np.zeros((3, 3)))
+    with pytest.raises(ValueError, match="finite"):
+        blind(kernel_size=3, init=np.full((3, 3), np.nan))
+    for key in ("eta", "l1"):
+        for bad in (-1.0, float("nan"), float("inf")):
+            with pytest.raises(ValueError, match=key):
+                blind(**{key: bad})
+    for bad in (0, -1, 1.5):
+        with pytest.raises(ValueError, match="n_iter"):
+            blind(n_iter=bad)
+    with pytest.raises(ValueError, match="n_iters"):                                      # a mistyped key does not run with the default
+        blind(n_iters=3)
+    assert blind(simulate=False, simulate_with=dict(name="motion_blur")).n_iter == 1       # the driver's keys pass through
+    path = os.path.join(tmp_path, "k.npy")
+    np.save(path, np.array([[1.0, 3.0, 0.0]]))
+    assert blind(kernel_size=3, init=path).kernel2d()[1].tolist() == [0.25, 0.75, 0.0]
+
+
+def test_build_degradation_refuses_blind_blur_by_name():
+    with pytest.raises(ValueError, match="blind_blur"):
+        M.build_degradation({"name": "blind_blur", "kernel_size": 5}, "cpu")
+    assert isinstance(M.build_degradation({"name": "psf_blur", "kernel": [[1.0]]}, "cpu"), M.PSFOperator)      # the others still build
+
+
+def test_poisson_noiser_is_refused_and_simulate_needs_its_operator():
+    from osmosis_diffusion_code_amd import sampling
+    from osmosis_diffusion_code_amd.guided_diffusion import condition_methods as CM
+    cond = CM.get_conditioning_method("ps", blind(kernel_size=5), M.get_noise("poisson", rate=1.0), scale="0.3")
+    with pytest.raises(NotImplementedError, match="poisson"):
+        cond.hip_ok(3)
+    assert CM.get_conditioning_method("ps", blind(kernel_size=5), M.get_noise("gaussian", sigma=0.0), scale="0.3").hip_ok(3)
+    fixed = CM.get_conditioning_method("ps", blind(kernel_size=5, learn=False), M.get_noise("poisson", rate=1.0), scale="0.3")
+    assert fixed.hip_ok(3) is False                                                        # a fixed kernel: as psf_blur, the generic loop
+
+    def cfg(**okw):
+        return {"measurement": {"operator": dict(name="blind_blur", kernel_size=5, **okw), "noise": {"name": "gaussian", "sigma": 0.0}},
+                "conditioning": {"method": "ps", "params": dict(scale="0.3")},
+                "diffusion": dict(sampler="ddpm", steps=1000, noise_schedule="linear", model_mean_type="epsilon",
+                                  model_var_type="learned_range", dynamic_threshold=False, clip_denoised=True, rescale_timesteps=False,
+                                  timestep_respacing="4"),
+                "sample_pattern": dict(pattern="original"), "aux_loss": {"aux_loss": None}, "unet_model": {"pretrain_model": "imagenet"},
+                "manual_seed": 0, "rgb_guidance": True}
+    ref = torch.zeros(1, 3, 16, 24)
+    with pytest.raises(ValueError, match="simulate_with"):
+        sampling.restore_image(None, ref, cfg(), device="cpu")
+    with pytest.raises(ValueError, match="size"):
+        sampling.restore_image(None, ref, cfg(simulate_with=dict(name="super_resolution", scale_factor=2)), device="cpu")
+    with pytest.raises(ValueError, match="grid"):
+        sampling.restore_image(None, ref, cfg(simulate_with=dict(name="noise")), device="cpu")
+    assert sampling.measurement_grid({"name": "blind_blur", "kernel_size": 5}, (16, 24)) == (16, 24)
+    pic = sampling.kernel_image_u8(np.array([[0.0, 0.5], [0.25, 0.0]]), side=8)
+    assert pic.shape == (8, 8) and pic.dtype == np.uint8 and (pic[:4, 4:] == 255).all() and (pic[4:, :4] == 128).all() and pic[0, 0] == 0
+
+
+def test_header_exports_and_bindings_agree():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_blind.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", body)) == NAMES == set(_lib.EXPORTS_BLIND)
+    for n in NAMES:
+        decl = re.search(n + r"\s*\(([^)]*)\)", body).group(1)
+        assert len(decl.split(",")) == len(_lib._SIGS_BLIND[n]), n
+    others = [_lib.EXPORTS, _lib.EXPORTS_LINOP, _lib.EXPORTS_PSF, _lib.EXPORTS_PHYSLIN, _lib.EXPORTS_PHYSGROUP]
+    assert not NAMES & set().union(*map(set, others)) and len(_lib.EXPORTS) == 99
+    for other in ("osmosis_hip.h", "osmosis_linop.h", "osmosis_psf.h", "osmosis_physlin.h", "osmosis_physgroup.h"):
+        assert not NAMES & set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", other)).read())), other
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    lib = _lib.load()
+    for n in NAMES:
+        assert hasattr(so, n) and getattr(lib, n).argtypes == _lib._SIGS_BLIND[n]
+    mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
+    assert "blind.hip" in mk and "osmosis_blind.h" in mk
+    assert int(re.search(r"#define OSM_BLIND_MAX_TAPS (\d+)", hdr).group(1)) == 65 * 65
+    from osmosis_diffusion_code_amd import ops, torch_ops
+    assert ops.BLIND_MAX_TAPS == 65 * 65 and ops.tap_grad_nparts(3, 36, 34) == 12 and ops.tap_grad_nparts(3, 32, 32) == 3
+    assert "ps_blind_loss_grad" in torch_ops.OPS and "ps_blind_loss_grad" not in torch_ops.OPS_C
+    schema = str(torch.ops.osmosis.ps_blind_loss_grad.default._schema)
+    assert "Tensor(a5!) w" in schema and schema.endswith("-> (Tensor, Tensor)"), schema          # w, and only w, is mutated
+    assert schema.count("!") == 1
+
+
+def test_entry_points_refuse_bad_arguments_before_any_launch():
+    lib = _lib.load()
+    p = 4096                                                                               # never dereferenced on the host
+
+    def refused(fn, good, changes):
+        for pos, val, word in changes:
+            args = list(good)
+            args[pos] = val
+            rc = getattr(lib, fn)(*args)
+            msg = lib.osm_last_error().decode()
+            assert rc != 0 and msg.startswith(fn + ":") and word in msg, (fn, pos, val, rc, msg)
+    # x, r, dy, dx, T, Ry, Rx, B, P, xs, rs, H, W, part, stream
+    refused("osm_psf_tap_grad", [p, p, p, p, 25, 2, 2, 2, 3, 3 * 64, 3 * 64, 8, 8, p, None],
+            [(0, None, "null"), (1, None, "null"), (2, None, "null"), (3, None, "null"), (13, None, "null"), (4, 0, "tap count"),
+             (5, 33, "Ry"), (6, 33, "Rx"), (5, -1, "Ry"), (5, 8, "reflection"), (6, 8, "reflection"), (7, 0, "batch"), (8, 0, "plane"),
+             (9, 100, "x_img_stride"), (10, 100, "r_img_stride"), (11, 0, "image")])
+    # w, part, loss, B, nparts, T, hw3, eta, l1, stream
+    refused("osm_psf_tap_step", [p, p, p, 2, 3, 25, 192, 0.1, 0.0, None],
+            [(0, None, "null"), (1, None, "null"), (2, None, "null"), (3, 0, "batch"), (4, 0, "partial"), (5, 0, "tap count"),
+             (5, 4226, "tap count"), (6, 0, "hw3"), (7, float("nan"), "NaN")])
+    # x0, y, mask, dy, dx, w, T, Ry, Rx, B, C, H, W, Ax, r, lpart, tpart, loss, g, n_iter, eta, l1, stream
+    good = [p, p, None, p, p, p, 25, 2, 2, 2, 4, 8, 8, p, p, p, p, p, p, 1, 0.1, 0.0, None]
+    refused("osm_ps_blind_optimize", good,
+            [(0, None, "null"), (1, None, "null"), (3, None, "null"), (5, None, "null"), (13, None, "null"), (16, None, "null"), (18, None, "null"),
+             (6, 0, "tap count"), (6, 4226, "tap count"), (7, 33, "Ry"), (7, 8, "reflection"), (8, 8, "reflection"), (9, 0, "batch"),
+             (10, 2, "channel"), (11, 0, "image"), (19, 0, "n_iter"), (20, float("nan"), "NaN")])
+
+
+def test_tap_correlation_of_the_oracle_equals_the_definition_and_is_linear_in_w():
+    """8 x 6 under a 5 x 5 support: both mirrors reach (Rx = 2 on W = 6, and i + dy runs past both edges)."""
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 3, 8, 6, generator=g, dtype=torch.float64)
+    r = torch.randn(2, 3, 8, 6, generator=g, dtype=torch.float64)
+    dy, dx = BO.dense_taps(5)
+    c = BO.tap_corr(r, x, 5, 5).reshape(2, 25).numpy()
+    direct = BO.tap_corr_direct(r, x, dy, dx)
+    assert np.abs(c - direct).max() <= 1e-12
+    # <r, A(w) x> = sum_t w[t] c[t]
+    w = torch.rand(5, 5, generator=g, dtype=torch.float64)
+    lhs = (r * BO.conv_reflect(x, w)).sum(dim=(1, 2, 3)).numpy()
+    assert np.abs(lhs - c @ w.reshape(-1).numpy()).max() <= 1e-12
+    # a 3 x 7 support through the same code
+    dy, dx = (np.repeat(np.arange(3) - 1, 7).astype(np.int32), np.tile(np.arange(7) - 3, 3).astype(np.int32))
+    x2, r2 = torch.randn(1, 3, 9, 8, generator=g, dtype=torch.float64), torch.randn(1, 3, 9, 8, generator=g, dtype=torch.float64)
+    assert np.abs(BO.tap_corr(r2, x2, 3, 7).reshape(1, 21).numpy() - BO.tap_corr_direct(r2, x2, dy, dx)).max() <= 1e-12
+
+
+def test_step_of_the_oracle_keeps_the_simplex_and_its_guards():
+    rng = np.random.default_rng(3)
+    w = rng.random(49).astype(np.float32)
+    w /= w.sum()
+    c = rng.standard_normal((2, 49))
+    new, u, S = BO.step(w, c, [1.5, 0.5], 3 * 36 * 34, 0.1)
+    assert new.dtype == np.float32 and (new >= 0).all() and abs(float(new.astype(np.float64).sum()) - 1) < 1e-6 and not np.array_equal(new, w)
+    assert BO.sum_t(np.arange(3000.0)) == 3000 * 2999 / 2
+    same, _, S = BO.step(w, c, [1.5, 0.5], 3 * 36 * 34, 0.1, l1=1e9)                      # every u clamped to 0
+    assert S == 0.0 and np.array_equal(same, w)
+    same, _, S = BO.step(w, c, [float("nan"), 0.5], 3 * 36 * 34, 0.1)
+    assert np.array_equal(same, w)
+    same, _, S = BO.step(w, c, [float("inf"), 0.5], 3 * 36 * 34, 0.1)
+    assert np.array_equal(same, w)
+
+
+def test_the_oracle_recovers_a_motion_kernel_when_the_image_is_known():
+    """eta = 1.0, n_iter = 200 from a gaussian of sigma 1.5: the final loss is <= 0.25 x the first and the l1 distance to the true kernel
+    <= 0.5 x the init's (in float64 the oracle reaches about 0.08 and 0.18 / 1.0: roughly 3 x room)."""
+    x, y, kstar, w0 = BO.recovery_problem()
+    assert x.shape == (1, 3, 36, 44) and x.dtype == torch.float64
+    res = BO.inner_loop(x, y, None, w0, 7, 7, 200, 1.0)
+    last, _ = BO.loss_and_r(BO.conv_reflect(x, torch.from_numpy(res["w"].astype(np.float64).reshape(7, 7))), y)
+    first, final = float(res["first_loss"][0]), float(last[0])
+    d0, d1 = np.abs(w0.astype(np.float64) - kstar.reshape(-1)).sum(), np.abs(res["w"].astype(np.float64) - kstar.reshape(-1)).sum()
+    print(f"BLINDRECOVERY oracle: loss {first:.3f} -> {final:.3f} ({final / first:.3f}), l1 distance {d0:.3f} -> {d1:.3f}")
+    assert final <= 0.25 * first and d1 <= 0.5 * d0
+    assert abs(float(res["w"].astype(np.float64).sum()) - 1) < 1e-6 and (res["w"] >= 0).all()
