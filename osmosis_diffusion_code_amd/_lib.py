@@ -1,5 +1,5 @@
 """ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
-include/osmosis_physlin.h, include/osmosis_physgroup.h and include/osmosis_blind.h).
+include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h and include/osmosis_depthprior.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -92,6 +92,12 @@ class GroupDesc(C.Structure):
         d._offs = (C.c_int * len(offs))(*offs)
         d.G, d.off, d.reduce = len(sizes), C.cast(d._offs, C.POINTER(C.c_int)), 1 if reduce == "mean" else 0
         return d
+
+
+class DepthDesc(C.Structure):
+    """osm_depth_desc (include/osmosis_depthprior.h): the range-map depth prior of the Osmosis data term."""
+    _fields_ = [("align", C.c_int), ("loss_type", C.c_int), ("lam", C.c_float), ("scale", C.c_float), ("scale_min", C.c_float),
+                ("depth_type", C.c_int), ("dval", C.c_float * 3), ("B", C.c_int), ("HW", C.c_int)]
 
 
 class ReconDesc(C.Structure):
@@ -232,6 +238,15 @@ _SIGS_BLIND = {
     "osm_ps_blind_optimize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
 }
 EXPORTS_BLIND = sorted(_SIGS_BLIND)
+# the entry points of the seventh header, include/osmosis_depthprior.h (a range-map depth prior in the Osmosis data term)
+_SIGS_DEPTHPRIOR = {
+    "osm_depth_nblk": [_I],
+    "osm_depth_reduce": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P],
+    "osm_depth_fit": [C.POINTER(DepthDesc), _P, _P, _P, _P],
+    "osm_depth_grad": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P, _P],
+    "osm_depth_loss_grad": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P, _P, _P, _P],
+}
+EXPORTS_DEPTHPRIOR = sorted(_SIGS_DEPTHPRIOR)
 
 _lib = None
 _lock = threading.Lock()
@@ -251,7 +266,7 @@ def load():
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
-                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()):
+                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int
@@ -386,4 +401,13 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     # int16 = packed bf16 / fp16 weight planes; float16 = activations of the fp16-storage family
     if t.dtype not in (torch.float32, torch.int32, torch.int16, torch.float16):
         raise OsmosisHipError(f"osmosis_hip kernels take fp32 (or fp16-family half) tensors; got {t.dtype}")
+    return t.data_ptr()
+
+
+def ptr_f64(t: Optional[torch.Tensor]) -> Optional[int]:
+    """Device address of a CUDA float64 tensor (None -> NULL): the fp64 workspaces of include/osmosis_depthprior.h."""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+        raise OsmosisHipError(f"expected a contiguous CUDA(HIP) float64 tensor, got {t.dtype} on {t.device}")
     return t.data_ptr()

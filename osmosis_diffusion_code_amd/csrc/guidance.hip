@@ -14,6 +14,7 @@
 // mask; a linear operator between the model and the residual), phys_finalize(_group)_kernel<LIN> over one shared device body --
 // and ONE host function, phys_optimize_launch, enqueues the inner loop of the plain, masked, grouped and composed entry points.
 #include "osm_common.h"
+#include "depth_conv.h"
 #include "../../include/osmosis_linop.h"
 #include "../../include/osmosis_psf.h"
 #include "../../include/osmosis_physlin.h"
@@ -23,25 +24,6 @@ namespace {
 
 constexpr int PPB = 1024;  // pixels per reduce workgroup
 constexpr int NRED = 16;
-
-__device__ __forceinline__ float conv_depth(float D, int type, const float* v, float& dd) {
-  if (type == 1) {  // gamma: ((D + v0) * v1) ^ v2
-    const float base = (D + v[0]) * v[1];
-    if (v[2] == 1.0f) {
-      dd = v[1];
-      return base;
-    }
-    const float pw = powf(base, v[2]);
-    dd = v[1] * v[2] * powf(base, v[2] - 1.0f);
-    return pw;
-  }
-  if (type == 2) {  // move
-    dd = 1.0f;
-    return D + v[0];
-  }
-  dd = 0.5f;  // original
-  return 0.5f * (D + 1.0f);
-}
 
 // MASKED: a per-pixel validity / confidence map M [B,3,HW] in [0, 1] (the layout of y) scales the residual: the effective weight of
 // channel c is wm[c] = w M_c wherever the unmasked code uses w (the residual, k2 and dLdI).  The `false` instantiations carry no

@@ -70,7 +70,93 @@ def validate_measurement_mask(mask, batch=None):
     return mask
 
 
+DEPTH_ALIGNS = ("none", "scale", "affine")
+DEPTH_LOSSES = ("norm", "mse")
+
+
+def validate_depth_prior(z, confidence=None, batch=None):
+    """A range map and its confidence as fp32 [B or 1, 1, H, W] each.  z: [B,1,H,W], [1,1,H,W] or [B,H,W], any unit; confidence: the
+    same shape within [0, 1] (None: 1 wherever the range is valid).  A range that is not finite or <= 0 is invalid: m = 0 and z = 0
+    there."""
+    z = torch.as_tensor(z)
+    if z.dim() == 3:
+        z = z[:, None]
+    if z.dim() != 4 or z.shape[1] != 1:
+        raise ValueError(f"depth prior must be [B,1,H,W], [1,1,H,W] or [B,H,W], got {tuple(z.shape)}")
+    if batch is not None and z.shape[0] not in (1, int(batch)):
+        raise ValueError(f"depth prior has batch {z.shape[0]}, the chain has {int(batch)} images (1 broadcasts)")
+    z = z.detach().to(torch.float32)
+    valid = torch.isfinite(z) & (z > 0)
+    if confidence is None:
+        m = valid.to(torch.float32)
+    else:
+        m = torch.as_tensor(confidence)
+        if m.dim() == 3:
+            m = m[:, None]
+        if tuple(m.shape) != tuple(z.shape):
+            raise ValueError(f"depth confidence {tuple(m.shape)} must have the shape of the depth prior {tuple(z.shape)}")
+        m = m.detach().to(torch.float32)
+        if not bool(torch.isfinite(m).all()):
+            raise ValueError("depth confidence must be finite")
+        if m.numel() and (float(m.min()) < 0.0 or float(m.max()) > 1.0):
+            raise ValueError(f"depth confidence must lie within [0, 1], got [{float(m.min())}, {float(m.max())}]")
+        m = torch.where(valid.to(m.device), m, torch.zeros_like(m))
+    z = torch.where(m > 0, z, torch.zeros_like(z))
+    return z, m
+
+
+def depth_prior_fit(d, z, m, align, scale=1.0, scale_min=1e-3):
+    """The closed-form fit d ~ a z + c of include/osmosis_depthprior.h on torch tensors [B,1,H,W] (any float dtype): (a [B], c [B],
+    ok [B] bool -- False where a guard skips the image, finite [B] bool -- False where a moment is not finite).  Differentiable;
+    callers that want the step's constants detach."""
+    dims = (1, 2, 3)
+    on = m > 0
+    z = torch.where(on, z, torch.zeros_like(z))
+    d0 = torch.where(on, d, torch.zeros_like(d))
+    Sm, Sz, Sd = m.sum(dims), (m * z).sum(dims), (m * d0).sum(dims)
+    Szz, Szd = (m * z * z).sum(dims), (m * z * d0).sum(dims)
+    finite = torch.isfinite(Sm + Sz + Sd + Szz + Szd + (m * d0 * d0).sum(dims))
+    ok = (Sm > 0) & finite
+    one = torch.ones_like(Sm)
+    if align == "none":
+        return scale * one, 0 * one, ok, finite
+    if align == "scale":
+        ok = ok & (Szz > 0)
+        a = torch.clamp(Szd / torch.where(ok, Szz, one), min=scale_min)
+        return a, 0 * one, ok, finite
+    if align != "affine":
+        raise ValueError(f"depth prior: align must be one of {DEPTH_ALIGNS}, got {align!r}")
+    det = Sm * Szz - Sz * Sz
+    ok = ok & (det > 2.0 ** -40 * Sm * Szz)
+    a = torch.clamp((Sm * Szd - Sz * Sd) / torch.where(ok, det, one), min=scale_min)
+    return a, (Sd - a * Sz) / torch.where(ok, Sm, one), ok, finite
+
+
+def depth_prior_term(d, z, m, align, loss, scale=1.0, scale_min=1e-3):
+    """(L [B], reported L [B], a [B], c [B]) of the range-map prior on torch tensors; L is differentiable w.r.t. d with (a, c) as
+    constants of the step (they minimise the residual, so this IS the gradient: the envelope theorem).  A guarded image has L = 0
+    and no gradient; the REPORTED loss of an image with a non-finite moment is NaN, as the kernels report it (it stays out of L, so
+    the data term's gradient survives)."""
+    a, c, ok, finite = depth_prior_fit(d.detach(), z, m, align, scale, scale_min)
+    a, c = a.detach(), c.detach()
+    on = (m > 0) & ok[:, None, None, None]
+    e = torch.where(on, d - (a[:, None, None, None] * z + c[:, None, None, None]), torch.zeros_like(d))
+    S = (m * e * e).sum((1, 2, 3))
+    if loss == "norm":
+        Sdd = torch.where(on, m * d.detach() ** 2, torch.zeros_like(d)).sum((1, 2, 3))
+        live = S.detach() > 2.0 ** -40 * Sdd
+        L = torch.where(live, torch.sqrt(torch.where(live, S, torch.ones_like(S))), torch.zeros_like(S))
+    elif loss == "mse":
+        L = S / torch.where(ok, m.sum((1, 2, 3)), torch.ones_like(S))
+    else:
+        raise ValueError(f"depth prior: loss must be one of {DEPTH_LOSSES}, got {loss!r}")
+    nan = torch.full_like(a, float("nan"))
+    return (L, torch.where(finite, L.detach(), nan), (a if align == "none" else torch.where(ok, a, nan)),
+            (c if align == "none" else torch.where(ok, c, nan)))
+
+
 class ConditioningMethod(ABC):
+    _depth = None           # the range-map depth prior (`PosteriorSamplingOsmosis.set_depth_prior`); class default: none
     _mask = None            # [B or 1, 3, HW] fp32 (`set_measurement_mask`); class default: conditioners without one are unmasked
     _mask_hw = None
 
@@ -185,6 +271,150 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("scale must have 1 or 4 entries (RGBD)")
         return s.to(device).contiguous()
 
+    # ---------------------------------------------------------------- range-map depth prior (include/osmosis_depthprior.h)
+    _depth_serial = 0
+
+    def set_depth_prior(self, z, confidence=None, weight=1.0, align="affine", loss="norm", scale=1.0, scale_min=1e-3, batch=None,
+                        device=None):
+        """Hand a range map to the data term: with d the operator's converted depth (what phi multiplies) and (a, c) the per-image
+        least-squares fit d ~ a z + c over the pixels with confidence m > 0, the objective of a guided sub-step becomes
+        data + auxiliary + weight * L_depth, L_depth = sqrt(sum m (d - a z - c)^2) ('norm') or that sum / sum m ('mse').
+        z: [B,1,H,W], [1,1,H,W] or [B,H,W] on the network's grid, any unit (metres make phi * a an attenuation per metre);
+        confidence: the same shape in [0, 1]; a range that is not finite or <= 0 is invalid (m = 0, z = 0 there).  align 'affine' |
+        'scale' (c = 0) | 'none' (a = `scale`, c = 0); `scale_min` > 0 bounds a from below.  None clears the prior.  The term does not
+        depend on phi: it is added to dL/dx0 once, after the route's inner loop, by three small kernels (csrc/depthprior.hip)."""
+        if z is None:
+            self._depth = None
+            return None
+        if align not in DEPTH_ALIGNS:
+            raise ValueError(f"depth prior: align must be one of {DEPTH_ALIGNS}, got {align!r}")
+        if loss not in DEPTH_LOSSES:
+            raise ValueError(f"depth prior: loss must be one of {DEPTH_LOSSES}, got {loss!r}")
+        weight, scale, scale_min = float(weight), float(scale), float(scale_min)
+        if not (weight >= 0.0 and weight < float("inf")):
+            raise ValueError(f"depth prior: weight must be finite and >= 0, got {weight}")
+        if not (scale_min > 0.0 and scale_min < float("inf")) or not (abs(scale) < float("inf")):
+            raise ValueError(f"depth prior: scale must be finite and scale_min finite and > 0, got {scale} and {scale_min}")
+        z, m = validate_depth_prior(z, confidence, batch)
+        B0 = z.shape[0] if batch is None else int(batch)
+        H, W = z.shape[2], z.shape[3]
+        if device is not None:
+            z, m = z.to(device), m.to(device)
+        self._depth = {"z": z.expand(B0, 1, H, W).reshape(B0, 1, H * W).contiguous(),
+                       "m": m.expand(B0, 1, H, W).reshape(B0, 1, H * W).contiguous(), "grid": (H, W), "weight": weight, "align": align,
+                       "loss": loss, "scale": scale, "scale_min": scale_min, "ver": PosteriorSamplingOsmosis._depth_serial + 1}
+        PosteriorSamplingOsmosis._depth_serial += 1     # (a workspace built for an earlier prior's parameters is rebuilt)
+        self._depth_store(self._depth)
+        return self._depth
+
+    @staticmethod
+    def _depth_store(dp):
+        """The prior's per-BATCH results, beside its rows: fit [B0,4] float64 = a, c, gs, L and loss [B0] fp32, NaN until a guided
+        sub-step has written them.  A call on a chunk writes the chunk's rows (`_depth_offset`), so a batch walked in chunks ends with
+        every image's own fit -- the counterpart of the data term's `loss_out` rows."""
+        z = dp["z"]
+        dp["out_fit"] = torch.full((z.shape[0], 4), float("nan"), device=z.device, dtype=torch.float64)
+        dp["out_loss"] = torch.full((z.shape[0],), float("nan"), device=z.device, dtype=torch.float32)
+
+    def depth_prior_rows(self, B, H, W, device):
+        """The stored prior as ([B,1,HW] range rows, [B,1,HW] confidence rows) on `device`, or None without a prior."""
+        dp = self._depth
+        if dp is None:
+            return None
+        z, m = dp["z"], dp["m"]
+        if dp["grid"] != (int(H), int(W)) or z.shape[0] not in (1, B):
+            raise ValueError(f"depth prior [{z.shape[0]},1,{dp['grid'][0]},{dp['grid'][1]}] does not fit an image batch [{B},4,{H},{W}] "
+                             "(the prior lives on the image's grid)")
+        if z.shape[0] != B or z.device != torch.device(device):
+            dp["z"] = z = z.to(device).expand(B, 1, H * W).contiguous()
+            dp["m"] = m = m.to(device).expand(B, 1, H * W).contiguous()
+            self._depth_store(dp)
+        return z, m
+
+    def _depth_offset(self, z, B):
+        """The first row of the stored prior that the range rows `z` [B,1,HW] in hand are (a chunk of its [B0,1,HW] block)."""
+        full = self._depth["z"]
+        r0, rem = divmod(z.data_ptr() - full.data_ptr(), full.shape[2] * 4)
+        if z.device != full.device or rem != 0 or r0 < 0 or r0 + B > full.shape[0]:
+            # the kernels write fit + b * 4 and loss + b for every row they are handed
+            raise ValueError("depth prior rows must be a row block of the conditioner's own prior (`depth_prior_rows(...)[0][a:b]`), got "
+                             f"{B} rows at byte offset {z.data_ptr() - full.data_ptr()} of its {full.shape[0]}")
+        return r0
+
+    def _depth_rows(self, x0, rows):
+        """The (range, confidence) rows [B,1,HW] a call on x0 [B,4,H,W] uses -- the caller's chunk (`rows`) or the stored prior's --
+        checked before anything launches; None without a prior."""
+        dp = self._depth
+        if dp is None:
+            if rows is not None:
+                raise ValueError("depth prior rows were handed over, but no prior is set (`set_depth_prior`)")
+            return None
+        B, _, H, W = x0.shape
+        if rows is None:
+            return self.depth_prior_rows(B, H, W, x0.device)
+        z, m = rows
+        if dp["grid"] != (int(H), int(W)) or z.numel() != B * H * W or m.numel() != B * H * W or not z.is_contiguous() \
+                or not m.is_contiguous():
+            raise ValueError(f"expected depth prior rows [{B},1,{H * W}] (range, confidence) on the prior's grid {dp['grid']}, got "
+                             f"{tuple(z.shape)} and {tuple(m.shape)} for an image batch {tuple(x0.shape)}")
+        self._depth_offset(z, B)
+        return z, m
+
+    def _apply_depth_prior(self, st, x0c, g, rows):
+        """The prior's launches on the g the route has just written: g[:, 3] += weight * d L_depth / d x0[:, 3] where m > 0."""
+        dp = self._depth
+        B, _, H, W = x0c.shape
+        HW = H * W
+        z, m = rows
+        if not g.is_contiguous() or g.numel() != B * 4 * HW:
+            raise ValueError("the depth prior adds into a contiguous [B,4,HW] gradient")
+        ws = st.get("depth")
+        if ws is None or ws["ver"] != dp["ver"]:
+            d = st["desc"]
+            ws = {"ver": dp["ver"],
+                  "desc": ops.depth_desc(dp["align"], dp["loss"], dp["weight"], dp["scale"], dp["scale_min"], d.depth_type, d.dval, B, HW),
+                  "part": torch.empty(B * ops.depth_nblk(HW) * 8, device=x0c.device, dtype=torch.float64)}
+            st["depth"] = ws
+        r0 = self._depth_offset(z, B)
+        fit, loss = dp["out_fit"][r0:r0 + B], dp["out_loss"][r0:r0 + B]       # this chunk's rows of the per-batch results
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            ops.depth_loss_grad(ws["desc"], x0c, z, m, ws["part"], fit, loss, g)
+            return
+        ops.depth_reduce(ws["desc"], x0c, z, m, ws["part"])
+        ops.depth_fit(ws["desc"], ws["part"], fit, loss)
+        ops.depth_grad(ws["desc"], x0c, z, m, fit, g)
+
+    def depth_prior_values(self):
+        """{'loss': [B], 'scale': [B], 'shift': [B]} over the prior's whole batch (device tensors, no sync), each image's from the last
+        guided sub-step that covered it -- also when the batch was walked in chunks: L_depth without its weight, and the fit's a and
+        c (NaN where a guard skipped the image; everything NaN before the first guided sub-step).  None without a prior."""
+        dp = self._depth
+        return None if dp is None else {"loss": dp["out_loss"], "scale": dp["out_fit"][:, 0], "shift": dp["out_fit"][:, 1]}
+
+    def _depth_torch(self, D):
+        """The operator's depth conversion on a torch tensor (the kernels' conv_depth; an operator without one: 'original')."""
+        code, v = getattr(self.operator, "depth_code", 0), getattr(self.operator, "depth_vals", (0.0, 1.0, 1.0))
+        if code == 1:
+            base = (D + v[0]) * v[1]
+            return base if v[2] == 1.0 else torch.pow(base, v[2])
+        return D + v[0] if code == 2 else 0.5 * (D + 1.0)
+
+    def _depth_autograd(self, x_0_hat):
+        """weight * sum_b L_depth[b] on torch tensors (the autograd routes), or None without a prior; keeps the values for
+        `depth_prior_values`."""
+        dp = self._depth
+        if dp is None:
+            return None
+        B, _, H, W = x_0_hat.shape
+        z, m = self.depth_prior_rows(B, H, W, x_0_hat.device)
+        L, reported, a, c = depth_prior_term(self._depth_torch(x_0_hat[:, 3:4]), z.view(B, 1, H, W).to(x_0_hat.dtype),
+                                             m.view(B, 1, H, W).to(x_0_hat.dtype), dp["align"], dp["loss"], dp["scale"], dp["scale_min"])
+        with torch.no_grad():
+            dp["out_loss"].copy_(reported)
+            dp["out_fit"][:, 0].copy_(a)
+            dp["out_fit"][:, 1].copy_(c)
+        return dp["weight"] * L.sum()
+
     def _degradation(self):
         """The operator's `degradation` when the composed kernels serve it (a blur / super-resolution / PSF operator), else None."""
         from .measurements import GRID_OPERATORS
@@ -259,20 +489,24 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             self._grp, self._grp_key = ops.group_desc(sizes, self.operator.phi_reduce), key
         return self._grp
 
-    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
+    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None, depth=None):
         """Inner phi-optimisation + dL/dx0.  x0 [B,4,H,W], y [B,3,H,W] contiguous device fp32.
         Returns (g [B,4,H,W] view of an internal buffer (or g_out), per-image data loss [B] (device)).
         `phi` / `loss_out` / `mask`: rows of the operator's [B][9] state / of a [B] loss vector / of the [B,3,HW] mask when the
         caller walks a batch in chunks of independent images (default: the operator's whole state, the mask of
         `set_measurement_mask`).
         An operator with `phi_groups`: the same launches with ONE phi step per group and inner iteration (osm_phys_optimize_g); loss
-        and g stay per image, and the call must cover the operator's whole batch."""
+        and g stay per image, and the call must cover the operator's whole batch.
+        With a range-map prior (`set_depth_prior`; `depth`: the chunk's (range, confidence) rows [B,1,HW], default the stored ones)
+        g's depth plane also carries weight * d L_depth / d x0, added after the inner loop; the returned loss stays the data loss
+        (`depth_prior_values` has the prior's)."""
         if getattr(self.operator, "degradation", None) is not None:
-            return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask)
+            return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask, depth)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] != 4:
             raise ValueError("expected x0 [B,4,H,W] and measurement [B,3,H,W]")
         grp = self._group(self.operator.phi if phi is None else phi)        # (refuses a chunk of a grouped batch before anything else)
+        depth = self._depth_rows(x0, depth) if (self._depth is not None or depth is not None) else None
         st = self._prepare(B, HW, x0.device)
         d, part, red, loss = st["desc"], st["part"], st["red"], st["loss"]
         opt = self._opt if d.optimizer != 0 else None       # read at call time: _prepare may have re-allocated it
@@ -300,6 +534,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                      partial(ops.phys_grad, d, x0c, yc, phi, red, g),
                      partial(ops.phys_optimize, d, x0c, yc, phi, part, red, loss, g))
         self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
+        if depth is not None:
+            self._apply_depth_prior(st, x0c, g, depth)
         return g.view(x0.shape), loss
 
     @staticmethod
@@ -323,7 +559,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             if not freeze_phi:
                 finalize(True, None, opt_state=rows)
 
-    def _loss_grad_x0_lin(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None):
+    def _loss_grad_x0_lin(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None, depth=None):
         """`loss_grad_x0` with the operator's `degradation` A between the image-formation model and the photo: y and the mask live on
         A's grid (h, w) = A.out_shape(H, W).  Per inner iteration: the image (and the depth weight) materialised, A, the residual on
         the measurement's grid, A^T, then the phi reductions and step with v = A^T u where the plain route forms -2 w r inline -- all
@@ -340,6 +576,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError(f"expected the measurement [{B},3,{h},{w}] (the degradation's grid for a {H} x {W} image), got {tuple(y.shape)}")
         HW, hw = H * W, h * w
         grp = self._group(self.operator.phi if phi is None else phi)
+        depth = self._depth_rows(x0, depth) if (self._depth is not None or depth is not None) else None
         st = self._prepare(B, HW, x0.device, grid=(H, W))
         d, lin, part, red, loss = st["desc"], st["lin"], st["part"], st["red"], st["loss"]
         F, AF, u, v, part_r = st["F"], st["AF"], st["u"], st["v"], st["part_r"]
@@ -374,6 +611,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             route = (reduce, partial(ops.phys_finalize_lin, d, hw, part, part_r, red, phi, masked=masked), grad,
                      partial(ops.phys_optimize_lin, d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g))
         self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
+        if depth is not None:                                   # the prior lives on the image's grid [H, W], not the measurement's
+            self._apply_depth_prior(st, x0c, g, depth)
         return g.view(x0.shape), loss
 
     def _opt_rows(self, opt, phi):
@@ -435,16 +674,21 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         m = self._mask_like(measurement)
         if m is not None:           # (mse below keeps its 3 HW denominator: a mask of ones is the unmasked loss)
             diff = diff * m
+        # the range-map prior, weight * sum_b L_depth[b] (None without one): part of the objective, not of the reported data loss
+        prior = self._depth_autograd(x_0_hat)
+
+        def total(data_loss):
+            return data_loss if prior is None else data_loss + prior
         if self.loss_function == "norm":
             sep = torch.norm(diff.detach().cpu(), p=2, dim=[1, 2, 3]).numpy()
             if getattr(self.operator, "group_sizes", None) is not None:
                 # shared water parameters: a group's objective is the SUM of its members' per-image norms (what the kernels pool),
                 # not the norm over the batch
-                return sep, torch.linalg.vector_norm(diff, dim=(1, 2, 3)).sum(), image.detach()
-            return sep, torch.linalg.norm(diff), image.detach()
+                return sep, total(torch.linalg.vector_norm(diff, dim=(1, 2, 3)).sum()), image.detach()
+            return sep, total(torch.linalg.norm(diff)), image.detach()
         if self.loss_function == "mse":
             mse = (diff ** 2).mean(dim=(1, 2, 3))
-            return mse.detach().cpu().numpy(), mse.sum(), image.detach()
+            return mse.detach().cpu().numpy(), total(mse.sum()), image.detach()
         raise NotImplementedError
 
     def _conditioning_autograd(self, x_prev, x_t, x_0_hat, measurement, **kwargs):
@@ -517,6 +761,12 @@ class PosteriorSampling(ConditioningMethod):
         super().__init__(operator, noiser)
         self.scale = _parse_scale(kwargs.get("scale", 1.0))
         self._states = {}
+
+    def set_depth_prior(self, z, *args, **kwargs):
+        if z is None:
+            return None
+        raise NotImplementedError("the 'ps' branch has no depth model (its data term is y - A x0[:, 0:3]): a range-map depth prior "
+                                  "needs the 'osmosis' conditioner")
 
     def _blind(self):
         """The operator when it is a `blind_blur` that learns its PSF (its data term steps the weights and couples the batch), else None."""

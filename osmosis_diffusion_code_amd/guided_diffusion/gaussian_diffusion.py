@@ -573,7 +573,14 @@ class GaussianDiffusion:
         noise1 = torch.zeros(1, C, H, W, **f32) if (shared and source == "aten" and not mean_only) else None
         noise_used = torch.empty(B, C, H, W, **f32) if (lib_rng and trace is not None) else None
         # (no mask: the call as it always was -- a conditioner subclass whose loss_grad_x0 predates the kwarg keeps working)
-        mk_rows = (lambda a, b: {}) if mask is None else (lambda a, b: {"mask": mask[a:b]})
+        # the range-map depth prior's (range, confidence) rows [B,1,HW], on the image's grid (`depth_prior=`): handed over only when set
+        prior = None if ps or getattr(cond, "_depth", None) is None else cond.depth_prior_rows(B, H, W, dev)
+
+        def mk_rows(a, b):
+            rows = {} if mask is None else {"mask": mask[a:b]}
+            if prior is not None:
+                rows["depth"] = (prior[0][a:b], prior[1][a:b])
+            return rows
         mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
         k = 0                                             # sub-step count (noise_fn's k)
         for idx in range(ch.first, ch.last - 1, -1):
@@ -728,6 +735,8 @@ class GaussianDiffusion:
         y = measurement.detach().to(dev, torch.float32).contiguous()
         mask = cond.measurement_mask(1, HW, dev)
         mk_rows = {} if mask is None else {"mask": mask}
+        if getattr(cond, "_depth", None) is not None:          # the range-map depth prior: a map over the CANVAS, one fit for it
+            mk_rows["depth"] = cond.depth_prior_rows(1, Hc, Wc, dev)
         phi = cond.operator.phi
         img_base = int(kwargs.get("image_index0", 0))
         noise = None if ch.lib_rng else torch.zeros(1, 4, Hc, Wc, **f32)      # the noise belongs to the canvas
@@ -808,13 +817,29 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ public loop
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root,
                       pretrain_model=None, image_idx=None, record_every=150, rgb_guidance=False,
-                      sample_pattern=None, measurement_mask=None, tiling=None, **kwargs):
+                      sample_pattern=None, measurement_mask=None, tiling=None, depth_prior=None, **kwargs):
         """measurement_mask: a per-pixel validity mask of the measurement ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
         [0, 1]; `ConditioningMethod.set_measurement_mask`), handed to the conditioner for this chain -- the fused loop and
         `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default).
         tiling: `dict(tile=, stride=, window=)` (`parse_tiling`) runs ONE canvas larger than the network's grid as overlapping
-        tiles of the network's size (`_tiled_loop`); None: nothing changes."""
+        tiles of the network's size (`_tiled_loop`); None: nothing changes.
+        depth_prior: `dict(z=, confidence=, weight=, align=, loss=, scale=, scale_min=)` sets a range-map depth prior on the
+        conditioner for this chain (`PosteriorSamplingOsmosis.set_depth_prior`; z on the image's grid, the canvas's when tiled);
+        None: the conditioner keeps whatever prior it was given directly (none by default)."""
         from .posterior_mean_variance import PreviousXMeanProcessor
+        if depth_prior is not None:
+            cond_obj = getattr(measurement_cond_fn, "__self__", None)
+            if not hasattr(cond_obj, "set_depth_prior"):
+                raise TypeError("depth_prior needs a conditioner with set_depth_prior (the 'osmosis' conditioning method)")
+            if not isinstance(depth_prior, dict) or "z" not in depth_prior:
+                raise ValueError("depth_prior must be a dict with the range map `z` (and confidence, weight, align, loss, scale, scale_min)")
+            unknown = set(depth_prior) - {"z", "confidence", "weight", "align", "loss", "scale", "scale_min"}
+            if unknown:
+                raise ValueError(f"depth_prior: unknown keys {sorted(unknown)}")
+            zt = torch.as_tensor(depth_prior["z"])
+            if tuple(zt.shape[-2:]) != tuple(x_start.shape[2:]):
+                raise ValueError(f"depth_prior z {tuple(zt.shape)} does not match the image grid {tuple(x_start.shape[2:])}")
+            cond_obj.set_depth_prior(**depth_prior, batch=x_start.shape[0], device=x_start.device)
         if measurement_mask is not None:
             cond_obj = getattr(measurement_cond_fn, "__self__", None)
             if not hasattr(cond_obj, "set_measurement_mask"):

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, query
+from ._lib import AttnDesc, ConvDesc, DepthDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, ptr_f64, query
 
 
 @dataclass
@@ -933,3 +933,65 @@ def phys_optimize_lin_g(desc: PhysDesc, grp: GroupDesc, lin: LinDesc, x0, y, mas
     call("osm_phys_optimize_lin_g", C.byref(desc), C.byref(grp), C.byref(lin), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(F), ptr(AF),
          ptr(u), ptr(v), ptr(part_r), ptr(part), ptr(red), ptr(loss_out), ptr(g), int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(),
          keep=(desc, grp, lin, x0, y, mask, phi, F, AF, u, v, part_r, part, red, loss_out, g, opt_state) + tuple(lin._keep))
+
+
+# ----------------------------------------------------------------------------- range-map depth prior (include/osmosis_depthprior.h)
+DEPTH_ALIGN = {"none": 0, "scale": 1, "affine": 2}
+DEPTH_LOSS = {"norm": 0, "mse": 1}
+
+
+def depth_nblk(HW: int) -> int:
+    return query("osm_depth_nblk", int(HW))
+
+
+def depth_desc(align, loss, weight, scale, scale_min, depth_type, dval, B, HW) -> DepthDesc:
+    """The osm_depth_desc of a prior: align 'none' | 'scale' | 'affine', loss 'norm' | 'mse', weight = lambda; depth_type / dval: the
+    operator's depth conversion (`PhysDesc.depth_type`, `.dval`)."""
+    if align not in DEPTH_ALIGN:
+        raise ValueError(f"depth prior: align must be one of {sorted(DEPTH_ALIGN)}, got {align!r}")
+    if loss not in DEPTH_LOSS:
+        raise ValueError(f"depth prior: loss must be one of {sorted(DEPTH_LOSS)}, got {loss!r}")
+    d = DepthDesc()
+    d.align, d.loss_type, d.lam, d.scale, d.scale_min = DEPTH_ALIGN[align], DEPTH_LOSS[loss], float(weight), float(scale), float(scale_min)
+    d.depth_type = int(depth_type)
+    for i in range(3):
+        d.dval[i] = float(dval[i])
+    d.B, d.HW = int(B), int(HW)
+    return d
+
+
+def _check_depth(name, desc: DepthDesc, **ts):
+    B, HW = desc.B, desc.HW
+    need = {"x0": B * 4 * HW, "g": B * 4 * HW, "z": B * HW, "m": B * HW, "depth_loss": B}
+    need64 = {"part": B * depth_nblk(HW) * 8, "fit": B * 4}
+    for k, t in ts.items():
+        if k in need64:
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < need64[k]:
+                raise ValueError(f"{name}: `{k}` must be contiguous float64 with at least {need64[k]} elements, got {tuple(t.shape)} {t.dtype}")
+        elif t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < need[k] or (k in ("z", "m") and t.numel() != need[k]):
+            raise ValueError(f"{name}: `{k}` must be contiguous fp32 with {need[k]} elements, got {tuple(t.shape)} {t.dtype}")
+
+
+def depth_reduce(desc: DepthDesc, x0, z, m, part):
+    """part (float64 [B][depth_nblk(HW)][8]) = the workgroup partials of the six moments of (m, z, d) (osm_depth_reduce)."""
+    _check_depth("depth_reduce", desc, x0=x0, z=z, m=m, part=part)
+    call("osm_depth_reduce", C.byref(desc), ptr(x0), ptr(z), ptr(m), ptr_f64(part), _s(), keep=(desc, x0, z, m, part))
+
+
+def depth_fit(desc: DepthDesc, part, fit, depth_loss):
+    """fit (float64 [B][4] = a, c, gs, L) and depth_loss (fp32 [B]) from the partials (osm_depth_fit)."""
+    _check_depth("depth_fit", desc, part=part, fit=fit, depth_loss=depth_loss)
+    call("osm_depth_fit", C.byref(desc), ptr_f64(part), ptr_f64(fit), ptr(depth_loss), _s(), keep=(desc, part, fit, depth_loss))
+
+
+def depth_grad(desc: DepthDesc, x0, z, m, fit, g):
+    """g[b,3,p] += (float)(gs m (d - (a z + c)) dd) where m > 0; nothing else of g [B,4,HW] is written (osm_depth_grad)."""
+    _check_depth("depth_grad", desc, x0=x0, z=z, m=m, fit=fit, g=g)
+    call("osm_depth_grad", C.byref(desc), ptr(x0), ptr(z), ptr(m), ptr_f64(fit), ptr(g), _s(), keep=(desc, x0, z, m, fit, g))
+
+
+def depth_loss_grad(desc: DepthDesc, x0, z, m, part, fit, depth_loss, g):
+    """The prior's three launches (reduce, fit, grad) enqueued by one call (osm_depth_loss_grad)."""
+    _check_depth("depth_loss_grad", desc, x0=x0, z=z, m=m, part=part, fit=fit, depth_loss=depth_loss, g=g)
+    call("osm_depth_loss_grad", C.byref(desc), ptr(x0), ptr(z), ptr(m), ptr_f64(part), ptr_f64(fit), ptr(depth_loss), ptr(g), _s(),
+         keep=(desc, x0, z, m, part, fit, depth_loss, g))

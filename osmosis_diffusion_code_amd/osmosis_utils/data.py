@@ -188,6 +188,47 @@ def transform_mask(mask, size=256, crop="center", multiple=32, geometry=None):
     return center_crop(resize(m, size), out_hw).clamp(0.0, 1.0).unsqueeze(0).contiguous()
 
 
+def transform_range(z, confidence=None, size=256, crop="center", multiple=32, geometry=None, min_cover=0.5):
+    """A range map given at the photo's own resolution (structure from motion, stereo, an altimeter; any unit), taken through the
+    geometry of the photo's transform, hole-aware: with v = [z finite and > 0],
+        z_out = resize(z v) / resize(v) where resize(v) >= min_cover, else 0         (a hole does not bleed towards 0)
+        m_out = resize(confidence v) [resize(v) >= min_cover]                        (confidence None: 1)
+    `resize` (bilinear, as the photo) and `center_crop` as in `transform_mask`; crop / geometry select the grid the same way.
+    z, confidence: [H0,W0] or [1,H0,W0].  Returns (z [1,1,h,w], m [1,1,h,w]) fp32: what `restore_image(depth=, depth_confidence=)`
+    and `p_sample_loop(depth_prior=dict(z=, confidence=))` accept."""
+    def plane(t, what):
+        t = torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t).to(torch.float32)
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or t.shape[0] != 1:
+            raise ValueError(f"{what} must be [H0,W0] or [1,H0,W0], got {tuple(t.shape)}")
+        return t
+    z = plane(z, "the range map")
+    if not 0.0 < float(min_cover) <= 1.0:
+        raise ValueError(f"min_cover must lie in (0, 1], got {min_cover}")
+    v = (torch.isfinite(z) & (z > 0)).to(torch.float32)
+    c = v if confidence is None else plane(confidence, "the confidence") * v
+    if tuple(c.shape) != tuple(z.shape):
+        raise ValueError(f"the confidence {tuple(c.shape)} must have the range map's shape {tuple(z.shape)}")
+    if confidence is not None and (not bool(torch.isfinite(c).all()) or float(c.min()) < 0.0 or float(c.max()) > 1.0):
+        raise ValueError("the confidence must be finite and lie within [0, 1]")
+    if geometry is not None:
+        if (z.shape[-2], z.shape[-1]) != (geometry.H0, geometry.W0):
+            raise ValueError(f"the range map is {z.shape[-2]} x {z.shape[-1]} but the geometry describes a {geometry.H0} x {geometry.W0} photo")
+        out_hw, size = [geometry.h, geometry.w], (geometry.nh, geometry.nw)      # the geometry's own resize, whatever `size` says
+    elif crop == "center":
+        out_hw = [size, size]
+    else:
+        geo = transform_geometry(z.shape[-2], z.shape[-1], size, crop, multiple)
+        out_hw = [geo.h, geo.w]
+    zv = torch.where(v > 0, z, torch.zeros_like(z))
+    rz, rv, rc = (center_crop(resize(t, size), out_hw) for t in (zv, v, c))
+    keep = rv >= float(min_cover)
+    z_out = torch.where(keep, rz / rv.clamp_min(1e-12), torch.zeros_like(rz))
+    m_out = torch.where(keep, rc, torch.zeros_like(rc)).clamp(0.0, 1.0)
+    return z_out.unsqueeze(0).contiguous(), m_out.unsqueeze(0).contiguous()
+
+
 # ----------------------------------------------------------------------------- datasets
 class ImagesFolder(Dataset):
     """data.py:15-38: every file of `root_dir` in natural order -> (transformed image, file name)."""

@@ -113,6 +113,73 @@ def observed_image(operator, out_xstart):
         return 2 * operator.observe(out_xstart.detach().to(operator.device, torch.float32).contiguous()) - 1
 
 
+DEPTH_PRIOR_KEYS = ("weight", "align", "loss", "scale", "scale_min", "path")
+
+
+def depth_prior_config(depth_cfg):
+    """The optional config key `measurement.depth: {weight, align, loss, scale, scale_min, path}` as keyword arguments of
+    `set_depth_prior` (only the keys given) and the `path` of a `.npy` range map at the photo's resolution (or None).  Unknown keys
+    raise."""
+    if not depth_cfg:
+        return {}, None
+    unknown = set(depth_cfg) - set(DEPTH_PRIOR_KEYS)
+    if unknown:
+        raise ValueError(f"measurement.depth: unknown key(s) {sorted(unknown)} (known: {', '.join(DEPTH_PRIOR_KEYS)})")
+    params = {k: depth_cfg[k] for k in ("align", "loss") if k in depth_cfg}
+    params.update({k: float(depth_cfg[k]) for k in ("weight", "scale", "scale_min") if k in depth_cfg})
+    return params, depth_cfg.get("path")
+
+
+def depth_prior_inputs(grid, depth_cfg=None, depth=None, depth_confidence=None, geometry=None):
+    """The `depth_prior=` dict of a chain whose images live on `grid` = (H, W), or None when no range map is given.  depth /
+    depth_confidence: [B,1,H,W], [1,1,H,W] or [B,H,W] on the network's grid (`data.transform_range` takes one from the photo's
+    resolution there); without `depth`, the `.npy` of `measurement.depth.path` at the photo's resolution goes through
+    `transform_range` with `geometry` (the photo's `data.Geometry`, as `fit_transform` returned it).  Without a geometry the
+    photo's transform is NOT known here and is assumed to be the default one for the grid: the [size, size] center crop of
+    `default_transform` for a square grid, `fit_transform`'s grid with its default multiple otherwise; a photo that was prepared
+    differently needs `geometry` or a ready-made `depth`.  `path` is ONE file: with B > 1 its map serves every image of the batch
+    (one scene), per-image maps go through `depth=` / `restore_images(depths=)`."""
+    params, path = depth_prior_config(depth_cfg)
+    if depth is None and path is None:
+        if depth_confidence is not None:
+            raise ValueError("depth_confidence comes with a range map (`depth=` or measurement.depth.path)")
+        return None
+    H, W = int(grid[0]), int(grid[1])
+    if depth is None:
+        from .osmosis_utils import data as datao
+        if geometry is not None:
+            depth, conf = datao.transform_range(np.load(path), geometry=geometry)
+        else:
+            depth, conf = datao.transform_range(np.load(path), size=min(H, W), crop="center" if H == W else "fit")
+        if depth_confidence is None:
+            depth_confidence = conf
+        else:
+            depth_confidence = torch.as_tensor(depth_confidence).to(torch.float32) * conf
+    depth = torch.as_tensor(depth)
+    if tuple(depth.shape[-2:]) != (H, W):
+        raise ValueError(f"the range map {tuple(depth.shape)} does not match the image grid {(H, W)} (the prior lives on the image's "
+                         "grid, also with a degradation)")
+    return dict(params, z=depth, confidence=depth_confidence)
+
+
+def attach_depth_prior(post, z, m, scale, shift, loss, align):
+    """The range prior's keys of one image's result (`post` from `postprocess`): `depth_prior` (z [H,W]), `depth_confidence` [H,W],
+    `depth_scale` / `depth_shift` (the fit d ~ a z + c at the chain's end), `depth_loss_final`, `depth_metric` [H,W] =
+    (depth_calc - c) / a -- the depth in the range map's unit, NaN where a is undefined (a guard skipped the image) -- and, when
+    align is 'scale' or 'none' (c = 0, so exp(-phi d) = exp(-(phi a) z)), `phi_metric`: phi_a a and phi_b a (phi_ab a) per unit of
+    range, phi_inf unchanged."""
+    a, c = float(scale), float(shift)
+    H, W = post["depth_calc"].shape[-2:]
+    post.update(depth_prior=z.detach().cpu().reshape(H, W).to(torch.float32), depth_confidence=m.detach().cpu().reshape(H, W).to(torch.float32),
+                depth_scale=a, depth_shift=c, depth_loss_final=float(loss), depth_align=align)
+    dc = post["depth_calc"][0].to(torch.float64)
+    post["depth_metric"] = ((dc - c) / a).to(torch.float32) if (np.isfinite(a) and np.isfinite(c) and a != 0.0) \
+        else torch.full((H, W), float("nan"))
+    if align in ("scale", "none") and np.isfinite(a):
+        post["phi_metric"] = {k: (v.clone() if k == "phi_inf" else v * a) for k, v in post["phi"].items()}
+    return post
+
+
 def load_config(path):
     """The reference's `arguments_from_file` (osmosis_utils/utils.py:466-476 -> load_yaml :357-360): the YAML file as a plain
     dictionary (the reference copies the same keys onto an argparse.Namespace; `restore_image(s)` reads them by key).
@@ -217,6 +284,14 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         os.makedirs(d, exist_ok=True)
         paths["mask"] = os.path.join(d, f"{name}_mask.png")
         Image.fromarray(_to_pil_u8(post["mask"][0].clamp(0, 1)), mode="RGB").save(paths["mask"])
+    if save_singles and post.get("depth_metric") is not None:       # only a chain with a range-map prior
+        d = os.path.join(out_dir, "single_images", "depth_metric")
+        os.makedirs(d, exist_ok=True)
+        metric_u8, prior_u8 = depth_metric_images_u8(post)
+        paths["depth_metric"] = os.path.join(d, f"{name}_depth_metric.png")
+        paths["depth_prior"] = os.path.join(d, f"{name}_depth_prior.png")
+        Image.fromarray(metric_u8, mode="RGB").save(paths["depth_metric"])
+        Image.fromarray(prior_u8, mode="RGB").save(paths["depth_prior"])
     if save_singles and post.get("kernel") is not None:     # only a `blind_blur` chain: the learnt PSF
         d = os.path.join(out_dir, "single_images", "kernel")
         os.makedirs(d, exist_ok=True)
@@ -235,6 +310,22 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         paths["depth_full"] = os.path.join(d, f"{name}_depth_full.png")
         Image.fromarray(full_depth_color_u8(full_res), mode="RGB").save(paths["depth_full"])
     return paths
+
+
+def depth_metric_images_u8(post):
+    """(`depth_metric`, `depth_prior`) of a result as viridis uint8 [H,W,3] images under ONE normalisation: the range of the valid
+    range-map pixels and the finite metric depths together, so equal colours are equal ranges; pixels without a value are black."""
+    metric, z, m = post["depth_metric"].to(torch.float64), post["depth_prior"].to(torch.float64), post["depth_confidence"]
+    have_m, have_z = torch.isfinite(metric), m > 0
+    vals = torch.cat([metric[have_m], z[have_z]])
+    lo, hi = (float(vals.min()), float(vals.max())) if vals.numel() else (0.0, 1.0)
+    span = hi - lo if hi > lo else 1.0
+    out = []
+    for plane, have in ((metric, have_m), (z, have_z)):
+        norm = torch.where(have, ((plane - lo) / span).clamp(0, 1), torch.zeros_like(plane))
+        col = utilso.depth_tensor_to_color_image(norm) * have.to(torch.float64)
+        out.append(_to_pil_u8(col.to(torch.float32)))
+    return out[0], out[1]
 
 
 def kernel_image_u8(kernel, side=128):
@@ -392,7 +483,8 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
 
 
 def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
-                  postprocess_batch=True, mask=None, tiling=None, **loop_kwargs):
+                  postprocess_batch=True, mask=None, tiling=None, depth=None, depth_confidence=None, depth_geometry=None,
+                  **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -412,6 +504,15 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     keys raise) for ONE image larger than the network's grid, e.g. the 512-class grid of `data.fit_transform(size=512)`: the
     network sees overlapping tiles of side `tile`, everything else acts on the whole image (`p_sample_loop(tiling=)`).  Every
     result then carries `tiling` = {tile, stride, window, origins int32 [n,2]}; without it nothing is passed and there is no such key.
+
+    `depth` / `depth_confidence` (and / or the optional config key `measurement.depth: {weight, align, loss, scale, scale_min, path}`,
+    see `depth_prior_inputs`): a range map on the network's grid, [B,1,H,W], [1,1,H,W] or [B,H,W] (`data.transform_range` takes one
+    from the photo's resolution there), handed to the data term as a prior on the depth plane (`p_sample_loop(depth_prior=)`,
+    include/osmosis_depthprior.h).  Every result then carries `depth_prior`, `depth_confidence`, `depth_scale`, `depth_shift`,
+    `depth_loss_final`, `depth_metric` and, for align 'scale' / 'none', `phi_metric` (`attach_depth_prior`) -- each image's own,
+    also when the batch is walked in chunks; a chain without a guided sub-step leaves the fit undefined (NaN).  Without a range
+    map nothing is passed and there are no such keys.  `depth_geometry`: the photo's `data.Geometry` for the map of
+    `measurement.depth.path` (`depth_prior_inputs` says what is assumed without it).
 
     Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
     carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
@@ -484,6 +585,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     if m_dev is not None:
         loop_kwargs = dict(loop_kwargs, measurement_mask=m_dev)
     shape[1] = 4 if pretrain == "osmosis" else shape[1]
+    prior = depth_prior_inputs(shape[2:], measure.get("depth"), depth, depth_confidence, depth_geometry)
+    if prior is not None:
+        loop_kwargs = dict(loop_kwargs, depth_prior=prior)
     results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
         torch.manual_seed(cfg.get("manual_seed", 0))
@@ -521,6 +625,13 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             if degraded:            # every image's `observed`, for the caller's per-image post-processing (`postprocess_each`)
                 post["observed"] = observed_image(operator, out_xstart).cpu()
         post.update(sample=sample.detach().cpu(), pred_xstart=out_xstart, measurement=y_n.detach().cpu())
+        if prior is not None:       # every image's fit and loss from the chain's last guided sub-step (NaN: there was none)
+            vals = {k: v.detach().cpu() for k, v in cond.depth_prior_values().items()}
+            zr, mr = (t.detach().cpu() for t in cond.depth_prior_rows(shape[0], shape[2], shape[3], device))
+            if postprocess_batch:
+                attach_depth_prior(post, zr[0], mr[0], vals["scale"][0], vals["shift"][0], vals["loss"][0], cond._depth["align"])
+            else:                   # every image's, for the caller's per-image post-processing
+                post["depth_fit"] = dict(vals, z=zr, m=mr, align=cond._depth["align"])
         if m_dev is not None:
             post["mask"] = m_dev.detach().cpu()
         if tiling_info is not None:
@@ -548,7 +659,8 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
-                   geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, **loop_kwargs):
+                   geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, depths=None,
+                   depth_confidences=None, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -566,7 +678,11 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     batch: one phi estimated from all its images (`_PhysicalOperator(phi_groups=)`; `measurement.operator.phi_reduce` chooses
     "mean" or "sum").  A batch of one stays ungrouped.  Every result carries `water_group`, the image indices that shared its phi;
     everything downstream reads the per-image phi rows as before.  Not with `tiling`, nor with a `ps` / rgb-guidance config (no
-    phi there)."""
+    phi there).
+
+    `depths` / `depth_confidences` (lists aligned with `images`: a range map [1,1,H,W] on the network's grid each, or None for an
+    image without one): rows per image, chunked with the images (`restore_image(depth=, depth_confidence=)`); in a batch, an image
+    without a map gets confidence 0 everywhere -- no prior for it.  The fit stays per image, also with `shared_water`."""
     if shared_water:
         if tiling is not None or cfg.get("tiling") is not None:
             raise NotImplementedError("shared_water: tiling is one canvas per call, water parameters are not shared across canvases")
@@ -580,6 +696,28 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
         raise NotImplementedError("full-resolution reconstruction with a degradation inside the physical operator is not implemented")
     if masks is not None and len(masks) != len(images):
         raise ValueError(f"masks must align with images: {len(masks)} masks for {len(images)} images")
+
+    for what, lst in (("depths", depths), ("depth_confidences", depth_confidences)):
+        if lst is not None and len(lst) != len(images):
+            raise ValueError(f"{what} must align with images: {len(lst)} for {len(images)} images")
+    if depth_confidences is not None and depths is None:
+        raise ValueError("depth_confidences come with depths")
+
+    def batch_depth(idxs):
+        """(depth, confidence) rows [n,1,H,W] of one batch from `depths` / `depth_confidences`, or {} when none of its images has a map."""
+        if depths is None or all(depths[i] is None for i in idxs):
+            return {}
+        zs, ms = [], []
+        for i in idxs:
+            hw = tuple(next(d for d in (depths[j] for j in idxs) if d is not None).shape[-2:])
+            z = torch.zeros(1, 1, *hw) if depths[i] is None else torch.as_tensor(depths[i]).to(torch.float32)
+            if z.dim() != 4 or z.shape[0] != 1 or z.shape[1] != 1:
+                raise ValueError(f"depths[{i}] must be [1,1,H,W], got {tuple(z.shape)}")
+            c = None if depth_confidences is None else depth_confidences[i]
+            m = (torch.isfinite(z) & (z > 0)).to(torch.float32) if c is None else torch.as_tensor(c).to(torch.float32).reshape(z.shape)
+            zs.append(z)
+            ms.append(m.to(z.device))
+        return dict(depth=torch.cat([z.to(zs[0].device) for z in zs], 0), depth_confidence=torch.cat([m.to(zs[0].device) for m in ms], 0))
 
     def batch_mask(idxs):
         """`masks` (a list aligned with `images`: [1,1,H,W] / [1,3,H,W] each, or None for an image without one) of one batch."""
@@ -599,14 +737,14 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
         idxs = mine[k:k + max(1, batch_size)]
         if len(idxs) == 1:
             res = [restore_image(model, images[idxs[0]], cfg, device=device, image_idx=idxs[0], mask=batch_mask(idxs),
-                                 **loop_kwargs)[-1]]
+                                 **batch_depth(idxs), **loop_kwargs)[-1]]
         else:
             ref = torch.cat([images[i] for i in idxs], 0)
             bcfg = cfg
             if shared_water:        # this batch is one water group (a copy: the caller's config stays as it is)
                 bcfg = dict(cfg, measurement=dict(cfg["measurement"], operator=dict(cfg["measurement"]["operator"], phi_groups="all")))
             full = restore_image(model, ref, bcfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
-                                 postprocess_batch=False, mask=batch_mask(idxs), **loop_kwargs)[-1]
+                                 postprocess_batch=False, mask=batch_mask(idxs), **batch_depth(idxs), **loop_kwargs)[-1]
             if "pred_xstart" in full:
                 res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"],
                                        observed=full.get("observed"))
@@ -615,6 +753,10 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
                              measurement=full["measurement"][b:b + 1])
             else:
                 res = [rgb_guidance_result(full["sample"][b:b + 1], full["measurement"][b:b + 1]) for b in range(len(idxs))]
+            if full.get("depth_fit") is not None and "pred_xstart" in full:
+                fit = full["depth_fit"]
+                for b, r in enumerate(res):
+                    attach_depth_prior(r, fit["z"][b], fit["m"][b], fit["scale"][b], fit["shift"][b], fit["loss"][b], fit["align"])
             if full.get("mask") is not None:
                 for b, r in enumerate(res):
                     r["mask"] = full["mask"][b:b + 1]

@@ -835,8 +835,41 @@ def _ps_blind_loss_grad_fake(x0, y, mask, dy, dx, w, Ry, Rx, n_iter, eta, l1):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
 
 
+# ---- range-map depth prior of the Osmosis data term (include/osmosis_depthprior.h): adds its envelope gradient INTO g
+@torch.library.custom_op("osmosis::depth_prior_loss_grad", mutates_args=("g",), device_types="cuda")
+def depth_prior_loss_grad(x0: torch.Tensor, z: torch.Tensor, m: torch.Tensor, g: torch.Tensor, align: str, loss: str, weight: float,
+                          scale: float, scale_min: float, depth_type: int, dval: List[float]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The range-map depth prior on x0 [B,4,H,W] (osm_depth_loss_grad): z, m [B,1,H,W] fp32 (range, confidence in [0, 1]; m = 0 where
+    there is no range), g [B,4,H,W] = dL/dx0 of the data term, whose depth plane receives `weight` times the gradient of the
+    prior's loss IN PLACE where m > 0 (nothing else of g is written).  align 'none' | 'scale' | 'affine', loss 'norm' | 'mse';
+    depth_type / dval: the operator's depth conversion.  Returns (depth_loss fp32 [B], without the weight; fit float64 [B,4] =
+    a, c, gs, L)."""
+    name = "osmosis::depth_prior_loss_grad"
+    B, HW = _chw(x0)
+    if x0.shape[1] != 4 or tuple(g.shape) != tuple(x0.shape) or g.dtype != torch.float32 or not g.is_contiguous():
+        raise OsmosisHipError(f"{name}: expected x0 [B,4,H,W] and a contiguous fp32 g of its shape, got {tuple(x0.shape)} and {tuple(g.shape)}")
+    want = (B, 1, x0.shape[2], x0.shape[3])
+    if tuple(z.shape) != want or tuple(m.shape) != want or len(dval) != 3:
+        raise OsmosisHipError(f"{name}: expected z and m {list(want)} and three dval entries, got {tuple(z.shape)} and {tuple(m.shape)}")
+    try:
+        d = ops.depth_desc(align, loss, weight, scale, scale_min, depth_type, dval, B, HW)
+    except ValueError as e:
+        raise OsmosisHipError(f"{name}: {e}") from None
+    dev = x0.device
+    part = torch.empty(B * ops.depth_nblk(HW) * 8, device=dev, dtype=torch.float64)
+    fit = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    depth_loss = torch.empty(B, device=dev, dtype=torch.float32)
+    ops.depth_loss_grad(d, x0, z.contiguous().view(B, 1, HW), m.contiguous().view(B, 1, HW), part, fit, depth_loss, g)
+    return depth_loss, fit
+
+
+@depth_prior_loss_grad.register_fake
+def _depth_prior_loss_grad_fake(x0, z, m, g, align, loss, weight, scale, scale_min, depth_type, dval):
+    return x0.new_empty((x0.shape[0],)), x0.new_empty((x0.shape[0], 4), dtype=torch.float64)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g", "ps_blind_loss_grad") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad") + OPS_C
