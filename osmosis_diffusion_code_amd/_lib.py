@@ -1,5 +1,6 @@
 """ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
-include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h and include/osmosis_depthprior.h).
+include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h and
+include/osmosis_solver.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -247,6 +248,12 @@ _SIGS_DEPTHPRIOR = {
     "osm_depth_loss_grad": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P, _P, _P, _P],
 }
 EXPORTS_DEPTHPRIOR = sorted(_SIGS_DEPTHPRIOR)
+# the entry points of the eighth header, include/osmosis_solver.h (few-step solvers: the DDIM / DPM-Solver++ 2M state update)
+_SIGS_SOLVER = {
+    "osm_solver_update_c": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
+    "osm_solver_update_rng_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
+}
+EXPORTS_SOLVER = sorted(_SIGS_SOLVER)
 
 _lib = None
 _lock = threading.Lock()
@@ -266,7 +273,7 @@ def load():
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
-                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()):
+                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

@@ -19,6 +19,7 @@
 #include "../../include/osmosis_psf.h"
 #include "../../include/osmosis_physlin.h"
 #include "../../include/osmosis_physgroup.h"
+#include "../../include/osmosis_solver.h"
 
 namespace {
 
@@ -764,6 +765,124 @@ __global__ __launch_bounds__(256) void guide_update_rng_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------- few-step solvers (include/osmosis_solver.h: DDIM, DPM-Solver++ 2M)
+// x_next = A x + B0 x0 + B1 hist + S z - scale[c] clamp(grad), hist <- x0, with the four coefficients of the rule in srow
+// (host, float64 -> fp32).  A lane owns four consecutive elements of the flat [B,C,HW] range: VEC (HW % 4 == 0, every pointer
+// 16-byte aligned: one quad lies in one channel of one image) moves them as one 16-byte access per tensor, otherwise one by one.
+// Every element is read (x, hist), then written (x_next, hist), by its one lane: x_next may alias x.
+
+// One element, no contraction: every product and every sum is rounded once, in this order.  The gradient arrives formed.
+__device__ __forceinline__ float solver_elem(float A, float B0, float B1, float S, bool noisy, float xv, float x0v, float hv, float zv,
+                                             bool guided, float sc, float clip, float grad) {
+#pragma clang fp contract(off)
+  float t = A * xv;
+  t += B0 * x0v;
+  if (B1 != 0.f) t += B1 * hv;
+  if (noisy) t += S * zv;
+  if (!guided) return t;
+  float gc = grad;
+  if (clip >= 0.f) gc = (grad != grad) ? grad : fminf(fmaxf(grad, -clip), clip);   // torch.clamp keeps NaN
+  return t - sc * gc;
+}
+
+struct SolverArgs {
+  const float* x0; const float* x; float* hist; const float* g; const float* dxu; const float* noise; const float* coef;
+  const float* srow; const float* scale; float clip; float* x_next; float* grad_out; float* noise_out; int B, C, HW;
+};
+
+// RNG: z is drawn here (counter words as guide_update_rng_kernel: element quad of the image, image, step | sub << 16, stream id)
+// instead of read from a.noise; it requires VEC.
+template <bool RNG, bool VEC>
+__device__ __forceinline__ void solver_update_body(const SolverArgs& a, unsigned k0, unsigned k1, unsigned step, int img0, int img_stride) {
+  static_assert(!RNG || VEC, "one Philox counter covers four consecutive elements of one channel");
+  const long long total = (long long)a.B * a.C * a.HW;
+  const long long nquad = (total + 3) >> 2;
+  const long long nq = ((long long)a.C * a.HW) >> 2;       // (VEC: quads per image)
+  const float c0 = a.coef[0];
+  const float A = a.srow[0], B0 = a.srow[1], B1 = a.srow[2], S = a.srow[3];
+  const bool noisy = S != 0.f && a.srow[4] != 0.f && (RNG || a.noise != nullptr);
+  const bool guided = a.g != nullptr;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nquad; i += (long long)gridDim.x * blockDim.x) {
+    const long long e0 = 4 * i;
+    float xv[4], x0v[4], hv[4] = {0.f, 0.f, 0.f, 0.f}, zv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f},
+          dv[4] = {0.f, 0.f, 0.f, 0.f}, sc[4] = {0.f, 0.f, 0.f, 0.f}, xo[4], go[4];
+    int n = 4;
+    if constexpr (VEC) {
+      const float4 vx = *reinterpret_cast<const float4*>(a.x + e0), v0 = *reinterpret_cast<const float4*>(a.x0 + e0);
+      xv[0] = vx.x; xv[1] = vx.y; xv[2] = vx.z; xv[3] = vx.w;
+      x0v[0] = v0.x; x0v[1] = v0.y; x0v[2] = v0.z; x0v[3] = v0.w;
+      if (B1 != 0.f) {
+        const float4 vh = *reinterpret_cast<const float4*>(a.hist + e0);
+        hv[0] = vh.x; hv[1] = vh.y; hv[2] = vh.z; hv[3] = vh.w;
+      }
+      if (guided) {
+        const float4 vg = *reinterpret_cast<const float4*>(a.g + e0);
+        gv[0] = vg.x; gv[1] = vg.y; gv[2] = vg.z; gv[3] = vg.w;
+        if (a.dxu) {
+          const float4 vd = *reinterpret_cast<const float4*>(a.dxu + e0);
+          dv[0] = vd.x; dv[1] = vd.y; dv[2] = vd.z; dv[3] = vd.w;
+        }
+        const float s = a.scale[(int)((e0 / a.HW) % a.C)];
+        sc[0] = sc[1] = sc[2] = sc[3] = s;
+      }
+      if (noisy) {
+        if constexpr (RNG) {
+          const long long b = i / nq, q = i - b * nq;
+          normal4(philox4x32_10((unsigned)q, (unsigned)(img0 + (int)b * img_stride), step, OSM_RNG_STREAM_STEP_NOISE, k0, k1), zv);
+        } else {
+          const float4 vz = *reinterpret_cast<const float4*>(a.noise + e0);
+          zv[0] = vz.x; zv[1] = vz.y; zv[2] = vz.z; zv[3] = vz.w;
+        }
+      }
+    } else {
+      n = (int)(total - e0 < 4 ? total - e0 : 4);
+      for (int e = 0; e < n; ++e) {
+        const long long k = e0 + e;
+        xv[e] = a.x[k]; x0v[e] = a.x0[k];
+        if (B1 != 0.f) hv[e] = a.hist[k];
+        if (guided) {
+          gv[e] = a.g[k];
+          if (a.dxu) dv[e] = a.dxu[k];
+          sc[e] = a.scale[(int)((k / a.HW) % a.C)];
+        }
+        if (noisy) zv[e] = a.noise[k];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e < n) {
+        go[e] = guided ? fmaf(c0, gv[e], dv[e]) : 0.f;        // c0 g + dx_unet as guide_update forms it: one rounding
+        xo[e] = solver_elem(A, B0, B1, S, noisy, xv[e], x0v[e], hv[e], zv[e], guided, sc[e], a.clip, go[e]);
+      }
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(a.x_next + e0) = make_float4(xo[0], xo[1], xo[2], xo[3]);
+      *reinterpret_cast<float4*>(a.hist + e0) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+      if (a.grad_out) *reinterpret_cast<float4*>(a.grad_out + e0) = make_float4(go[0], go[1], go[2], go[3]);
+      if (a.noise_out) *reinterpret_cast<float4*>(a.noise_out + e0) = make_float4(zv[0], zv[1], zv[2], zv[3]);
+    } else {
+      for (int e = 0; e < n; ++e) {
+        const long long k = e0 + e;
+        a.x_next[k] = xo[e];
+        a.hist[k] = x0v[e];
+        if (a.grad_out) a.grad_out[k] = go[e];
+        if (a.noise_out) a.noise_out[k] = zv[e];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void solver_update_kernel(SolverArgs a, int vec) {
+  if (vec) solver_update_body<false, true>(a, 0u, 0u, 0u, 0, 0);
+  else solver_update_body<false, false>(a, 0u, 0u, 0u, 0, 0);
+}
+
+__global__ __launch_bounds__(256) void solver_update_rng_kernel(SolverArgs a, unsigned k0, unsigned k1,
+                                                                 const int* __restrict__ step_dev, int step_offset, unsigned sub,
+                                                                 int img0, int img_stride) {
+  solver_update_body<true, true>(a, k0, k1, step_word((unsigned)(*step_dev + step_offset), sub), img0, img_stride);
+}
+
 // DDIM step + guidance (gaussian_diffusion.py:505-535, condition_methods.py:247-251), in the reference's operation order:
 //   eps = (r0 x - x0) / r1 ; sigma = eta sqrt((1 - abp) / (1 - ab)) sqrt(1 - ab / abp) ;
 //   x_next = x0 sqrt(abp) + sqrt(1 - abp - sigma^2) eps + [t != 0] sigma noise - scale[c] clamp(grad) ; grad = c0 g + dx_unet
@@ -1250,6 +1369,45 @@ int ddim_update_launch(const char* name, const float* x0, const float* x, const 
   return osm::check_launch("ddim_update_kernel");
 }
 
+// The argument checks of include/osmosis_solver.h, before any launch; *vec: whether every tensor can move as 16-byte quads.
+int solver_check(const char* name, const SolverArgs& a, int* vec) {
+  OSM_REQUIRE(a.x0 && a.x && a.hist && a.coef && a.srow && a.x_next, "%s: x0, x, hist, coef, srow and x_next must be given", name);
+  OSM_REQUIRE(a.B > 0 && a.C > 0 && a.HW > 0, "%s: bad shape B %d, C %d, HW %d", name, a.B, a.C, a.HW);
+  OSM_REQUIRE(!a.g || a.scale, "%s: guidance needs the per-channel scale", name);
+  OSM_REQUIRE(a.g || !a.dxu, "%s: dx_unet without g", name);
+  OSM_REQUIRE(a.clip == a.clip, "%s: clip is NaN (negative: no clamp)", name);
+  OSM_REQUIRE(a.hist != a.x0 && a.hist != a.x && a.hist != a.x_next, "%s: hist must be a buffer of its own", name);
+  const size_t bits = reinterpret_cast<size_t>(a.x0) | reinterpret_cast<size_t>(a.x) | reinterpret_cast<size_t>(a.hist) |
+                      reinterpret_cast<size_t>(a.g) | reinterpret_cast<size_t>(a.dxu) | reinterpret_cast<size_t>(a.noise) |
+                      reinterpret_cast<size_t>(a.x_next) | reinterpret_cast<size_t>(a.grad_out) | reinterpret_cast<size_t>(a.noise_out);
+  *vec = a.HW % 4 == 0 && (bits & 15) == 0;
+  return OSM_OK;
+}
+
+int solver_update_launch(const char* name, const SolverArgs& a, void* stream) {
+  int vec = 0;
+  const int rc = solver_check(name, a, &vec);
+  if (rc != OSM_OK) return rc;
+  const long long nquad = ((long long)a.B * a.C * a.HW + 3) / 4;
+  hipLaunchKernelGGL(solver_update_kernel, dim3(grid_for(nquad)), dim3(256), 0, (hipStream_t)stream, a, vec);
+  return osm::check_launch("solver_update_kernel");
+}
+
+int solver_update_rng_launch(const char* name, const SolverArgs& a, unsigned long long seed, const int* step, int step_offset, int sub,
+                             int img0, int img_stride, void* stream) {
+  int vec = 0;
+  const int rc = solver_check(name, a, &vec);
+  if (rc != OSM_OK) return rc;
+  OSM_REQUIRE(step, "%s: the device step counter must be given", name);
+  OSM_REQUIRE(sub >= 0 && sub < 65536, "%s: sub must be in [0, 65536), got %d", name, sub);
+  OSM_REQUIRE(a.HW % 4 == 0, "%s: H*W must be a multiple of 4 (one Philox counter per four elements of one channel)", name);
+  OSM_REQUIRE(vec, "%s: tensors must be 16-byte aligned", name);
+  const long long nquad = (long long)a.B * a.C * (a.HW / 4);
+  hipLaunchKernelGGL(solver_update_rng_kernel, dim3(grid_for(nquad)), dim3(256), 0, (hipStream_t)stream, a,
+                     (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step, step_offset, (unsigned)sub, img0, img_stride);
+  return osm::check_launch("solver_update_rng_kernel");
+}
+
 int randn_launch(const char* name, float* out, int B, long long n, unsigned long long seed, const int* step_dev, int step_const,
                  int sub, int img0, int img_stride, void* stream) {
   OSM_REQUIRE(out && B > 0 && n > 0, "%s: bad argument", name);
@@ -1393,6 +1551,21 @@ extern "C" int osm_ddim_update_c(const float* x0, const float* x, const float* g
                                  const float* coef, const float* dcoef, const float* scale, float clip, float* x_next,
                                  float* grad_out, int B, int C, int HW, void* stream) {
   return ddim_update_launch("osm_ddim_update_c", x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, grad_out, B, C, HW, stream);
+}
+
+extern "C" int osm_solver_update_c(const float* x0, const float* x, float* hist, const float* g, const float* dx_unet, const float* noise,
+                                   const float* coef, const float* srow, const float* scale, float clip, float* x_next,
+                                   float* grad_out, float* noise_out, int B, int C, int HW, void* stream) {
+  const SolverArgs a{x0, x, hist, g, dx_unet, noise, coef, srow, scale, clip, x_next, grad_out, noise_out, B, C, HW};
+  return solver_update_launch("osm_solver_update_c", a, stream);
+}
+
+extern "C" int osm_solver_update_rng_c(const float* x0, const float* x, float* hist, const float* g, const float* dx_unet,
+                                       const float* coef, const float* srow, const float* scale, float clip, float* x_next,
+                                       float* grad_out, float* noise_out, int B, int C, int HW, unsigned long long seed,
+                                       const int* step, int step_offset, int sub, int img0, int img_stride, void* stream) {
+  const SolverArgs a{x0, x, hist, g, dx_unet, nullptr, coef, srow, scale, clip, x_next, grad_out, noise_out, B, C, HW};
+  return solver_update_rng_launch("osm_solver_update_rng_c", a, seed, step, step_offset, sub, img0, img_stride, stream);
 }
 
 extern "C" int osm_fetch_coefs(const float* table, int n_rows, int* step, int delta, float* coef_out, float* t_out,

@@ -24,6 +24,9 @@ operators / processors, a chunked batch with dynamic_threshold) falls back to a 
 top of the HIP UNet operator through torch.autograd.
 `p_sample_loop(tiling=)` runs ONE canvas larger than the network's grid as overlapping tiles of the network's size (`_tiled_loop`,
 `tile_grid`; osm_tile_gather / osm_tile_blend move canvas <-> tiles): the network is tiled, every other part of the step acts on the canvas.
+A sampler built with `solver="ddim" | "dpmpp_2m"` (few-step solvers; include/osmosis_solver.h) replaces the state update of all three
+loops by x_next = A x_t + B0 x0 + B1 x0_prev + S z - scale clamp(grad) (`solver_table`; osm_solver_update(_rng)_c on the fused and
+tiled loops); `create_sampler(timestep_spacing=)` picks the few indices (`select_timesteps`).  `solver=None`: nothing changes.
 """
 import math
 
@@ -54,15 +57,35 @@ def get_sampler(name: str):
 
 
 def create_sampler(sampler, steps, noise_schedule, model_mean_type, model_var_type, dynamic_threshold,
-                   clip_denoised, rescale_timesteps, timestep_respacing="", **kwargs):
+                   clip_denoised, rescale_timesteps, timestep_respacing="", timestep_spacing="uniform", solver=None,
+                   solver_eta=0.0, **kwargs):
+    """timestep_spacing: 'uniform' = `space_timesteps(steps, timestep_respacing)`; 'quad' / 'logsnr' take ONE integer count in
+    `timestep_respacing` and pick the indices with `select_timesteps` (the low-noise end resolved: few-step chains).
+    solver / solver_eta: a few-step solver as the step rule (`SOLVERS`; None: the sampler class's own)."""
     cls = get_sampler(name=sampler)
     betas = get_named_beta_schedule(noise_schedule, steps)
-    if not timestep_respacing:
-        timestep_respacing = [steps]
-    return cls(use_timesteps=space_timesteps(steps, timestep_respacing), betas=betas,
+    if timestep_spacing not in TIMESTEP_SPACINGS:
+        raise ValueError(f"timestep_spacing must be one of {TIMESTEP_SPACINGS}, got {timestep_spacing!r}")
+    extra = {}
+    if solver is not None:            # (a sampler without one is built exactly as it always was)
+        extra = dict(solver=solver, solver_eta=solver_eta)
+    if timestep_spacing == "uniform":
+        if not timestep_respacing:
+            timestep_respacing = [steps]
+        use = space_timesteps(steps, timestep_respacing)
+    else:
+        try:
+            if isinstance(timestep_respacing, (bool, float, list, tuple)):
+                raise ValueError
+            count = int(timestep_respacing)
+        except (TypeError, ValueError):
+            raise ValueError(f"timestep_spacing={timestep_spacing!r} takes one integer count in timestep_respacing, got "
+                             f"{timestep_respacing!r}") from None
+        use = set(select_timesteps(np.cumprod(1.0 - betas, axis=0), count, timestep_spacing))
+    return cls(use_timesteps=use, betas=betas,
                model_mean_type=model_mean_type, model_var_type=model_var_type,
                dynamic_threshold=dynamic_threshold, clip_denoised=clip_denoised,
-               rescale_timesteps=rescale_timesteps, annealing_time=kwargs.get("annealing_time", False))
+               rescale_timesteps=rescale_timesteps, annealing_time=kwargs.get("annealing_time", False), **extra)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
@@ -104,6 +127,96 @@ def space_timesteps(num_timesteps, section_counts):
             pos += stride
         start += size
     return set(picked)
+
+
+SOLVERS = ("ddim", "dpmpp_2m")
+TIMESTEP_SPACINGS = ("uniform", "quad", "logsnr")
+
+
+def select_timesteps(base_alphas_cumprod, N, spacing):
+    """N distinct indices of a T-step schedule for a few-step chain, ascending, always with 0 and T - 1.  Targets from the noisiest
+    end, k = N - 1 .. 0: 'quad' (T - 1) (k / (N - 1))^2, nearest index floor(v + 1/2); 'logsnr' N values uniform in
+    lambda = log(alpha / sigma) from lambda(T - 1) to lambda(0), nearest index argmin |lambda - v|.  Each target takes its nearest
+    index clamped to [targets still to come, previous pick - 1]."""
+    ac = np.asarray(base_alphas_cumprod, dtype=np.float64)
+    T = int(ac.shape[0])
+    if spacing not in ("quad", "logsnr"):
+        raise ValueError(f"select_timesteps: spacing must be 'quad' or 'logsnr', got {spacing!r}")
+    if isinstance(N, bool) or int(N) != N or not 2 <= int(N) <= T:
+        raise ValueError(f"select_timesteps: the step count must be an integer in [2, {T}], got {N!r}")
+    N = int(N)
+    if spacing == "quad":
+        near = [int(math.floor((T - 1) * (k / (N - 1)) ** 2 + 0.5)) for k in range(N - 1, -1, -1)]
+    else:
+        lam = 0.5 * (np.log(ac) - np.log1p(-ac))
+        near = [int(np.argmin(np.abs(lam - v))) for v in np.linspace(lam[T - 1], lam[0], N)]
+    picks, prev = [], T
+    for j, i in enumerate(near):
+        prev = min(max(i, N - 1 - j), prev - 1)
+        picks.append(prev)
+    return picks[::-1]
+
+
+def solver_table(sampler, rule, eta=0.0, first=None):
+    """float64 [T][4] = A, B0, B1, S of a few-step solver over the sampler's own (respaced) schedule: the deterministic part of the
+    state after index i is A x_t + B0 x0 + B1 x0_prev, plus S z (include/osmosis_solver.h states the rules; 'ddim': Song et al.
+    2021 eq. 12 with `eta`; 'dpmpp_2m': Lu et al. 2022, DPM-Solver++ multistep, data prediction, eta = 0).  first: the first
+    executed index (default T - 1) -- history starts empty there, so its 2M row is first order.  The last index' row is
+    (0, 1, 0, 0): the sample is x0."""
+    rule, eta = check_solver(rule if rule is not None else "", eta)
+    ab = np.asarray(sampler.alphas_cumprod, dtype=np.float64)
+    abp = np.asarray(sampler.alphas_cumprod_prev, dtype=np.float64)
+    T = int(ab.shape[0])
+    first = T - 1 if first is None else int(first)
+    if not 0 <= first <= T - 1:
+        raise ValueError(f"first must be in [0, {T - 1}], got {first}")
+    tab = np.zeros((T, 4), dtype=np.float64)
+    for i in range(T):
+        if abp[i] == 1.0:
+            tab[i] = (0.0, 1.0, 0.0, 0.0)
+            continue
+        al, sg, alp, sgp = math.sqrt(ab[i]), math.sqrt(1.0 - ab[i]), math.sqrt(abp[i]), math.sqrt(1.0 - abp[i])
+        if rule == "ddim":
+            s = eta * math.sqrt((1.0 - abp[i]) / (1.0 - ab[i])) * math.sqrt(1.0 - ab[i] / abp[i])
+            A = math.sqrt(1.0 - abp[i] - s * s) / sg
+            tab[i] = (A, alp - A * al, 0.0, s)
+            continue
+        h = math.log(alp / sgp) - math.log(al / sg)
+        beta = -alp * math.expm1(-h)
+        if i == first or i == T - 1:
+            tab[i] = (sgp / sg, beta, 0.0, 0.0)
+        else:
+            r = (math.log(al / sg) - math.log(math.sqrt(ab[i + 1]) / math.sqrt(1.0 - ab[i + 1]))) / h      # h_prev / h
+            tab[i] = (sgp / sg, beta * (1.0 + 1.0 / (2.0 * r)), -beta / (2.0 * r), 0.0)
+    return tab
+
+
+def check_solver(solver, solver_eta):
+    """The (name, eta) of a sampler's solver, validated; (None, 0.0): the sampler's own step rule."""
+    if solver is None:
+        return None, 0.0
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown solver {solver!r}: one of {', '.join(SOLVERS)} (or None for the sampler's own step rule)")
+    eta = float(solver_eta)
+    if not eta >= 0.0:
+        raise ValueError(f"solver_eta must be >= 0, got {solver_eta!r}")
+    if solver == "dpmpp_2m" and eta != 0.0:
+        raise ValueError(f"the dpmpp_2m solver is deterministic: solver_eta must be 0, got {solver_eta!r}")
+    return solver, eta
+
+
+def solver_refusals(diffusion, sample_pattern, mean_only):
+    """What a chain with a solver does not carry, raised on the host: the PCGS inner alternation (a step repeated at one t has no
+    multistep meaning) and the mean-only branch."""
+    if diffusion.solver is None:
+        return
+    if mean_only:
+        raise NotImplementedError(f"solver={diffusion.solver!r}: the mean-only branch (pretrain_model != 'osmosis' without "
+                                  "rgb_guidance) has no solver step")
+    if max(a for _, _, a in pcgs_schedule(sample_pattern, diffusion.num_timesteps)) > 1 or (
+            sample_pattern is not None and sample_pattern.get("pattern") not in (None, "original")
+            and int(sample_pattern.get("local_M", 1)) > 1):
+        raise ValueError(f"solver={diffusion.solver!r} with local_M > 1: a step repeated at the same t has no multistep meaning")
 
 
 def guidance_flag(sample_pattern, idx, T):
@@ -222,6 +335,9 @@ class _Chain:
         if not (0 <= self.last <= self.first <= T - 1):
             raise ValueError(f"index_range must satisfy 0 <= last <= first <= {T - 1}, got ({self.first}, {self.last})")
         self.sched = pcgs_schedule(sample_pattern, T)     # (an invalid pattern raises here)
+        self.solver = diffusion.solver                    # a few-step solver as the state update (None: the class's own rule)
+        solver_refusals(diffusion, sample_pattern, mean_only)
+        self.solver_noisy = self.solver == "ddim" and diffusion.solver_eta > 0.0      # (S can be non-zero)
         if T > 1 << 16 and max(a for _, _, a in self.sched) > 1:
             raise ValueError("sub-steps need a chain of at most 65536 indices (the step counter word holds step | sub << 16)")
         self.noise_fn = kwargs.get("noise_fn", None)      # (k, shape) -> tensor : injected noise (parity runs)
@@ -240,10 +356,11 @@ class _Chain:
         self.records = kwargs.get("record_out", [] if record else None)   # (idx, pred_xstart cpu) snapshots
         self.have_loss = False
 
-    def open(self, model, n, h, w, dev, scale, clip):
+    def open(self, model, n, h, w, dev, scale, clip, state_shape=None):
         """The device side, for n network inputs of h x w (independent chains, SURVEY.md F1/F2: a batch whose kept activations would
         not fit the device -- ~8 GB per 256 x 256 image in fp32 -- is walked in chunks per step, contiguous row blocks).  scale, clip:
-        the conditioner's per-channel guidance scale [C] and gradient clip, used at the guided indices."""
+        the conditioner's per-channel guidance scale [C] and gradient clip, used at the guided indices.  state_shape: the state's
+        [B,C,H,W] where it is not the network inputs' (the canvas of a tiled chain): a solver's history has that shape."""
         sizes = self.diffusion.chunk_sizes(n, model.images_in_flight(n, h, w))
         self.chunks, c0 = [], 0
         for sz in sizes:
@@ -255,13 +372,24 @@ class _Chain:
         self.eng = self.engs[sizes[0]]
         self.single = len(self.chunks) == 1
         self.scale, self.clip = scale, clip
-        self.table = torch.from_numpy(self.diffusion.coef_table()).to(dev)
+        table = self.diffusion.coef_table()
+        self.table = torch.from_numpy(table).to(dev)
         self.step = torch.tensor([self.first], device=dev, dtype=torch.int32)
         self.coef = torch.zeros(8, device=dev, dtype=torch.float32)
         self.dtable = self.dcoef = None
         if self.ddim:
             self.dtable = torch.from_numpy(self.diffusion.ddim_table(float(self.kwargs.get("eta", 0.0)))).to(dev)
             self.dcoef = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.stable = self.scoef = self.hist = None
+        if self.solver is not None:   # rows [A, B0, B1, S, noise_on, 0, 0, t_model]; history starts empty at `first`
+            rows = np.zeros((self.diffusion.num_timesteps, 8), dtype=np.float32)
+            rows[:, 0:4] = solver_table(self.diffusion, self.solver, self.diffusion.solver_eta, first=self.first)
+            rows[:, 4] = rows[:, 3] != 0
+            rows[:, 7] = table[:, 7]
+            self.stable = torch.from_numpy(rows).to(dev)
+            self.scoef = torch.zeros(8, device=dev, dtype=torch.float32)
+            # the previous index' processed x0 of every image of the state (the canvas's, for a tiled chain)
+            self.hist = torch.empty(*(state_shape or (n, model.in_channels, h, w)), device=dev, dtype=torch.float32)
         self.seed = 0
         if self.source == "library":
             self.seed = self.kwargs.get("noise_seed")
@@ -278,16 +406,28 @@ class _Chain:
                 ops.fetch_coefs(self.table, self.step, 0, self.coef, e2.t_dev, e2.B)
         if self.ddim:
             ops.fetch_coefs(self.dtable, self.step, 0, self.dcoef, eng.t_dev, eng.B)
+        if self.solver is not None:
+            ops.fetch_coefs(self.stable, self.step, 0, self.scoef, eng.t_dev, eng.B)
         ops.fetch_coefs(self.table, self.step, -1 if final else 0, self.coef, eng.t_dev, eng.B)
 
-    def update(self, a, b, g, dxu, noise, x_next, grad_out, noise_out, sub, final, img0, img_stride):
+    def update(self, a, b, g, dxu, noise, x_next, grad_out, noise_out, sub, final, img0, img_stride, rows=None):
         """x_next [Bc,C,H,W] = the state of one row block after this sub-step, from (a, b) = its (mean, log variance) -- for DDIM its
         (pred_xstart, x_t).  g, dxu: the data term's gradient and the network's dx, None at an unguided index (no scale, no clip);
-        noise: the step noise as a tensor, or None (drawn in the kernel into noise_out if given; the mean-only step: none added)."""
+        noise: the step noise as a tensor, or None (drawn in the kernel into noise_out if given; the mean-only step: none added).
+        With a solver (a, b) = (pred_xstart, x_t) as for DDIM and rows = the block's rows of the state (None: all of it), whose
+        history the same launch reads and renews; the noise is drawn in the kernel when the source is the library's stream and
+        the rule can add any."""
         Bc, C, H, W = x_next.shape
         HW = H * W
         sc, cl = (None, -1.0) if g is None else (self.scale, self.clip)
-        if self.ddim:
+        if self.solver is not None:
+            hist = self.hist if rows is None else self.hist[rows[0]:rows[1]]
+            if self.lib_rng and self.solver_noisy:
+                ops.solver_update_rng_c(a, b, hist, g, dxu, self.coef, self.scoef, sc, cl, x_next, grad_out, noise_out, Bc, C, HW,
+                                        self.seed, self.step, step_offset=1 if final else 0, sub=sub, img0=img0, img_stride=img_stride)
+            else:
+                ops.solver_update_c(a, b, hist, g, dxu, noise, self.coef, self.scoef, sc, cl, x_next, grad_out, noise_out, Bc, C, HW)
+        elif self.ddim:
             ops.ddim_update_c(a, b, g, dxu, noise, self.coef, self.dcoef, sc, cl, x_next, grad_out, Bc, C, HW)
         elif self.lib_rng:                                # (+1 after the last sub-step's fetch: it moved the counter)
             ops.guide_update_rng_c(a, b, g, dxu, self.coef, sc, cl, x_next, grad_out, noise_out, Bc, C, HW, self.seed, self.step,
@@ -327,7 +467,10 @@ class _Chain:
 
 class GaussianDiffusion:
     def __init__(self, betas, model_mean_type, model_var_type, dynamic_threshold, clip_denoised,
-                 rescale_timesteps, **kwargs):
+                 rescale_timesteps, solver=None, solver_eta=0.0, **kwargs):
+        """solver: None (the class's own step rule; nothing changes) or one of `SOLVERS` -- a few-step solver replaces the state
+        update of every loop (`solver_table`); solver_eta: DDIM's eta (0: deterministic), 0 for dpmpp_2m."""
+        self.solver, self.solver_eta = check_solver(solver, solver_eta)
         betas = np.array(betas, dtype=np.float64)
         self.betas = betas
         assert betas.ndim == 1, "betas must be 1-D"
@@ -524,7 +667,7 @@ class GaussianDiffusion:
         so its step pools every image's tap gradient -- ONE `loss_grad_x0` over [0, B))."""
         from .condition_methods import PosteriorSampling
         ps = isinstance(cond, PosteriorSampling)
-        ddim = ps and not mean_only and getattr(type(self), "p_sample", None) is DDIM.p_sample
+        ddim = self.solver is None and ps and not mean_only and getattr(type(self), "p_sample", None) is DDIM.p_sample
         dev = x_start.device
         B, C, H, W = x_start.shape
         Cout = model.out_channels
@@ -660,10 +803,10 @@ class GaussianDiffusion:
                         ce.run_backward()
                         gg, dxu = g[c0:c1], ce.dx
                         grad_out = grad_all[c0:c1] if trace is not None else None
-                    a, b = (x0[c0:c1], ce.x_in) if ddim else (mean[c0:c1], logvar[c0:c1])
+                    a, b = (x0[c0:c1], ce.x_in) if (ddim or ch.solver is not None) else (mean[c0:c1], logvar[c0:c1])
                     ch.update(a, b, gg, dxu, None if noise is None else noise[c0:c1], x_state[c0:c1], grad_out,
                               None if noise_used is None else noise_used[c0:c1], sub, final,
-                              img_base + (0 if shared else c0), img_stride)
+                              img_base + (0 if shared else c0), img_stride, rows=(c0, c1))
                 if trace is not None:
                     ch.trace_record(idx, sub, x_in, x0, mean, x_state, model_out, loss_all, phi, noise_used, q_dev, grad_all)
                 k += 1
@@ -719,7 +862,7 @@ class GaussianDiffusion:
         HW, T, n = Hc * Wc, self.num_timesteps, origins.shape[0]
         ch = _Chain(self, sample_pattern, kwargs, HW, record, record_every)
         # ---- everything above is host-side; from here on the device is used
-        ch.open(model, n, th, tw, dev, cond.scale4(dev), cond.clip_value)
+        ch.open(model, n, th, tw, dev, cond.scale4(dev), cond.clip_value, state_shape=(1, 4, Hc, Wc))
         chunks, engs, eng, single, coef, trace = ch.chunks, ch.engs, ch.eng, ch.single, ch.coef, ch.trace
         f32 = dict(device=dev, dtype=torch.float32)
         org, wy, wx, inv_norm = origins.to(dev), wy.to(dev), wx.to(dev), inv_norm.to(dev).contiguous()
@@ -785,7 +928,8 @@ class GaussianDiffusion:
                     ops.tile_blend(eng.dx if single else dx_tiles, dx, org)
                     gg, dxu = g, dx
                     grad_out = torch.empty_like(g) if trace is not None else None
-                ch.update(mean, logvar, gg, dxu, noise, x_state, grad_out, noise_used, sub, final, img_base, 1)
+                a, b = (mean, logvar) if ch.solver is None else (x0, x_state)
+                ch.update(a, b, gg, dxu, noise, x_state, grad_out, noise_used, sub, final, img_base, 1)
                 if trace is not None:
                     ch.trace_record(idx, sub, x_in, x0, mean, x_state, model_out.clone(), loss_all, phi, noise_used, grad=grad_out)
                 k += 1
@@ -873,7 +1017,13 @@ class GaussianDiffusion:
                       kwargs, record=False, record_every=150):
         """Third-party conditioners / operators / processors the fused loop has no kernels for: the reference's control flow
         (gaussian_diffusion.py:213-340) over `p_mean_variance` / `p_sample` with torch.autograd through the HIP UNet operator.
-        `record=True` snapshots pred_xstart at the reference's indices (:308-327) here as well."""
+        `record=True` snapshots pred_xstart at the reference's indices (:308-327) here as well.
+        With a solver the step rule is `solver_table`'s row applied to torch tensors: the sample handed to the conditioner is the
+        deterministic part A x + B0 x0 + B1 x0_prev (the history lives in this loop), and S z is added where the ancestral
+        noise was (Osmosis branch: after the conditioner; rgb-guidance branch: in `p_sample`'s place, z drawn there)."""
+        solver_refusals(self, sample_pattern, pretrain_model != "osmosis" and not rgb_guidance)
+        stab = None if self.solver is None else solver_table(self, self.solver, self.solver_eta).astype(np.float32)
+        hist = None
         img = x_start
         device = x_start.device
         T = self.num_timesteps
@@ -886,7 +1036,18 @@ class GaussianDiffusion:
             alt = utilso.set_alternate_length(sample_pattern, idx, T) if sample_pattern is not None else 1
             for _ in range(alt):
                 img = img.detach().requires_grad_(bool(guided))
-                if rgb_guidance:
+                if stab is not None:
+                    A, B0, B1, S = (float(v) for v in stab[idx])
+                    out = self.p_mean_variance(model=model, x=img, t=time)
+                    det = A * img + B0 * out["pred_xstart"]
+                    if B1 != 0.0:
+                        det = det + B1 * hist
+                    hist = out["pred_xstart"].detach()
+                    if rgb_guidance:
+                        z = torch.randn_like(img)          # drawn at every index, as `p_sample` does
+                        det = det + S * z if S != 0.0 else det
+                    out["sample"] = det
+                elif rgb_guidance:
                     out = self.p_sample(x=img, t=time, model=model)
                 else:
                     out = self.p_mean_variance(model=model, x=img, t=time)
@@ -906,7 +1067,10 @@ class GaussianDiffusion:
                     img = out["sample"]
                 noise = torch.randn_like(img)
                 img = img.detach()
-                if idx != 0:
+                if stab is not None:
+                    if S != 0.0:
+                        img = img + S * noise
+                elif idx != 0:
                     img = img + torch.exp(0.5 * out["log_variance"].detach()) * noise
             if records is not None and ((idx % record_every == 0) or idx == 0 or idx == 999):
                 records.append((idx, out["pred_xstart"].detach().cpu()))

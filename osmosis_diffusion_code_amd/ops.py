@@ -584,6 +584,23 @@ def ddim_update_c(x0, x, g, dx_unet, noise, coef, dcoef, scale, clip, x_next, gr
          ptr(x_next), ptr(grad_out), B, Cc, HW, _s(), keep=(x0, x, g, dx_unet, noise, coef, dcoef, scale, x_next, grad_out))
 
 
+def solver_update_c(x0, x, hist, g, dx_unet, noise, coef, srow, scale, clip, x_next, grad_out, noise_out, B, Cc, HW):
+    """The few-step solver step (osm_solver_update_c, include/osmosis_solver.h): x_next = A x + B0 x0 + B1 hist + S noise -
+    scale[c] clamp(c0 g + dx_unet) with srow = [A, B0, B1, S, noise_on, ..] (`gaussian_diffusion.solver_table`), then hist <- x0.
+    x_next may alias x; hist is read only when B1 != 0."""
+    call("osm_solver_update_c", ptr(x0), ptr(x), ptr(hist), ptr(g), ptr(dx_unet), ptr(noise), ptr(coef), ptr(srow), ptr(scale),
+         float(clip), ptr(x_next), ptr(grad_out), ptr(noise_out), B, Cc, HW, _s(),
+         keep=(x0, x, hist, g, dx_unet, noise, coef, srow, scale, x_next, grad_out, noise_out))
+
+
+def solver_update_rng_c(x0, x, hist, g, dx_unet, coef, srow, scale, clip, x_next, grad_out, noise_out, B, Cc, HW, seed, step,
+                        step_offset=0, sub=0, img0=0, img_stride=1):
+    """`solver_update_c` with the noise drawn in the kernel: the counter words of `guide_update_rng_c`, so `randn_sub` draws the same."""
+    call("osm_solver_update_rng_c", ptr(x0), ptr(x), ptr(hist), ptr(g), ptr(dx_unet), ptr(coef), ptr(srow), ptr(scale), float(clip),
+         ptr(x_next), ptr(grad_out), ptr(noise_out), B, Cc, HW, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), int(step_offset), int(sub),
+         int(img0), int(img_stride), _s(), keep=(x0, x, hist, g, dx_unet, coef, srow, scale, x_next, grad_out, noise_out, step))
+
+
 def ps_loss_grad_c(x0, y, part, loss, g, B, Cc, HW):
     """loss[b] = ||y[b] - x0[b, 0:3]||, g = d loss / d x0 (zero beyond channel 2); part: fp32 [B * phys_nblk(HW)] workspace."""
     call("osm_ps_loss_grad_c", ptr(x0), ptr(y), ptr(part), ptr(loss), ptr(g), B, Cc, HW, _s(), keep=(x0, y, part, loss, g))

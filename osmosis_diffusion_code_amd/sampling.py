@@ -500,6 +500,10 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     through it (`p_sample_loop(measurement_mask=)`) and every result carries it as `mask` [B,3,H,W]; without either, nothing
     is passed and the results have no such key.
 
+    `diffusion: {solver, solver_eta, timestep_spacing}` (optional config keys; `create_sampler`): a few-step solver ('ddim' |
+    'dpmpp_2m') as the step rule and 'quad' / 'logsnr' index selection for `timestep_respacing: "<count>"`.  Every result then
+    carries `solver` and `steps` (the indices the chain has); without a solver there are no such keys.
+
     `tiling` (or the optional top-level config key `tiling`; the argument wins): `{tile, stride, window}` (`parse_tiling`; unknown
     keys raise) for ONE image larger than the network's grid, e.g. the 512-class grid of `data.fit_transform(size=512)`: the
     network sees overlapping tiles of side `tile`, everything else acts on the whole image (`p_sample_loop(tiling=)`).  Every
@@ -614,6 +618,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
                 results[-1]["mask"] = m_dev.detach().cpu()
             if is_blind:
                 results[-1]["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
+            if getattr(sampler, "solver", None) is not None:
+                results[-1].update(solver=sampler.solver, steps=sampler.num_timesteps)
             continue
         sample, variable_dict, loss, out_xstart = ret
         if postprocess_batch:
@@ -638,6 +644,8 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             post["tiling"] = tiling_info
         if is_blind:
             post["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
+        if getattr(sampler, "solver", None) is not None:
+            post.update(solver=sampler.solver, steps=sampler.num_timesteps)
         results.append(post)
     return results
 

@@ -868,8 +868,35 @@ def _depth_prior_loss_grad_fake(x0, z, m, g, align, loss, weight, scale, scale_m
     return x0.new_empty((x0.shape[0],)), x0.new_empty((x0.shape[0], 4), dtype=torch.float64)
 
 
+# ---- few-step solvers (include/osmosis_solver.h): the state update of a DDIM / DPM-Solver++ 2M step, in place
+@torch.library.custom_op("osmosis::solver_update", mutates_args=("x_next", "hist"), device_types="cuda")
+def solver_update(x0: torch.Tensor, x: torch.Tensor, hist: torch.Tensor, g: Optional[torch.Tensor], dx_unet: Optional[torch.Tensor],
+                  noise: Optional[torch.Tensor], coef: torch.Tensor, srow: torch.Tensor, scale: torch.Tensor, clip: float,
+                  x_next: torch.Tensor) -> torch.Tensor:
+    """osm_solver_update_c: x_next = A x + B0 x0 + B1 hist + S noise - scale[c] clamp(c0 g + dx_unet), written IN PLACE, then
+    hist <- x0 IN PLACE (read only when B1 != 0).  coef: the posterior row; srow = [A, B0, B1, S, noise_on, 0, 0, t_model], a row of
+    `gaussian_diffusion.solver_table` as `_Chain.open` lays it out; scale [C]; clip < 0: no clamp.  Returns grad = c0 g + dx_unet
+    (zeros without g).  x_next may be x itself only through the C ABI (an operator argument that is mutated cannot alias another)."""
+    name = "osmosis::solver_update"
+    B, HW = _chw(x0)
+    Cc = _channel_scale(name, scale, x0)
+    for t, what in ((x, "x"), (hist, "hist"), (x_next, "x_next"), (g, "g"), (dx_unet, "dx_unet"), (noise, "noise")):
+        if t is not None and (tuple(t.shape) != tuple(x0.shape) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise OsmosisHipError(f"{name}: {what} must be a contiguous fp32 tensor of x0's shape {tuple(x0.shape)}")
+    if coef.numel() < 8 or srow.numel() < 8:
+        raise OsmosisHipError(f"{name}: coef and srow are rows of 8 floats")
+    grad = torch.zeros_like(x0) if g is None else torch.empty_like(x0)
+    ops.solver_update_c(x0, x, hist, g, dx_unet, noise, coef, srow, scale, clip, x_next, None if g is None else grad, None, B, Cc, HW)
+    return grad
+
+
+@solver_update.register_fake
+def _solver_update_fake(x0, x, hist, g, dx_unet, noise, coef, srow, scale, clip, x_next):
+    return torch.empty_like(x0)
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update") + OPS_C

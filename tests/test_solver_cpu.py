@@ -1,0 +1,273 @@
+"""Few-step solvers, host side (no GPU): the coefficient tables against their identities and the oracle's restatement
+(tests/solver_oracle.py), timestep selection, the order of convergence on a closed-form test bed, the refusals (all raised before
+any device use) and the eighth header of the C ABI against the library and `_lib.EXPORTS_SOLVER`."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import solver_oracle as SO
+from oracle import diffusion_ref as D
+from osmosis_diffusion_code_amd import _lib
+from osmosis_diffusion_code_amd.guided_diffusion import gaussian_diffusion as gd
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"osm_solver_update_c", "osm_solver_update_rng_c"}
+BASE = dict(steps=1000, noise_schedule="linear", model_mean_type="epsilon", model_var_type="learned_range", dynamic_threshold=False,
+            clip_denoised=False, rescale_timesteps=False)
+PATTERN = dict(pattern="pcgs", update_start=0.7, update_end=0, global_N=1, local_M=1, s_start=1, s_end=0, n_iter=20,
+               start_guidance=1, stop_guidance=0)
+
+
+def sampler_of(name="ddpm", **kw):
+    return gd.create_sampler(name, **dict(BASE, **kw))
+
+
+# ------------------------------------------------------------------------------------------------------------ tables
+@pytest.mark.parametrize("schedule", ["linear", "cosine"])
+@pytest.mark.parametrize("respacing", ["10", "50", ""])
+def test_table_identities_in_float64(schedule, respacing):
+    s = sampler_of(noise_schedule=schedule, timestep_respacing=respacing)
+    T = s.num_timesteps
+    ddim0, ddim5 = gd.solver_table(s, "ddim", 0.0), gd.solver_table(s, "ddim", 0.5)
+    assert ddim0.dtype == np.float64 and ddim0.shape == (T, 4)
+    # the first-order 2M row is the DDIM eta = 0 row: at the first executed index, whichever it is
+    for first in (T - 1, T // 2, 1):
+        two = gd.solver_table(s, "dpmpp_2m", 0.0, first=first)
+        scale = np.abs(ddim0[first]).max()
+        assert np.abs(two[first] - ddim0[first]).max() <= 1e-14 * max(1.0, scale), (first, two[first], ddim0[first])
+        assert two[first, 2] == 0.0 and two[first, 3] == 0.0
+        if first >= 2:
+            assert two[first - 1, 2] != 0.0                      # ... and the next index has its history
+    two = gd.solver_table(s, "dpmpp_2m")
+    assert np.array_equal(two, gd.solver_table(s, "dpmpp_2m", 0.0, first=T - 1)) and two[T - 1, 2] == 0.0
+    for tab in (ddim0, ddim5, two):
+        assert tuple(tab[0]) == (0.0, 1.0, 0.0, 0.0)             # the last index: the sample is x0
+        assert np.isfinite(tab).all()
+    assert (ddim0[:, 2:] == 0).all() and (ddim5[1:, 3] > 0).all() and (two[:, 3] == 0).all()
+    # consistency of a 2M row: a constant x0 is a fixed point of the data-prediction form, B0 + B1 = beta = alpha' - A alpha
+    assert np.abs((two[1:, 1] + two[1:, 2]) - ddim0[1:, 1]).max() <= 1e-13
+    # the oracle's own restatement of the rules
+    tb = D.Tables(D.named_beta_schedule(schedule, 1000), s.use_timesteps)
+    for rule, eta, first in (("ddim", 0.0, None), ("ddim", 0.5, None), ("dpmpp_2m", 0.0, None), ("dpmpp_2m", 0.0, T // 2)):
+        got, want = gd.solver_table(s, rule, eta, first=first), SO.coefs(tb, rule, eta, first)
+        n = T if first is None else first + 1
+        assert np.abs(got[:n] - want[:n]).max() <= 1e-12 * max(1.0, np.abs(want[:n]).max()), (rule, eta, first)
+
+
+@pytest.mark.parametrize("eta", [0.0, 0.5, 1.0])
+def test_ddim_rows_reproduce_step_scalars_in_x0_form(eta):
+    """`DDIM.step_scalars` gives x_next = x0 sa + sb (c0 x - x0) / c1 + sigma z in fp32; in (x_t, x0) form that is A = sb c0 / c1,
+    B0 = sa - sb / c1, S = sigma.  The float64 rows agree to the fp32 rounding of `step_scalars` itself, which forms its square roots
+    from fp32 operands: u = 1 - ab', 1 - ab and 1 - ab / ab' each carry up to 2 x 2^-24 absolute (the rounded table entry and one
+    operation), so sqrt(u) carries that over 2 u relative; sigma collects the three, sb = sqrt(1 - ab' - sigma^2) its own operand's
+    and 2 sigma d sigma, over 2 sb; A and B0 inherit sb's through c0 / c1 and 1 / c1, plus 4 ulp of their largest term."""
+    e = 2.0 ** -24
+    s = sampler_of("ddim", timestep_respacing="10")
+    tab = gd.solver_table(s, "ddim", eta)
+    for i in range(1, s.num_timesteps):
+        c0, c1, sa, sb, sigma = (float(v) for v in s.step_scalars(i, eta))
+        A, B0, S = sb * c0 / c1, sa - sb / c1, sigma
+        ab, abp = s.alphas_cumprod[i], s.alphas_cumprod_prev[i]
+        tol_S = sigma * e * (1.0 / (1.0 - abp) + 1.0 / (1.0 - ab) + 1.0 / (1.0 - ab / abp) + 4.0)
+        tol_sb = (2.0 * e + 2.0 * sigma * tol_S) / (2.0 * sb) + 2.0 * e * sb
+        tol_A = tol_sb * c0 / c1 + 4.0 * e * abs(A)
+        tol_B0 = tol_sb / c1 + 4.0 * e * max(abs(sa), abs(sb / c1))
+        assert abs(tab[i, 0] - A) <= tol_A and abs(tab[i, 1] - B0) <= tol_B0 and abs(tab[i, 3] - S) <= tol_S, (
+            i, tab[i], (A, B0, S), (tol_A, tol_B0, tol_S))
+        if eta == 0.0:                       # (without sigma^2 under the root the allowance is a rounding allowance: < 1e-3 of A)
+            assert tol_A <= 1e-3 * abs(A) and tab[i, 3] == 0.0 == S
+
+
+# ------------------------------------------------------------------------------------------------------------ timestep selection
+@pytest.mark.parametrize("schedule", ["linear", "cosine"])
+@pytest.mark.parametrize("spacing", ["quad", "logsnr"])
+@pytest.mark.parametrize("N", [2, 10, 50, 1000])
+def test_select_timesteps_gives_n_distinct_indices_with_both_ends(schedule, spacing, N):
+    ac = np.cumprod(1.0 - gd.get_named_beta_schedule(schedule, 1000))
+    picks = gd.select_timesteps(ac, N, spacing)
+    assert len(picks) == N == len(set(picks)) and picks == sorted(picks) and picks[0] == 0 and picks[-1] == 999
+    s = sampler_of(noise_schedule=schedule, timestep_respacing=str(N), timestep_spacing=spacing)
+    assert s.num_timesteps == N and s.timestep_map == picks
+
+
+def test_the_logsnr_list_and_uniform_is_todays_set():
+    ac = np.cumprod(1.0 - gd.get_named_beta_schedule("linear", 1000))
+    assert gd.select_timesteps(ac, 10, "logsnr") == [0, 5, 22, 73, 202, 410, 603, 757, 886, 999]
+    quad = gd.select_timesteps(ac, 10, "quad")
+    assert quad == [int(np.floor(999 * (k / 9) ** 2 + 0.5)) for k in range(10)]          # (no clamp binds at N = 10)
+    for resp in ("10", "250", "ddim50", "10,20,30", ""):
+        a, b = sampler_of(timestep_respacing=resp), sampler_of(timestep_respacing=resp, timestep_spacing="uniform")
+        want = gd.space_timesteps(1000, resp if resp else [1000])
+        assert a.use_timesteps == b.use_timesteps == want and np.array_equal(a.betas, b.betas)
+    plain = sampler_of(timestep_respacing="10")
+    assert plain.solver is None and plain.solver_eta == 0.0
+    assert sampler_of(timestep_respacing="10", solver="dpmpp_2m").solver == "dpmpp_2m"
+    assert sampler_of(timestep_respacing="10", solver="ddim", solver_eta=0.5).solver_eta == 0.5
+
+
+# ------------------------------------------------------------------------------------------------------------ order of convergence
+def test_order_of_convergence_on_the_gaussian_test_bed():
+    """Data N(0.3, 0.25) has a closed-form denoiser and probability-flow solution (tests/solver_oracle.gaussian_chain_error): 64
+    seeded samples, linear 1000 schedule, logsnr spacing, max-abs error at the end, through `solver_table` and `select_timesteps`
+    (fp32-rounded coefficients, as the kernels receive them).  Measured in float64: N = 10 / 20 / 40 / 80 -> DDIM 0.274 / 0.139 /
+    0.0701 / 0.0352, dpmpp_2m 0.0369 / 0.0169 / 0.00418 / 0.00084."""
+    err = {}
+    for rule in ("ddim", "dpmpp_2m"):
+        for N in (10, 20, 40, 80):
+            s = sampler_of(timestep_respacing=str(N), timestep_spacing="logsnr")
+            tab = gd.solver_table(s, rule).astype(np.float32).astype(np.float64)
+            err[rule, N] = SO.gaussian_chain_error(tab, s.alphas_cumprod)
+    print("SOLVERORDER", {k: f"{v:.4g}" for k, v in err.items()})
+    assert err["dpmpp_2m", 20] / err["dpmpp_2m", 40] >= 3.0          # order 2 (measured 4.05)
+    assert err["ddim", 20] / err["ddim", 40] <= 2.5                  # order 1 (measured 1.98)
+    assert err["ddim", 20] / err["dpmpp_2m", 20] >= 5.0              # (measured 8.2)
+    for (rule, N), want in {("ddim", 10): 0.274, ("ddim", 80): 0.0352, ("dpmpp_2m", 10): 0.0369, ("dpmpp_2m", 80): 0.00084}.items():
+        assert abs(err[rule, N] - want) <= 0.01 * want, (rule, N, err[rule, N])
+
+
+# ------------------------------------------------------------------------------------------------------------ refusals
+def test_refusals_are_raised_on_the_host():
+    with pytest.raises(ValueError, match="ddim, dpmpp_2m"):
+        sampler_of(solver="heun")
+    with pytest.raises(ValueError, match="solver_eta must be 0"):
+        sampler_of(solver="dpmpp_2m", solver_eta=0.5)
+    with pytest.raises(ValueError, match="solver_eta"):
+        sampler_of(solver="ddim", solver_eta=-0.1)
+    with pytest.raises(ValueError, match="solver_eta must be 0"):
+        gd.solver_table(sampler_of(timestep_respacing="10"), "dpmpp_2m", 0.3)
+    for bad in ("euler", None):
+        with pytest.raises(ValueError, match="ddim, dpmpp_2m"):
+            gd.solver_table(sampler_of(timestep_respacing="10"), bad)
+    with pytest.raises(ValueError, match="timestep_spacing must be one of"):
+        sampler_of(timestep_respacing="10", timestep_spacing="karras")
+    for bad in ("10,20", [10, 20], "ddim50", ""):
+        with pytest.raises(ValueError, match="one integer count"):
+            sampler_of(timestep_respacing=bad, timestep_spacing="quad")
+    for n in (1, 1001):
+        with pytest.raises(ValueError, match=r"\[2, 1000\]"):
+            sampler_of(timestep_respacing=str(n), timestep_spacing="logsnr")
+    with pytest.raises(ValueError, match="spacing must be"):
+        gd.select_timesteps(np.linspace(0.99, 0.01, 100), 10, "uniform")
+    # the chain plan: host only, before any engine, seed or kernel
+    s = sampler_of(timestep_respacing="10", solver="dpmpp_2m")
+    m2 = dict(PATTERN, local_M=2, s_start=0.6, s_end=0.2)
+    with pytest.raises(ValueError, match="local_M > 1"):
+        gd._Chain(s, m2, {}, 16 * 24, False, 150)
+    with pytest.raises(NotImplementedError, match="mean-only"):
+        gd._Chain(s, PATTERN, {}, 16 * 24, False, 150, mean_only=True)
+    ch = gd._Chain(s, PATTERN, {}, 16 * 24, False, 150)
+    assert ch.solver == "dpmpp_2m" and not ch.solver_noisy and ch.lib_rng
+    assert gd._Chain(sampler_of(timestep_respacing="10", solver="ddim", solver_eta=0.5), PATTERN, {}, 384, False, 150).solver_noisy
+    assert gd._Chain(sampler_of(timestep_respacing="10"), m2, {}, 384, False, 150).solver is None         # (no solver: nothing refused)
+
+
+def test_the_loops_refuse_on_a_cpu_model_before_anything_launches():
+    """Through `p_sample_loop` with the network on the CPU (any launch would raise "no CPU fallback"): the fused, tiled and generic
+    loops all refuse local_M > 1 and the mean-only branch."""
+    from osmosis_diffusion_code_amd.guided_diffusion import condition_methods as CM
+    from osmosis_diffusion_code_amd.guided_diffusion import measurements as M
+    from osmosis_diffusion_code_amd.guided_diffusion import unet
+    kw = dict(image_size=256, num_channels=32, num_res_blocks=1, channel_mult="1,2,2", attention_resolutions="128,64",
+              num_head_channels=16, num_heads=4, learn_sigma=True, use_scale_shift_norm=True, resblock_updown=True)
+    m2 = dict(PATTERN, local_M=2, s_start=0.6, s_end=0.2)
+    s = sampler_of(timestep_respacing="10", solver="dpmpp_2m")
+    okw = dict(depth_type="gamma", value="1.4,1.4,1", phi_a="1.1,0.95,0.95", phi_b="0.95, 0.8, 0.8", phi_inf="0.14, 0.29, 0.49")
+
+    def loop(model, cond, x, pattern, **extra):
+        return s.p_sample_loop(model=model, x_start=x, measurement=torch.zeros(1, 3, *x.shape[-2:]), measurement_cond_fn=cond.conditioning,
+                               record=False, save_root=None, sample_pattern=pattern, **extra)
+    model48 = unet.create_model(**kw, pretrain_model="osmosis")
+    op = M.get_operator("underwater_physical_revised", device="cpu", batch_size=1, optimizer="sgd", **okw)
+    cond = CM.get_conditioning_method("osmosis", op, M.get_noise("clean"), loss_function="norm", loss_weight="depth",
+                                      weight_function="gamma,1.4,1.4,1", scale="7,7,7,0.9", gradient_x_prev=True,
+                                      gradient_clip="True,0.005", **m2, aux_loss=None)
+    x4 = torch.zeros(1, 4, 16, 24)
+    assert s._fast_path_ok(model48, cond.conditioning, "osmosis", False, m2, tuple(x4.shape)) is cond
+    with pytest.raises(ValueError, match="local_M > 1"):
+        loop(model48, cond, x4, m2, pretrain_model="osmosis", rgb_guidance=False)
+    with pytest.raises(ValueError, match="local_M > 1"):
+        loop(model48, cond, torch.zeros(1, 4, 24, 36), m2, pretrain_model="osmosis", rgb_guidance=False, tiling=dict(tile=16, stride=8))
+    cond.hip_ok = lambda: False                                                   # -> `_generic_loop`
+    with pytest.raises(ValueError, match="local_M > 1"):
+        loop(model48, cond, x4, m2, pretrain_model="osmosis", rgb_guidance=False)
+    model36 = unet.create_model(**kw, pretrain_model="imagenet")
+    ps = CM.get_conditioning_method("ps", M.get_operator("noise", device="cpu", batch_size=1), M.get_noise("gaussian", sigma=0.0), scale="0.3")
+    x3 = torch.zeros(1, 3, 16, 24)
+    assert s._fast_path_ok(model36, ps.conditioning, "imagenet", False, PATTERN, tuple(x3.shape)) is ps
+    with pytest.raises(NotImplementedError, match="mean-only"):
+        loop(model36, ps, x3, PATTERN, pretrain_model="imagenet", rgb_guidance=False)
+    ps.hip_ok = lambda channels=4: False
+    with pytest.raises(NotImplementedError, match="mean-only"):
+        loop(model36, ps, x3, PATTERN, pretrain_model="imagenet", rgb_guidance=False)
+
+
+# ------------------------------------------------------------------------------------------------------------ header and bindings
+def test_header_exports_and_bindings_agree():
+    hdr = open(os.path.join(ROOT, "include", "osmosis_solver.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert set(re.findall(r"\bint\s+(osm_[a-z0-9_]+)\s*\(", body)) == NAMES == set(_lib.EXPORTS_SOLVER)
+    for n in NAMES:
+        decl = re.search(n + r"\s*\(([^)]*)\)", body).group(1)
+        assert len(decl.split(",")) == len(_lib._SIGS_SOLVER[n]), n
+    assert len(_lib._SIGS_SOLVER["osm_solver_update_c"]) == 17 and len(_lib._SIGS_SOLVER["osm_solver_update_rng_c"]) == 22
+    for rule in ("ddim", "dpmpp_2m", "expm1", "h_prev / h", "sqrt(1 - ab' - s^2)"):
+        assert rule in hdr, rule                                                  # the rule formulas are stated in the header
+    others = [_lib.EXPORTS, _lib.EXPORTS_LINOP, _lib.EXPORTS_PSF, _lib.EXPORTS_PHYSLIN, _lib.EXPORTS_PHYSGROUP, _lib.EXPORTS_BLIND,
+              _lib.EXPORTS_DEPTHPRIOR]
+    assert not NAMES & set().union(*map(set, others))
+    main = open(os.path.join(ROOT, "include", "osmosis_hip.h")).read()
+    assert len(_lib.EXPORTS) == 99 and "osm_solver" not in main                   # the main header is what it was
+    assert set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S))) == set(_lib.EXPORTS)
+    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    lib = _lib.load()
+    for n in NAMES:
+        assert hasattr(so, n) and getattr(lib, n).argtypes == _lib._SIGS_SOLVER[n]
+    mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
+    assert "osmosis_solver.h" in mk
+    from osmosis_diffusion_code_amd import ops, torch_ops
+    assert callable(ops.solver_update_c) and callable(ops.solver_update_rng_c)
+    assert "solver_update" in torch_ops.OPS and "solver_update" not in torch_ops.OPS_C
+    schema = str(torch.ops.osmosis.solver_update.default._schema)
+    assert "Tensor(a2!) hist" in schema and "Tensor(a10!) x_next" in schema and schema.count("!") == 2 and schema.endswith("-> Tensor"), schema
+    for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
+        assert "osmosis_solver.h" in open(os.path.join(ROOT, doc)).read(), doc
+    assert "DPM-Solver++" in open(os.path.join(ROOT, "PAPERS.md")).read()
+
+
+def test_entry_points_refuse_bad_arguments_before_any_launch():
+    lib = _lib.load()
+    p, q = 4096, 16384                                                            # never dereferenced on the host
+    ok = [p, p + 4096, q, p, p, p, p, p, p, 0.005, p + 4096, None, None, 2, 4, 48, None]
+
+    def call(**kw):
+        a = list(ok)
+        names = ["x0", "x", "hist", "g", "dxu", "noise", "coef", "srow", "scale", "clip", "x_next", "grad_out", "noise_out", "B", "C", "HW"]
+        for k, v in kw.items():
+            a[names.index(k)] = v
+        return lib.osm_solver_update_c(*a)
+    for kw, msg in [(dict(x0=None), "must be given"), (dict(hist=None), "must be given"), (dict(srow=None), "must be given"),
+                    (dict(coef=None), "must be given"), (dict(x_next=None), "must be given"), (dict(B=0), "bad shape"),
+                    (dict(C=0), "bad shape"), (dict(HW=-4), "bad shape"), (dict(scale=None), "per-channel scale"),
+                    (dict(g=None), "dx_unet without g"), (dict(clip=float("nan")), "clip is NaN"), (dict(hist=p), "buffer of its own"),
+                    (dict(hist=p + 4096), "buffer of its own")]:
+        assert call(**kw) != 0, kw
+        assert msg in lib.osm_last_error().decode(), (kw, lib.osm_last_error().decode())
+    rng_ok = [p, p + 4096, q, p, p, p, p, p, 0.005, p + 4096, None, None, 2, 4, 48, 7, p, 1, 0, 0, 1, None]
+
+    def call_rng(**kw):
+        a = list(rng_ok)
+        names = ["x0", "x", "hist", "g", "dxu", "coef", "srow", "scale", "clip", "x_next", "grad_out", "noise_out", "B", "C", "HW", "seed",
+                 "step", "step_offset", "sub", "img0", "img_stride"]
+        for k, v in kw.items():
+            a[names.index(k)] = v
+        return lib.osm_solver_update_rng_c(*a)
+    for kw, msg in [(dict(step=None), "step counter"), (dict(sub=65536), "sub must be"), (dict(sub=-1), "sub must be"),
+                    (dict(HW=35), "multiple of 4"), (dict(x0=p + 4), "16-byte aligned"), (dict(noise_out=p + 8), "16-byte aligned"),
+                    (dict(hist=None), "must be given"), (dict(scale=None), "per-channel scale")]:
+        assert call_rng(**kw) != 0, kw
+        assert msg in lib.osm_last_error().decode(), (kw, lib.osm_last_error().decode())
