@@ -1,6 +1,6 @@
 """ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
-include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h and
-include/osmosis_solver.h).
+include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h,
+include/osmosis_solver.h and include/osmosis_robust.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -99,6 +99,12 @@ class DepthDesc(C.Structure):
     """osm_depth_desc (include/osmosis_depthprior.h): the range-map depth prior of the Osmosis data term."""
     _fields_ = [("align", C.c_int), ("loss_type", C.c_int), ("lam", C.c_float), ("scale", C.c_float), ("scale_min", C.c_float),
                 ("depth_type", C.c_int), ("dval", C.c_float * 3), ("B", C.c_int), ("HW", C.c_int)]
+
+
+class RobustDesc(C.Structure):
+    """osm_robust_desc (include/osmosis_robust.h): the IRLS weights of the robust data term."""
+    _fields_ = [("loss", C.c_int), ("c", C.c_float), ("scale_mode", C.c_int), ("scale", C.c_float), ("sigma_min", C.c_float),
+                ("per_pixel", C.c_int), ("B", C.c_int), ("hw", C.c_int)]
 
 
 class ReconDesc(C.Structure):
@@ -254,6 +260,14 @@ _SIGS_SOLVER = {
     "osm_solver_update_rng_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
 }
 EXPORTS_SOLVER = sorted(_SIGS_SOLVER)
+# the entry points of the ninth header, include/osmosis_robust.h (a robust data term: IRLS weights from an on-device MAD scale)
+_SIGS_ROBUST = {
+    "osm_robust_resid": [C.POINTER(RobustDesc), _P, _LL, _F, _F, _P, _P, _P],
+    "osm_robust_scale": [C.POINTER(RobustDesc), _P, _P, _P, _P, _P],
+    "osm_robust_weights": [C.POINTER(RobustDesc), _P, _P, _P, _P, _P, _P],
+    "osm_robust_mask": [C.POINTER(RobustDesc), _P, _LL, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
+}
+EXPORTS_ROBUST = sorted(_SIGS_ROBUST)
 
 _lib = None
 _lock = threading.Lock()
@@ -273,7 +287,8 @@ def load():
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
-                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()):
+                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()) + \
+                    list(_SIGS_ROBUST.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

@@ -155,14 +155,197 @@ def depth_prior_term(d, z, m, align, loss, scale=1.0, scale_min=1e-3):
             (c if align == "none" else torch.where(ok, c, nan)))
 
 
+ROBUST_LOSSES = ("huber", "tukey", "cauchy")
+
+
+def robust_weights_torch(e, M0, loss, c, scale="mad", sigma_min=2.0 / 255.0, per_pixel=False):
+    """include/osmosis_robust.h on torch tensors, in e's dtype: e [B,3,...] the raw residual, M0 of its shape or None (ones) ->
+    (M_eff like e, omega like e, sigma [B], n_valid [B] int64), all constants of the step (nothing is differentiated through them).
+    The two-rank median by torch.sort over the valid entries (M0 > 0 and e finite)."""
+    e = e.detach()
+    B = e.shape[0]
+    ef = e.reshape(B, -1)
+    m0 = torch.ones_like(ef) if M0 is None else M0.detach().to(e.dtype).expand(e.shape).reshape(B, -1)
+    a = ef.abs()
+    valid = (m0 > 0) & torch.isfinite(ef)
+    n = valid.sum(dim=1)
+    if isinstance(scale, str):
+        srt = torch.sort(torch.where(valid, a, torch.full_like(a, float("inf"))), dim=1).values      # the valid entries come first
+        nn = n.clamp(min=1)
+        lo, hi = srt.gather(1, ((nn - 1) >> 1)[:, None])[:, 0], srt.gather(1, (nn >> 1)[:, None])[:, 0]
+        sigma = torch.clamp(1.4826 * (0.5 * (lo + hi)), min=float(sigma_min))
+        sigma = torch.where(n > 0, sigma, torch.full_like(sigma, float("nan")))
+    else:
+        sigma = torch.full((B,), float(scale), device=e.device, dtype=e.dtype)
+    u = torch.where(a == 0, torch.zeros_like(a), a / (float(c) * sigma)[:, None])
+    ok = valid & ~torch.isnan(sigma)[:, None]
+    if per_pixel:
+        u3 = torch.where(ok, u, torch.zeros_like(u)).view(B, 3, -1)
+        u = u3.amax(dim=1, keepdim=True).expand(B, 3, u3.shape[2]).reshape(B, -1)
+    one = torch.ones_like(u)
+    if loss == "huber":
+        w = torch.where(u <= 1, one, 1.0 / torch.where(u <= 1, one, u))
+        s = torch.sqrt(w)
+    elif loss == "tukey":
+        s = torch.where(u < 1, 1.0 - u * u, torch.zeros_like(u))
+        w = s * s
+    elif loss == "cauchy":
+        w = 1.0 / (1.0 + u * u)
+        s = torch.sqrt(w)
+    else:
+        raise ValueError(f"robust: loss must be one of {ROBUST_LOSSES}, got {loss!r}")
+    return (torch.where(ok, m0 * s, m0).view(e.shape), torch.where(ok, w, one).view(e.shape), sigma, n)
+
+
 class ConditioningMethod(ABC):
     _depth = None           # the range-map depth prior (`PosteriorSamplingOsmosis.set_depth_prior`); class default: none
     _mask = None            # [B or 1, 3, HW] fp32 (`set_measurement_mask`); class default: conditioners without one are unmasked
     _mask_hw = None
+    _robust = None          # the robust data term's setting and per-batch state (`set_robust`); class default: plain least squares
+    _robust_hold = None     # the autograd route's M_eff while it walks the inner iterations of ONE sub-step
+    _robust_holding = False
 
     def __init__(self, operator, noiser, **kwargs):
         self.operator = operator
         self.noiser = noiser
+
+    # ---------------------------------------------------------------- robust data term (include/osmosis_robust.h)
+    def set_robust(self, loss="tukey", c=None, scale="mad", sigma_min=2.0 / 255.0, per_pixel=False):
+        """Make the data term robust to outliers in the measurement (marine snow, highlights, caustics, a fish): per guided sub-step
+        and per image, the raw residual e = y - prediction (osmosis: 2 I - 1 at the phi the sub-step starts from; 'ps': x0) gives a
+        scale sigma = max(1.4826 median |e|, sigma_min) over the valid entries (mask > 0, e finite; the three channels pooled), the
+        weights omega(|e| / (c sigma)) of `loss` 'huber' | 'tukey' | 'cauchy', and the data term runs its masked route with
+        M sqrt(omega) in the mask's place (iteratively re-weighted least squares: omega is a constant of the sub-step; the reported
+        loss is the weighted one).  c: the tuning constant (None: 1.345 / 4.685 / 2.385, 95 % efficiency at the normal); scale: 'mad'
+        or a fixed sigma > 0; per_pixel: one weight per pixel from its worst valid channel.  `set_robust(None)` clears the setting;
+        with none set nothing changes.  Three small kernels (csrc/robust.hip), outside the phi loop, no host sync."""
+        if loss is None:
+            self._robust = None
+            return None
+        if loss not in ROBUST_LOSSES:
+            raise ValueError(f"robust: loss must be one of {ROBUST_LOSSES}, got {loss!r}")
+        d = ops.robust_desc(loss, c, scale, sigma_min, per_pixel, 1, 1)       # (the host-side range checks; nothing launches)
+        self._robust = {"loss": loss, "c": float(d.c), "scale": "mad" if d.scale_mode == 0 else float(d.scale),
+                        "sigma_min": float(d.sigma_min), "per_pixel": bool(per_pixel), "state": None, "ones": None}
+        self._robust_refuse()
+        return self._robust
+
+    def _robust_refuse(self):
+        """The routings that are not built: the residual on a linear operator's grid."""
+        if self._robust is None:
+            return
+        from .measurements import GRID_OPERATORS
+        if getattr(self.operator, "degradation", None) is not None:
+            raise NotImplementedError("robust: the robust data term is not routed through a physical operator with a `degradation` "
+                                      "(the residual would live on the degradation's grid)")
+        if isinstance(self.operator, GRID_OPERATORS):
+            raise NotImplementedError(f"robust: the robust data term is not routed through a 'ps' grid operator "
+                                      f"({type(self.operator).__name__}); the identity operator is")
+
+    def _robust_kw(self):
+        rb = self._robust
+        return dict(loss=rb["loss"], c=rb["c"], scale=rb["scale"], sigma_min=rb["sigma_min"], per_pixel=rb["per_pixel"])
+
+    def robust_base_mask(self, B, hw, device):
+        """The [B,3,hw] base-mask rows M0 the robust term weighs: the stored mask, or without one a mask of ones kept beside the
+        setting (so that a chunked walk can hand row blocks of it over); None with robust unset and no mask."""
+        m = self.measurement_mask(B, hw, device)
+        rb = self._robust
+        if m is not None or rb is None:
+            return m
+        ones = rb["ones"]
+        if ones is None or tuple(ones.shape) != (B, 3, hw) or ones.device != torch.device(device):
+            ones = rb["ones"] = torch.ones(B, 3, hw, device=device, dtype=torch.float32)
+        return ones
+
+    def robust_open(self, B, hw, device):
+        """What a loop calls once per chain: the base-mask rows it hands on in chunks (`robust_base_mask`), with the per-batch state
+        allocated, so that `robust_values` reads NaN / 0 until the first guided sub-step."""
+        m = self.robust_base_mask(B, hw, device)
+        if self._robust is not None:
+            self._robust_refuse()
+            self._robust_state(m, device)
+        return m
+
+    def _robust_state(self, base, device):
+        """The per-BATCH state beside the base mask `base` [B0,3,hw]: e, M_eff, omega [B0,3,hw], sigma [B0] (NaN) and
+        n_valid [B0] int32 (0) until a guided sub-step writes them.  A call on a chunk writes the chunk's rows."""
+        rb = self._robust
+        st = rb["state"]
+        B0, hw = base.shape[0], base.shape[2]
+        if st is None or st["key"] != (B0, hw, str(device)):
+            f32 = dict(device=device, dtype=torch.float32)
+            st = rb["state"] = {"key": (B0, hw, str(device)), "e": torch.zeros(B0, 3, hw, **f32), "meff": torch.zeros(B0, 3, hw, **f32),
+                                "omega": torch.zeros(B0, 3, hw, **f32),
+                                "sigma": torch.full((B0,), float("nan"), **f32),
+                                "n": torch.zeros(B0, device=device, dtype=torch.int32), "desc": {}}
+        return st
+
+    def _robust_rows(self, mask, B, hw, device):
+        """(M0 rows [B,3,hw], the state, the first row r0 of the state these rows are) for a call on B images: `mask` rows handed in
+        by a chunked walk must be a row block of the conditioner's own base mask (`robust_base_mask`), or cover the whole batch."""
+        if mask is None:
+            mask = self.robust_base_mask(B, hw, device)
+        elif mask.numel() != B * 3 * hw or not mask.is_contiguous():
+            raise ValueError(f"expected mask rows [{B},3,{hw}], got {tuple(mask.shape)}")
+        base = self._mask if self._mask is not None else self._robust["ones"]
+        if base is not None and base.device == mask.device and base.shape[2] == hw:
+            r0, rem = divmod(mask.data_ptr() - base.data_ptr(), 3 * hw * 4)
+            if rem == 0 and 0 <= r0 and r0 + B <= base.shape[0]:
+                return mask, self._robust_state(base, device), r0
+        st = self._robust["state"]
+        if st is not None and st["key"] == (B, hw, str(device)):
+            return mask, st, 0                     # rows of a foreign mask over the whole batch
+        if base is None or base.shape[0] == B:
+            return mask, self._robust_state(mask, device), 0
+        # the kernels write sigma + b and the weight rows of every image they are handed
+        raise ValueError("robust: mask rows must be a row block of the conditioner's own mask (`robust_base_mask(...)[a:b]`) or cover "
+                         f"the whole batch, got {B} rows against its {base.shape[0]}")
+
+    def _robust_mask_rows(self, pred, pa, pb, y, mask, B, hw):
+        """The sub-step's M_eff rows [B,3,hw] from the prediction `pred` [B,P>=3,hw] (its first three planes): the three launches of
+        include/osmosis_robust.h from one call, or singly with OSM_PHYS_PY_LOOP=1."""
+        M0, st, r0 = self._robust_rows(mask, B, hw, y.device)
+        d = st["desc"].get(B)
+        if d is None:
+            d = st["desc"][B] = ops.robust_desc(B=B, hw=hw, **self._robust_kw())
+        e, meff, omega = st["e"][r0:r0 + B], st["meff"][r0:r0 + B], st["omega"][r0:r0 + B]
+        sigma, n = st["sigma"][r0:r0 + B], st["n"][r0:r0 + B]
+        if d.scale_mode == 1:           # a fixed scale: the kernels write neither; the reported sigma is the scale, nothing is counted
+            sigma.fill_(float(d.scale))
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            ops.robust_mask(d, pred, pa, pb, y, M0, e, sigma, n, meff, omega)
+            return meff
+        ops.robust_resid(d, pred, pa, pb, y, e)
+        if d.scale_mode == 0:
+            ops.robust_scale(d, e, M0, sigma, n)
+        ops.robust_weights(d, e, M0, sigma, meff, omega)
+        return meff
+
+    def _robust_torch(self, e, measurement):
+        """M_eff shaped like the measurement [B,3,H,W] on the torch routes (the same contract by torch.sort), kept for
+        `robust_values`."""
+        B, _, H, W = measurement.shape
+        M0, st, r0 = self._robust_rows(None, B, H * W, measurement.device)
+        meff, omega, sigma, n = robust_weights_torch(e.to(torch.float32), M0.view(B, 3, H, W), **self._robust_kw())
+        with torch.no_grad():
+            st["meff"][r0:r0 + B].copy_(meff.reshape(B, 3, H * W))
+            st["omega"][r0:r0 + B].copy_(omega.reshape(B, 3, H * W))
+            st["sigma"][r0:r0 + B].copy_(sigma)
+            st["n"][r0:r0 + B].copy_(n if isinstance(self._robust["scale"], str) else torch.zeros_like(n))
+        return meff.to(e.dtype)
+
+    def robust_values(self):
+        """{'scale': sigma [B], 'n_valid': [B] int32, 'weight': omega [B,3,hw]} over the whole batch (device tensors, no sync), each
+        image's from the last guided sub-step that covered it -- also when the batch was walked in chunks.  Before the first guided
+        sub-step: scale NaN, n_valid 0, weight 0.  With a fixed scale nothing is selected or counted: scale is the fixed value once a
+        guided sub-step has run, and n_valid stays 0.
+        None with robust unset or before the state exists."""
+        rb = self._robust
+        if rb is None or rb["state"] is None:
+            return None
+        st = rb["state"]
+        return {"scale": st["sigma"], "n_valid": st["n"], "weight": st["omega"]}
 
     # ---------------------------------------------------------------- per-pixel validity mask of the measurement
     def set_measurement_mask(self, mask, batch=None, device=None):
@@ -209,13 +392,20 @@ class ConditioningMethod(ABC):
 
     def grad_and_value(self, x_prev, x_0_hat, measurement, **kwargs):
         """DPS data term for the rgb-guidance variant (reference :35-53); torch autograd."""
+        self._robust_refuse()
         if self.noiser.__name__ == "gaussian":
             diff = measurement - self.operator.forward(x_0_hat[:, 0:3], **kwargs)
-            m = self._mask_like(measurement)
+            if self._robust is not None:        # the robust term: M sqrt(omega) from the raw residual, a constant of the step
+                m = self._robust_torch(diff, measurement)
+            else:
+                m = self._mask_like(measurement)
             if m is not None:
                 diff = diff * m
             loss = torch.linalg.norm(diff)
         elif self.noiser.__name__ == "poisson":
+            if self._robust is not None:
+                raise NotImplementedError("robust: the robust data term is defined on the gaussian data term only; the poisson noiser's "
+                                          "is not weighted")
             diff = measurement - self.operator.forward(x_0_hat, **kwargs)
             loss = (torch.linalg.norm(diff) / measurement.abs()).mean()
         else:
@@ -500,6 +690,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         With a range-map prior (`set_depth_prior`; `depth`: the chunk's (range, confidence) rows [B,1,HW], default the stored ones)
         g's depth plane also carries weight * d L_depth / d x0, added after the inner loop; the returned loss stays the data loss
         (`depth_prior_values` has the prior's)."""
+        self._robust_refuse()
         if getattr(self.operator, "degradation", None) is not None:
             return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask, depth)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
@@ -517,7 +708,15 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("phi must be a contiguous [B][9] block")
         g = g_out if g_out is not None else st["g"]
         x0c, yc = x0.contiguous(), y.contiguous()
-        if mask is None:
+        if self._robust is not None:
+            # the robust term: the model image at the phi this sub-step starts from, the raw residual's MAD scale and the IRLS weights
+            # folded into the mask -- M_eff rows in the mask's place, constants of the inner loop below
+            F = st.get("F_robust")
+            if F is None:
+                F = st["F_robust"] = torch.empty(B, ops.phys_lin_planes(d), HW, device=x0.device, dtype=torch.float32)
+            ops.phys_forward(d, x0c, phi, F)
+            mask = self._robust_mask_rows(F, 2.0, -1.0, yc, mask, B, HW)
+        elif mask is None:
             mask = self.measurement_mask(B, HW, x0.device)
         # the route's four calls: reduce, finalize, grad, optimize (the schedule: _inner_loop)
         if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
@@ -663,6 +862,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
 
     def _loss_autograd(self, x_0_hat, measurement, **kwargs):
         """condition_methods.py:109-144 on torch tensors, for operators the kernels do not know: (sep_loss ndarray[B], loss, image)."""
+        self._robust_refuse()
         deg = getattr(self.operator, "degradation", None)
         # with a degradation A the photo is A I on A's grid (`observe`); the weight plane goes through A too (a constant of the step)
         image = self.operator.forward(x_0_hat, **kwargs) if deg is None else self.operator.observe(x_0_hat, **kwargs)
@@ -670,8 +870,18 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                                    degraded_image=image.detach(), x_0_hat=x_0_hat.detach())
         if deg is not None and torch.is_tensor(w):
             w = deg.forward(w.detach().contiguous())
-        diff = (measurement - (2 * image - 1)) * w
-        m = self._mask_like(measurement)
+        raw = measurement - (2 * image - 1)
+        diff = raw * w
+        if self._robust is not None:
+            # the robust term: M_eff from the raw residual at the phi the sub-step starts from (`_conditioning_autograd` holds it
+            # over its inner iterations), a constant of the step
+            m = self._robust_hold
+            if m is None:
+                m = self._robust_torch(raw, measurement)
+                if self._robust_holding:
+                    self._robust_hold = m
+        else:
+            m = self._mask_like(measurement)
         if m is not None:           # (mse below keeps its 3 HW denominator: a mask of ones is the unmasked loss)
             diff = diff * m
         # the range-map prior, weight * sum_b L_depth[b] (None without one): part of the objective, not of the reported data loss
@@ -698,19 +908,23 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         if not self.gradient_x_prev:
             raise NotImplementedError("gradient_x_prev=False raises in the reference too (backward(inputs=[x_prev]) on a tensor whose "
                                       "requires_grad it has just switched off, condition_methods.py:152-157, :186-191)")
-        with torch.enable_grad():
-            self.operator.set_variable_gradients(value=not freeze_phi)
-            n = 1 if freeze_phi else self.n_iter
-            for it in range(n):
-                sep_loss, loss, _ = self._loss_autograd(x_0_hat, measurement, time_index=kwargs.get("time_index", None))
-                aux_dict = None
-                if self.aux_loss is not None:
-                    aux, aux_dict = self.aux_loss.forward(x_0_hat)
-                    loss = loss + aux
-                phis = [] if freeze_phi else list(self.operator.get_variable_list())
-                last = it == n - 1
-                loss.backward(inputs=([x_prev] if last else []) + phis, retain_graph=not last)
-                variables = self.operator.optimize(freeze_phi=freeze_phi)
+        self._robust_hold, self._robust_holding = None, True        # the robust weights: the first iteration's, for all of them
+        try:
+            with torch.enable_grad():
+                self.operator.set_variable_gradients(value=not freeze_phi)
+                n = 1 if freeze_phi else self.n_iter
+                for it in range(n):
+                    sep_loss, loss, _ = self._loss_autograd(x_0_hat, measurement, time_index=kwargs.get("time_index", None))
+                    aux_dict = None
+                    if self.aux_loss is not None:
+                        aux, aux_dict = self.aux_loss.forward(x_0_hat)
+                        loss = loss + aux
+                    phis = [] if freeze_phi else list(self.operator.get_variable_list())
+                    last = it == n - 1
+                    loss.backward(inputs=([x_prev] if last else []) + phis, retain_graph=not last)
+                    variables = self.operator.optimize(freeze_phi=freeze_phi)
+        finally:                        # (also when an iteration raises: a later call must not meet stale weights)
+            self._robust_hold, self._robust_holding = None, False
         with torch.no_grad():
             grads = x_prev.grad
             if self.gradient_clip:
@@ -720,6 +934,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
 
     def grad_and_value(self, x_prev, x_0_hat, measurement, **kwargs):
         if not self._has_kernels():
+            self._robust_hold, self._robust_holding = None, False
             return self._loss_autograd(x_0_hat, measurement, **kwargs)
         g, loss = self.loss_grad_x0(x_0_hat.detach(), measurement, freeze_phi=True)
         I = self.operator.forward(x_0_hat.detach())
@@ -796,6 +1011,7 @@ class PosteriorSampling(ConditioningMethod):
         loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`); a `PSFOperator` (motion blur, a
         measured point-spread function) goes the same way with its own kernel."""
         from .measurements import GRID_OPERATORS
+        self._robust_refuse()
         if self._blind() is not None:
             return self._loss_grad_x0_blind(x0, y, g_out, loss_out, mask)
         if isinstance(self.operator, GRID_OPERATORS):
@@ -822,7 +1038,9 @@ class PosteriorSampling(ConditioningMethod):
             self._states[key] = st
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
-        if mask is None:
+        if self._robust is not None:    # the robust term: e = y - x0[:, 0:3], its MAD scale, M_eff rows in the mask's place
+            mask = self._robust_mask_rows(x0.contiguous(), 1.0, 0.0, y.contiguous(), mask, B, HW)
+        elif mask is None:
             mask = self.measurement_mask(B, HW, x0.device)
         if mask is not None and C == 4:
             ops.phys_optimize_m(st["desc"], x0.contiguous(), y.contiguous(), mask, st["phi"], st["part"], st["red"], loss, g, 1, True)

@@ -702,7 +702,11 @@ class GaussianDiffusion:
         y = measurement.detach().to(dev, torch.float32).contiguous()
         # [B,3,hw] rows like y, or None (`measurement_mask=`): the mask lives on the measurement's grid (the image's, except for a
         # downsampling operator of the 'ps' branch)
-        mask = cond.measurement_mask(B, y.shape[2] * y.shape[3] if y.dim() == 4 else HW, dev)
+        hw_y = y.shape[2] * y.shape[3] if y.dim() == 4 else HW
+        if getattr(cond, "_robust", None) is None:
+            mask = cond.measurement_mask(B, hw_y, dev)
+        else:       # the robust data term (`robust=`): the base-mask rows its weights multiply, a mask of ones without a mask
+            mask = cond.robust_open(B, hw_y, dev)
         phi = None if ps else cond.operator.phi
         # a data term that couples the images of the batch: shared water parameters, or on the 'ps' branch an operator with
         # `couples_batch` (`blind_blur`: one learnt PSF for all images)
@@ -876,7 +880,8 @@ class GaussianDiffusion:
         x0_raw = torch.empty(1, 4, Hc, Wc, **f32) if self.mean_processor.clip_denoised else None
         loss_all = torch.zeros(1, **f32)
         y = measurement.detach().to(dev, torch.float32).contiguous()
-        mask = cond.measurement_mask(1, HW, dev)
+        # (the robust data term, `robust=`: its weights are over the whole canvas, one sigma; its base mask is ones without a mask)
+        mask = cond.measurement_mask(1, HW, dev) if getattr(cond, "_robust", None) is None else cond.robust_open(1, HW, dev)
         mk_rows = {} if mask is None else {"mask": mask}
         if getattr(cond, "_depth", None) is not None:          # the range-map depth prior: a map over the CANVAS, one fit for it
             mk_rows["depth"] = cond.depth_prior_rows(1, Hc, Wc, dev)
@@ -961,7 +966,7 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ public loop
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root,
                       pretrain_model=None, image_idx=None, record_every=150, rgb_guidance=False,
-                      sample_pattern=None, measurement_mask=None, tiling=None, depth_prior=None, **kwargs):
+                      sample_pattern=None, measurement_mask=None, tiling=None, depth_prior=None, robust=None, **kwargs):
         """measurement_mask: a per-pixel validity mask of the measurement ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
         [0, 1]; `ConditioningMethod.set_measurement_mask`), handed to the conditioner for this chain -- the fused loop and
         `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default).
@@ -969,8 +974,21 @@ class GaussianDiffusion:
         tiles of the network's size (`_tiled_loop`); None: nothing changes.
         depth_prior: `dict(z=, confidence=, weight=, align=, loss=, scale=, scale_min=)` sets a range-map depth prior on the
         conditioner for this chain (`PosteriorSamplingOsmosis.set_depth_prior`; z on the image's grid, the canvas's when tiled);
-        None: the conditioner keeps whatever prior it was given directly (none by default)."""
+        None: the conditioner keeps whatever prior it was given directly (none by default).
+        robust: `dict(loss=, c=, scale=, sigma_min=, per_pixel=)` makes the data term robust for this chain
+        (`ConditioningMethod.set_robust`; on a tiled canvas the weights are over the whole canvas, with one sigma); None: the
+        conditioner keeps whatever setting it was given directly (none by default)."""
         from .posterior_mean_variance import PreviousXMeanProcessor
+        if robust is not None:
+            cond_obj = getattr(measurement_cond_fn, "__self__", None)
+            if not hasattr(cond_obj, "set_robust"):
+                raise TypeError("robust needs a conditioner with set_robust (a ConditioningMethod)")
+            if not isinstance(robust, dict):
+                raise ValueError("robust must be a dict (loss, c, scale, sigma_min, per_pixel)")
+            unknown = set(robust) - {"loss", "c", "scale", "sigma_min", "per_pixel"}
+            if unknown:
+                raise ValueError(f"robust: unknown keys {sorted(unknown)}")
+            cond_obj.set_robust(**robust)
         if depth_prior is not None:
             cond_obj = getattr(measurement_cond_fn, "__self__", None)
             if not hasattr(cond_obj, "set_depth_prior"):

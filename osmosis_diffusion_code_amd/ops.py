@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, DepthDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, call, current_stream_ptr, ptr, ptr_f64, query
+from ._lib import AttnDesc, ConvDesc, DepthDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, RobustDesc, call, current_stream_ptr, ptr, ptr_f64, query
 
 
 @dataclass
@@ -1012,3 +1012,85 @@ def depth_loss_grad(desc: DepthDesc, x0, z, m, part, fit, depth_loss, g):
     _check_depth("depth_loss_grad", desc, x0=x0, z=z, m=m, part=part, fit=fit, depth_loss=depth_loss, g=g)
     call("osm_depth_loss_grad", C.byref(desc), ptr(x0), ptr(z), ptr(m), ptr_f64(part), ptr_f64(fit), ptr(depth_loss), ptr(g), _s(),
          keep=(desc, x0, z, m, part, fit, depth_loss, g))
+
+
+# ----------------------------------------------------------------------------- robust data term (include/osmosis_robust.h)
+ROBUST_LOSS = {"huber": 0, "tukey": 1, "cauchy": 2}
+ROBUST_C = {"huber": 1.345, "tukey": 4.685, "cauchy": 2.385}      # 95 % efficiency at the normal (Holland & Welsch 1977)
+
+
+def robust_desc(loss, c, scale, sigma_min, per_pixel, B, hw) -> RobustDesc:
+    """The osm_robust_desc of a setting: loss 'huber' | 'tukey' | 'cauchy', c > 0 (None: the loss's default), scale 'mad' or a fixed
+    sigma > 0, sigma_min >= 0, per_pixel."""
+    if loss not in ROBUST_LOSS:
+        raise ValueError(f"robust: loss must be one of {sorted(ROBUST_LOSS)}, got {loss!r}")
+    c = ROBUST_C[loss] if c is None else float(c)
+    if not (c > 0.0 and c < float("inf")):
+        raise ValueError(f"robust: c must be finite and > 0, got {c}")
+    sigma_min = float(sigma_min)
+    if not (sigma_min >= 0.0 and sigma_min < float("inf")):
+        raise ValueError(f"robust: sigma_min must be finite and >= 0, got {sigma_min}")
+    d = RobustDesc()
+    if isinstance(scale, str):
+        if scale != "mad":
+            raise ValueError(f"robust: scale must be 'mad' or a float > 0, got {scale!r}")
+        d.scale_mode, d.scale = 0, 0.0
+    else:
+        scale = float(scale)
+        if not (scale > 0.0 and scale < float("inf")):
+            raise ValueError(f"robust: a fixed scale must be finite and > 0, got {scale}")
+        d.scale_mode, d.scale = 1, scale
+    d.loss, d.c, d.sigma_min, d.per_pixel, d.B, d.hw = ROBUST_LOSS[loss], c, sigma_min, int(bool(per_pixel)), int(B), int(hw)
+    return d
+
+
+def _check_robust(name, desc: RobustDesc, pred=None, **ts):
+    B, hw = desc.B, desc.hw
+    for k, t in ts.items():
+        if t is None:
+            continue
+        if k == "n_valid":
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B:
+                raise ValueError(f"{name}: `n_valid` must be contiguous int32 [{B}], got {tuple(t.shape)} {t.dtype}")
+            continue
+        need = B if k == "sigma" else B * 3 * hw
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != need:
+            raise ValueError(f"{name}: `{k}` must be contiguous fp32 with {need} elements, got {tuple(t.shape)} {t.dtype}")
+    if pred is not None:
+        if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() < 2 or pred.shape[0] != B or \
+                pred.numel() // B < 3 * hw or (pred.numel() // B) % hw != 0:
+            raise ValueError(f"{name}: `pred` must be contiguous fp32 [{B},P>=3,{hw}], got {tuple(pred.shape)} {pred.dtype}")
+        return pred.numel() // B
+    return None
+
+
+def robust_resid(desc: RobustDesc, pred, pa, pb, y, e):
+    """e [B,3,hw] = y - (pa pred + pb), unfused; pred [B,P>=3,hw]: its first three planes are read (osm_robust_resid)."""
+    bs = _check_robust("robust_resid", desc, pred=pred, y=y, e=e)
+    call("osm_robust_resid", C.byref(desc), ptr(pred), bs, float(pa), float(pb), ptr(y), ptr(e), _s(), keep=(desc, pred, y, e))
+
+
+def robust_scale(desc: RobustDesc, e, M0, sigma, n_valid):
+    """sigma [B] = max(1.4826 median |e|, sigma_min) over the entries with M0 > 0 (None: all) and e finite; n_valid [B] int32 their
+    number (osm_robust_scale: an exact select, one workgroup per image)."""
+    _check_robust("robust_scale", desc, e=e, M0=M0, sigma=sigma, n_valid=n_valid)
+    call("osm_robust_scale", C.byref(desc), ptr(e), ptr(M0), ptr(sigma), ptr(n_valid), _s(), keep=(desc, e, M0, sigma, n_valid))
+
+
+def robust_weights(desc: RobustDesc, e, M0, sigma, M_eff, omega=None):
+    """M_eff [B,3,hw] = M0 sqrt(omega) (and omega) from e, M0 (None: ones) and sigma [B] (None with a fixed scale)
+    (osm_robust_weights)."""
+    _check_robust("robust_weights", desc, e=e, M0=M0, sigma=sigma, M_eff=M_eff, omega=omega)
+    if sigma is None and desc.scale_mode != 1:
+        raise ValueError("robust_weights: the mad scale reads `sigma`")
+    call("osm_robust_weights", C.byref(desc), ptr(e), ptr(M0), ptr(sigma), ptr(M_eff), ptr(omega), _s(),
+         keep=(desc, e, M0, sigma, M_eff, omega))
+
+
+def robust_mask(desc: RobustDesc, pred, pa, pb, y, M0, e, sigma, n_valid, M_eff, omega=None):
+    """The launches of the robust weights from one call (osm_robust_mask): resid, scale (the mad scale only), weights."""
+    bs = _check_robust("robust_mask", desc, pred=pred, y=y, M0=M0, e=e, sigma=sigma, n_valid=n_valid, M_eff=M_eff, omega=omega)
+    if (sigma is None or n_valid is None) and desc.scale_mode != 1:
+        raise ValueError("robust_mask: the mad scale writes `sigma` and `n_valid`")
+    call("osm_robust_mask", C.byref(desc), ptr(pred), bs, float(pa), float(pb), ptr(y), ptr(M0), ptr(e), ptr(sigma), ptr(n_valid),
+         ptr(M_eff), ptr(omega), _s(), keep=(desc, pred, y, M0, e, sigma, n_valid, M_eff, omega))

@@ -130,6 +130,31 @@ def depth_prior_config(depth_cfg):
     return params, depth_cfg.get("path")
 
 
+ROBUST_KEYS = ("loss", "c", "scale", "sigma_min", "per_pixel")
+
+
+def robust_config(robust_cfg=None, robust=None):
+    """The `robust=` dict of a chain (`p_sample_loop(robust=)`, `ConditioningMethod.set_robust`) from the optional config key
+    `measurement.robust: {loss, c, scale, sigma_min, per_pixel}` or the argument `robust` (a dict, which wins over the config), or
+    None when neither is given.  Unknown keys raise."""
+    chosen, where = (robust, "robust") if robust is not None else (robust_cfg, "measurement.robust")
+    if not chosen:
+        return None
+    if not isinstance(chosen, dict):
+        raise ValueError(f"{where} must be a mapping of {', '.join(ROBUST_KEYS)}")
+    unknown = set(chosen) - set(ROBUST_KEYS)
+    if unknown:
+        raise ValueError(f"{where}: unknown key(s) {sorted(unknown)} (known: {', '.join(ROBUST_KEYS)})")
+    return dict(chosen)
+
+
+def attach_robust(post, weight, scale):
+    """The robust term's keys of one image's result: `robust_weight` (omega [3,h,w] of the chain's last guided sub-step, on the
+    measurement's grid) and `robust_scale` (its sigma)."""
+    post.update(robust_weight=weight.detach().cpu().to(torch.float32), robust_scale=float(scale))
+    return post
+
+
 def depth_prior_inputs(grid, depth_cfg=None, depth=None, depth_confidence=None, geometry=None):
     """The `depth_prior=` dict of a chain whose images live on `grid` = (H, W), or None when no range map is given.  depth /
     depth_confidence: [B,1,H,W], [1,1,H,W] or [B,H,W] on the network's grid (`data.transform_range` takes one from the photo's
@@ -284,6 +309,12 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         os.makedirs(d, exist_ok=True)
         paths["mask"] = os.path.join(d, f"{name}_mask.png")
         Image.fromarray(_to_pil_u8(post["mask"][0].clamp(0, 1)), mode="RGB").save(paths["mask"])
+    if save_singles and post.get("robust_weight") is not None:      # only a chain with the robust data term
+        d = os.path.join(out_dir, "single_images", "robust")
+        os.makedirs(d, exist_ok=True)
+        paths["robust"] = os.path.join(d, f"{name}_robust.png")
+        lo = post["robust_weight"].to(torch.float32).amin(dim=0).clamp(0.0, 1.0)        # the per-pixel minimum of omega over the channels
+        Image.fromarray((lo * 255.0 + 0.5).to(torch.uint8).numpy(), mode="L").save(paths["robust"])
     if save_singles and post.get("depth_metric") is not None:       # only a chain with a range-map prior
         d = os.path.join(out_dir, "single_images", "depth_metric")
         os.makedirs(d, exist_ok=True)
@@ -484,7 +515,7 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
 
 def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
                   postprocess_batch=True, mask=None, tiling=None, depth=None, depth_confidence=None, depth_geometry=None,
-                  **loop_kwargs):
+                  robust=None, **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -517,6 +548,12 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     also when the batch is walked in chunks; a chain without a guided sub-step leaves the fit undefined (NaN).  Without a range
     map nothing is passed and there are no such keys.  `depth_geometry`: the photo's `data.Geometry` for the map of
     `measurement.depth.path` (`depth_prior_inputs` says what is assumed without it).
+
+    `robust` (or the optional config key `measurement.robust: {loss, c, scale, sigma_min, per_pixel}`; the argument wins; unknown
+    keys raise): the robust data term (`p_sample_loop(robust=)`, include/osmosis_robust.h).  Every result then carries
+    `robust_weight` (omega [3,h,w] of the last guided sub-step) and `robust_scale` (its sigma) -- each image's own, also when the
+    batch is walked in chunks; `save_outputs` writes the per-pixel minimum of omega over the channels as `<name>_robust.png`.
+    Without it nothing is passed and there are no such keys.
 
     Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
     carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
@@ -592,6 +629,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     prior = depth_prior_inputs(shape[2:], measure.get("depth"), depth, depth_confidence, depth_geometry)
     if prior is not None:
         loop_kwargs = dict(loop_kwargs, depth_prior=prior)
+    robust = robust_config(measure.get("robust"), robust)
+    if robust is not None:
+        loop_kwargs = dict(loop_kwargs, robust=robust)
     results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
         torch.manual_seed(cfg.get("manual_seed", 0))
@@ -616,6 +656,7 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             results.append(rgb_guidance_result(ret.detach().cpu(), y_n.detach().cpu()))
             if m_dev is not None:
                 results[-1]["mask"] = m_dev.detach().cpu()
+            _attach_robust_values(results[-1], cond, robust, y_n, postprocess_batch)
             if is_blind:
                 results[-1]["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
             if getattr(sampler, "solver", None) is not None:
@@ -640,6 +681,7 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
                 post["depth_fit"] = dict(vals, z=zr, m=mr, align=cond._depth["align"])
         if m_dev is not None:
             post["mask"] = m_dev.detach().cpu()
+        _attach_robust_values(post, cond, robust, y_n, postprocess_batch)
         if tiling_info is not None:
             post["tiling"] = tiling_info
         if is_blind:
@@ -648,6 +690,22 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             post.update(solver=sampler.solver, steps=sampler.num_timesteps)
         results.append(post)
     return results
+
+
+def _attach_robust_values(post, cond, robust, y, postprocess_batch):
+    """The robust term's values of a chain's end on its result: image 0's keys (`attach_robust`), or with `postprocess_batch` off
+    every image's under `robust_fit` for the caller's per-image post-processing."""
+    if robust is None:
+        return
+    vals = cond.robust_values()
+    if vals is None:                # (a chain without a guided sub-step on a loop that never opened the state)
+        return
+    B, _, h, w = y.shape
+    weight, scale = vals["weight"].detach().cpu().view(B, 3, h, w), vals["scale"].detach().cpu()
+    if postprocess_batch:
+        attach_robust(post, weight[0], scale[0])
+    else:
+        post["robust_fit"] = dict(weight=weight, scale=scale)
 
 
 def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None, observed=None):
@@ -668,7 +726,7 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
                    geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, depths=None,
-                   depth_confidences=None, **loop_kwargs):
+                   depth_confidences=None, robust=None, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -690,7 +748,12 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
 
     `depths` / `depth_confidences` (lists aligned with `images`: a range map [1,1,H,W] on the network's grid each, or None for an
     image without one): rows per image, chunked with the images (`restore_image(depth=, depth_confidence=)`); in a batch, an image
-    without a map gets confidence 0 everywhere -- no prior for it.  The fit stays per image, also with `shared_water`."""
+    without a map gets confidence 0 everywhere -- no prior for it.  The fit stays per image, also with `shared_water`.
+
+    `robust` goes to `restore_image` as it is (it wins over `measurement.robust`); every result carries its own `robust_weight` and
+    `robust_scale`, also in chunked batches."""
+    if robust is not None:
+        loop_kwargs = dict(loop_kwargs, robust=robust)
     if shared_water:
         if tiling is not None or cfg.get("tiling") is not None:
             raise NotImplementedError("shared_water: tiling is one canvas per call, water parameters are not shared across canvases")
@@ -765,6 +828,9 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
                 fit = full["depth_fit"]
                 for b, r in enumerate(res):
                     attach_depth_prior(r, fit["z"][b], fit["m"][b], fit["scale"][b], fit["shift"][b], fit["loss"][b], fit["align"])
+            if full.get("robust_fit") is not None:
+                for b, r in enumerate(res):
+                    attach_robust(r, full["robust_fit"]["weight"][b], full["robust_fit"]["scale"][b])
             if full.get("mask") is not None:
                 for b, r in enumerate(res):
                     r["mask"] = full["mask"][b:b + 1]

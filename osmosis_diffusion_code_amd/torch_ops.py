@@ -895,8 +895,43 @@ def _solver_update_fake(x0, x, hist, g, dx_unet, noise, coef, srow, scale, clip,
     return torch.empty_like(x0)
 
 
+# ---- robust data term (include/osmosis_robust.h): the IRLS weights of a sub-step folded into the mask, written IN PLACE
+@torch.library.custom_op("osmosis::robust_mask", mutates_args=("m_eff", "omega", "sigma", "n_valid"), device_types="cuda")
+def robust_mask(pred: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], m_eff: torch.Tensor, omega: torch.Tensor,
+                sigma: torch.Tensor, n_valid: torch.Tensor, pa: float, pb: float, loss: str, c: float, scale: float, sigma_min: float,
+                per_pixel: bool) -> None:
+    """osm_robust_mask: e = y - (pa pred[:, 0:3] + pb) (pred [B,P>=3,H,W], y [B,3,H,W]); sigma [B] = max(1.4826 median |e|, sigma_min)
+    over the entries with mask > 0 (mask [B,3,H,W] or [B,1,H,W], None: ones) and e finite, n_valid [B] int32 their number -- or, with
+    `scale` > 0, sigma is that value and neither is written (`scale` = 0 selects the mad scale); m_eff = mask sqrt(omega) and omega
+    [B,3,H,W] of loss 'huber' | 'tukey' | 'cauchy' at u = |e| / (c sigma), all written IN PLACE."""
+    name = "osmosis::robust_mask"
+    B, hw = _chw(y)
+    if pred.dim() != 4 or pred.shape[0] != B or pred.shape[1] < 3 or pred.shape[2:] != y.shape[2:] or y.shape[1] != 3 \
+            or pred.dtype != torch.float32 or not pred.is_contiguous():
+        raise OsmosisHipError(f"{name}: expected a contiguous fp32 pred [B,P>=3,H,W] and y [B,3,H,W], got {tuple(pred.shape)} and "
+                              f"{tuple(y.shape)}")
+    for t, what in ((m_eff, "m_eff"), (omega, "omega")):
+        if tuple(t.shape) != tuple(y.shape) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise OsmosisHipError(f"{name}: {what} must be a contiguous fp32 tensor of y's shape {tuple(y.shape)}")
+    if tuple(sigma.shape) != (B,) or sigma.dtype != torch.float32 or tuple(n_valid.shape) != (B,) or n_valid.dtype != torch.int32:
+        raise OsmosisHipError(f"{name}: sigma must be fp32 [{B}] and n_valid int32 [{B}]")
+    if not scale >= 0.0:
+        raise OsmosisHipError(f"{name}: scale must be > 0 (a fixed sigma) or 0 (the mad scale), got {scale}")
+    try:
+        d = ops.robust_desc(loss, c, "mad" if scale == 0.0 else scale, sigma_min, per_pixel, B, hw)
+    except ValueError as err:
+        raise OsmosisHipError(f"{name}: {err}") from None
+    e = torch.empty_like(y)
+    ops.robust_mask(d, pred, pa, pb, y, None if mask is None else _mask_rows(name, mask, y), e, sigma, n_valid, m_eff, omega)
+
+
+@robust_mask.register_fake
+def _robust_mask_fake(pred, y, mask, m_eff, omega, sigma, n_valid, pa, pb, loss, c, scale, sigma_min, per_pixel):
+    return None
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask") + OPS_C
