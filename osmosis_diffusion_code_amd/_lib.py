@@ -1,6 +1,6 @@
 """ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
 include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h,
-include/osmosis_solver.h and include/osmosis_robust.h).
+include/osmosis_solver.h, include/osmosis_robust.h and include/osmosis_gain.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -105,6 +105,13 @@ class RobustDesc(C.Structure):
     """osm_robust_desc (include/osmosis_robust.h): the IRLS weights of the robust data term."""
     _fields_ = [("loss", C.c_int), ("c", C.c_float), ("scale_mode", C.c_int), ("scale", C.c_float), ("sigma_min", C.c_float),
                 ("per_pixel", C.c_int), ("B", C.c_int), ("hw", C.c_int)]
+
+
+class GainDesc(C.Structure):
+    """osm_gain_desc (include/osmosis_gain.h): the learnt vignetting gain field of the Osmosis data term."""
+    _fields_ = [("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("gh", C.c_int), ("gw", C.c_int), ("P", C.c_int),
+                ("loss_type", C.c_int), ("eta", C.c_float), ("lambda", C.c_float), ("g_min", C.c_float), ("n_iter", C.c_int),
+                ("learn", C.c_int)]
 
 
 class ReconDesc(C.Structure):
@@ -268,6 +275,14 @@ _SIGS_ROBUST = {
     "osm_robust_mask": [C.POINTER(RobustDesc), _P, _LL, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 EXPORTS_ROBUST = sorted(_SIGS_ROBUST)
+# the entry points of the tenth header, include/osmosis_gain.h (a learnt vignetting gain field in the Osmosis data term)
+_SIGS_GAIN = {
+    "osm_gain_expand": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "osm_gain_rows": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "osm_gain_step": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P],
+    "osm_gain_prepare": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+}
+EXPORTS_GAIN = sorted(_SIGS_GAIN)
 
 _lib = None
 _lock = threading.Lock()
@@ -288,7 +303,7 @@ def load():
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
                     list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()) + \
-                    list(_SIGS_ROBUST.items()):
+                    list(_SIGS_ROBUST.items()) + list(_SIGS_GAIN.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

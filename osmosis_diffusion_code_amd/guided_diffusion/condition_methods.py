@@ -20,6 +20,7 @@ from abc import ABC, abstractmethod
 from functools import partial
 
 import os
+import numpy as np
 import torch
 
 from .. import ops
@@ -197,7 +198,60 @@ def robust_weights_torch(e, M0, loss, c, scale="mad", sigma_min=2.0 / 255.0, per
     return (torch.where(ok, m0 * s, m0).view(e.shape), torch.where(ok, w, one).view(e.shape), sigma, n)
 
 
+def gain_hats(H, W, gh, gw, device, dtype=torch.float64):
+    """The hat matrices (Hy [H,gh], Hx [W,gw]) of include/osmosis_gain.h from the fp32 tables: G = Hy n Hx^T."""
+    iy0, fy, ix0, fx = (torch.from_numpy(a) for a in ops.gain_tables_host(H, W, gh, gw))
+
+    def hat(i0, f, g):
+        n = i0.shape[0]
+        Hm = torch.zeros(n, g, dtype=torch.float64)
+        rows = torch.arange(n)
+        Hm[rows, i0.long()] += 1.0 - f.double()
+        Hm[rows, i0.long() + 1] += f.double()
+        return Hm.to(device=device, dtype=dtype)
+    return hat(iy0, fy, gh), hat(ix0, fx, gw)
+
+
+def gain_learn_torch(nodes, F, w, y, M0, loss_function, eta, n_iter, smooth, g_min):
+    """include/osmosis_gain.h's n_iter x (node gradient, step) on torch tensors, in float64 whatever the inputs are: nodes
+    [B,gh,gw], F and y [B,3,H,W], w [B,1,H,W] or a number, M0 like y or None.  Returns the new nodes (float64); constants of the
+    sub-step, nothing is differentiated through them."""
+    n = nodes.detach().double().clone()
+    F, y = F.detach().double(), y.detach().double()
+    B, _, H, W = y.shape
+    w = w.detach().double() if torch.is_tensor(w) else float(w)
+    M = 1.0 if M0 is None else M0.detach().double()
+    Hy, Hx = gain_hats(H, W, n.shape[1], n.shape[2], y.device)
+    for _ in range(int(n_iter)):
+        G = (Hy @ n @ Hx.T)[:, None]
+        r = (y - (2 * G * F - 1)) * w * M
+        q = (r * (-2 * F * w * M)).sum(dim=1)
+        S = (r * r).sum(dim=(1, 2, 3))
+        c_raw = Hy.T @ q @ Hx
+        gscale = 1.0 / torch.sqrt(S) if loss_function == "norm" else torch.full_like(S, 2.0 / (3 * H * W))
+        Ln = torch.zeros_like(n)
+        Ln[:, 1:, :] += n[:, 1:, :] - n[:, :-1, :]
+        Ln[:, :-1, :] += n[:, :-1, :] - n[:, 1:, :]
+        Ln[:, :, 1:] += n[:, :, 1:] - n[:, :, :-1]
+        Ln[:, :, :-1] += n[:, :, :-1] - n[:, :, 1:]
+        v = n - float(eta) * (gscale[:, None, None] * c_raw + float(smooth) * Ln)
+        gm = torch.full_like(v, float(g_min))
+        u = torch.where(v < gm, gm, v)                          # (a NaN survives into max(u))
+        um = u.flatten(1).max(dim=1).values
+        um = torch.where(torch.isnan(u).flatten(1).any(dim=1), torch.full_like(um, float("nan")), um)
+        ok = torch.isfinite(S) & torch.isfinite(um)
+        if loss_function == "norm":
+            ok = ok & (S != 0)
+        nn = u / um[:, None, None]
+        nn = torch.where(nn < gm, gm, nn)
+        n = torch.where(ok[:, None, None], nn, n).float().double()     # stored as fp32, as the kernels store them
+    return n
+
+
 class ConditioningMethod(ABC):
+    _gain = None            # the learnt vignetting gain field (`PosteriorSamplingOsmosis.set_gain_field`); class default: none
+    _gain_hold = None       # the autograd route's G while it walks the inner iterations of ONE sub-step
+    _gain_freeze = False    # that sub-step freezes phi: the field is not stepped either
     _depth = None           # the range-map depth prior (`PosteriorSamplingOsmosis.set_depth_prior`); class default: none
     _mask = None            # [B or 1, 3, HW] fp32 (`set_measurement_mask`); class default: conditioners without one are unmasked
     _mask_hw = None
@@ -228,7 +282,19 @@ class ConditioningMethod(ABC):
         self._robust = {"loss": loss, "c": float(d.c), "scale": "mad" if d.scale_mode == 0 else float(d.scale),
                         "sigma_min": float(d.sigma_min), "per_pixel": bool(per_pixel), "state": None, "ones": None}
         self._robust_refuse()
+        self._gain_refuse()
         return self._robust
+
+    def _gain_refuse(self):
+        """What the gain field is not routed through: the robust term, a degradation inside the physical operator."""
+        if self._gain is None:
+            return
+        if self._robust is not None:
+            raise NotImplementedError("gain_field: the gain field together with the robust data term (`set_robust`) is not built -- both "
+                                      "claim the mask of the masked route")
+        if getattr(self.operator, "degradation", None) is not None:
+            raise NotImplementedError("gain_field: the gain field is not routed through a physical operator with a `degradation` (the "
+                                      "field would live on the degradation's grid)")
 
     def _robust_refuse(self):
         """The routings that are not built: the residual on a linear operator's grid."""
@@ -461,6 +527,123 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("scale must have 1 or 4 entries (RGBD)")
         return s.to(device).contiguous()
 
+    # ---------------------------------------------------------------- learnt vignetting gain field (include/osmosis_gain.h)
+    def set_gain_field(self, grid=(5, 5), eta=0.01, n_iter=1, smooth=0.0, g_min=0.05, init=None, learn=True):
+        """Model the photo as G F(x0; phi) with one smooth gain G(p) <= 1 per pixel (lens vignetting, the fall-off of a strobe): G is
+        the bilinear interpolation of `grid` = (gh, gw) nodes on the image corners, 2 <= gh, gw <= 32.  Per guided sub-step that does
+        not freeze phi and per image, `n_iter` projected gradient steps of size `eta` on the nodes at the phi the sub-step starts
+        from (`smooth` weighs the 4-neighbour Laplacian; the nodes stay >= `g_min` and are scaled to max = 1, since a global gain is
+        a scaling of J and phi_inf), then the data term runs its masked route on y' = (y + 1) / G - 1 with the mask M G -- which IS
+        the residual of G F, so the phi loop and dL/dx0 are the existing kernels'.  init: nodes [gh,gw] or [B,gh,gw] (scaled to
+        max = 1 per image), default a flat field; `learn=False` keeps them: the way in for a measured flat field.
+        `set_gain_field(None)` clears the setting; with none set nothing changes.  Three small kernels (csrc/gainfield.hip) before
+        the phi loop, no host sync.  The per-batch state starts afresh with every call."""
+        if grid is None:
+            self._gain = None
+            return None
+        gh, gw, eta, n_iter, smooth, g_min = ops.gain_check(grid, eta, n_iter, smooth, g_min)
+        if init is not None:
+            init = torch.as_tensor(np.asarray(init.detach().cpu() if torch.is_tensor(init) else init, dtype=np.float64))
+            if init.dim() == 2:
+                init = init[None]
+            if init.dim() != 3 or tuple(init.shape[1:]) != (gh, gw):
+                raise ValueError(f"gain_field: init must be nodes [{gh},{gw}] or [B,{gh},{gw}], got {tuple(init.shape)}")
+            if not bool(torch.isfinite(init).all()) or not bool((init > 0).all()):
+                raise ValueError("gain_field: init must be finite and > 0 everywhere")
+            init = (init / init.flatten(1).max(dim=1).values[:, None, None]).clamp(min=g_min).to(torch.float32)
+        self._gain = {"grid": (gh, gw), "eta": eta, "n_iter": n_iter, "smooth": smooth, "g_min": g_min, "learn": bool(learn),
+                      "init": init, "state": None}
+        self._gain_refuse()
+        return self._gain
+
+    def gain_open(self, B, H, W, device):
+        """What a loop calls once per chain: the per-BATCH state (nodes [B,gh,gw], field [B,1,HW], the rows y' and M' [B,3,HW]) at
+        its initial values, so that `gain_values` reads them until the first guided sub-step.  A call on a chunk writes its rows."""
+        gn = self._gain
+        self._gain_refuse()
+        st = gn["state"]
+        key = (int(B), int(H), int(W), str(device))
+        if st is not None and st["key"] == key:
+            return st
+        gh, gw = gn["grid"]
+        if gh > H or gw > W:
+            raise ValueError(f"gain_field: grid {gh} x {gw} has more nodes than the image has pixels ({H} x {W})")
+        init = gn["init"]
+        if init is not None and init.shape[0] not in (1, B):
+            raise ValueError(f"gain_field: init [{init.shape[0]},{gh},{gw}] does not fit a batch of {B}")
+        f32 = dict(device=device, dtype=torch.float32)
+        nodes = torch.ones(B, gh, gw, **f32) if init is None else init.to(device).expand(B, gh, gw).contiguous()
+        Hy, Hx = gain_hats(H, W, gh, gw, device)
+        st = gn["state"] = {"key": key, "nodes": nodes, "field": (Hy @ nodes.double() @ Hx.T).to(torch.float32).reshape(B, 1, H * W),
+                            "y_eff": torch.zeros(B, 3, H * W, **f32), "m_eff": torch.zeros(B, 3, H * W, **f32), "ws": {}}
+        return st
+
+    def _gain_rows(self, phi, B, H, W, device):
+        """(the state, the first row r0 of it) for a call on B images: the phi rows in hand say which images they are -- a row block
+        of the operator's own [B0][9] block, as a chunked walk hands them over."""
+        full = self.operator.phi
+        r0, rem = divmod(phi.data_ptr() - full.data_ptr(), 9 * 4)
+        if phi.device != full.device or rem != 0 or r0 < 0 or r0 + B > full.shape[0]:
+            # the kernels write the node, field and (y', M') rows of every image they are handed
+            raise ValueError("gain_field: `phi` must be a row block of the operator's own phi tensor, got "
+                             f"{B} rows at byte offset {phi.data_ptr() - full.data_ptr()} of its {full.shape[0]}")
+        return self.gain_open(full.shape[0], H, W, device), r0
+
+    def _gain_prepare(self, d, x0c, yc, M0, phi, freeze_phi):
+        """The sub-step's (y' rows, M' rows) [B,3,HW]: osm_phys_forward at the starting phi, then the 2 n_iter + 1 launches of
+        include/osmosis_gain.h from one call, or singly with OSM_PHYS_PY_LOOP=1."""
+        gn = self._gain
+        B, _, H, W = x0c.shape
+        st, r0 = self._gain_rows(phi, B, H, W, x0c.device)
+        if M0 is not None and (M0.numel() != B * 3 * H * W or not M0.is_contiguous()):
+            raise ValueError(f"expected mask rows [{B},3,{H * W}], got {tuple(M0.shape)}")
+        ws = st["ws"].get((B, d.loss_type, d.weight_type))
+        if ws is None:
+            P = ops.phys_lin_planes(d)
+            gd = ops.gain_desc(gn["grid"], gn["eta"], gn["n_iter"], gn["smooth"], gn["g_min"], gn["learn"], d.loss_type, P, B, H, W)
+            ws = st["ws"][(B, d.loss_type, d.weight_type)] = {
+                "desc": gd, "F": torch.empty(B, P, H * W, device=x0c.device, dtype=torch.float32), "tsc": ops.gain_workspace(gd, x0c.device)}
+        gd, F, (t, s, cs) = ws["desc"], ws["F"], ws["tsc"]
+        tabs = ops.gain_tables(H, W, gd.gh, gd.gw, x0c.device)
+        nodes, field = st["nodes"][r0:r0 + B], st["field"][r0:r0 + B]
+        y_eff, m_eff = st["y_eff"][r0:r0 + B], st["m_eff"][r0:r0 + B]
+        learn = gn["learn"] and not freeze_phi
+        if learn:
+            ops.phys_forward(d, x0c, phi, F)
+        if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
+            ops.gain_prepare(gd, tabs, F, yc, M0, nodes, t, s, cs, y_eff, m_eff, field, freeze_phi=freeze_phi)
+            return y_eff, m_eff
+        if learn:
+            for _ in range(gd.n_iter):
+                ops.gain_rows(gd, tabs, nodes, F, yc, M0, t, s)
+                ops.gain_step(gd, tabs, t, s, nodes, cs)
+        ops.gain_expand(gd, tabs, nodes, yc, M0, y_eff, m_eff, field)
+        return y_eff, m_eff
+
+    def _gain_torch(self, image, w, measurement):
+        """G [B,1,H,W] on the torch routes, in the measurement's dtype: the same gradient and step (`gain_learn_torch`) at the phi the
+        sub-step starts from, the state kept for `gain_values`."""
+        gn = self._gain
+        B, _, H, W = measurement.shape
+        st = self.gain_open(B, H, W, measurement.device)
+        if gn["learn"] and not self._gain_freeze:
+            n = gain_learn_torch(st["nodes"], image, w, measurement, self._mask_like(measurement), self.loss_function, gn["eta"],
+                                 gn["n_iter"], gn["smooth"], gn["g_min"])
+            st["nodes"].copy_(n)
+        Hy, Hx = gain_hats(H, W, gn["grid"][0], gn["grid"][1], measurement.device)
+        G = (Hy @ st["nodes"].double() @ Hx.T)[:, None]
+        st["field"].copy_(G.reshape(B, 1, H * W))
+        return G.to(measurement.dtype)
+
+    def gain_values(self):
+        """{'nodes': [B,gh,gw], 'field': G [B,1,HW]} over the whole batch (device tensors, no sync), each image's from the last guided
+        sub-step that covered it -- also when the batch was walked in chunks; the initial values until the first guided sub-step.
+        None with no gain field set or before a loop has opened the state."""
+        gn = self._gain
+        if gn is None or gn["state"] is None:
+            return None
+        return {"nodes": gn["state"]["nodes"], "field": gn["state"]["field"]}
+
     # ---------------------------------------------------------------- range-map depth prior (include/osmosis_depthprior.h)
     _depth_serial = 0
 
@@ -689,8 +872,11 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         and g stay per image, and the call must cover the operator's whole batch.
         With a range-map prior (`set_depth_prior`; `depth`: the chunk's (range, confidence) rows [B,1,HW], default the stored ones)
         g's depth plane also carries weight * d L_depth / d x0, added after the inner loop; the returned loss stays the data loss
-        (`depth_prior_values` has the prior's)."""
+        (`depth_prior_values` has the prior's).
+        With a gain field (`set_gain_field`) the nodes are stepped first (not when `freeze_phi`), and the route runs masked on
+        (y', M G) of include/osmosis_gain.h; `phi` rows then say which images of the batch these are."""
         self._robust_refuse()
+        self._gain_refuse()
         if getattr(self.operator, "degradation", None) is not None:
             return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask, depth)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
@@ -708,7 +894,13 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise ValueError("phi must be a contiguous [B][9] block")
         g = g_out if g_out is not None else st["g"]
         x0c, yc = x0.contiguous(), y.contiguous()
-        if self._robust is not None:
+        if self._gain is not None:
+            # the gain field: the nodes learnt at the phi this sub-step starts from, then (y', M G) rows in the place of (y, mask) --
+            # the masked residual on them is the residual of the model G F, so everything below is what it was
+            if mask is None:
+                mask = self.measurement_mask(B, HW, x0.device)
+            yc, mask = self._gain_prepare(d, x0c, yc, mask, phi, freeze_phi)
+        elif self._robust is not None:
             # the robust term: the model image at the phi this sub-step starts from, the raw residual's MAD scale and the IRLS weights
             # folded into the mask -- M_eff rows in the mask's place, constants of the inner loop below
             F = st.get("F_robust")
@@ -870,6 +1062,16 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                                    degraded_image=image.detach(), x_0_hat=x_0_hat.detach())
         if deg is not None and torch.is_tensor(w):
             w = deg.forward(w.detach().contiguous())
+        if self._gain is not None:
+            # the gain field: the model is G image, G from the nodes stepped at the phi the sub-step starts from
+            # (`_conditioning_autograd` holds it over its inner iterations), a constant of the step
+            self._gain_refuse()
+            G = self._gain_hold
+            if G is None:
+                G = self._gain_torch(image.detach(), w, measurement)
+                if self._robust_holding:
+                    self._gain_hold = G
+            image = G * image
         raw = measurement - (2 * image - 1)
         diff = raw * w
         if self._robust is not None:
@@ -909,6 +1111,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             raise NotImplementedError("gradient_x_prev=False raises in the reference too (backward(inputs=[x_prev]) on a tensor whose "
                                       "requires_grad it has just switched off, condition_methods.py:152-157, :186-191)")
         self._robust_hold, self._robust_holding = None, True        # the robust weights: the first iteration's, for all of them
+        self._gain_hold, self._gain_freeze = None, bool(freeze_phi)  # the gain field alike; a frozen sub-step does not step it
         try:
             with torch.enable_grad():
                 self.operator.set_variable_gradients(value=not freeze_phi)
@@ -925,6 +1128,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                     variables = self.operator.optimize(freeze_phi=freeze_phi)
         finally:                        # (also when an iteration raises: a later call must not meet stale weights)
             self._robust_hold, self._robust_holding = None, False
+            self._gain_hold, self._gain_freeze = None, False
         with torch.no_grad():
             grads = x_prev.grad
             if self.gradient_clip:
@@ -935,7 +1139,11 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
     def grad_and_value(self, x_prev, x_0_hat, measurement, **kwargs):
         if not self._has_kernels():
             self._robust_hold, self._robust_holding = None, False
-            return self._loss_autograd(x_0_hat, measurement, **kwargs)
+            self._gain_hold, self._gain_freeze = None, True         # (an evaluation, as freeze_phi=True below: nothing is stepped)
+            try:
+                return self._loss_autograd(x_0_hat, measurement, **kwargs)
+            finally:
+                self._gain_freeze = False
         g, loss = self.loss_grad_x0(x_0_hat.detach(), measurement, freeze_phi=True)
         I = self.operator.forward(x_0_hat.detach())
         return loss.detach().cpu().numpy(), loss.sum(), I
@@ -982,6 +1190,12 @@ class PosteriorSampling(ConditioningMethod):
             return None
         raise NotImplementedError("the 'ps' branch has no depth model (its data term is y - A x0[:, 0:3]): a range-map depth prior "
                                   "needs the 'osmosis' conditioner")
+
+    def set_gain_field(self, grid=(5, 5), *args, **kwargs):
+        if grid is None:
+            return None
+        raise NotImplementedError("gain_field: the 'ps' branch has no image-formation model to put a gain field in (its data term is "
+                                  "y - A x0[:, 0:3]); the 'osmosis' conditioner has one")
 
     def _blind(self):
         """The operator when it is a `blind_blur` that learns its PSF (its data term steps the weights and couples the batch), else None."""

@@ -966,7 +966,8 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ public loop
     def p_sample_loop(self, model, x_start, measurement, measurement_cond_fn, record, save_root,
                       pretrain_model=None, image_idx=None, record_every=150, rgb_guidance=False,
-                      sample_pattern=None, measurement_mask=None, tiling=None, depth_prior=None, robust=None, **kwargs):
+                      sample_pattern=None, measurement_mask=None, tiling=None, depth_prior=None, robust=None, gain_field=None,
+                      **kwargs):
         """measurement_mask: a per-pixel validity mask of the measurement ([B,3,H,W], [B,1,H,W], [1,3,H,W] or [1,1,H,W] in
         [0, 1]; `ConditioningMethod.set_measurement_mask`), handed to the conditioner for this chain -- the fused loop and
         `_generic_loop` alike; None: the conditioner keeps whatever mask it was given directly (none by default).
@@ -977,8 +978,27 @@ class GaussianDiffusion:
         None: the conditioner keeps whatever prior it was given directly (none by default).
         robust: `dict(loss=, c=, scale=, sigma_min=, per_pixel=)` makes the data term robust for this chain
         (`ConditioningMethod.set_robust`; on a tiled canvas the weights are over the whole canvas, with one sigma); None: the
-        conditioner keeps whatever setting it was given directly (none by default)."""
+        conditioner keeps whatever setting it was given directly (none by default).
+        gain_field: `dict(grid=, eta=, n_iter=, smooth=, g_min=, init=, learn=)` puts a learnt vignetting gain field into the Osmosis
+        data term for this chain (`PosteriorSamplingOsmosis.set_gain_field`; on a tiled canvas one field over the canvas), its state
+        starting afresh; None: the conditioner keeps whatever setting it was given directly (none by default)."""
         from .posterior_mean_variance import PreviousXMeanProcessor
+        if gain_field is not None:
+            cond_obj = getattr(measurement_cond_fn, "__self__", None)
+            if not hasattr(cond_obj, "set_gain_field"):
+                raise TypeError("gain_field needs a conditioner with set_gain_field (the 'osmosis' conditioning method)")
+            if not isinstance(gain_field, dict):
+                raise ValueError("gain_field must be a dict (grid, eta, n_iter, smooth, g_min, init, learn)")
+            unknown = set(gain_field) - {"grid", "eta", "n_iter", "smooth", "g_min", "init", "learn"}
+            if unknown:
+                raise ValueError(f"gain_field: unknown keys {sorted(unknown)}")
+            cond_obj.set_gain_field(**gain_field)
+        if getattr(getattr(measurement_cond_fn, "__self__", None), "_gain", None) is not None:
+            # the per-batch state at its initial values (`gain_values` reads them until the first guided sub-step); refusals first
+            cond_obj = measurement_cond_fn.__self__
+            phi_all = getattr(cond_obj.operator, "phi", None)       # (a third-party operator keeps its parameters elsewhere)
+            cond_obj.gain_open(x_start.shape[0] if phi_all is None else phi_all.shape[0], x_start.shape[2], x_start.shape[3],
+                               x_start.device)
         if robust is not None:
             cond_obj = getattr(measurement_cond_fn, "__self__", None)
             if not hasattr(cond_obj, "set_robust"):

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, ConvDesc, DepthDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, RobustDesc, call, current_stream_ptr, ptr, ptr_f64, query
+from ._lib import AttnDesc, ConvDesc, DepthDesc, GainDesc, GemmDesc, GroupDesc, LinDesc, PhysDesc, ReconDesc, RobustDesc, call, current_stream_ptr, ptr, ptr_f64, query
 
 
 @dataclass
@@ -1094,3 +1094,131 @@ def robust_mask(desc: RobustDesc, pred, pa, pb, y, M0, e, sigma, n_valid, M_eff,
         raise ValueError("robust_mask: the mad scale writes `sigma` and `n_valid`")
     call("osm_robust_mask", C.byref(desc), ptr(pred), bs, float(pa), float(pb), ptr(y), ptr(M0), ptr(e), ptr(sigma), ptr(n_valid),
          ptr(M_eff), ptr(omega), _s(), keep=(desc, pred, y, M0, e, sigma, n_valid, M_eff, omega))
+
+
+# ----------------------------------------------------------------------------- learnt vignetting gain field (include/osmosis_gain.h)
+GAIN_MAX_GRID = 32
+_gain_tables = {}       # (H, W, gh, gw, device) -> (iy0, fy, ix0, fx) on the device
+
+
+def gain_tables_host(H, W, gh, gw):
+    """The interpolation tables of include/osmosis_gain.h on the host: (iy0 [H] int32, fy [H] fp32, ix0 [W] int32, fx [W] fp32), the
+    positions j (n - 1) / (g - 1) in float64, the fractions rounded to fp32."""
+    import numpy as np
+
+    def axis(n, g):
+        pos = np.arange(n, dtype=np.float64) * (g - 1) / (n - 1)
+        i0 = np.minimum(np.floor(pos), g - 2).astype(np.int32)
+        return i0, (pos - i0).astype(np.float32)
+    iy0, fy = axis(int(H), int(gh))
+    ix0, fx = axis(int(W), int(gw))
+    return iy0, fy, ix0, fx
+
+
+def gain_tables(H, W, gh, gw, device):
+    """`gain_tables_host` as device tensors, cached per (H, W, gh, gw, device)."""
+    key = (int(H), int(W), int(gh), int(gw), str(device))
+    tabs = _gain_tables.get(key)
+    if tabs is None:
+        while len(_gain_tables) >= 16:
+            _gain_tables.pop(next(iter(_gain_tables)))
+        tabs = _gain_tables[key] = tuple(torch.from_numpy(a).to(device) for a in gain_tables_host(H, W, gh, gw))
+    return tabs
+
+
+def gain_check(grid, eta, n_iter, smooth, g_min, H=None, W=None):
+    """The host-side range checks of a gain-field setting; returns (gh, gw, eta, n_iter, smooth, g_min)."""
+    try:
+        gh, gw = (int(v) for v in grid)
+        ok = (gh, gw) == tuple(grid)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"gain_field: grid must be a pair of ints (gh, gw), got {grid!r}")
+    if not (2 <= gh <= GAIN_MAX_GRID and 2 <= gw <= GAIN_MAX_GRID):
+        raise ValueError(f"gain_field: grid must be within 2 .. {GAIN_MAX_GRID} per side, got {gh} x {gw}")
+    if H is not None and (gh > H or gw > W):
+        raise ValueError(f"gain_field: grid {gh} x {gw} has more nodes than the image has pixels ({H} x {W})")
+    eta, smooth, g_min = float(eta), float(smooth), float(g_min)
+    if not (eta >= 0.0 and eta < float("inf")):
+        raise ValueError(f"gain_field: eta must be finite and >= 0, got {eta}")
+    if not (smooth >= 0.0 and smooth < float("inf")):
+        raise ValueError(f"gain_field: smooth must be finite and >= 0, got {smooth}")
+    if not (g_min > 0.0 and g_min <= 1.0):
+        raise ValueError(f"gain_field: g_min must be in (0, 1], got {g_min}")
+    if int(n_iter) != n_iter or not 1 <= int(n_iter) <= 1024:
+        raise ValueError(f"gain_field: n_iter must be an int in [1, 1024], got {n_iter!r}")
+    return gh, gw, eta, int(n_iter), smooth, g_min
+
+
+def gain_desc(grid, eta, n_iter, smooth, g_min, learn, loss_type, P, B, H, W) -> GainDesc:
+    """The osm_gain_desc of a setting on a [B,*,H,W] batch: loss_type 0 norm / 1 mse, P the planes of F (3, or 4 with the depth
+    weight)."""
+    gh, gw, eta, n_iter, smooth, g_min = gain_check(grid, eta, n_iter, smooth, g_min, H, W)
+    d = GainDesc()
+    d.B, d.H, d.W, d.gh, d.gw, d.P, d.loss_type = int(B), int(H), int(W), gh, gw, int(P), int(loss_type)
+    d.eta, d.g_min, d.n_iter, d.learn = eta, g_min, n_iter, int(bool(learn))
+    setattr(d, "lambda", smooth)
+    return d
+
+
+def gain_workspace(desc: GainDesc, device):
+    """(t [B,H,gw] fp32, s [B,H] fp32, cs [B, gh gw + 1] float64) of a learning sub-step."""
+    return (torch.empty(desc.B, desc.H, desc.gw, device=device, dtype=torch.float32),
+            torch.empty(desc.B, desc.H, device=device, dtype=torch.float32),
+            torch.empty(desc.B, desc.gh * desc.gw + 1, device=device, dtype=torch.float64))
+
+
+def _check_gain(name, desc: GainDesc, tabs, **ts):
+    B, HW, ng = desc.B, desc.H * desc.W, desc.gh * desc.gw
+    need = {"nodes": B * ng, "y": B * 3 * HW, "M0": B * 3 * HW, "y_eff": B * 3 * HW, "m_eff": B * 3 * HW, "field": B * HW,
+            "F": B * desc.P * HW, "t": B * desc.H * desc.gw, "s": B * desc.H}
+    for k, t in ts.items():
+        if t is None:
+            continue
+        if k == "cs":
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != B * (ng + 1):
+                raise ValueError(f"{name}: `cs` must be contiguous float64 with {B * (ng + 1)} elements, got {tuple(t.shape)} {t.dtype}")
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != need[k]:
+            raise ValueError(f"{name}: `{k}` must be contiguous fp32 with {need[k]} elements, got {tuple(t.shape)} {t.dtype}")
+    iy0, fy, ix0, fx = tabs
+    for k, t, n, dt in (("iy0", iy0, desc.H, torch.int32), ("fy", fy, desc.H, torch.float32), ("ix0", ix0, desc.W, torch.int32),
+                        ("fx", fx, desc.W, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"{name}: table `{k}` must be contiguous {dt} [{n}], got {tuple(t.shape)} {t.dtype}")
+
+
+def gain_expand(desc: GainDesc, tabs, nodes, y, M0, y_eff, m_eff, field):
+    """y_eff = (y + 1) / G - 1, m_eff = M0 G (M0 None: ones) and field = G from the nodes [B,gh,gw] (osm_gain_expand)."""
+    _check_gain("gain_expand", desc, tabs, nodes=nodes, y=y, M0=M0, y_eff=y_eff, m_eff=m_eff, field=field)
+    iy0, fy, ix0, fx = tabs
+    call("osm_gain_expand", C.byref(desc), ptr(iy0), ptr(fy), ptr(ix0), ptr(fx), ptr(nodes), ptr(y), ptr(M0), ptr(y_eff), ptr(m_eff),
+         ptr(field), _s(), keep=(desc, tabs, nodes, y, M0, y_eff, m_eff, field))
+
+
+def gain_rows(desc: GainDesc, tabs, nodes, F, y, M0, t, s):
+    """t [B,H,gw] and s [B,H]: the node gradient's row sums and the rows' sums of r^2 at the nodes, on F [B,P,HW] (osm_gain_rows)."""
+    _check_gain("gain_rows", desc, tabs, nodes=nodes, F=F, y=y, M0=M0, t=t, s=s)
+    iy0, fy, ix0, fx = tabs
+    call("osm_gain_rows", C.byref(desc), ptr(iy0), ptr(fy), ptr(ix0), ptr(fx), ptr(nodes), ptr(F), ptr(y), ptr(M0), ptr(t), ptr(s), _s(),
+         keep=(desc, tabs, nodes, F, y, M0, t, s))
+
+
+def gain_step(desc: GainDesc, tabs, t, s, nodes, cs):
+    """cs [B, gh gw + 1] float64 = (c_raw, S) from t and s, then the projected step on the nodes in place (osm_gain_step)."""
+    _check_gain("gain_step", desc, tabs, t=t, s=s, nodes=nodes, cs=cs)
+    iy0, fy, _, _ = tabs
+    call("osm_gain_step", C.byref(desc), ptr(iy0), ptr(fy), ptr(t), ptr(s), ptr(nodes), ptr_f64(cs), _s(), keep=(desc, tabs, t, s, nodes, cs))
+
+
+def gain_prepare(desc: GainDesc, tabs, F, y, M0, nodes, t, s, cs, y_eff, m_eff, field, freeze_phi=False):
+    """The sub-step's launches from one call (osm_gain_prepare): n_iter x (rows, step), then the expand; freeze_phi or a desc with
+    learn = 0: the expand alone (F, t, s, cs may then be None)."""
+    _check_gain("gain_prepare", desc, tabs, F=F, y=y, M0=M0, nodes=nodes, t=t, s=s, cs=cs, y_eff=y_eff, m_eff=m_eff, field=field)
+    if desc.learn == 1 and not freeze_phi and any(v is None for v in (F, t, s, cs)):
+        raise ValueError("gain_prepare: a learning sub-step needs F, t, s and cs")
+    iy0, fy, ix0, fx = tabs
+    call("osm_gain_prepare", C.byref(desc), ptr(iy0), ptr(fy), ptr(ix0), ptr(fx), ptr(F), ptr(y), ptr(M0), ptr(nodes), ptr(t), ptr(s),
+         ptr_f64(cs), ptr(y_eff), ptr(m_eff), ptr(field), int(bool(freeze_phi)), _s(),
+         keep=(desc, tabs, F, y, M0, nodes, t, s, cs, y_eff, m_eff, field))

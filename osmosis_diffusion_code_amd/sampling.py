@@ -148,6 +148,70 @@ def robust_config(robust_cfg=None, robust=None):
     return dict(chosen)
 
 
+GAIN_KEYS = ("grid", "eta", "n_iter", "smooth", "g_min", "learn", "path")
+
+
+def gain_nodes_from_flat_field(flat, grid):
+    """The [gh,gw] nodes whose bilinear field (include/osmosis_gain.h: nodes on the image corners) is closest in least squares to a
+    full-resolution flat field [H,W] > 0, on the host in float64; scaled to max = 1."""
+    from .ops import gain_tables_host
+    flat = np.asarray(flat, dtype=np.float64)
+    if flat.ndim != 2 or not np.isfinite(flat).all() or not (flat > 0).all():
+        raise ValueError(f"measurement.gain: a flat field must be a finite [H,W] array > 0, got shape {flat.shape}")
+    gh, gw = grid
+    H, W = flat.shape
+    iy0, fy, ix0, fx = gain_tables_host(H, W, gh, gw)
+
+    def hat(i0, f, g):
+        Hm = np.zeros((i0.shape[0], g))
+        Hm[np.arange(i0.shape[0]), i0] += 1.0 - f.astype(np.float64)
+        Hm[np.arange(i0.shape[0]), i0 + 1] += f.astype(np.float64)
+        return Hm
+    Hy, Hx = hat(iy0, fy, gh), hat(ix0, fx, gw)
+    nodes = np.linalg.pinv(Hy) @ flat @ np.linalg.pinv(Hx).T         # argmin ||Hy n Hx^T - flat||_F (both have full column rank)
+    if not (nodes > 0).all():
+        raise ValueError("measurement.gain: the flat field's least-squares nodes are not all > 0")
+    return nodes / nodes.max()
+
+
+def gain_config(gain_cfg=None, gain=None, grid_hw=None):
+    """The `gain_field=` dict of a chain (`p_sample_loop(gain_field=)`, `PosteriorSamplingOsmosis.set_gain_field`) from the optional
+    config key `measurement.gain: {grid, eta, n_iter, smooth, g_min, learn, path}` or the argument `gain` (a dict, which wins over
+    the config; it may carry `init` nodes instead of `path`), or None when neither is given.  `path`: a .npy of nodes [gh,gw] or of a
+    full-resolution flat field [H,W] on the network's grid `grid_hw`, reduced to nodes by least squares.  Unknown keys raise."""
+    chosen, where = (gain, "gain") if gain is not None else (gain_cfg, "measurement.gain")
+    if not chosen:
+        return None
+    if not isinstance(chosen, dict):
+        raise ValueError(f"{where} must be a mapping of {', '.join(GAIN_KEYS)}")
+    unknown = set(chosen) - set(GAIN_KEYS) - {"init"}
+    if unknown:
+        raise ValueError(f"{where}: unknown key(s) {sorted(unknown)} (known: {', '.join(GAIN_KEYS)})")
+    out = dict(chosen)
+    out["grid"] = tuple(int(v) for v in out.get("grid", (5, 5)))
+    path = out.pop("path", None)
+    if path is not None:
+        if out.get("init") is not None:
+            raise ValueError(f"{where}: give `path` or `init`, not both")
+        arr = np.load(path)
+        if arr.ndim == 2 and tuple(arr.shape) == out["grid"]:
+            out["init"] = np.asarray(arr, dtype=np.float64)
+        elif arr.ndim == 2 and (grid_hw is None or tuple(arr.shape) == tuple(grid_hw)):
+            out["init"] = gain_nodes_from_flat_field(arr, out["grid"])
+        else:
+            raise ValueError(f"{where}: {path} holds {arr.shape}: neither nodes {out['grid']} nor a flat field on the grid {grid_hw}")
+    return out
+
+
+def attach_gain(post, nodes, field, y):
+    """The gain field's keys of one image's result: `gain_nodes` [gh,gw], `gain_field` [H,W] (both of the chain's last guided
+    sub-step) and `flat_fielded` = clip((y + 1) / (2 G), 0, 1) [3,H,W], the photo with the field divided out."""
+    G = field.detach().cpu().to(torch.float32).view(y.shape[-2], y.shape[-1])
+    post.update(gain_nodes=nodes.detach().cpu().to(torch.float32), gain_field=G,
+                flat_fielded=((y.detach().cpu().to(torch.float32) + 1.0) / (2.0 * G)).clamp(0.0, 1.0))
+    return post
+
+
 def attach_robust(post, weight, scale):
     """The robust term's keys of one image's result: `robust_weight` (omega [3,h,w] of the chain's last guided sub-step, on the
     measurement's grid) and `robust_scale` (its sigma)."""
@@ -315,6 +379,11 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         paths["robust"] = os.path.join(d, f"{name}_robust.png")
         lo = post["robust_weight"].to(torch.float32).amin(dim=0).clamp(0.0, 1.0)        # the per-pixel minimum of omega over the channels
         Image.fromarray((lo * 255.0 + 0.5).to(torch.uint8).numpy(), mode="L").save(paths["robust"])
+    if save_singles and post.get("gain_field") is not None:         # only a chain with a gain field
+        d = os.path.join(out_dir, "single_images", "gain")
+        os.makedirs(d, exist_ok=True)
+        paths["gain"] = os.path.join(d, f"{name}_gain.png")
+        Image.fromarray((post["gain_field"].to(torch.float32).clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).numpy(), mode="L").save(paths["gain"])
     if save_singles and post.get("depth_metric") is not None:       # only a chain with a range-map prior
         d = os.path.join(out_dir, "single_images", "depth_metric")
         os.makedirs(d, exist_ok=True)
@@ -515,7 +584,7 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
 
 def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
                   postprocess_batch=True, mask=None, tiling=None, depth=None, depth_confidence=None, depth_geometry=None,
-                  robust=None, **loop_kwargs):
+                  robust=None, gain=None, **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -554,6 +623,13 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     `robust_weight` (omega [3,h,w] of the last guided sub-step) and `robust_scale` (its sigma) -- each image's own, also when the
     batch is walked in chunks; `save_outputs` writes the per-pixel minimum of omega over the channels as `<name>_robust.png`.
     Without it nothing is passed and there are no such keys.
+
+    `gain` (or the optional config key `measurement.gain: {grid, eta, n_iter, smooth, g_min, learn, path}`; the argument wins;
+    unknown keys raise): a learnt vignetting gain field in the Osmosis data term (`p_sample_loop(gain_field=)`,
+    include/osmosis_gain.h); `path`: a .npy of nodes or of a full-resolution flat field (least squares to nodes, `gain_config`),
+    with `learn: False` a measured flat field that stays fixed.  The field starts afresh at every global iteration.  Every result
+    then carries `gain_field` [H,W], `gain_nodes` [gh,gw] and `flat_fielded` = clip((y + 1) / (2 G), 0, 1) -- each image's own,
+    also in chunked batches; `save_outputs` writes `<name>_gain.png`.  Without it nothing is passed and there are no such keys.
 
     Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
     carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
@@ -632,6 +708,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     robust = robust_config(measure.get("robust"), robust)
     if robust is not None:
         loop_kwargs = dict(loop_kwargs, robust=robust)
+    gain = gain_config(measure.get("gain"), gain, shape[2:])
+    if gain is not None:
+        loop_kwargs = dict(loop_kwargs, gain_field=gain)
     results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
         torch.manual_seed(cfg.get("manual_seed", 0))
@@ -682,6 +761,12 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
         if m_dev is not None:
             post["mask"] = m_dev.detach().cpu()
         _attach_robust_values(post, cond, robust, y_n, postprocess_batch)
+        if gain is not None:
+            vals = cond.gain_values()
+            if postprocess_batch:
+                attach_gain(post, vals["nodes"][0], vals["field"][0], y_n[0])
+            else:                   # every image's, for the caller's per-image post-processing
+                post["gain_fit"] = dict(nodes=vals["nodes"].detach().cpu(), field=vals["field"].detach().cpu())
         if tiling_info is not None:
             post["tiling"] = tiling_info
         if is_blind:
@@ -726,7 +811,7 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
 
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
                    geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, depths=None,
-                   depth_confidences=None, robust=None, **loop_kwargs):
+                   depth_confidences=None, robust=None, gain=None, **loop_kwargs):
     """images[rank::world] (no collective on the path; SURVEY.md 8e).  Returns {image index: result dict of the
     last global iteration}; when `gt_rgb` (list of [3,H,W] in [0,1]) is given each result carries `psnr`.
 
@@ -754,6 +839,8 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     `robust_scale`, also in chunked batches."""
     if robust is not None:
         loop_kwargs = dict(loop_kwargs, robust=robust)
+    if gain is not None:        # (goes to `restore_image` as it is; every result carries its own `gain_field` / `gain_nodes` / `flat_fielded`)
+        loop_kwargs = dict(loop_kwargs, gain=gain)
     if shared_water:
         if tiling is not None or cfg.get("tiling") is not None:
             raise NotImplementedError("shared_water: tiling is one canvas per call, water parameters are not shared across canvases")
@@ -831,6 +918,9 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
             if full.get("robust_fit") is not None:
                 for b, r in enumerate(res):
                     attach_robust(r, full["robust_fit"]["weight"][b], full["robust_fit"]["scale"][b])
+            if full.get("gain_fit") is not None:
+                for b, r in enumerate(res):
+                    attach_gain(r, full["gain_fit"]["nodes"][b], full["gain_fit"]["field"][b], full["measurement"][b])
             if full.get("mask") is not None:
                 for b, r in enumerate(res):
                     r["mask"] = full["mask"][b:b + 1]

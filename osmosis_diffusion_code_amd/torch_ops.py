@@ -930,8 +930,42 @@ def _robust_mask_fake(pred, y, mask, m_eff, omega, sigma, n_valid, pa, pb, loss,
     return None
 
 
+# ---- learnt vignetting gain field (include/osmosis_gain.h): the sub-step's node steps and (y', M G), written IN PLACE
+@torch.library.custom_op("osmosis::gain_prepare", mutates_args=("nodes", "y_eff", "m_eff", "field", "t", "s", "cs"), device_types="cuda")
+def gain_prepare(F: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], nodes: torch.Tensor, y_eff: torch.Tensor,
+                 m_eff: torch.Tensor, field: torch.Tensor, t: torch.Tensor, s: torch.Tensor, cs: torch.Tensor, loss: str, eta: float,
+                 n_iter: int, smooth: float, g_min: float, learn: bool, freeze_phi: bool) -> None:
+    """osm_gain_prepare: with G the bilinear interpolation of nodes [B,gh,gw] over y's grid, `n_iter` x (the gradient of the `loss`
+    'norm' | 'mse' of the model G F with respect to the nodes on F [B,P,H,W] (P = 4: plane 3 the depth weight), y [B,3,H,W] and mask
+    ([B,3,H,W] or [B,1,H,W], None: ones); the projected step of include/osmosis_gain.h) unless `freeze_phi` or not `learn`, then
+    y_eff = (y + 1) / G - 1, m_eff = mask G [B,3,H,W] and field = G [B,1,H,W]; t [B,H,gw], s [B,H] and cs [B, gh gw + 1] float64 are
+    the workspaces.  Everything is written IN PLACE."""
+    name = "osmosis::gain_prepare"
+    B, hw = _chw(y)
+    if y.dim() != 4 or y.shape[1] != 3 or F.dim() != 4 or F.shape[0] != B or F.shape[1] not in (3, 4) or F.shape[2:] != y.shape[2:] \
+            or F.dtype != torch.float32 or not F.is_contiguous():
+        raise OsmosisHipError(f"{name}: expected a contiguous fp32 F [B,3 or 4,H,W] and y [B,3,H,W], got {tuple(F.shape)} and "
+                              f"{tuple(y.shape)}")
+    if nodes.dim() != 3 or nodes.shape[0] != B:
+        raise OsmosisHipError(f"{name}: nodes must be [B,gh,gw], got {tuple(nodes.shape)}")
+    if loss not in ("norm", "mse"):
+        raise OsmosisHipError(f"{name}: loss must be 'norm' or 'mse', got {loss!r}")
+    H, W = y.shape[2], y.shape[3]
+    try:
+        d = ops.gain_desc(tuple(nodes.shape[1:]), eta, n_iter, smooth, g_min, learn, 0 if loss == "norm" else 1, F.shape[1], B, H, W)
+        ops.gain_prepare(d, ops.gain_tables(H, W, d.gh, d.gw, y.device), F, y.contiguous(),
+                         None if mask is None else _mask_rows(name, mask, y), nodes, t, s, cs, y_eff, m_eff, field, freeze_phi=freeze_phi)
+    except ValueError as err:
+        raise OsmosisHipError(f"{name}: {err}") from None
+
+
+@gain_prepare.register_fake
+def _gain_prepare_fake(F, y, mask, nodes, y_eff, m_eff, field, t, s, cs, loss, eta, n_iter, smooth, g_min, learn, freeze_phi):
+    return None
+
+
 OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd_c", "guide_update_c", "guide_update_rng_c",
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask", "gain_prepare") + OPS_C

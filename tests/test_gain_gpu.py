@@ -1,0 +1,568 @@
+"""The learnt vignetting gain field on the GPU (include/osmosis_gain.h, csrc/gainfield.hip): the three kernels against the float32
+restatement (bit for bit) and against float64 under the header's bound, the step against the numpy float64 step, the bit-equalities,
+`loss_grad_x0` with a learnt field against the composed oracle (tests/gain_oracle.py), chains against the oracle's loop with the term,
+the chain equalities and the driver."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import gain_oracle as GA
+from oracle import diffusion_ref as D
+from oracle import unet_ref as U
+from test_mask_gpu import (AUX, COND, OPERATORS, OPS, PATTERN, T, _free_running_bar, _no_generic, _replay_randn_like, _same_bits, etas,
+                           make_masks, make_sampler, model48, pkg)  # noqa: F401  (fixtures)
+from test_physgroup_gpu import gcond, inputs
+from test_robust_gpu import _ref_setup, chain_cond, driver_cfg
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NAN = float("nan")
+# (B, H, W, grid, off): ragged against 4-wide accesses and 64 lanes; a non-square grid; node spacing under 2 px; the scalar path with
+# the minimum grid; the maximum grid (cells of about one pixel); one float off alignment (the unaligned path)
+SHAPES = [(2, 36, 34, (5, 5), 0), (3, 74, 58, (3, 7), 0), (1, 8, 12, (5, 5), 0), (1, 5, 7, (2, 2), 0), (1, 36, 34, (32, 32), 0),
+          (2, 36, 36, (5, 5), 0), (2, 36, 36, (5, 5), 1)]
+IDS = ["b2_36x34_g5x5", "b3_74x58_g3x7", "b1_8x12_g5x5", "b1_5x7_g2x2", "b1_36x34_g32x32", "b2_36x36_aligned", "b2_36x36_off_by_one_float"]
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def dev_buf(shape, off=0, fill=NAN, dtype=torch.float32):
+    """A `fill`-filled device tensor of `shape` whose address is `off` elements past an allocation's start."""
+    n = int(np.prod(shape))
+    return torch.full((n + off,), fill, device=DEV, dtype=dtype)[off:].view(*shape)
+
+
+def to_dev(a, off=0, dtype=torch.float32):
+    t = torch.as_tensor(np.asarray(a)).to(dtype)
+    out = dev_buf(tuple(t.shape), off, 0, dtype)
+    out.copy_(t)
+    return out
+
+
+def kernel_problem(B, H, W, grid, seed, P=3, masked=True):
+    g = torch.Generator().manual_seed(seed)
+    F = torch.rand(B, P, H, W, generator=g)
+    if P == 4:
+        F[:, 3] = 0.5 + F[:, 3]
+    y = torch.rand(B, 3, H, W, generator=g) * 1.6 - 0.8
+    M0 = (torch.rand(B, 3, H, W, generator=g) * (torch.rand(B, 1, H, W, generator=g) > 0.3).float()) if masked else None
+    nodes = 0.3 + 0.7 * torch.rand(B, *grid, generator=g)
+    nodes = nodes / nodes.flatten(1).max(dim=1).values[:, None, None]
+    return F, y, M0, nodes
+
+
+def desc_of(pkg, B, H, W, grid, P=3, loss="norm", eta=0.01, n_iter=1, smooth=0.0, g_min=0.05, learn=True):
+    from osmosis_diffusion_code_amd import ops
+    d = ops.gain_desc(grid, eta, n_iter, smooth, g_min, learn, 0 if loss == "norm" else 1, P, B, H, W)
+    return d, ops.gain_tables(H, W, grid[0], grid[1], DEV)
+
+
+def run_expand(pkg, B, H, W, grid, nodes, y, M0, off=0):
+    from osmosis_diffusion_code_amd import ops
+    d, tabs = desc_of(pkg, B, H, W, grid)
+    ye, me, fld = dev_buf((B, 3, H * W), off), dev_buf((B, 3, H * W), off), dev_buf((B, 1, H * W), off)
+    ops.gain_expand(d, tabs, to_dev(nodes), to_dev(y.reshape(B, 3, -1), off), None if M0 is None else to_dev(M0.reshape(B, 3, -1), off),
+                    ye, me, fld)
+    return ye.cpu().view(B, 3, H, W), me.cpu().view(B, 3, H, W), fld.cpu().view(B, H, W)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_expand_is_the_float32_restatement_bit_for_bit(pkg, shape):
+    B, H, W, grid, off = shape
+    F, y, M0, nodes = kernel_problem(B, H, W, grid, 100 + SHAPES.index(shape))
+    tabs = GA.tables(H, W, *grid)
+    for m in (M0, None):
+        ye, me, fld = run_expand(pkg, B, H, W, grid, nodes, y, m, off)
+        wy, wm, wG = GA.expand32(nodes.numpy(), tabs, y.numpy(), None if m is None else m.numpy())
+        assert _bits_equal(fld, torch.from_numpy(wG)), "G"
+        assert _bits_equal(ye, torch.from_numpy(wy)), "y'"
+        assert _bits_equal(me, torch.from_numpy(wm)), "M'"
+    ones = run_expand(pkg, B, H, W, grid, nodes, y, torch.ones(B, 3, H, W), off)
+    assert all(_bits_equal(a, b) for a, b in zip(ones, (ye, me, fld)))             # M0 = NULL is a mask of ones
+    assert float((fld - GA.field64(nodes, tabs)[:, 0].float()).abs().max()) <= 8 * 2.0 ** -24
+
+
+def run_grad(pkg, B, H, W, grid, nodes, F, y, M0, loss="norm", off=0, **kw):
+    """(c_raw [B,gh,gw], S [B]) float64 as the rows and step kernels form them, and the nodes after the step."""
+    from osmosis_diffusion_code_amd import ops
+    P = F.shape[1]
+    d, tabs = desc_of(pkg, B, H, W, grid, P=P, loss=loss, **kw)
+    t, s = dev_buf((B, H, grid[1])), dev_buf((B, H))
+    cs = dev_buf((B, grid[0] * grid[1] + 1), 0, NAN, torch.float64)
+    n = to_dev(nodes)
+    ops.gain_rows(d, tabs, n, to_dev(F.reshape(B, P, -1), off), to_dev(y.reshape(B, 3, -1), off),
+                  None if M0 is None else to_dev(M0.reshape(B, 3, -1), off), t, s)
+    ops.gain_step(d, tabs, t, s, n, cs)
+    cs = cs.cpu()
+    assert bool(torch.isfinite(t).all()) and bool(torch.isfinite(s).all())           # every NaN-filled entry was written
+    return cs[:, :-1].reshape(B, *grid), cs[:, -1], n.cpu()
+
+
+WORST = {"c_raw": 0.0, "S": 0.0}
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+@pytest.mark.parametrize("P,masked", [(3, False), (4, True)])
+def test_rows_and_step_vs_float64_under_the_headers_bound(pkg, shape, P, masked):
+    B, H, W, grid, off = shape
+    F, y, M0, nodes = kernel_problem(B, H, W, grid, 200 + SHAPES.index(shape), P, masked)
+    c_raw, S, _ = run_grad(pkg, B, H, W, grid, nodes, F, y, M0, off=off)
+    w = F[:, 3:4] if P == 4 else 1
+    _, want_c, want_S, bc, bS = GA.grad64(nodes, GA.tables(H, W, *grid), F[:, 0:3], w, y, M0, "norm")
+    ec = (c_raw - want_c).abs()
+    assert bool((ec[bc == 0] == 0).all())                   # a node whose whole support is masked out: the sum is exactly 0
+    rc, rS = float((ec / bc.clamp(min=1e-300)).max()), float(((S - want_S).abs() / bS).max())
+    WORST["c_raw"], WORST["S"] = max(WORST["c_raw"], rc), max(WORST["S"], rS)
+    print(f"GAINGRAD {IDS[SHAPES.index(shape)]} P {P}: worst |err| / bound c_raw {rc:.3f} S {rS:.3f} (running worst {WORST})")
+    assert rc <= 1.0 and rS <= 1.0, (rc, rS)
+    assert float((c_raw - want_c).abs().max()) > 0 or H * W < 100                 # (the bound is not vacuous: fp32 does round here)
+
+
+def test_exact_case_every_sum_is_the_float64_sum_bit_for_bit(pkg):
+    """33 x 33 with 5 x 5 nodes: the hat weights are multiples of 1/8; F, y, M small integers (over a power of two), w = 1, nodes 1:
+    every product and sum is exact in fp32, so c_raw and S equal the float64 sums bit for bit -- one mis-indexed pixel shows."""
+    B, H, W, grid = 2, 33, 33, (5, 5)
+    g = torch.Generator().manual_seed(7)
+    F = torch.randint(0, 4, (B, 3, H, W), generator=g).float()
+    y = torch.randint(-3, 4, (B, 3, H, W), generator=g).float()
+    M0 = torch.randint(0, 3, (B, 3, H, W), generator=g).float()
+    nodes = torch.ones(B, 5, 5)
+    for m in (M0, None):
+        c_raw, S, _ = run_grad(pkg, B, H, W, grid, nodes, F, y, m)
+        _, want_c, want_S, _, _ = GA.grad64(nodes, GA.tables(H, W, *grid), F, 1, y, m, "norm")
+        assert torch.equal(c_raw, want_c) and torch.equal(S, want_S)
+        assert float(want_c.abs().min()) > 0 and len(set(want_c.flatten().tolist())) > 40
+
+
+def run_step(pkg, B, H, W, grid, nodes, t, s, loss, eta, smooth, g_min):
+    from osmosis_diffusion_code_amd import ops
+    d, tabs = desc_of(pkg, B, H, W, grid, loss=loss, eta=eta, smooth=smooth, g_min=g_min)
+    n = to_dev(nodes)
+    cs = dev_buf((B, grid[0] * grid[1] + 1), 0, NAN, torch.float64)
+    ops.gain_step(d, tabs, to_dev(t), to_dev(s), n, cs)
+    return n.cpu(), cs.cpu()
+
+
+@pytest.mark.parametrize("loss", ["norm", "mse"])
+@pytest.mark.parametrize("B,H,W,grid", [(2, 36, 34, (5, 5)), (1, 40, 33, (32, 32)), (3, 9, 8, (2, 3))])
+def test_step_vs_the_numpy_float64_step_and_the_guards(pkg, loss, B, H, W, grid):
+    rng = np.random.default_rng(B * 100 + H)
+    nodes = (0.1 + 0.9 * rng.random((B,) + grid)).astype(np.float32)
+    t = rng.standard_normal((B, H, grid[1])).astype(np.float32)
+    s = rng.random((B, H)).astype(np.float32)
+    Hy = GA.hat_matrix(*GA.tables(H, W, *grid)[:2], grid[0], fp32=True)          # the hat weights as the header holds them: fp32
+    c_raw, S = np.einsum("yj,byx->bjx", Hy, t.astype(np.float64)), s.astype(np.float64).sum(axis=1)
+    gscale = 1 / np.sqrt(S) if loss == "norm" else np.full(B, 2.0 / (3 * H * W))
+    eta = float(0.6 / np.abs(gscale[:, None, None] * c_raw).mean())                # about half the nodes end at the floor
+    got, cs = run_step(pkg, B, H, W, grid, nodes, t, s, loss, eta, 0.2, 0.05)
+    assert np.allclose(cs[:, :-1].numpy().reshape(c_raw.shape), c_raw, rtol=1e-13, atol=1e-14)    # (float64 sums in another order)
+    assert np.allclose(cs[:, -1].numpy(), S, rtol=1e-14)
+    want = GA.step64(nodes, cs[:, :-1].numpy().reshape(c_raw.shape), cs[:, -1].numpy(), loss, H * W, eta, 0.2, 0.05)
+    w32 = want.astype(np.float32)
+    ulp = np.abs(got.numpy().view(np.int32).astype(np.int64) - w32.view(np.int32).astype(np.int64)).max()
+    floor = float((w32 == np.float32(0.05)).mean())
+    print(f"GAINSTEP {loss} B {B} {H}x{W} grid {grid}: {ulp} ulp, {floor:.2f} of the nodes at g_min")
+    lo, hi = (0.25, 0.75) if nodes.size >= 50 else (1.0 / nodes.size, 1.0 - 1.0 / nodes.size)    # (18 nodes: some at the floor, some not)
+    assert ulp <= 1 and lo <= floor <= hi and float(got.max()) == 1.0 and float(got.min()) == float(np.float32(0.05))
+    # the guards, each in its own case, leave the nodes' bits alone -- and only the guarded image's
+    for what, tt, ss in (("S nan", t, np.where(np.arange(H)[None] == 3, np.nan, s).astype(np.float32)),
+                         ("S inf", t, np.where(np.arange(H)[None] == 0, np.inf, s).astype(np.float32)),
+                         ("S zero", t, np.zeros_like(s)), ("max(u) inf", np.where(np.arange(H)[None, :, None] == 2, -np.inf, t).astype(np.float32), s),
+                         ("max(u) nan", np.where(np.arange(H)[None, :, None] == 2, np.nan, t).astype(np.float32), s)):
+        tt, ss = tt.copy(), ss.copy()
+        tt[1:], ss[1:] = t[1:], s[1:]                                             # only image 0 is guarded
+        out, _ = run_step(pkg, B, H, W, grid, nodes, tt, ss, loss, eta, 0.2, 0.05)
+        guarded = not (what == "S zero" and loss == "mse")
+        assert _bits_equal(out[0], torch.from_numpy(nodes[0])) == guarded, what
+        assert B == 1 or _bits_equal(out[1:], got[1:]), what
+
+
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[1], SHAPES[6]], ids=[IDS[0], IDS[1], IDS[6]])
+def test_one_call_is_the_single_launches_a_repeat_repeats_batches_are_independent_and_a_fixed_field_stays(pkg, shape):
+    from osmosis_diffusion_code_amd import ops
+    B, H, W, grid, off = shape
+    F, y, M0, nodes = kernel_problem(B, H, W, grid, 300 + SHAPES.index(shape), 4, True)
+
+    def prepare(sl=slice(None), single=False, learn=True, freeze=False, n_iter=3):
+        b = len(range(B)[sl])
+        d, tabs = desc_of(pkg, b, H, W, grid, P=4, eta=0.05, n_iter=n_iter, smooth=0.1, learn=learn)
+        n, Fd, yd, md = to_dev(nodes[sl]), to_dev(F[sl].reshape(b, 4, -1), off), to_dev(y[sl].reshape(b, 3, -1), off), to_dev(M0[sl].reshape(b, 3, -1), off)
+        t, s, cs = dev_buf((b, H, grid[1])), dev_buf((b, H)), dev_buf((b, grid[0] * grid[1] + 1), 0, NAN, torch.float64)
+        ye, me, fld = dev_buf((b, 3, H * W), off), dev_buf((b, 3, H * W), off), dev_buf((b, 1, H * W), off)
+        if not single:
+            ops.gain_prepare(d, tabs, Fd, yd, md, n, t, s, cs, ye, me, fld, freeze_phi=freeze)
+        else:
+            for _ in range(n_iter if learn and not freeze else 0):
+                ops.gain_rows(d, tabs, n, Fd, yd, md, t, s)
+                ops.gain_step(d, tabs, t, s, n, cs)
+            ops.gain_expand(d, tabs, n, yd, md, ye, me, fld)
+        return [v.cpu() for v in (n, ye, me, fld)]
+    one = prepare()
+    assert not _bits_equal(one[0], nodes) and bool(torch.isfinite(torch.cat([v.flatten() for v in one])).all())
+    for other, what in ((prepare(single=True), "single launches"), (prepare(), "a repeat")):
+        assert all(_bits_equal(a, b) for a, b in zip(one, other)), what
+    for b in range(B):
+        alone = prepare(slice(b, b + 1))
+        assert all(_bits_equal(a[b:b + 1], v) for a, v in zip(one, alone)), f"image {b} alone"
+    for kw in (dict(learn=False), dict(freeze=True)):
+        fixed = prepare(**kw)
+        assert _bits_equal(fixed[0], nodes) and _bits_equal(fixed[3].view(B, H, W), torch.from_numpy(GA.field32(nodes.numpy(), GA.tables(H, W, *grid))))
+
+
+def test_opcheck_and_the_operator_is_the_c_call(pkg):
+    from osmosis_diffusion_code_amd import ops
+    B, H, W, grid = 2, 12, 20, (3, 4)
+    F, y, M0, nodes = kernel_problem(B, H, W, grid, 5, 4, True)
+    mask = M0[:, 0:1].contiguous()
+
+    def args(m=mask, loss="norm", learn=True, freeze=False):
+        return (F.to(DEV), y.to(DEV), None if m is None else m.to(DEV), nodes.to(DEV).clone(), dev_buf((B, 3, H, W)), dev_buf((B, 3, H, W)),
+                dev_buf((B, 1, H, W)), dev_buf((B, H, 4)), dev_buf((B, H)), dev_buf((B, 13), 0, NAN, torch.float64), loss, 0.05, 2, 0.1, 0.05,
+                learn, freeze)
+    a = args()
+    assert torch.ops.osmosis.gain_prepare(*a) is None
+    d, tabs = desc_of(pkg, B, H, W, grid, P=4, eta=0.05, n_iter=2, smooth=0.1)
+    n = nodes.to(DEV).clone()
+    out = [dev_buf((B, 3, H * W)), dev_buf((B, 3, H * W)), dev_buf((B, 1, H * W))]
+    ops.gain_prepare(d, tabs, F.to(DEV).view(B, 4, -1), y.to(DEV).view(B, 3, -1), mask.expand(B, 3, H, W).reshape(B, 3, -1).contiguous().to(DEV),
+                     n, *ops.gain_workspace(d, DEV), *out)
+    assert _bits_equal(a[3], n) and all(_bits_equal(a[4 + i].view(B, -1), out[i].view(B, -1)) for i in range(3))
+    with pytest.raises(Exception, match="loss"):
+        torch.ops.osmosis.gain_prepare(*args(loss="l1"))
+    torch.library.opcheck(torch.ops.osmosis.gain_prepare.default, args())
+    torch.library.opcheck(torch.ops.osmosis.gain_prepare.default, args(m=None, loss="mse", freeze=True))
+
+
+# ------------------------------------------------------------------------------------------------------------ loss_grad_x0
+# (operator, loss, weight, base mask, auxiliary losses): the three operators x norm / mse x none / depth x mask x aux, cycled
+TERM = [("underwater_physical_revised", "norm", "depth", None, AUX), ("haze_physical", "mse", "none", "uniform", None),
+        ("underwater_physical", "norm", "none", "binary", AUX), ("underwater_physical_revised", "mse", "depth", "uniform", AUX),
+        ("haze_physical", "norm", "depth", None, None), ("underwater_physical", "mse", "depth", None, None)]
+TERM_G = [("underwater_physical_revised", "norm", "depth", "uniform", AUX), ("haze_physical", "norm", "none", None, None),
+          ("underwater_physical", "mse", "depth", "binary", AUX)]
+
+
+def vignetted(y, k=0.7):
+    """y [B,3,H,W] in [-1, 1] seen through the cos^4 vignette of the oracle."""
+    G = torch.from_numpy(GA.vignette(y.shape[-2], y.shape[-1], k)).to(y.dtype)
+    return (G * (y + 1) - 1).contiguous()
+
+
+def gain_of(lf, **kw):
+    return dict(GA.GAIN_DEFAULT, eta=0.05 if lf == "norm" else 5.0, n_iter=2, smooth=0.05, **kw)
+
+
+def dist(a, b, B):
+    """(loss relative, phi, gradient of its max, nodes) distances of two oracle-shaped results."""
+    return (float((np.abs(np.asarray(a[0], dtype=np.float64) - b[0]) / np.abs(b[0])).max()),
+            max(float((a[1][n].double() - b[1][n].double()).abs().max()) for n in b[1]),
+            max(float((a[2][i].double() - b[2][i]).abs().max()) / float(b[2][i].abs().max()) for i in range(B)),
+            float(np.abs(np.asarray(a[3], dtype=np.float64) - b[3]).max()))
+
+
+@pytest.mark.parametrize("case", TERM + TERM_G, ids=lambda c: "-".join(str(v if not isinstance(v, dict) else "aux") for v in c))
+def test_loss_grad_x0_with_a_learnt_field_vs_the_composed_oracle(pkg, case):
+    """5 inner iterations after 2 node steps.  Bars: the plain kernels' (loss 3e-5 relative, phi 3e-6, gradient 3e-5 of its max);
+    the nodes at most 5 x the oracle's own float64-versus-float32 distance on the case.  That distance is taken between the two
+    oracles' nodes BEFORE the last step's rounding to fp32 (after it, it would read 0 or whole ulps) plus the 2^-24 that storing a
+    node <= 1 in fp32 costs either of them.  The result is `torch.equal` to the masked route fed the same (y', M'), and a depth
+    prior changes neither phi nor the data loss."""
+    opname, lf, lw, mkind, aux = case
+    grouped = case in TERM_G
+    B, H, W, groups = (3, 74, 58, (2, 1)) if grouped else (2, 36, 34, None)
+    seed = 700 + 10 * (TERM + TERM_G).index(case)
+    x0, y = inputs(B, H, W, H, W, seed)
+    y = vignetted(y)
+    mask = None if mkind is None else make_masks(mkind, B, H, W, seed + 2)
+    gain = gain_of(lf)
+
+    def cond_with(field=True, m=mask):
+        c = gcond(pkg, opname, B, groups, "mean", "sgd", 5, aux, lf, lw)
+        if m is not None:
+            c.set_measurement_mask(m, batch=B, device=DEV)
+        if field:
+            c.set_gain_field(**gain)
+        return c
+    cond = cond_with()
+    g, sep = cond.loss_grad_x0(x0.to(DEV), y.to(DEV), freeze_phi=False)
+    vals = cond.gain_values()
+    got = (sep.cpu().numpy(), {n: v.cpu() for n, v in cond.operator.variables().items()}, g.cpu(), vals["nodes"].cpu().numpy())
+    okw = dict(OPS[opname], **etas(OPS[opname], 1e-3))
+    args = (groups or (1,) * B, opname, okw, x0.double(), y.double(), None if mask is None else mask.double(), 5, "sgd", aux, lf, lw, "mean",
+            gain, np.ones((B, 5, 5)))
+    want = GA.inner_loop(*args)
+    alt = GA.inner_loop(*args, fp32=True)
+    own = dist(alt, want, B)
+    e = dist(got, want, B)
+    bar_n = 5 * (float(np.abs(alt[5] - want[5]).max()) + 2.0 ** -24)
+    print(f"GAINTERM {case[:4]}: loss(rel) {e[0]:.2e} phi {e[1]:.2e} grad {e[2]:.2e} of its max, nodes {e[3]:.2e} (bar {bar_n:.2e}; the "
+          f"oracle's own f64-vs-f32 distance {own}); nodes in [{want[3].min():.3f}, {want[3].max():.3f}]")
+    assert e[0] <= 3e-5 and e[1] <= 3e-6 and e[2] <= 3e-5 and e[3] <= bar_n, (case, e, bar_n)
+    assert want[3].max() == 1.0 and want[3].min() < 0.98                           # the nodes have moved
+    assert float((vals["field"].cpu().double().view(B, 1, H, W) - want[4]).abs().max()) <= bar_n + 8 * 2.0 ** -24   # (+ G's 8 roundings)
+    # the masked route fed the same (y', M'): the same bits
+    st = cond._gain["state"]
+    ye, me = st["y_eff"].clone().view(B, 3, H, W), st["m_eff"].clone()
+    plain = cond_with(field=False, m=None)
+    g2, sep2 = plain.loss_grad_x0(x0.to(DEV), ye, freeze_phi=False, mask=me)
+    assert torch.equal(g2, g) and torch.equal(sep2, sep) and torch.equal(plain.operator.phi, cond.operator.phi)
+    # with a depth prior, phi and the data loss are what they are without it
+    withp = cond_with()
+    z = (1.0 + torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(seed + 5))).to(DEV)
+    withp.set_depth_prior(z, weight=0.5, batch=B, device=DEV)
+    g3, sep3 = withp.loss_grad_x0(x0.to(DEV), y.to(DEV), freeze_phi=False)
+    assert torch.equal(sep3, sep) and torch.equal(withp.operator.phi, cond.operator.phi) and torch.equal(g3[:, 0:3], g[:, 0:3])
+    assert not torch.equal(g3[:, 3], g[:, 3]) and torch.equal(withp.gain_values()["nodes"], vals["nodes"])
+
+
+def test_py_loop_freeze_chunk_rows_and_refusals(pkg, monkeypatch):
+    B, H, W = 3, 36, 34
+    x0, y = inputs(B, H, W, H, W, 801)
+    y = vignetted(y)
+    mask = make_masks("uniform", B, H, W, 802)
+
+    def run(env=None, freeze=False, chunks=((0, 3),), learn=True):
+        if env:
+            monkeypatch.setenv("OSM_PHYS_PY_LOOP", env)
+        cond = gcond(pkg, "underwater_physical_revised", B, None, "mean", "sgd", 5, AUX, "norm", "depth")
+        m = cond.set_measurement_mask(mask, batch=B, device=DEV)
+        cond.set_gain_field(**gain_of("norm", learn=learn))
+        g, loss = torch.empty(B, 4, H, W, device=DEV), torch.empty(B, device=DEV)
+        xd, yd = x0.to(DEV), y.to(DEV)
+        for a, b in chunks:
+            cond.loss_grad_x0(xd[a:b], yd[a:b], freeze_phi=freeze, g_out=g[a:b], phi=cond.operator.phi[a:b], loss_out=loss[a:b], mask=m[a:b])
+        monkeypatch.delenv("OSM_PHYS_PY_LOOP", raising=False)
+        v = cond.gain_values()
+        return g.cpu(), loss.cpu(), cond.operator.phi.cpu().clone(), v["nodes"].cpu().clone(), v["field"].cpu().clone(), cond
+    one = run()
+    for other, what in ((run(env="1"), "OSM_PHYS_PY_LOOP=1"), (run(chunks=((0, 2), (2, 3))), "chunks [2, 1]"), (run(chunks=((2, 3), (0, 1), (1, 2))), "rows")):
+        assert all(torch.equal(a, b) for a, b in zip(one[:5], other[:5])), what
+    assert len({tuple(n.flatten().tolist()) for n in one[3]}) == 3               # every image its own field
+    for kw in (dict(freeze=True), dict(learn=False)):
+        fixed = run(**kw)
+        assert torch.equal(fixed[3], torch.ones(B, 5, 5)) and torch.equal(fixed[4], torch.ones(B, 1, H * W))
+    cond = one[5]
+    with pytest.raises(ValueError, match="row block"):
+        cond.loss_grad_x0(x0[:2].to(DEV), y[:2].to(DEV), phi=cond.operator.phi[:2].clone(), mask=cond.measurement_mask(B, H * W, DEV)[:2])
+
+
+def test_torch_route_agrees_with_the_kernels(pkg):
+    """`_loss_autograd` (what `_generic_loop` and foreign operators use) with the field: the same node steps in torch -- loss and
+    nodes against `loss_grad_x0` on the same inputs (loss 3e-5 relative, the masked kernels' bar; nodes 1e-5)."""
+    B, H, W = 2, 36, 34
+    x0, y = inputs(B, H, W, H, W, 811)
+    y = vignetted(y)
+    conds = []
+    for _ in range(2):
+        cond = gcond(pkg, "underwater_physical_revised", B, None, "mean", "sgd", 5, None, "norm", "depth")
+        cond.set_measurement_mask(make_masks("uniform", B, H, W, 813), batch=B, device=DEV)
+        cond.set_gain_field(**gain_of("norm"))
+        conds.append(cond)
+    sep, _, _ = conds[0]._loss_autograd(x0.to(DEV), y.to(DEV))
+    conds[1].n_iter = 1
+    _, loss = conds[1].loss_grad_x0(x0.to(DEV), y.to(DEV), freeze_phi=False)
+    assert np.allclose(sep, loss.cpu().numpy(), rtol=3e-5)
+    a, b = conds[0].gain_values(), conds[1].gain_values()
+    assert float((a["nodes"] - b["nodes"]).abs().max()) <= 1e-5 and float((a["field"] - b["field"]).abs().max()) <= 1e-5
+    assert float(b["nodes"].min()) < 0.98
+
+
+# ============================================================================================================ chain level
+CH, CW = 16, 24
+GAIN_CHAIN = dict(GA.GAIN_DEFAULT, eta=0.05, smooth=0.05)
+# (operator, base mask, solver rule, groups, tiled, seed)
+CHAINS = {"revised": ("underwater_physical_revised", False, None, None, False, 901),
+          "haze+mask": ("haze_physical", True, None, None, False, 902),
+          "revised+dpmpp_2m": ("underwater_physical_revised", False, "dpmpp_2m", None, False, 903),
+          "shared_water[2,1]": ("underwater_physical_revised", False, None, (2, 1), False, 904),
+          "tiled24x36": ("underwater_physical_revised", False, None, None, True, 905)}
+
+
+def chain_inputs(B, seed, hw=(CH, CW)):
+    H, W = hw
+    g = torch.Generator().manual_seed(seed)
+    x_T = 0.5 * torch.randn(B, 4, H, W, generator=g)
+    y = vignetted(torch.rand(B, 3, H, W, generator=g) * 1.6 - 0.8)
+    noise = torch.randn(T, B, 4, H, W, generator=g)
+    mask = torch.rand(B, 3, H, W, generator=g) * (torch.rand(B, 1, H, W, generator=g) > 0.3).float()
+    return x_T, y, noise, mask
+
+
+def oracle_chain(case, bump=None):
+    """The oracle's loop with the term, group by group (an independent image is a group of one): (merged last record, nodes, inputs)."""
+    import solver_oracle as SO
+    from osmosis_diffusion_code_amd.guided_diffusion import gaussian_diffusion as gd
+    from test_tiled_gpu import CANVAS, TILING, tiled_oracle_model
+    opname, masked, rule, groups, tiled, seed = CHAINS[case]
+    cfg, sd, tb = _ref_setup()
+    B = 1 if groups is None else sum(groups)
+    x_T, y, noise, mask = chain_inputs(B, seed, CANVAS if tiled else (CH, CW))
+    mask = mask if masked else None
+    x_in = x_T if bump is None else x_T + bump
+    okw = {k: v for k, v in OPERATORS[opname].items() if k.startswith("phi") and not k.endswith("flag")}
+    net = lambda x, t: U.unet_forward(sd, cfg, x, t)  # noqa: E731
+    if tiled:
+        origins, wy, wx, inv = gd.tile_grid(*CANVAS, TILING["tile"], TILING["stride"], "hann")
+        net = tiled_oracle_model(sd, cfg, origins, wy, wx, inv, *TILING["tile"])
+    recs, nodes, lo = [], [], 0
+    for n in (groups or (1,)):
+        sl = slice(lo, lo + n)
+        rg = GA.make_guidance(opname, dict(okw, depth_type="gamma", value="1.4,1.4,1"), None if mask is None else mask[sl], 20, AUX,
+                              COND["loss_function"], COND["loss_weight"], GAIN_CHAIN, np.ones((n, 5, 5)), scale=COND["scale"],
+                              gradient_clip=COND["gradient_clip"])
+        trace = []
+        if rule is None:
+            D.p_sample_loop(net, tb, x_in[sl], y[sl], rg, PATTERN, [noise[k][sl] for k in range(T)], trace)
+        else:
+            SO.osmosis_loop(net, tb, x_in[sl], y[sl], rg, PATTERN, [noise[k][sl] for k in range(T)], rule, 0.0, first=T - 1, trace=trace)
+        recs.append(trace[-1])
+        nodes.append(rg.nodes)
+        lo += n
+    last = {"x_out": torch.cat([r["x_out"] for r in recs]), "x0": torch.cat([r["x0"] for r in recs]),
+            "loss": np.concatenate([np.asarray(r["loss"]).reshape(-1) for r in recs]),
+            "phi": {name: torch.cat([r["phi"][name] for r in recs]) for name in recs[0]["phi"]}}
+    return last, np.concatenate(nodes), (x_T, y, noise, mask)
+
+
+def fused_chain(pkg, monkeypatch, model, opname, x_T, y, noise, mask, gain, rule=None, groups=None, tiling=None, sizes=None, fused=True,
+                pass_gain=True):
+    _, gd, _, _ = pkg
+    B = x_T.shape[0]
+    sampler = make_sampler(gd) if rule is None else make_sampler(gd, solver=rule, solver_eta=0.0)
+    if sizes is not None:
+        monkeypatch.setattr(gd.GaussianDiffusion, "chunk_sizes", staticmethod(lambda B_, cap: list(sizes)))
+    cond = chain_cond(pkg, opname, B, groups)
+    nd = noise.to(DEV)
+    kw = dict(model=model, x_start=x_T.to(DEV), measurement=y.to(DEV), measurement_cond_fn=cond.conditioning, record=False, save_root=None,
+              pretrain_model="osmosis", rgb_guidance=False, sample_pattern=PATTERN, measurement_mask=mask)
+    if pass_gain:
+        kw["gain_field"] = gain
+    if tiling is not None:
+        kw["tiling"] = tiling
+    trace = []
+    if fused:
+        _no_generic(monkeypatch, sampler)
+        out = sampler.p_sample_loop(noise_fn=lambda k, shape: nd[k], trace=trace, **kw)
+    else:
+        cond.hip_ok = lambda: False             # the conditioner declines the fused loop; its step (the kernels) stays
+        assert sampler._fast_path_ok(model, cond.conditioning, "osmosis", False, PATTERN, tuple(x_T.shape)) is None
+        _replay_randn_like(monkeypatch, nd, 4)
+        out = sampler.p_sample_loop(**kw)
+    monkeypatch.undo()
+    return out, cond, trace
+
+
+@pytest.mark.parametrize("case", list(CHAINS))
+def test_fused_chain_with_the_field_vs_the_oracles_loop(pkg, monkeypatch, model48, case):
+    """Free-running against the oracle's p_sample_loop with the term: final image, pred_xstart and the nodes within 10 x the oracle's
+    own drift under a 1e-6 perturbation of x_T (`_free_running_bar`, floor 2e-5), loss 20 x that, phi 2e-6 -- the chain protocol of
+    the other suites.  The drift staying below 1e-3 is asserted: no case is skipped to teacher forcing."""
+    from test_tiled_gpu import TILING
+    opname, masked, rule, groups, tiled, seed = CHAINS[case]
+    ref, ref_nodes, (x_T, y, noise, mask) = oracle_chain(case)
+    bump = 1e-6 * torch.randn(x_T.shape, generator=torch.Generator().manual_seed(99))
+    pert, pert_nodes, _ = oracle_chain(case, bump)
+    drift = max(float((pert["x_out"] - ref["x_out"]).abs().max()), float(np.abs(pert_nodes - ref_nodes).max()))
+    bar = _free_running_bar(drift)
+    assert bar is not None, (case, drift)
+    out, cond, trace = fused_chain(pkg, monkeypatch, model48, opname, x_T, y, noise, mask, GAIN_CHAIN, rule, groups,
+                                   dict(TILING, window="hann") if tiled else None)
+    B = x_T.shape[0]
+    a = trace[-1]
+    e_img, e_x0 = float((a["x_out"].cpu() - ref["x_out"]).abs().max()), float((a["x0"].cpu() - ref["x0"]).abs().max())
+    want = np.asarray(ref["loss"], dtype=np.float64).reshape(-1)
+    e_loss = float((np.abs(a["loss"].cpu().numpy().reshape(-1) - want) / want).max())
+    e_phi = max(float((a["phi"][:, off:off + n].cpu() - ref["phi"][name].reshape(B, -1)[:, :n]).abs().max())
+                for name, (off, n) in cond.operator._slots().items())
+    v = cond.gain_values()
+    e_n = float(np.abs(v["nodes"].cpu().numpy().astype(np.float64) - ref_nodes).max())
+    print(f"GAINCHAIN {case}: oracle drift_1e-6 {drift:.2e}, bar {bar:.2e}: final image {e_img:.2e} x0 {e_x0:.2e} loss(rel) {e_loss:.2e} "
+          f"phi {e_phi:.2e} nodes {e_n:.2e}; nodes in [{ref_nodes.min():.3f}, {ref_nodes.max():.3f}]")
+    assert e_img < bar and e_x0 < bar and e_n < bar and e_loss < 20.0 * bar and e_phi < 2e-6, (case, e_img, e_x0, e_n, e_loss, e_phi, bar)
+    assert float(v["nodes"].max()) == 1.0 and float(ref_nodes.min()) < 0.99 and tuple(v["field"].shape) == (B, 1, y.shape[2] * y.shape[3])
+
+
+def test_chunks_one_tile_and_gain_none_bit_for_bit(pkg, monkeypatch, model48):
+    """B = 3 walked as [2, 1] is the one pass, `gain_values()` included row by row; one tile covering the canvas is the untiled chain;
+    `gain_field=None` is a call without the keyword."""
+    op = "underwater_physical_revised"
+    x_T, y, noise, mask = chain_inputs(3, 911)
+    for m in (None, mask):
+        whole, cw, _ = fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, m, GAIN_CHAIN, sizes=[3])
+        chunked, cc, _ = fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, m, GAIN_CHAIN, sizes=[2, 1])
+        _same_bits(chunked, whole, f"gain field: one pass vs chunks of [2, 1] (mask {m is not None})")
+        vw, vc = cw.gain_values(), cc.gain_values()
+        for k in ("nodes", "field"):
+            assert vc[k].shape[0] == 3 and torch.equal(vc[k], vw[k]), k
+        assert len({tuple(n.flatten().tolist()) for n in vc["nodes"].cpu()}) == 3 and float(vc["nodes"].min()) < 1.0
+    free, c0, _ = fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, None, None, sizes=[3])
+    assert not torch.equal(free[0], whole[0]) and c0.gain_values() is None                        # the term matters
+    _same_bits(fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, None, None, sizes=[3], pass_gain=False)[0], free,
+               "gain_field=None vs no keyword")
+    x1, y1, n1, _ = chain_inputs(1, 912)
+    one, c1, _ = fused_chain(pkg, monkeypatch, model48, op, x1, y1, n1, None, GAIN_CHAIN)
+    tiled, ct, _ = fused_chain(pkg, monkeypatch, model48, op, x1, y1, n1, None, GAIN_CHAIN, tiling=dict(tile=(CH, CW), stride=(CH, CW), window="uniform"))
+    _same_bits(tiled, one, "gain field: one 16 x 24 tile vs the untiled fused chain")
+    assert torch.equal(ct.gain_values()["nodes"], c1.gain_values()["nodes"])
+
+
+def test_fused_chain_with_the_field_equals_the_generic_loop(pkg, monkeypatch, model48):
+    """Osmosis, B = 2 with a mask: both loops at tests/test_mask_gpu.py's fused-versus-generic bars (image and pred_xstart 1e-4, loss
+    rtol 1e-5, phi 1e-6); the generic loop takes the kernels' step through `conditioning`."""
+    op = "underwater_physical_revised"
+    x_T, y, noise, mask = chain_inputs(2, 921)
+    f, cf, _ = fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, mask, GAIN_CHAIN)
+    g, cg, _ = fused_chain(pkg, monkeypatch, model48, op, x_T, y, noise, mask, GAIN_CHAIN, fused=False)
+    e_img, e_x0 = float((f[0].cpu() - g[0].detach().cpu()).abs().max()), float((f[3] - g[3]).abs().max())
+    e_phi = max(float((f[1][k].cpu() - g[1][k].detach().cpu()).abs().max()) for k in f[1])
+    e_n = float((cf.gain_values()["nodes"] - cg.gain_values()["nodes"]).abs().max())
+    print(f"GAINGENERIC: fused vs generic img {e_img:.2e} x0 {e_x0:.2e} phi {e_phi:.2e} nodes {e_n:.2e} loss {f[2]} / {g[2]}")
+    assert e_img < 1e-4 and e_x0 < 1e-4 and e_phi < 1e-6 and e_n < 1e-4 and np.allclose(f[2], g[2], rtol=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------------------ the driver
+def test_restore_image_with_the_field(pkg, monkeypatch, model48, tmp_path):
+    """`restore_image` on the 3-index low-noise sub-chain: the result keys, max(gain_nodes) = 1, gain_field >= g_min, `_gain.png`
+    written; the argument wins over the config; a fixed flat field from a file stays; without the key no result key and no file;
+    chunked batches give every image its own."""
+    from osmosis_diffusion_code_amd import sampling
+    _, gd, _, _ = pkg
+    monkeypatch.setattr(gd.GaussianDiffusion, "_generic_loop", lambda *a, **k: 1 / 0)
+    photo = vignetted(torch.rand(1, 3, 256, 256, generator=torch.Generator().manual_seed(701)) * 1.2 - 0.6).to(DEV)
+    sub = dict(index_range=(2, 0), x_scale=0.05, noise_seed=7)
+
+    def cfg(gain=None):
+        c = driver_cfg()
+        if gain is not None:
+            c["measurement"]["gain"] = gain
+        return c
+    setting = dict(grid=[5, 5], eta=0.05)
+    res = sampling.restore_image(model48, photo, cfg(setting), **sub)[-1]
+    G, n, ff = res["gain_field"], res["gain_nodes"], res["flat_fielded"]
+    assert tuple(G.shape) == (256, 256) and tuple(n.shape) == (5, 5) and tuple(ff.shape) == (3, 256, 256)
+    assert float(n.max()) == 1.0 and float(n.min()) < 1.0 and float(G.min()) >= 0.05 and float(G.max()) <= 1.0
+    assert float(ff.min()) >= 0.0 and float(ff.max()) <= 1.0
+    assert torch.equal(ff, ((res["measurement"][0] + 1) / (2 * G)).clamp(0, 1))
+    paths = sampling.save_outputs(res, photo, str(tmp_path), "photo")
+    assert paths["gain"].endswith("photo_gain.png") and os.path.getsize(paths["gain"]) > 0
+    by_arg = sampling.restore_image(model48, photo, cfg(dict(grid=[3, 3])), gain=dict(setting), **sub)[-1]
+    assert torch.equal(by_arg["sample"], res["sample"]) and torch.equal(by_arg["gain_nodes"], n)
+    free = sampling.restore_image(model48, photo, cfg(), **sub)[-1]
+    assert not any(k in free for k in ("gain_field", "gain_nodes", "flat_fielded")) and not torch.equal(free["sample"], res["sample"])
+    assert "gain" not in sampling.save_outputs(free, photo, str(tmp_path / "free"), "photo")
+    with pytest.raises(ValueError, match="unknown key"):
+        sampling.restore_image(model48, photo, cfg(dict(grid=[5, 5], rate=4.0)), **sub)
+    np.save(tmp_path / "flat.npy", GA.vignette(256, 256))
+    fixed = sampling.restore_image(model48, photo, cfg(dict(grid=[5, 5], learn=False, path=str(tmp_path / "flat.npy"))), **sub)[-1]
+    want = torch.from_numpy(sampling.gain_nodes_from_flat_field(GA.vignette(256, 256), (5, 5))).float()
+    assert torch.equal(fixed["gain_nodes"], want) and float((fixed["gain_field"] - torch.from_numpy(GA.vignette(256, 256))).abs().max()) < 0.1
+    photos = [photo.cpu(), photo.cpu().flip(-1).contiguous() * 0.5]
+    monkeypatch.setattr(gd.GaussianDiffusion, "chunk_sizes", staticmethod(lambda B_, cap: [1] * B_))
+    two = sampling.restore_images(model48, photos, cfg(), device=DEV, batch_size=2, gain=dict(setting), **sub)
+    assert all(tuple(two[i]["gain_field"].shape) == (256, 256) and float(two[i]["gain_nodes"].max()) == 1.0 for i in (0, 1))
+    assert not torch.equal(two[0]["gain_nodes"], two[1]["gain_nodes"])
+    assert float((two[0]["gain_nodes"] - n).abs().max()) <= 1e-4
