@@ -103,7 +103,10 @@ __global__ __launch_bounds__(512, 2) void conv3_wino8_kernel(const act_t* __rest
   const int nslab = p.ksteps;
   const int per = (nslab + p.splitk - 1) / p.splitk;
   const int kc0 = ks * per;
-  const int kc1 = min(nslab, kc0 + per);
+  // The weight image pads K to a multiple of 32 with zero rows.  The pipelined loop (K % 16 == 0) has no channel-tail mask, so a
+  // padding slab would multiply those zeros with the 16 columns BEHIND the Cin window (0 x NaN = NaN): it stops at the last live slab
+  const int nlive = (HP && W8_PIPE && !GNF && PIPE) ? min(nslab, (p.K + 15) >> 4) : nslab;
+  const int kc1 = min(nlive, kc0 + per);
 
   // ---- raw staging coordinates: piece s = tid + 512 j -> channel quad tid & 3, halo pixel (tid >> 2) + 128 j
   const int q4 = tid & 3;

@@ -706,6 +706,8 @@ int launch(IGemmParams& p, int taps, bool b_kn, hipStream_t st, int wfmt = 0, bo
   int rc = osm::check_launch("igemm kernel");
   if (rc) return rc;
   if (p.splitk > 1 && p.colsum) {
+    if (p.stat_mode == 2 && !(p.ld_sx % 4 == 0 && osm::aligned_act4(p.stat_x) && osm::aligned16(p.stat_table)))
+      return osm::fail(OSM_ERR_UNSUPPORTED, "column sums with split-K read stat_x / stat_table as 4-element vectors");
     if (!(p.N % 4 == 0 && p.ldc % 4 == 0 && (!p.res || p.ldr % 4 == 0) && osm::aligned_act4(p.C) && osm::aligned16(p.ws) &&
           (!p.res || osm::aligned_act4(p.res)) && p.M % 8 == 0 && (p.H * p.W) % 8 == 0 && p.nbatch == 1))
       return osm::fail(OSM_ERR_UNSUPPORTED, "column sums with split-K need N %% 4 == 0, 8-row aligned images, aligned rows");
