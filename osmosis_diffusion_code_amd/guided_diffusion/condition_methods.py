@@ -18,6 +18,7 @@ Two ways in:
 """
 from abc import ABC, abstractmethod
 from functools import partial
+from operator import index
 
 import os
 import numpy as np
@@ -258,10 +259,62 @@ class ConditioningMethod(ABC):
     _robust = None          # the robust data term's setting and per-batch state (`set_robust`); class default: plain least squares
     _robust_hold = None     # the autograd route's M_eff while it walks the inner iterations of ONE sub-step
     _robust_holding = False
+    _batch = None           # the open batch (`open_batch`): (B0, the image's grid, the measurement's grid, the device)
 
     def __init__(self, operator, noiser, **kwargs):
         self.operator = operator
         self.noiser = noiser
+
+    # ---------------------------------------------------------------- the batch, and the rows of it that a call is
+    def open_batch(self, B, image_grid, measurement_grid, device):
+        """What a loop calls once per chain, before its first data-term call: fixes the batch size B0 = B that `rows=` ranges count
+        in, puts the mask rows [B0,3,hw] on `device` and creates the per-batch state of the robust term, the depth prior and the
+        gain field at its initial values, so that `*_values()` read NaN / 0 / a flat field until the first guided sub-step.  State
+        that fits these shapes is kept; the routings that are not built are refused here.  A `set_*` call closes the batch."""
+        self._robust_refuse()
+        self._gain_refuse()
+        (H, W), (h, w) = (int(v) for v in image_grid), (int(v) for v in measurement_grid)
+        self.measurement_mask(B, h * w, device)
+        if self._robust is not None:
+            self._robust_state(B, h * w, device)
+        if self._depth is not None:
+            self.depth_prior_rows(B, H, W, device)
+        if self._gain is not None:
+            self.gain_open(B, H, W, device)
+        self._batch = (int(B), (H, W), (h, w), torch.device(device))
+
+    def _batch_rows(self, rows, x0, y):
+        """(r0, r1): which images of the open batch a call on x0 [B,C,H,W], y [B,3,h,w] is.  Every per-batch store is sliced [r0:r1],
+        and the kernels write the optimizer, fit, sigma and node rows of every image they are handed: this is the ONE check between
+        a wrong chunk and an out-of-bounds device write, made before anything is allocated or launched.  rows=None: the whole
+        batch -- one is opened at the call's own shapes (state that fits is kept)."""
+        if x0.dim() != 4 or y.dim() != 4:
+            raise ValueError(f"expected x0 [B,C,H,W] and measurement [B,3,h,w], got {tuple(x0.shape)} and {tuple(y.shape)}")
+        B, grids = x0.shape[0], (tuple(x0.shape[2:]), tuple(y.shape[2:]))
+        if rows is None:
+            self.open_batch(B, *grids, x0.device)
+            return 0, B
+        bt = self._batch
+        if bt is None or bt[1:3] != grids or bt[3].type != x0.device.type or bt[3].index not in (None, x0.device.index):
+            raise ValueError(f"rows={rows!r}: no batch with this call's grids {grids} on {x0.device} is open (`open_batch`)")
+        try:
+            r0, r1 = (index(r) for r in rows)
+            ok = 0 <= r0 < r1 <= bt[0] and r1 - r0 == B
+        except (TypeError, ValueError):         # no pair, or not of integers
+            ok = False
+        if not ok:
+            raise ValueError(f"rows must be ints (r0, r1) with 0 <= r0 < r1 <= {bt[0]} (the open batch) and r1 - r0 = {B} (this call's "
+                             f"images), got {rows!r}")
+        return r0, r1
+
+    def _mask_rows(self, mask, r0, r1, hw):
+        """The mask rows [r1-r0,3,hw] of a call: the caller's own (`mask=`) in the stored mask's place, else rows [r0:r1] of the stored
+        mask; None without either."""
+        if mask is None:
+            return None if self._mask is None else self._mask[r0:r1]
+        if mask.numel() != (r1 - r0) * 3 * hw or not mask.is_contiguous():
+            raise ValueError(f"expected mask rows [{r1 - r0},3,{hw}], got {tuple(mask.shape)}")
+        return mask
 
     # ---------------------------------------------------------------- robust data term (include/osmosis_robust.h)
     def set_robust(self, loss="tukey", c=None, scale="mad", sigma_min=2.0 / 255.0, per_pixel=False):
@@ -273,6 +326,7 @@ class ConditioningMethod(ABC):
         loss is the weighted one).  c: the tuning constant (None: 1.345 / 4.685 / 2.385, 95 % efficiency at the normal); scale: 'mad'
         or a fixed sigma > 0; per_pixel: one weight per pixel from its worst valid channel.  `set_robust(None)` clears the setting;
         with none set nothing changes.  Three small kernels (csrc/robust.hip), outside the phi loop, no host sync."""
+        self._batch = None      # (the per-batch state changes: `open_batch` again)
         if loss is None:
             self._robust = None
             return None
@@ -280,7 +334,7 @@ class ConditioningMethod(ABC):
             raise ValueError(f"robust: loss must be one of {ROBUST_LOSSES}, got {loss!r}")
         d = ops.robust_desc(loss, c, scale, sigma_min, per_pixel, 1, 1)       # (the host-side range checks; nothing launches)
         self._robust = {"loss": loss, "c": float(d.c), "scale": "mad" if d.scale_mode == 0 else float(d.scale),
-                        "sigma_min": float(d.sigma_min), "per_pixel": bool(per_pixel), "state": None, "ones": None}
+                        "sigma_min": float(d.sigma_min), "per_pixel": bool(per_pixel), "state": None}
         self._robust_refuse()
         self._gain_refuse()
         return self._robust
@@ -312,33 +366,11 @@ class ConditioningMethod(ABC):
         rb = self._robust
         return dict(loss=rb["loss"], c=rb["c"], scale=rb["scale"], sigma_min=rb["sigma_min"], per_pixel=rb["per_pixel"])
 
-    def robust_base_mask(self, B, hw, device):
-        """The [B,3,hw] base-mask rows M0 the robust term weighs: the stored mask, or without one a mask of ones kept beside the
-        setting (so that a chunked walk can hand row blocks of it over); None with robust unset and no mask."""
-        m = self.measurement_mask(B, hw, device)
-        rb = self._robust
-        if m is not None or rb is None:
-            return m
-        ones = rb["ones"]
-        if ones is None or tuple(ones.shape) != (B, 3, hw) or ones.device != torch.device(device):
-            ones = rb["ones"] = torch.ones(B, 3, hw, device=device, dtype=torch.float32)
-        return ones
-
-    def robust_open(self, B, hw, device):
-        """What a loop calls once per chain: the base-mask rows it hands on in chunks (`robust_base_mask`), with the per-batch state
-        allocated, so that `robust_values` reads NaN / 0 until the first guided sub-step."""
-        m = self.robust_base_mask(B, hw, device)
-        if self._robust is not None:
-            self._robust_refuse()
-            self._robust_state(m, device)
-        return m
-
-    def _robust_state(self, base, device):
-        """The per-BATCH state beside the base mask `base` [B0,3,hw]: e, M_eff, omega [B0,3,hw], sigma [B0] (NaN) and
-        n_valid [B0] int32 (0) until a guided sub-step writes them.  A call on a chunk writes the chunk's rows."""
+    def _robust_state(self, B0, hw, device):
+        """The per-BATCH state: e, M_eff, omega [B0,3,hw], sigma [B0] (NaN) and n_valid [B0] int32 (0) until a guided sub-step writes
+        them.  A call on a chunk writes the chunk's rows."""
         rb = self._robust
         st = rb["state"]
-        B0, hw = base.shape[0], base.shape[2]
         if st is None or st["key"] != (B0, hw, str(device)):
             f32 = dict(device=device, dtype=torch.float32)
             st = rb["state"] = {"key": (B0, hw, str(device)), "e": torch.zeros(B0, 3, hw, **f32), "meff": torch.zeros(B0, 3, hw, **f32),
@@ -347,36 +379,16 @@ class ConditioningMethod(ABC):
                                 "n": torch.zeros(B0, device=device, dtype=torch.int32), "desc": {}}
         return st
 
-    def _robust_rows(self, mask, B, hw, device):
-        """(M0 rows [B,3,hw], the state, the first row r0 of the state these rows are) for a call on B images: `mask` rows handed in
-        by a chunked walk must be a row block of the conditioner's own base mask (`robust_base_mask`), or cover the whole batch."""
-        if mask is None:
-            mask = self.robust_base_mask(B, hw, device)
-        elif mask.numel() != B * 3 * hw or not mask.is_contiguous():
-            raise ValueError(f"expected mask rows [{B},3,{hw}], got {tuple(mask.shape)}")
-        base = self._mask if self._mask is not None else self._robust["ones"]
-        if base is not None and base.device == mask.device and base.shape[2] == hw:
-            r0, rem = divmod(mask.data_ptr() - base.data_ptr(), 3 * hw * 4)
-            if rem == 0 and 0 <= r0 and r0 + B <= base.shape[0]:
-                return mask, self._robust_state(base, device), r0
+    def _robust_mask_rows(self, pred, pa, pb, y, M0, r0, r1):
+        """The sub-step's M_eff rows [B,3,hw] from the prediction `pred` [B,P>=3,hw] (its first three planes) and the base-mask rows
+        M0 (None: ones, which the entry points take as a null pointer): the three launches of include/osmosis_robust.h from one call,
+        or singly with OSM_PHYS_PY_LOOP=1."""
         st = self._robust["state"]
-        if st is not None and st["key"] == (B, hw, str(device)):
-            return mask, st, 0                     # rows of a foreign mask over the whole batch
-        if base is None or base.shape[0] == B:
-            return mask, self._robust_state(mask, device), 0
-        # the kernels write sigma + b and the weight rows of every image they are handed
-        raise ValueError("robust: mask rows must be a row block of the conditioner's own mask (`robust_base_mask(...)[a:b]`) or cover "
-                         f"the whole batch, got {B} rows against its {base.shape[0]}")
-
-    def _robust_mask_rows(self, pred, pa, pb, y, mask, B, hw):
-        """The sub-step's M_eff rows [B,3,hw] from the prediction `pred` [B,P>=3,hw] (its first three planes): the three launches of
-        include/osmosis_robust.h from one call, or singly with OSM_PHYS_PY_LOOP=1."""
-        M0, st, r0 = self._robust_rows(mask, B, hw, y.device)
+        B, hw = r1 - r0, st["key"][1]
         d = st["desc"].get(B)
         if d is None:
             d = st["desc"][B] = ops.robust_desc(B=B, hw=hw, **self._robust_kw())
-        e, meff, omega = st["e"][r0:r0 + B], st["meff"][r0:r0 + B], st["omega"][r0:r0 + B]
-        sigma, n = st["sigma"][r0:r0 + B], st["n"][r0:r0 + B]
+        e, meff, omega, sigma, n = (st[k][r0:r1] for k in ("e", "meff", "omega", "sigma", "n"))
         if d.scale_mode == 1:           # a fixed scale: the kernels write neither; the reported sigma is the scale, nothing is counted
             sigma.fill_(float(d.scale))
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
@@ -389,16 +401,16 @@ class ConditioningMethod(ABC):
         return meff
 
     def _robust_torch(self, e, measurement):
-        """M_eff shaped like the measurement [B,3,H,W] on the torch routes (the same contract by torch.sort), kept for
-        `robust_values`."""
+        """M_eff shaped like the measurement [B,3,H,W] on the torch routes (the same contract by torch.sort) over the whole batch,
+        kept for `robust_values`."""
         B, _, H, W = measurement.shape
-        M0, st, r0 = self._robust_rows(None, B, H * W, measurement.device)
-        meff, omega, sigma, n = robust_weights_torch(e.to(torch.float32), M0.view(B, 3, H, W), **self._robust_kw())
+        st = self._robust_state(B, H * W, measurement.device)
+        meff, omega, sigma, n = robust_weights_torch(e.to(torch.float32), self._mask_like(measurement), **self._robust_kw())
         with torch.no_grad():
-            st["meff"][r0:r0 + B].copy_(meff.reshape(B, 3, H * W))
-            st["omega"][r0:r0 + B].copy_(omega.reshape(B, 3, H * W))
-            st["sigma"][r0:r0 + B].copy_(sigma)
-            st["n"][r0:r0 + B].copy_(n if isinstance(self._robust["scale"], str) else torch.zeros_like(n))
+            st["meff"].copy_(meff.reshape(B, 3, H * W))
+            st["omega"].copy_(omega.reshape(B, 3, H * W))
+            st["sigma"].copy_(sigma)
+            st["n"].copy_(n if isinstance(self._robust["scale"], str) else torch.zeros_like(n))
         return meff.to(e.dtype)
 
     def robust_values(self):
@@ -422,6 +434,7 @@ class ConditioningMethod(ABC):
         their normalisation: mse still divides by 3 HW, so a mask of ones IS the unmasked loss; the auxiliary losses act on the
         prediction and are not masked.  An image that is masked out entirely has loss 0, no data-term gradient and (norm) no phi
         step."""
+        self._batch = None      # (the per-batch state changes: `open_batch` again)
         if mask is None:
             self._mask = self._mask_hw = None
             return None
@@ -538,6 +551,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         max = 1 per image), default a flat field; `learn=False` keeps them: the way in for a measured flat field.
         `set_gain_field(None)` clears the setting; with none set nothing changes.  Three small kernels (csrc/gainfield.hip) before
         the phi loop, no host sync.  The per-batch state starts afresh with every call."""
+        self._batch = None      # (the per-batch state changes: `open_batch` again)
         if grid is None:
             self._gain = None
             return None
@@ -557,7 +571,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         return self._gain
 
     def gain_open(self, B, H, W, device):
-        """What a loop calls once per chain: the per-BATCH state (nodes [B,gh,gw], field [B,1,HW], the rows y' and M' [B,3,HW]) at
+        """What `open_batch` creates: the per-BATCH state (nodes [B,gh,gw], field [B,1,HW], the rows y' and M' [B,3,HW]) at
         its initial values, so that `gain_values` reads them until the first guided sub-step.  A call on a chunk writes its rows."""
         gn = self._gain
         self._gain_refuse()
@@ -578,25 +592,12 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                             "y_eff": torch.zeros(B, 3, H * W, **f32), "m_eff": torch.zeros(B, 3, H * W, **f32), "ws": {}}
         return st
 
-    def _gain_rows(self, phi, B, H, W, device):
-        """(the state, the first row r0 of it) for a call on B images: the phi rows in hand say which images they are -- a row block
-        of the operator's own [B0][9] block, as a chunked walk hands them over."""
-        full = self.operator.phi
-        r0, rem = divmod(phi.data_ptr() - full.data_ptr(), 9 * 4)
-        if phi.device != full.device or rem != 0 or r0 < 0 or r0 + B > full.shape[0]:
-            # the kernels write the node, field and (y', M') rows of every image they are handed
-            raise ValueError("gain_field: `phi` must be a row block of the operator's own phi tensor, got "
-                             f"{B} rows at byte offset {phi.data_ptr() - full.data_ptr()} of its {full.shape[0]}")
-        return self.gain_open(full.shape[0], H, W, device), r0
-
-    def _gain_prepare(self, d, x0c, yc, M0, phi, freeze_phi):
+    def _gain_prepare(self, d, x0c, yc, M0, phi, freeze_phi, r0, r1):
         """The sub-step's (y' rows, M' rows) [B,3,HW]: osm_phys_forward at the starting phi, then the 2 n_iter + 1 launches of
         include/osmosis_gain.h from one call, or singly with OSM_PHYS_PY_LOOP=1."""
         gn = self._gain
         B, _, H, W = x0c.shape
-        st, r0 = self._gain_rows(phi, B, H, W, x0c.device)
-        if M0 is not None and (M0.numel() != B * 3 * H * W or not M0.is_contiguous()):
-            raise ValueError(f"expected mask rows [{B},3,{H * W}], got {tuple(M0.shape)}")
+        st = gn["state"]
         ws = st["ws"].get((B, d.loss_type, d.weight_type))
         if ws is None:
             P = ops.phys_lin_planes(d)
@@ -605,8 +606,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                 "desc": gd, "F": torch.empty(B, P, H * W, device=x0c.device, dtype=torch.float32), "tsc": ops.gain_workspace(gd, x0c.device)}
         gd, F, (t, s, cs) = ws["desc"], ws["F"], ws["tsc"]
         tabs = ops.gain_tables(H, W, gd.gh, gd.gw, x0c.device)
-        nodes, field = st["nodes"][r0:r0 + B], st["field"][r0:r0 + B]
-        y_eff, m_eff = st["y_eff"][r0:r0 + B], st["m_eff"][r0:r0 + B]
+        nodes, field, y_eff, m_eff = (st[k][r0:r1] for k in ("nodes", "field", "y_eff", "m_eff"))
         learn = gn["learn"] and not freeze_phi
         if learn:
             ops.phys_forward(d, x0c, phi, F)
@@ -656,6 +656,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         confidence: the same shape in [0, 1]; a range that is not finite or <= 0 is invalid (m = 0, z = 0 there).  align 'affine' |
         'scale' (c = 0) | 'none' (a = `scale`, c = 0); `scale_min` > 0 bounds a from below.  None clears the prior.  The term does not
         depend on phi: it is added to dL/dx0 once, after the route's inner loop, by three small kernels (csrc/depthprior.hip)."""
+        self._batch = None      # (the per-batch state changes: `open_batch` again)
         if z is None:
             self._depth = None
             return None
@@ -683,7 +684,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
     @staticmethod
     def _depth_store(dp):
         """The prior's per-BATCH results, beside its rows: fit [B0,4] float64 = a, c, gs, L and loss [B0] fp32, NaN until a guided
-        sub-step has written them.  A call on a chunk writes the chunk's rows (`_depth_offset`), so a batch walked in chunks ends with
+        sub-step has written them.  A call on a chunk writes the chunk's rows (`rows=`), so a batch walked in chunks ends with
         every image's own fit -- the counterpart of the data term's `loss_out` rows."""
         z = dp["z"]
         dp["out_fit"] = torch.full((z.shape[0], 4), float("nan"), device=z.device, dtype=torch.float64)
@@ -704,41 +705,13 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             self._depth_store(dp)
         return z, m
 
-    def _depth_offset(self, z, B):
-        """The first row of the stored prior that the range rows `z` [B,1,HW] in hand are (a chunk of its [B0,1,HW] block)."""
-        full = self._depth["z"]
-        r0, rem = divmod(z.data_ptr() - full.data_ptr(), full.shape[2] * 4)
-        if z.device != full.device or rem != 0 or r0 < 0 or r0 + B > full.shape[0]:
-            # the kernels write fit + b * 4 and loss + b for every row they are handed
-            raise ValueError("depth prior rows must be a row block of the conditioner's own prior (`depth_prior_rows(...)[0][a:b]`), got "
-                             f"{B} rows at byte offset {z.data_ptr() - full.data_ptr()} of its {full.shape[0]}")
-        return r0
-
-    def _depth_rows(self, x0, rows):
-        """The (range, confidence) rows [B,1,HW] a call on x0 [B,4,H,W] uses -- the caller's chunk (`rows`) or the stored prior's --
-        checked before anything launches; None without a prior."""
-        dp = self._depth
-        if dp is None:
-            if rows is not None:
-                raise ValueError("depth prior rows were handed over, but no prior is set (`set_depth_prior`)")
-            return None
-        B, _, H, W = x0.shape
-        if rows is None:
-            return self.depth_prior_rows(B, H, W, x0.device)
-        z, m = rows
-        if dp["grid"] != (int(H), int(W)) or z.numel() != B * H * W or m.numel() != B * H * W or not z.is_contiguous() \
-                or not m.is_contiguous():
-            raise ValueError(f"expected depth prior rows [{B},1,{H * W}] (range, confidence) on the prior's grid {dp['grid']}, got "
-                             f"{tuple(z.shape)} and {tuple(m.shape)} for an image batch {tuple(x0.shape)}")
-        self._depth_offset(z, B)
-        return z, m
-
-    def _apply_depth_prior(self, st, x0c, g, rows):
-        """The prior's launches on the g the route has just written: g[:, 3] += weight * d L_depth / d x0[:, 3] where m > 0."""
+    def _apply_depth_prior(self, st, x0c, g, r0, r1):
+        """The prior's launches on the g the route has just written: g[:, 3] += weight * d L_depth / d x0[:, 3] where m > 0, with
+        rows [r0:r1] of the prior and of its per-batch results."""
         dp = self._depth
         B, _, H, W = x0c.shape
         HW = H * W
-        z, m = rows
+        z, m, fit, loss = (dp[k][r0:r1] for k in ("z", "m", "out_fit", "out_loss"))
         if not g.is_contiguous() or g.numel() != B * 4 * HW:
             raise ValueError("the depth prior adds into a contiguous [B,4,HW] gradient")
         ws = st.get("depth")
@@ -748,8 +721,6 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
                   "desc": ops.depth_desc(dp["align"], dp["loss"], dp["weight"], dp["scale"], dp["scale_min"], d.depth_type, d.dval, B, HW),
                   "part": torch.empty(B * ops.depth_nblk(HW) * 8, device=x0c.device, dtype=torch.float64)}
             st["depth"] = ws
-        r0 = self._depth_offset(z, B)
-        fit, loss = dp["out_fit"][r0:r0 + B], dp["out_loss"][r0:r0 + B]       # this chunk's rows of the per-batch results
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
             ops.depth_loss_grad(ws["desc"], x0c, z, m, ws["part"], fit, loss, g)
             return
@@ -847,59 +818,51 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         self._state = st
         return st
 
-    def _group(self, phi):
+    def _group(self, r0, r1):
         """The group descriptor of an operator with shared water parameters (`phi_groups`), None without.  A group's members are
-        pooled inside ONE launch, so the phi rows in hand must be the operator's whole batch."""
+        pooled inside ONE launch, so the call must be the whole batch."""
         sizes = getattr(self.operator, "group_sizes", None)
         if sizes is None:
             return None
-        full = self.operator.phi
-        if phi.data_ptr() != full.data_ptr() or phi.shape[0] != full.shape[0]:
-            raise ValueError(f"phi_groups: a water group spans chunks -- the data term got {phi.shape[0]} phi rows of the operator's "
-                             f"{full.shape[0]}; a grouped batch takes ONE call over all its images")
+        if (r0, r1) != (0, self._batch[0]):
+            raise ValueError(f"phi_groups: a water group spans chunks -- the data term got rows {r0}:{r1} of the batch's "
+                             f"{self._batch[0]}; a grouped batch takes ONE call over all its images")
         key = (sizes, self.operator.phi_reduce)
         if getattr(self, "_grp_key", None) != key:
             self._grp, self._grp_key = ops.group_desc(sizes, self.operator.phi_reduce), key
         return self._grp
 
-    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None, depth=None):
+    def loss_grad_x0(self, x0, y, freeze_phi=False, g_out=None, loss_out=None, mask=None, rows=None):
         """Inner phi-optimisation + dL/dx0.  x0 [B,4,H,W], y [B,3,H,W] contiguous device fp32.
         Returns (g [B,4,H,W] view of an internal buffer (or g_out), per-image data loss [B] (device)).
-        `phi` / `loss_out` / `mask`: rows of the operator's [B][9] state / of a [B] loss vector / of the [B,3,HW] mask when the
-        caller walks a batch in chunks of independent images (default: the operator's whole state, the mask of
-        `set_measurement_mask`).
+        `rows` = (r0, r1): which images of the open batch (`open_batch`) x0 / y / g_out / loss_out are, when the caller walks a batch
+        in chunks of independent images; every per-batch store -- the operator's phi [B0][9], the optimizer state, the stored mask,
+        the robust / depth-prior / gain-field state -- is read and written at its rows [r0:r1].  None: the call is the whole batch.
+        `mask`: mask rows [B,3,HW] for exactly this call's images, in the place of the one of `set_measurement_mask`.
         An operator with `phi_groups`: the same launches with ONE phi step per group and inner iteration (osm_phys_optimize_g); loss
-        and g stay per image, and the call must cover the operator's whole batch.
-        With a range-map prior (`set_depth_prior`; `depth`: the chunk's (range, confidence) rows [B,1,HW], default the stored ones)
-        g's depth plane also carries weight * d L_depth / d x0, added after the inner loop; the returned loss stays the data loss
-        (`depth_prior_values` has the prior's).
+        and g stay per image, and the call must be the whole batch.
+        With a range-map prior (`set_depth_prior`) g's depth plane also carries weight * d L_depth / d x0, added after the inner
+        loop; the returned loss stays the data loss (`depth_prior_values` has the prior's).
         With a gain field (`set_gain_field`) the nodes are stepped first (not when `freeze_phi`), and the route runs masked on
-        (y', M G) of include/osmosis_gain.h; `phi` rows then say which images of the batch these are."""
-        self._robust_refuse()
-        self._gain_refuse()
+        (y', M G) of include/osmosis_gain.h."""
+        r0, r1 = self._batch_rows(rows, x0, y)
         if getattr(self.operator, "degradation", None) is not None:
-            return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, phi, loss_out, mask, depth)
+            return self._loss_grad_x0_lin(x0, y, freeze_phi, g_out, loss_out, mask, r0, r1)
         B, HW = x0.shape[0], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or x0.shape[1] != 4:
             raise ValueError("expected x0 [B,4,H,W] and measurement [B,3,H,W]")
-        grp = self._group(self.operator.phi if phi is None else phi)        # (refuses a chunk of a grouped batch before anything else)
-        depth = self._depth_rows(x0, depth) if (self._depth is not None or depth is not None) else None
+        grp = self._group(r0, r1)               # (refuses a chunk of a grouped batch before anything else)
         st = self._prepare(B, HW, x0.device)
-        d, part, red, loss = st["desc"], st["part"], st["red"], st["loss"]
-        opt = self._opt if d.optimizer != 0 else None       # read at call time: _prepare may have re-allocated it
-        if loss_out is not None:
-            loss = loss_out
-        phi = self.operator.phi if phi is None else phi
-        if phi.shape[0] != B or not phi.is_contiguous():
-            raise ValueError("phi must be a contiguous [B][9] block")
+        d, part, red = st["desc"], st["part"], st["red"]
+        phi, opt = self._phi_rows(d, r0, r1)
+        loss = st["loss"] if loss_out is None else loss_out
         g = g_out if g_out is not None else st["g"]
         x0c, yc = x0.contiguous(), y.contiguous()
+        mask = self._mask_rows(mask, r0, r1, HW)
         if self._gain is not None:
             # the gain field: the nodes learnt at the phi this sub-step starts from, then (y', M G) rows in the place of (y, mask) --
             # the masked residual on them is the residual of the model G F, so everything below is what it was
-            if mask is None:
-                mask = self.measurement_mask(B, HW, x0.device)
-            yc, mask = self._gain_prepare(d, x0c, yc, mask, phi, freeze_phi)
+            yc, mask = self._gain_prepare(d, x0c, yc, mask, phi, freeze_phi, r0, r1)
         elif self._robust is not None:
             # the robust term: the model image at the phi this sub-step starts from, the raw residual's MAD scale and the IRLS weights
             # folded into the mask -- M_eff rows in the mask's place, constants of the inner loop below
@@ -907,9 +870,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             if F is None:
                 F = st["F_robust"] = torch.empty(B, ops.phys_lin_planes(d), HW, device=x0.device, dtype=torch.float32)
             ops.phys_forward(d, x0c, phi, F)
-            mask = self._robust_mask_rows(F, 2.0, -1.0, yc, mask, B, HW)
-        elif mask is None:
-            mask = self.measurement_mask(B, HW, x0.device)
+            mask = self._robust_mask_rows(F, 2.0, -1.0, yc, mask, r0, r1)
         # the route's four calls: reduce, finalize, grad, optimize (the schedule: _inner_loop)
         if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
             route = (partial(ops.phys_reduce_m, d, x0c, yc, mask, phi, part),
@@ -924,10 +885,17 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             route = (partial(ops.phys_reduce, d, x0c, yc, phi, part), partial(ops.phys_finalize, d, part, red, phi),
                      partial(ops.phys_grad, d, x0c, yc, phi, red, g),
                      partial(ops.phys_optimize, d, x0c, yc, phi, part, red, loss, g))
-        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
-        if depth is not None:
-            self._apply_depth_prior(st, x0c, g, depth)
+        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, opt)
+        if self._depth is not None:
+            self._apply_depth_prior(st, x0c, g, r0, r1)
         return g.view(x0.shape), loss
+
+    def _phi_rows(self, d, r0, r1):
+        """Rows [r0:r1] of the operator's [B0][9] phi block and of the optimizer state beside it (None with plain SGD)."""
+        full = self.operator.phi
+        if full.shape[0] != self._batch[0] or not full.is_contiguous():
+            raise ValueError(f"phi must be a contiguous [B][9] block over the batch's {self._batch[0]} images, got {tuple(full.shape)}")
+        return full[r0:r1], (self._opt[r0:r1] if d.optimizer != 0 else None)
 
     @staticmethod
     def _inner_loop(route, n_inner, freeze_phi, loss, rows):
@@ -950,7 +918,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             if not freeze_phi:
                 finalize(True, None, opt_state=rows)
 
-    def _loss_grad_x0_lin(self, x0, y, freeze_phi=False, g_out=None, phi=None, loss_out=None, mask=None, depth=None):
+    def _loss_grad_x0_lin(self, x0, y, freeze_phi, g_out, loss_out, mask, r0, r1):
         """`loss_grad_x0` with the operator's `degradation` A between the image-formation model and the photo: y and the mask live on
         A's grid (h, w) = A.out_shape(H, W).  Per inner iteration: the image (and the depth weight) materialised, A, the residual on
         the measurement's grid, A^T, then the phi reductions and step with v = A^T u where the plain route forms -2 w r inline -- all
@@ -966,26 +934,15 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         if tuple(y.shape) != (B, 3, h, w):
             raise ValueError(f"expected the measurement [{B},3,{h},{w}] (the degradation's grid for a {H} x {W} image), got {tuple(y.shape)}")
         HW, hw = H * W, h * w
-        grp = self._group(self.operator.phi if phi is None else phi)
-        depth = self._depth_rows(x0, depth) if (self._depth is not None or depth is not None) else None
+        grp = self._group(r0, r1)
         st = self._prepare(B, HW, x0.device, grid=(H, W))
-        d, lin, part, red, loss = st["desc"], st["lin"], st["part"], st["red"], st["loss"]
+        d, lin, part, red = st["desc"], st["lin"], st["part"], st["red"]
         F, AF, u, v, part_r = st["F"], st["AF"], st["u"], st["v"], st["part_r"]
-        opt = self._opt if d.optimizer != 0 else None
-        if loss_out is not None:
-            loss = loss_out
-        phi = self.operator.phi if phi is None else phi
-        if phi.shape[0] != B or not phi.is_contiguous():
-            raise ValueError("phi must be a contiguous [B][9] block")
+        phi, opt = self._phi_rows(d, r0, r1)
+        loss = st["loss"] if loss_out is None else loss_out
         g = g_out if g_out is not None else st["g"]
         x0c, yc = x0.contiguous(), y.contiguous()
-        if mask is None:
-            if self._mask is not None and self._mask.shape[2] != hw:
-                raise ValueError(f"measurement mask [{self._mask.shape[0]},3,{self._mask.shape[2]}] does not fit a measurement "
-                                 f"[{B},3,{h},{w}] (the mask lives on the measurement's grid)")
-            mask = self.measurement_mask(B, hw, x0.device)
-        elif mask.numel() != B * 3 * hw:
-            raise ValueError(f"expected mask rows [{B},3,{hw}] (the measurement's grid {h} x {w}), got {tuple(mask.shape)}")
+        mask = self._mask_rows(mask, r0, r1, hw)        # (the mask lives on the measurement's grid)
         P, masked = ops.phys_lin_planes(d), mask is not None
 
         def reduce():
@@ -1001,26 +958,10 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         else:
             route = (reduce, partial(ops.phys_finalize_lin, d, hw, part, part_r, red, phi, masked=masked), grad,
                      partial(ops.phys_optimize_lin, d, lin, x0c, yc, mask, phi, F, AF, u, v, part_r, part, red, loss, g))
-        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, self._opt_rows(opt, phi))
-        if depth is not None:                                   # the prior lives on the image's grid [H, W], not the measurement's
-            self._apply_depth_prior(st, x0c, g, depth)
+        self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, opt)
+        if self._depth is not None:                             # the prior lives on the image's grid [H, W], not the measurement's
+            self._apply_depth_prior(st, x0c, g, r0, r1)
         return g.view(x0.shape), loss
-
-    def _opt_rows(self, opt, phi):
-        """The optimizer-state rows that belong to the phi rows in hand (a chunk of the operator's [B][9] block)."""
-        if opt is None:
-            return None
-        full = self.operator.phi
-        if phi.data_ptr() == full.data_ptr() and phi.shape[0] == full.shape[0]:
-            return opt
-        off = phi.data_ptr() - full.data_ptr()
-        r0, rem = divmod(off, 9 * 4)
-        if rem != 0 or r0 < 0 or r0 + phi.shape[0] > full.shape[0]:
-            # the kernel writes opt_state + b * 20 for every phi row it is handed: rows of anything but the operator's own
-            # [B][9] block would be an out-of-bounds device write (ADVICE r03)
-            raise ValueError("optimizer: adam needs `phi` to be a row block of the operator's own phi tensor "
-                             f"(byte offset {off}, {phi.shape[0]} rows of {full.shape[0]})")
-        return opt[r0:r0 + phi.shape[0]]
 
     def aux_values(self):
         """{'avrg_loss': [B], 'val_loss': [B]} from the last reduction (device tensors, no sync)."""
@@ -1216,17 +1157,23 @@ class PosteriorSampling(ConditioningMethod):
             raise ValueError(f"scale must have 1 or {channels} entries")
         return (s.repeat(channels) if s.numel() == 1 else s).to(device).contiguous()
 
-    def loss_grad_x0(self, x0, y, g_out=None, loss_out=None, mask=None):
+    def loss_grad_x0(self, x0, y, g_out=None, loss_out=None, mask=None, rows=None):
         """loss[b] = ||y[b] - x0[b, 0:3]||_2 and g = d loss / d x0 (zero on any channel beyond the colours), per image (B = 1: the
         reference's batch-global norm).  x0 [B,C,H,W] with C = 4 (RGBD) or 3 (the RGB model family), y [B,3,H,W] contiguous device
-        fp32.  With a mask M (`mask`: [B,3,HW] rows, default the one of `set_measurement_mask`): loss[b] = ||M (y - x0[0:3])||,
+        fp32.  `rows` = (r0, r1): which images of the open batch (`open_batch`) these are -- the stored mask and the robust state are
+        taken at their rows [r0:r1]; None: the whole batch.  With a mask M (`mask`: [B,3,HW] rows for exactly this call's images,
+        default the one of `set_measurement_mask`): loss[b] = ||M (y - x0[0:3])||,
         g = -M^2 (y - x0) / loss, and g = 0 for an image that is masked out entirely.
         With a `SeparableOperator` A (blur, super-resolution) the measurement y [B,3,h,w] lives on A's own grid, and so does the mask:
         loss[b] = ||M (y - A x0[b, 0:3])||, g[:, 0:3] = A^T d loss / d (A x0) (`_loss_grad_x0_separable`); a `PSFOperator` (motion blur, a
         measured point-spread function) goes the same way with its own kernel."""
         from .measurements import GRID_OPERATORS
-        self._robust_refuse()
+        r0, r1 = self._batch_rows(rows, x0, y)
+        mask = self._mask_rows(mask, r0, r1, y.shape[2] * y.shape[3])
         if self._blind() is not None:
+            if (r0, r1) != (0, self._batch[0]):
+                raise ValueError(f"blind_blur: the learnt PSF is shared by the batch -- the data term got rows {r0}:{r1} of the batch's "
+                                 f"{self._batch[0]}; it takes ONE call over all its images")
             return self._loss_grad_x0_blind(x0, y, g_out, loss_out, mask)
         if isinstance(self.operator, GRID_OPERATORS):
             return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask)
@@ -1253,9 +1200,7 @@ class PosteriorSampling(ConditioningMethod):
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
         if self._robust is not None:    # the robust term: e = y - x0[:, 0:3], its MAD scale, M_eff rows in the mask's place
-            mask = self._robust_mask_rows(x0.contiguous(), 1.0, 0.0, y.contiguous(), mask, B, HW)
-        elif mask is None:
-            mask = self.measurement_mask(B, HW, x0.device)
+            mask = self._robust_mask_rows(x0.contiguous(), 1.0, 0.0, y.contiguous(), mask, r0, r1)
         if mask is not None and C == 4:
             ops.phys_optimize_m(st["desc"], x0.contiguous(), y.contiguous(), mask, st["phi"], st["part"], st["red"], loss, g, 1, True)
         elif mask is not None:
@@ -1289,8 +1234,6 @@ class PosteriorSampling(ConditioningMethod):
             self._states[key] = st
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
-        if mask is None:
-            mask = self.measurement_mask(B, hw, x0.device)
         Ax, r = st["Ax"], st["r"]
         if isinstance(self.operator, PSFOperator):
             taps, (Ry, Rx) = self.operator.taps(x0.device), self.operator.radius()
@@ -1335,8 +1278,6 @@ class PosteriorSampling(ConditioningMethod):
             self._states[key] = st
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
-        if mask is None:
-            mask = self.measurement_mask(B, HW, x0.device)
         x0, y = x0.contiguous(), y.contiguous()
         Ax, r, tpart = st["Ax"], st["r"], st["tpart"]
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":

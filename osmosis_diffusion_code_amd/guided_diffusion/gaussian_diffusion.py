@@ -700,13 +700,9 @@ class GaussianDiffusion:
         g = torch.empty(B, C, H, W, **f32)
         loss_all = torch.zeros(B, **f32)
         y = measurement.detach().to(dev, torch.float32).contiguous()
-        # [B,3,hw] rows like y, or None (`measurement_mask=`): the mask lives on the measurement's grid (the image's, except for a
-        # downsampling operator of the 'ps' branch)
-        hw_y = y.shape[2] * y.shape[3] if y.dim() == 4 else HW
-        if getattr(cond, "_robust", None) is None:
-            mask = cond.measurement_mask(B, hw_y, dev)
-        else:       # the robust data term (`robust=`): the base-mask rows its weights multiply, a mask of ones without a mask
-            mask = cond.robust_open(B, hw_y, dev)
+        # the chain's batch: the mask rows [B,3,hw] on the measurement's grid (the image's, except for a downsampling operator of the
+        # 'ps' branch) and the robust / depth-prior / gain-field state at its initial values; the data term takes chunks by `rows=`
+        cond.open_batch(B, (H, W), tuple(y.shape[2:]) if y.dim() == 4 else (H, W), dev)
         phi = None if ps else cond.operator.phi
         # a data term that couples the images of the batch: shared water parameters, or on the 'ps' branch an operator with
         # `couples_batch` (`blind_blur`: one learnt PSF for all images)
@@ -719,15 +715,6 @@ class GaussianDiffusion:
         noise = None if (lib_rng or mean_only) else torch.zeros(B, C, H, W, **f32)
         noise1 = torch.zeros(1, C, H, W, **f32) if (shared and source == "aten" and not mean_only) else None
         noise_used = torch.empty(B, C, H, W, **f32) if (lib_rng and trace is not None) else None
-        # (no mask: the call as it always was -- a conditioner subclass whose loss_grad_x0 predates the kwarg keeps working)
-        # the range-map depth prior's (range, confidence) rows [B,1,HW], on the image's grid (`depth_prior=`): handed over only when set
-        prior = None if ps or getattr(cond, "_depth", None) is None else cond.depth_prior_rows(B, H, W, dev)
-
-        def mk_rows(a, b):
-            rows = {} if mask is None else {"mask": mask[a:b]}
-            if prior is not None:
-                rows["depth"] = (prior[0][a:b], prior[1][a:b])
-            return rows
         mk, vk = self.mean_processor.kernel_kind, self.var_processor.kernel_kind
         k = 0                                             # sub-step count (noise_fn's k)
         for idx in range(ch.first, ch.last - 1, -1):
@@ -773,10 +760,10 @@ class GaussianDiffusion:
                 for act, (c0, c1) in walk:
                     if act == "data":
                         if ps:
-                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
+                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], g_out=g[c0:c1], loss_out=loss_all[c0:c1], rows=(c0, c1))
                         else:
-                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], phi=phi[c0:c1],
-                                              loss_out=loss_all[c0:c1], **mk_rows(c0, c1))
+                            cond.loss_grad_x0(x0[c0:c1], y[c0:c1], freeze_phi=freeze, g_out=g[c0:c1], loss_out=loss_all[c0:c1],
+                                              rows=(c0, c1))
                         ch.have_loss = True
                         continue
                     ce, Bc = engs[c1 - c0], c1 - c0        # this chunk's engine (`eng` stays the first one)
@@ -880,11 +867,8 @@ class GaussianDiffusion:
         x0_raw = torch.empty(1, 4, Hc, Wc, **f32) if self.mean_processor.clip_denoised else None
         loss_all = torch.zeros(1, **f32)
         y = measurement.detach().to(dev, torch.float32).contiguous()
-        # (the robust data term, `robust=`: its weights are over the whole canvas, one sigma; its base mask is ones without a mask)
-        mask = cond.measurement_mask(1, HW, dev) if getattr(cond, "_robust", None) is None else cond.robust_open(1, HW, dev)
-        mk_rows = {} if mask is None else {"mask": mask}
-        if getattr(cond, "_depth", None) is not None:          # the range-map depth prior: a map over the CANVAS, one fit for it
-            mk_rows["depth"] = cond.depth_prior_rows(1, Hc, Wc, dev)
+        # a batch of ONE canvas: the mask, the robust weights (one sigma), the depth prior (one fit) and the gain field are over it
+        cond.open_batch(1, (Hc, Wc), (Hc, Wc), dev)
         phi = cond.operator.phi
         img_base = int(kwargs.get("image_index0", 0))
         noise = None if ch.lib_rng else torch.zeros(1, 4, Hc, Wc, **f32)      # the noise belongs to the canvas
@@ -917,7 +901,7 @@ class GaussianDiffusion:
                 ops.posterior_c(model_out, x_state, coef, x0, mean, logvar, 1, 4, 8, HW, mk, vk, x0_raw)
                 gg = dxu = grad_out = None
                 if guided:
-                    cond.loss_grad_x0(x0, y, freeze_phi=freeze, g_out=g, phi=phi, loss_out=loss_all, **mk_rows)
+                    cond.loss_grad_x0(x0, y, freeze_phi=freeze, g_out=g, loss_out=loss_all)
                     ch.have_loss = True
                     if x0_raw is not None:
                         ops.clamp_bwd(g, x0_raw)

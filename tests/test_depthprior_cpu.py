@@ -174,11 +174,16 @@ def test_set_depth_prior_shapes_ranges_and_grid():
     vals = cond.depth_prior_values()                                                       # per batch, undefined before a guided sub-step
     assert set(vals) == {"loss", "scale", "shift"} and all(tuple(v.shape) == (2,) and bool(torch.isnan(v).all()) for v in vals.values())
     zr, mr = cond.depth_prior_rows(2, 8, 6, "cpu")
-    assert cond._depth_offset(zr, 2) == 0 and cond._depth_offset(zr[1:2], 1) == 1          # a chunk's rows know their place
-    with pytest.raises(ValueError, match="row block"):
-        cond._depth_offset(zr.clone(), 2)
-    with pytest.raises(ValueError, match="row block"):
-        cond._depth_offset(zr[1:2], 2)
+    x0, y = torch.zeros(2, 4, 8, 6), torch.zeros(2, 3, 8, 6)
+    with pytest.raises(ValueError, match="open_batch"):                                    # a chunk's place is its range of the OPEN batch
+        cond._batch_rows((0, 2), x0, y)
+    cond.open_batch(2, (8, 6), (8, 6), "cpu")
+    assert cond._batch_rows((0, 2), x0, y) == (0, 2) and cond._batch_rows((1, 2), x0[1:2], y[1:2]) == (1, 2)
+    assert cond._batch_rows(None, x0, y) == (0, 2) and cond._depth["z"].data_ptr() == zr.data_ptr()
+    with pytest.raises(ValueError, match="rows must be"):
+        cond._batch_rows((1, 2), x0, y)                                                    # one row for two images
+    with pytest.raises(ValueError, match="rows must be"):
+        cond._batch_rows((1, 3), x0, y)                                                    # past the prior's rows
     assert cond.set_depth_prior(z[:, 0])["z"].shape == (2, 1, 48)                          # [B,H,W]
     assert cond.set_depth_prior(z[:1], batch=3)["z"].shape == (3, 1, 48)                   # [1,1,H,W] broadcasts
     zr, mr = cond.depth_prior_rows(3, 8, 6, "cpu")

@@ -279,7 +279,8 @@ def test_loss_grad_x0_with_a_prior_vs_the_composed_oracle(pkg, monkeypatch, rout
 
 
 def test_prior_rows_of_a_chunk_and_errors(pkg):
-    """The caller hands over a chunk's rows by the `depth` kwarg; a grid mismatch raises before any launch."""
+    """A chunk takes its rows of the stored prior by `rows=`; a range that is not the call's images, or that ends past the batch, and
+    a grid mismatch raise before any launch."""
     B, H, W = 3, 36, 34
     z, m = route_prior(B, H, W, 61)
     x0, y = inputs(B, H, W, H, W, 62)
@@ -289,18 +290,19 @@ def test_prior_rows_of_a_chunk_and_errors(pkg):
     g, phi = g.cpu().clone(), whole.operator.phi.cpu().clone()
     chunks = gcond(pkg, "underwater_physical_revised", B, None, n_iter=3)
     chunks.set_depth_prior(z, confidence=m, weight=0.5, batch=B, device=DEV)
-    zr, mr = chunks.depth_prior_rows(B, H, W, DEV)
+    chunks.open_batch(B, (H, W), (H, W), DEV)
     for lo, hi in ((0, 2), (2, 3)):
-        gc, _ = chunks.loss_grad_x0(x0[lo:hi].to(DEV), y[lo:hi].to(DEV), phi=chunks.operator.phi[lo:hi], depth=(zr[lo:hi], mr[lo:hi]))
+        gc, _ = chunks.loss_grad_x0(x0[lo:hi].to(DEV), y[lo:hi].to(DEV), rows=(lo, hi))
         assert torch.equal(gc.cpu(), g[lo:hi]), (lo, hi)
     assert torch.equal(chunks.operator.phi.cpu(), phi)
+    for a, b in zip(whole.depth_prior_values().values(), chunks.depth_prior_values().values()):
+        assert torch.equal(a, b)
     with pytest.raises(ValueError, match="does not fit"):
         whole.loss_grad_x0(x0[:, :, :, :32].contiguous().to(DEV), y[:, :, :, :32].contiguous().to(DEV))
-    with pytest.raises(ValueError, match="rows"):
-        whole.loss_grad_x0(x0.to(DEV), y.to(DEV), depth=(zr[0:2], mr[0:2]))
-    whole.set_depth_prior(None)
-    with pytest.raises(ValueError, match="no prior is set"):
-        whole.loss_grad_x0(x0.to(DEV), y.to(DEV), depth=(zr, mr))
+    for bad in ((0, 3), (2, 4)):        # not this call's two images; past the batch's three: fit + b * 4 would be written out of bounds
+        with pytest.raises(ValueError, match="rows must be"):
+            chunks.loss_grad_x0(x0[0:2].to(DEV), y[0:2].to(DEV), rows=bad)
+    assert torch.equal(chunks.operator.phi.cpu(), phi)
 
 
 # ============================================================================================================ chain level

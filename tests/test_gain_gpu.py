@@ -329,12 +329,13 @@ def test_py_loop_freeze_chunk_rows_and_refusals(pkg, monkeypatch):
         if env:
             monkeypatch.setenv("OSM_PHYS_PY_LOOP", env)
         cond = gcond(pkg, "underwater_physical_revised", B, None, "mean", "sgd", 5, AUX, "norm", "depth")
-        m = cond.set_measurement_mask(mask, batch=B, device=DEV)
+        cond.set_measurement_mask(mask, batch=B, device=DEV)
         cond.set_gain_field(**gain_of("norm", learn=learn))
+        cond.open_batch(B, (H, W), (H, W), DEV)
         g, loss = torch.empty(B, 4, H, W, device=DEV), torch.empty(B, device=DEV)
         xd, yd = x0.to(DEV), y.to(DEV)
         for a, b in chunks:
-            cond.loss_grad_x0(xd[a:b], yd[a:b], freeze_phi=freeze, g_out=g[a:b], phi=cond.operator.phi[a:b], loss_out=loss[a:b], mask=m[a:b])
+            cond.loss_grad_x0(xd[a:b], yd[a:b], freeze_phi=freeze, g_out=g[a:b], loss_out=loss[a:b], rows=(a, b))
         monkeypatch.delenv("OSM_PHYS_PY_LOOP", raising=False)
         v = cond.gain_values()
         return g.cpu(), loss.cpu(), cond.operator.phi.cpu().clone(), v["nodes"].cpu().clone(), v["field"].cpu().clone(), cond
@@ -346,8 +347,11 @@ def test_py_loop_freeze_chunk_rows_and_refusals(pkg, monkeypatch):
         fixed = run(**kw)
         assert torch.equal(fixed[3], torch.ones(B, 5, 5)) and torch.equal(fixed[4], torch.ones(B, 1, H * W))
     cond = one[5]
-    with pytest.raises(ValueError, match="row block"):
-        cond.loss_grad_x0(x0[:2].to(DEV), y[:2].to(DEV), phi=cond.operator.phi[:2].clone(), mask=cond.measurement_mask(B, H * W, DEV)[:2])
+    phi, nodes = cond.operator.phi.clone(), cond.gain_values()["nodes"].clone()
+    for bad in ((0, 3), (2, 4)):        # not this call's two images; past the batch's three: the node rows would be written out of bounds
+        with pytest.raises(ValueError, match="rows must be"):
+            cond.loss_grad_x0(x0[:2].to(DEV), y[:2].to(DEV), rows=bad)
+    assert torch.equal(cond.operator.phi, phi) and torch.equal(cond.gain_values()["nodes"], nodes)      # (nothing was launched)
 
 
 def test_torch_route_agrees_with_the_kernels(pkg):

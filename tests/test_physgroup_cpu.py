@@ -204,13 +204,15 @@ def test_a_row_block_that_is_not_the_whole_batch_is_refused():
     cond = CM.get_conditioning_method("osmosis", op, M.get_noise("clean"), gradient_x_prev=True)
     x0 = torch.zeros(2, 4, 8, 12)
     y = torch.zeros(2, 3, 8, 12)
+    cond.open_batch(3, (8, 12), (8, 12), "cpu")
     with pytest.raises(ValueError, match="water group spans chunks"):
-        cond.loss_grad_x0(x0, y, phi=op.phi[0:2])
+        cond.loss_grad_x0(x0, y, rows=(0, 2))
     opl = M.get_operator("underwater_physical_revised", device="cpu", batch_size=3, phi_groups="all", degradation=DEGRADATIONS["sr2_box"],
                          **OKW)
     condl = CM.get_conditioning_method("osmosis", opl, M.get_noise("clean"), gradient_x_prev=True)
+    condl.open_batch(3, (8, 12), (4, 6), "cpu")
     with pytest.raises(ValueError, match="water group spans chunks"):
-        condl.loss_grad_x0(x0, torch.zeros(2, 3, 4, 6), phi=opl.phi[1:3])
+        condl.loss_grad_x0(x0, torch.zeros(2, 3, 4, 6), rows=(0, 2))
 
 
 class HalfPool:

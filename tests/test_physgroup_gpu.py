@@ -482,8 +482,9 @@ def test_one_group_walked_in_chunks_is_the_one_pass_chain(pkg, monkeypatch, mode
 def test_a_chunk_of_a_grouped_batch_is_refused_on_the_device(pkg):
     cond = chain_cond(pkg, "underwater_physical_revised", "sgd", None, (2, 1))
     x0, y = (t.to(DEV) for t in inputs(3, CH, CW, CH, CW, 5))
+    cond.open_batch(3, (CH, CW), (CH, CW), DEV)
     with pytest.raises(ValueError, match="water group spans chunks"):
-        cond.loss_grad_x0(x0[0:2], y[0:2], phi=cond.operator.phi[0:2])
+        cond.loss_grad_x0(x0[0:2], y[0:2], rows=(0, 2))
 
 
 @pytest.mark.parametrize("case", ["plain", "local_M2", "clip_denoised"])

@@ -378,8 +378,9 @@ def test_all_zero_weights_hold_the_fully_masked_guard(pkg):
 
 
 def test_chunk_rows_write_their_rows_and_refusals(pkg):
-    """`mask=` rows of the conditioner's own base mask: a [2, 1] walk is the one pass bit for bit, `robust_values()` included;
-    foreign rows that do not cover the batch raise; a degradation and a 'ps' grid operator are refused naming `robust`."""
+    """`rows=` ranges of the open batch: a [2, 1] walk is the one pass bit for bit, `robust_values()` included; a range that is not
+    the call's images, or that ends past the batch, raises before any launch; a degradation and a 'ps' grid operator are refused
+    naming `robust`."""
     _, _, M, CM = pkg
     B, H, W = 3, 36, 34
     x0, y = inputs(B, H, W, H, W, 91)
@@ -391,20 +392,25 @@ def test_chunk_rows_write_their_rows_and_refusals(pkg):
             if masked:
                 cond.set_measurement_mask(make_masks("uniform", B, H, W, 93), batch=B, device=DEV)
             cond.set_robust(loss="tukey")
-            rows = cond.robust_open(B, H * W, DEV)
+            cond.open_batch(B, (H, W), (H, W), DEV)
             v = cond.robust_values()
             assert bool(torch.isnan(v["scale"]).all()) and int(v["n_valid"].abs().max()) == 0 and float(v["weight"].abs().max()) == 0.0
             gs = []
             for lo, hi in walk:
-                g, _ = cond.loss_grad_x0(x0[lo:hi].to(DEV), y[lo:hi].to(DEV), phi=cond.operator.phi[lo:hi], mask=rows[lo:hi])
+                g, _ = cond.loss_grad_x0(x0[lo:hi].to(DEV), y[lo:hi].to(DEV), rows=(lo, hi))
                 gs.append(g.cpu().clone())
             v = cond.robust_values()
             runs.append((torch.cat(gs), cond.operator.phi.cpu().clone(), v["scale"].cpu().clone(), v["n_valid"].cpu().clone(),
                          v["weight"].cpu().clone()))
         assert all(torch.equal(a, b) for a, b in zip(*runs)), masked
         assert tuple(runs[1][2].shape) == (B,) and len(set(runs[1][2].tolist())) == B
-    with pytest.raises(ValueError, match="row block"):
-        cond.loss_grad_x0(x0[0:2].to(DEV), y[0:2].to(DEV), phi=cond.operator.phi[0:2], mask=torch.ones(2, 3, H * W, device=DEV))
+    before = [t.clone() for t in cond.robust_values().values()]
+    for bad in ((0, 3), (2, 4)):        # not this call's two images; past the batch's three: sigma + b would be written out of bounds
+        with pytest.raises(ValueError, match="rows must be"):
+            cond.loss_grad_x0(x0[0:2].to(DEV), y[0:2].to(DEV), rows=bad, mask=torch.ones(2, 3, H * W, device=DEV))
+    assert all(torch.equal(a, b) for a, b in zip(before, cond.robust_values().values()))        # (nothing was launched)
+    g, _ = cond.loss_grad_x0(x0[0:2].to(DEV), y[0:2].to(DEV), rows=(0, 2), mask=torch.ones(2, 3, H * W, device=DEV))
+    assert bool(torch.isfinite(g).all())                  # any mask rows for exactly the call's images are legal: `rows` has the place
     from physlin_oracle import DEGRADATIONS
     deg = gcond(pkg, "underwater_physical_revised", 1, None, deg=DEGRADATIONS["gaussian_blur"])
     with pytest.raises(NotImplementedError, match="robust"):
