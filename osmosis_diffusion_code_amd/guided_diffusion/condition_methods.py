@@ -317,6 +317,8 @@ class ConditioningMethod(ABC):
         return mask
 
     # ---------------------------------------------------------------- robust data term (include/osmosis_robust.h)
+    ROBUST_CHAIN_KEYS = ("loss", "c", "scale", "sigma_min", "per_pixel")       # what `set_robust` takes from a chain (`p_sample_loop(robust=)`)
+
     def set_robust(self, loss="tukey", c=None, scale="mad", sigma_min=2.0 / 255.0, per_pixel=False):
         """Make the data term robust to outliers in the measurement (marine snow, highlights, caustics, a fish): per guided sub-step
         and per image, the raw residual e = y - prediction (osmosis: 2 I - 1 at the phi the sub-step starts from; 'ps': x0) gives a
@@ -541,6 +543,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         return s.to(device).contiguous()
 
     # ---------------------------------------------------------------- learnt vignetting gain field (include/osmosis_gain.h)
+    GAIN_FIELD_CHAIN_KEYS = ("grid", "eta", "n_iter", "smooth", "g_min", "init", "learn")      # what `set_gain_field` takes from a chain
+
     def set_gain_field(self, grid=(5, 5), eta=0.01, n_iter=1, smooth=0.0, g_min=0.05, init=None, learn=True):
         """Model the photo as G F(x0; phi) with one smooth gain G(p) <= 1 per pixel (lens vignetting, the fall-off of a strobe): G is
         the bilinear interpolation of `grid` = (gh, gw) nodes on the image corners, 2 <= gh, gw <= 32.  Per guided sub-step that does
@@ -646,6 +650,7 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
 
     # ---------------------------------------------------------------- range-map depth prior (include/osmosis_depthprior.h)
     _depth_serial = 0
+    DEPTH_PRIOR_CHAIN_KEYS = ("z", "confidence", "weight", "align", "loss", "scale", "scale_min")     # what `set_depth_prior` takes from a chain
 
     def set_depth_prior(self, z, confidence=None, weight=1.0, align="affine", loss="norm", scale=1.0, scale_min=1e-3, batch=None,
                         device=None):

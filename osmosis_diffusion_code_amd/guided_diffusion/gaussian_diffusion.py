@@ -35,6 +35,7 @@ import torch
 
 from .. import ops
 from ..osmosis_utils import utils as utilso
+from .condition_methods import ConditioningMethod, PosteriorSamplingOsmosis
 from .posterior_mean_variance import get_mean_processor, get_var_processor
 
 __SAMPLER__ = {}
@@ -463,6 +464,31 @@ class _Chain:
         variables = operator.optimize(freeze_phi=True)
         loss_np = loss_all.detach().cpu().numpy() if self.have_loss else None
         return img, variables, loss_np, x0.detach().cpu()
+
+
+def _depth_prior_extras(depth_prior, x_start):
+    """`p_sample_loop(depth_prior=)`: the range map lives on the image's grid; the setter's further keyword arguments."""
+    zt = torch.as_tensor(depth_prior["z"])
+    if tuple(zt.shape[-2:]) != tuple(x_start.shape[2:]):
+        raise ValueError(f"depth_prior z {tuple(zt.shape)} does not match the image grid {tuple(x_start.shape[2:])}")
+    return dict(batch=x_start.shape[0], device=x_start.device)
+
+
+# The data-term options of a chain, in the order `p_sample_loop` applies them.  keyword -> (the conditioner's setter, the keys it takes
+# from a chain (declared beside the setter), a key that must be there, the TypeError without the setter, the ValueError for anything but
+# such a dict, a further check that returns the setter's extra keyword arguments).  `measurement_mask` is a tensor and keeps its own lines.
+CHAIN_OPTIONS = {
+    "gain_field": ("set_gain_field", PosteriorSamplingOsmosis.GAIN_FIELD_CHAIN_KEYS, None,
+                   "gain_field needs a conditioner with set_gain_field (the 'osmosis' conditioning method)",
+                   "gain_field must be a dict (grid, eta, n_iter, smooth, g_min, init, learn)", None),
+    "robust": ("set_robust", ConditioningMethod.ROBUST_CHAIN_KEYS, None,
+               "robust needs a conditioner with set_robust (a ConditioningMethod)",
+               "robust must be a dict (loss, c, scale, sigma_min, per_pixel)", None),
+    "depth_prior": ("set_depth_prior", PosteriorSamplingOsmosis.DEPTH_PRIOR_CHAIN_KEYS, "z",
+                    "depth_prior needs a conditioner with set_depth_prior (the 'osmosis' conditioning method)",
+                    "depth_prior must be a dict with the range map `z` (and confidence, weight, align, loss, scale, scale_min)",
+                    _depth_prior_extras),
+}
 
 
 class GaussianDiffusion:
@@ -965,49 +991,29 @@ class GaussianDiffusion:
         conditioner keeps whatever setting it was given directly (none by default).
         gain_field: `dict(grid=, eta=, n_iter=, smooth=, g_min=, init=, learn=)` puts a learnt vignetting gain field into the Osmosis
         data term for this chain (`PosteriorSamplingOsmosis.set_gain_field`; on a tiled canvas one field over the canvas), its state
-        starting afresh; None: the conditioner keeps whatever setting it was given directly (none by default)."""
+        starting afresh; None: the conditioner keeps whatever setting it was given directly (none by default).
+        The three dicts go through one walk over `CHAIN_OPTIONS` -- gain field (and the opening of its state), robust, depth prior,
+        in that order, then the mask: a conditioner without the setter is a TypeError, anything but a dict of the keys declared
+        beside the setter a ValueError, before the setter runs."""
         from .posterior_mean_variance import PreviousXMeanProcessor
-        if gain_field is not None:
-            cond_obj = getattr(measurement_cond_fn, "__self__", None)
-            if not hasattr(cond_obj, "set_gain_field"):
-                raise TypeError("gain_field needs a conditioner with set_gain_field (the 'osmosis' conditioning method)")
-            if not isinstance(gain_field, dict):
-                raise ValueError("gain_field must be a dict (grid, eta, n_iter, smooth, g_min, init, learn)")
-            unknown = set(gain_field) - {"grid", "eta", "n_iter", "smooth", "g_min", "init", "learn"}
-            if unknown:
-                raise ValueError(f"gain_field: unknown keys {sorted(unknown)}")
-            cond_obj.set_gain_field(**gain_field)
-        if getattr(getattr(measurement_cond_fn, "__self__", None), "_gain", None) is not None:
-            # the per-batch state at its initial values (`gain_values` reads them until the first guided sub-step); refusals first
-            cond_obj = measurement_cond_fn.__self__
-            phi_all = getattr(cond_obj.operator, "phi", None)       # (a third-party operator keeps its parameters elsewhere)
-            cond_obj.gain_open(x_start.shape[0] if phi_all is None else phi_all.shape[0], x_start.shape[2], x_start.shape[3],
-                               x_start.device)
-        if robust is not None:
-            cond_obj = getattr(measurement_cond_fn, "__self__", None)
-            if not hasattr(cond_obj, "set_robust"):
-                raise TypeError("robust needs a conditioner with set_robust (a ConditioningMethod)")
-            if not isinstance(robust, dict):
-                raise ValueError("robust must be a dict (loss, c, scale, sigma_min, per_pixel)")
-            unknown = set(robust) - {"loss", "c", "scale", "sigma_min", "per_pixel"}
-            if unknown:
-                raise ValueError(f"robust: unknown keys {sorted(unknown)}")
-            cond_obj.set_robust(**robust)
-        if depth_prior is not None:
-            cond_obj = getattr(measurement_cond_fn, "__self__", None)
-            if not hasattr(cond_obj, "set_depth_prior"):
-                raise TypeError("depth_prior needs a conditioner with set_depth_prior (the 'osmosis' conditioning method)")
-            if not isinstance(depth_prior, dict) or "z" not in depth_prior:
-                raise ValueError("depth_prior must be a dict with the range map `z` (and confidence, weight, align, loss, scale, scale_min)")
-            unknown = set(depth_prior) - {"z", "confidence", "weight", "align", "loss", "scale", "scale_min"}
-            if unknown:
-                raise ValueError(f"depth_prior: unknown keys {sorted(unknown)}")
-            zt = torch.as_tensor(depth_prior["z"])
-            if tuple(zt.shape[-2:]) != tuple(x_start.shape[2:]):
-                raise ValueError(f"depth_prior z {tuple(zt.shape)} does not match the image grid {tuple(x_start.shape[2:])}")
-            cond_obj.set_depth_prior(**depth_prior, batch=x_start.shape[0], device=x_start.device)
+        cond_obj = getattr(measurement_cond_fn, "__self__", None)
+        for name, value in (("gain_field", gain_field), ("robust", robust), ("depth_prior", depth_prior)):
+            if value is not None:
+                setter, keys, required, needs, must_be, extras = CHAIN_OPTIONS[name]
+                if not hasattr(cond_obj, setter):
+                    raise TypeError(needs)
+                if not isinstance(value, dict) or (required is not None and required not in value):
+                    raise ValueError(must_be)
+                unknown = set(value) - set(keys)
+                if unknown:
+                    raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+                getattr(cond_obj, setter)(**value, **({} if extras is None else extras(value, x_start)))
+            if name == "gain_field" and getattr(cond_obj, "_gain", None) is not None:
+                # the per-batch state at its initial values (`gain_values` reads them until the first guided sub-step); refusals first
+                phi_all = getattr(cond_obj.operator, "phi", None)       # (a third-party operator keeps its parameters elsewhere)
+                cond_obj.gain_open(x_start.shape[0] if phi_all is None else phi_all.shape[0], x_start.shape[2], x_start.shape[3],
+                                   x_start.device)
         if measurement_mask is not None:
-            cond_obj = getattr(measurement_cond_fn, "__self__", None)
             if not hasattr(cond_obj, "set_measurement_mask"):
                 raise TypeError("measurement_mask needs a conditioner with set_measurement_mask (a ConditioningMethod)")
             if tuple(measurement_mask.shape[2:]) != tuple(measurement.shape[2:]):

@@ -21,11 +21,12 @@ Beyond the reference (which only ever writes 256 x 256 results):
     tile_grid(Hc, Wc, tile, stride, window) the tiles of a canvas: origins, the separable window and the blend normalisation
 """
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from .guided_diffusion.condition_methods import get_conditioning_method
+from .guided_diffusion.condition_methods import ConditioningMethod, PosteriorSamplingOsmosis, get_conditioning_method
 from .guided_diffusion.gaussian_diffusion import create_sampler, parse_tiling, tile_grid  # noqa: F401  (tile_grid: public helper)
 from .guided_diffusion.measurements import GRID_OPERATORS, get_noise, get_operator
 from .osmosis_utils import utils as utilso
@@ -113,7 +114,30 @@ def observed_image(operator, out_xstart):
         return 2 * operator.observe(out_xstart.detach().to(operator.device, torch.float32).contiguous()) - 1
 
 
-DEPTH_PRIOR_KEYS = ("weight", "align", "loss", "scale", "scale_min", "path")
+def _refuse_unknown_keys(where, given, known, also=()):
+    """`where`: unknown key(s) ... (known: ...) for a mapping with keys outside `known` (+ `also`, accepted but not advertised)."""
+    unknown = set(given) - set(known) - set(also)
+    if unknown:
+        raise ValueError(f"{where}: unknown key(s) {sorted(unknown)} (known: {', '.join(known)})")
+
+
+def _option_mapping(argument, name, config_value, config_key, known, also=()):
+    """An option given as an argument (a dict, which wins) or under a config key: (a copy of the chosen mapping, or None when
+    neither is given; how to name it in a message).  Anything but a mapping raises, and so do unknown keys."""
+    chosen, where = (argument, name) if argument is not None else (config_value, config_key)
+    if not chosen:
+        return None, where
+    if not isinstance(chosen, dict):
+        raise ValueError(f"{where} must be a mapping of {', '.join(known)}")
+    _refuse_unknown_keys(where, chosen, known, also)
+    return dict(chosen), where
+
+
+# The keys a config can carry for each option: what the option's setter takes from a chain (declared beside it in
+# condition_methods.py), with a `path` to a .npy in the place of the arrays.
+DEPTH_PRIOR_KEYS = tuple(k for k in PosteriorSamplingOsmosis.DEPTH_PRIOR_CHAIN_KEYS if k not in ("z", "confidence")) + ("path",)
+ROBUST_KEYS = ConditioningMethod.ROBUST_CHAIN_KEYS
+GAIN_KEYS = tuple(k for k in PosteriorSamplingOsmosis.GAIN_FIELD_CHAIN_KEYS if k != "init") + ("path",)
 
 
 def depth_prior_config(depth_cfg):
@@ -122,33 +146,17 @@ def depth_prior_config(depth_cfg):
     raise."""
     if not depth_cfg:
         return {}, None
-    unknown = set(depth_cfg) - set(DEPTH_PRIOR_KEYS)
-    if unknown:
-        raise ValueError(f"measurement.depth: unknown key(s) {sorted(unknown)} (known: {', '.join(DEPTH_PRIOR_KEYS)})")
+    _refuse_unknown_keys("measurement.depth", depth_cfg, DEPTH_PRIOR_KEYS)
     params = {k: depth_cfg[k] for k in ("align", "loss") if k in depth_cfg}
     params.update({k: float(depth_cfg[k]) for k in ("weight", "scale", "scale_min") if k in depth_cfg})
     return params, depth_cfg.get("path")
-
-
-ROBUST_KEYS = ("loss", "c", "scale", "sigma_min", "per_pixel")
 
 
 def robust_config(robust_cfg=None, robust=None):
     """The `robust=` dict of a chain (`p_sample_loop(robust=)`, `ConditioningMethod.set_robust`) from the optional config key
     `measurement.robust: {loss, c, scale, sigma_min, per_pixel}` or the argument `robust` (a dict, which wins over the config), or
     None when neither is given.  Unknown keys raise."""
-    chosen, where = (robust, "robust") if robust is not None else (robust_cfg, "measurement.robust")
-    if not chosen:
-        return None
-    if not isinstance(chosen, dict):
-        raise ValueError(f"{where} must be a mapping of {', '.join(ROBUST_KEYS)}")
-    unknown = set(chosen) - set(ROBUST_KEYS)
-    if unknown:
-        raise ValueError(f"{where}: unknown key(s) {sorted(unknown)} (known: {', '.join(ROBUST_KEYS)})")
-    return dict(chosen)
-
-
-GAIN_KEYS = ("grid", "eta", "n_iter", "smooth", "g_min", "learn", "path")
+    return _option_mapping(robust, "robust", robust_cfg, "measurement.robust", ROBUST_KEYS)[0]
 
 
 def gain_nodes_from_flat_field(flat, grid):
@@ -179,15 +187,9 @@ def gain_config(gain_cfg=None, gain=None, grid_hw=None):
     config key `measurement.gain: {grid, eta, n_iter, smooth, g_min, learn, path}` or the argument `gain` (a dict, which wins over
     the config; it may carry `init` nodes instead of `path`), or None when neither is given.  `path`: a .npy of nodes [gh,gw] or of a
     full-resolution flat field [H,W] on the network's grid `grid_hw`, reduced to nodes by least squares.  Unknown keys raise."""
-    chosen, where = (gain, "gain") if gain is not None else (gain_cfg, "measurement.gain")
-    if not chosen:
+    out, where = _option_mapping(gain, "gain", gain_cfg, "measurement.gain", GAIN_KEYS, also=("init",))
+    if out is None:
         return None
-    if not isinstance(chosen, dict):
-        raise ValueError(f"{where} must be a mapping of {', '.join(GAIN_KEYS)}")
-    unknown = set(chosen) - set(GAIN_KEYS) - {"init"}
-    if unknown:
-        raise ValueError(f"{where}: unknown key(s) {sorted(unknown)} (known: {', '.join(GAIN_KEYS)})")
-    out = dict(chosen)
     out["grid"] = tuple(int(v) for v in out.get("grid", (5, 5)))
     path = out.pop("path", None)
     if path is not None:
@@ -568,9 +570,7 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
             raise ValueError(f"mask {tuple(m.shape)} does not match the image grid {tuple(ref_img.shape[2:])}")
         out = m.to(ref_img.device).expand(ref_img.shape[0], 3, *ref_img.shape[2:]).contiguous()
     if mask_cfg:
-        unknown = set(mask_cfg) - {"auto_exposure"}
-        if unknown:
-            raise ValueError(f"measurement.mask: unknown key(s) {sorted(unknown)} (known: auto_exposure)")
+        _refuse_unknown_keys("measurement.mask", mask_cfg, ("auto_exposure",))
         ae = mask_cfg.get("auto_exposure")
         if ae:
             from . import ops
@@ -582,9 +582,8 @@ def measurement_mask(ref_img, mask_cfg=None, mask=None):
     return out
 
 
-def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False,
-                  postprocess_batch=True, mask=None, tiling=None, depth=None, depth_confidence=None, depth_geometry=None,
-                  robust=None, gain=None, **loop_kwargs):
+def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False, mask=None, tiling=None,
+                  depth=None, depth_confidence=None, depth_geometry=None, robust=None, gain=None, **loop_kwargs):
     """One image through the reference's per-image sequence: fresh operator / noiser / conditioning method /
     sampler (:142-155), y = noiser(ref) (+ degamma), manual_seed + x_T ~ N(0, I) per global iteration
     (:191-196), guided p_sample_loop, post-processing.  Returns a list with one dict per global iteration.
@@ -592,8 +591,9 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     `ref_img` may carry B > 1 images: one batch of independent chains.  With `same_seed_per_image` every image of
     the batch starts from the SAME x_T and receives the SAME per-step noise -- exactly what B separate calls (each
     re-seeded with `manual_seed`, as the reference driver does per image) would draw -- so an image's result does not
-    depend on how images are grouped into batches or spread over ranks.  `postprocess_batch=False` skips the
-    reference's image-0-only post-processing (a caller that post-processes every image of the batch itself).
+    depend on how images are grouped into batches or spread over ranks.  Like the reference, only image 0 of a batch is
+    post-processed (`_image_result(whole=True)`): `sample`, `pred_xstart`, `measurement` and `mask` are over the whole batch, every
+    other key is image 0's.  `restore_images` builds every image's result from the same chain (`_run_chains`).
 
     `mask` (and / or the optional config key `measurement.mask`, see `measurement_mask`): a per-pixel validity mask of the
     measurement on the network grid (`data.transform_mask` takes one from the photo's resolution there).  The chain is guided
@@ -635,6 +635,21 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
     `simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` -- the blur that makes y = noiser(A* ref); it must keep the
     image's size.  ONE PSF serves the whole batch: B > 1 means photos through one optical system, not unrelated shakes."""
+    return [_image_result(run, 0, whole=True)
+            for run in _run_chains(model, ref_img, cfg, device=device, image_idx=image_idx, x_scale=x_scale,
+                                   same_seed_per_image=same_seed_per_image, mask=mask, tiling=tiling, depth=depth,
+                                   depth_confidence=depth_confidence, depth_geometry=depth_geometry, robust=robust, gain=gain,
+                                   **loop_kwargs)]
+
+
+def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same_seed_per_image=False, mask=None, tiling=None,
+                depth=None, depth_confidence=None, depth_geometry=None, robust=None, gain=None, **loop_kwargs):
+    """`restore_image`'s arguments through set-up and `p_sample_loop`: one record per global iteration of what the chain left for the
+    WHOLE batch, on the host -- what `_image_result` builds any image's result dict from.  Fields (None where the chain has no such
+    thing): `sample`; on the Osmosis branch `variables`, `loss`, `pred_xstart`, `observed` [B,3,h,w] (`observed_image`, a
+    degradation), `depth` {z, m [B,1,HW], scale, shift, loss [B], align}, `gain` {nodes, field} and `tiling`; `mask` [B,3,h,w];
+    `robust` {weight [B,3,h,w], scale [B]}; `kernel`; `solver` / `steps`; `measurement` (y_n); `ref_img` and `operator_cfg` for
+    `postprocess`."""
     tiling = tiling if tiling is not None else cfg.get("tiling")
     tiling_info = None
     if tiling is not None:
@@ -711,7 +726,6 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     gain = gain_config(measure.get("gain"), gain, shape[2:])
     if gain is not None:
         loop_kwargs = dict(loop_kwargs, gain_field=gain)
-    results = []
     for global_ii in range(global_iterations(cfg["sample_pattern"])):
         torch.manual_seed(cfg.get("manual_seed", 0))
         if is_blind:
@@ -729,68 +743,102 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
             record=cfg.get("record_process", False) and loop_kwargs.get("save_grids_path") is not None, save_root=None,
             pretrain_model=pretrain, image_idx=image_idx, record_every=cfg.get("record_every", 150),
             rgb_guidance=rgb_guidance, sample_pattern=cfg["sample_pattern"], global_iteration=global_ii, **loop_kwargs)
+        solver = getattr(sampler, "solver", None)
+        run = SimpleNamespace(
+            ref_img=ref_img, operator_cfg=measure["operator"], measurement=y_n.detach().cpu(), variables=None, loss=None,
+            pred_xstart=None, observed=None, depth=None, gain=None, tiling=None, robust=None,
+            mask=None if m_dev is None else m_dev.detach().cpu(),
+            kernel=torch.from_numpy(operator.kernel2d()).to(torch.float32) if is_blind else None,
+            solver=solver, steps=None if solver is None else sampler.num_timesteps)
+        vals = None if robust is None else cond.robust_values()     # (None: no guided sub-step on a loop that never opened the state)
+        if vals is not None:
+            run.robust = dict(weight=vals["weight"].detach().cpu().view(y_n.shape[0], 3, *y_n.shape[2:]), scale=vals["scale"].detach().cpu())
         if rgb_guidance or pretrain != "osmosis":
             # the rgb-guidance / non-osmosis chain returns the sample only (gaussian_diffusion.py:340); the
             # reference driver splits it into RGB and depth (osmosis_sampling.py:366-380): no phi, no recomposition
-            results.append(rgb_guidance_result(ret.detach().cpu(), y_n.detach().cpu()))
-            if m_dev is not None:
-                results[-1]["mask"] = m_dev.detach().cpu()
-            _attach_robust_values(results[-1], cond, robust, y_n, postprocess_batch)
-            if is_blind:
-                results[-1]["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
-            if getattr(sampler, "solver", None) is not None:
-                results[-1].update(solver=sampler.solver, steps=sampler.num_timesteps)
+            run.sample = ret.detach().cpu()
+            yield run
             continue
-        sample, variable_dict, loss, out_xstart = ret
-        if postprocess_batch:
-            post = postprocess(out_xstart, variable_dict, ref_img, measure["operator"], loss,
-                               observed=observed_image(operator, out_xstart)[0] if degraded else None)
-        else:
-            post = dict(phi={k: v.detach().cpu() for k, v in variable_dict.items()},
-                        loss=None if loss is None else np.asarray(loss))
-            if degraded:            # every image's `observed`, for the caller's per-image post-processing (`postprocess_each`)
-                post["observed"] = observed_image(operator, out_xstart).cpu()
-        post.update(sample=sample.detach().cpu(), pred_xstart=out_xstart, measurement=y_n.detach().cpu())
+        sample, variables, loss, run.pred_xstart = ret
+        run.sample, run.variables = sample.detach().cpu(), {k: v.detach().cpu() for k, v in variables.items()}
+        run.loss, run.tiling = None if loss is None else np.asarray(loss), tiling_info
+        if degraded:
+            run.observed = observed_image(operator, run.pred_xstart).cpu()
         if prior is not None:       # every image's fit and loss from the chain's last guided sub-step (NaN: there was none)
-            vals = {k: v.detach().cpu() for k, v in cond.depth_prior_values().items()}
             zr, mr = (t.detach().cpu() for t in cond.depth_prior_rows(shape[0], shape[2], shape[3], device))
-            if postprocess_batch:
-                attach_depth_prior(post, zr[0], mr[0], vals["scale"][0], vals["shift"][0], vals["loss"][0], cond._depth["align"])
-            else:                   # every image's, for the caller's per-image post-processing
-                post["depth_fit"] = dict(vals, z=zr, m=mr, align=cond._depth["align"])
-        if m_dev is not None:
-            post["mask"] = m_dev.detach().cpu()
-        _attach_robust_values(post, cond, robust, y_n, postprocess_batch)
+            run.depth = dict({k: v.detach().cpu() for k, v in cond.depth_prior_values().items()}, z=zr, m=mr, align=cond._depth["align"])
         if gain is not None:
-            vals = cond.gain_values()
-            if postprocess_batch:
-                attach_gain(post, vals["nodes"][0], vals["field"][0], y_n[0])
-            else:                   # every image's, for the caller's per-image post-processing
-                post["gain_fit"] = dict(nodes=vals["nodes"].detach().cpu(), field=vals["field"].detach().cpu())
-        if tiling_info is not None:
-            post["tiling"] = tiling_info
-        if is_blind:
-            post["kernel"] = torch.from_numpy(operator.kernel2d()).to(torch.float32)
-        if getattr(sampler, "solver", None) is not None:
-            post.update(solver=sampler.solver, steps=sampler.num_timesteps)
-        results.append(post)
-    return results
+            run.gain = {k: v.detach().cpu() for k, v in cond.gain_values().items()}
+        yield run
 
 
-def _attach_robust_values(post, cond, robust, y, postprocess_batch):
-    """The robust term's values of a chain's end on its result: image 0's keys (`attach_robust`), or with `postprocess_batch` off
-    every image's under `robust_fit` for the caller's per-image post-processing."""
-    if robust is None:
-        return
-    vals = cond.robust_values()
-    if vals is None:                # (a chain without a guided sub-step on a loop that never opened the state)
-        return
-    B, _, h, w = y.shape
-    weight, scale = vals["weight"].detach().cpu().view(B, 3, h, w), vals["scale"].detach().cpu()
-    if postprocess_batch:
-        attach_robust(post, weight[0], scale[0])
+def _image_result(run, b, whole=False):
+    """Image b's result dict from a chain's record (`_run_chains`): the one place where the end of a chain becomes a result.
+    whole (`restore_image`'s contract, b = 0): post-processing sees the batch as the reference's driver does and keeps image 0's
+    outputs, `sample` / `pred_xstart` / `measurement` / `mask` stay over the whole batch, and the result names the chain's `solver` /
+    `steps`.  Otherwise (`restore_images` with a batch) all of them are image b's rows [1,...], and there is no `solver` / `steps`."""
+    rows = slice(None) if whole else slice(b, b + 1)
+    if run.variables is None:
+        post = rgb_guidance_result(run.sample[rows], run.measurement[rows])
     else:
-        post["robust_fit"] = dict(weight=weight, scale=scale)
+        post = postprocess(run.pred_xstart[rows], {k: v[rows] for k, v in run.variables.items()}, run.ref_img[rows], run.operator_cfg,
+                           run.loss if whole or run.loss is None else run.loss[rows], observed=None if run.observed is None else run.observed[b])
+        post.update(sample=run.sample[rows], pred_xstart=run.pred_xstart[rows], measurement=run.measurement[rows])
+        if run.depth is not None:
+            d = run.depth
+            attach_depth_prior(post, d["z"][b], d["m"][b], d["scale"][b], d["shift"][b], d["loss"][b], d["align"])
+        if run.gain is not None:
+            attach_gain(post, run.gain["nodes"][b], run.gain["field"][b], run.measurement[b])
+        if run.tiling is not None:
+            post["tiling"] = run.tiling
+    if run.mask is not None:
+        post["mask"] = run.mask[rows]
+    if run.robust is not None:
+        attach_robust(post, run.robust["weight"][b], run.robust["scale"][b])
+    if run.kernel is not None:
+        post["kernel"] = run.kernel
+    if whole and run.solver is not None:
+        post.update(solver=run.solver, steps=run.steps)
+    return post
+
+
+def _rows_of_batch(items, idxs, blank, channels, what):
+    """The walk `batch_depth` and `batch_mask` share: the [1,C,H,W] entries of a list aligned with the images as the float32 rows of the
+    batch `idxs`, `blank(i)` for an image without one; None when the list is, or none of the batch's images has one."""
+    if items is None or all(items[i] is None for i in idxs):
+        return None
+    rows = []
+    for i in idxs:
+        t = blank(i) if items[i] is None else torch.as_tensor(items[i]).to(torch.float32)
+        if t.dim() != 4 or t.shape[0] != 1 or t.shape[1] not in channels:
+            raise ValueError(f"{what}[{i}] must be {' or '.join(f'[1,{c},H,W]' for c in channels)}, got {tuple(t.shape)}")
+        rows.append(t)
+    return rows
+
+
+def _cat_rows(rows):
+    return torch.cat([r.to(rows[0].device) for r in rows], 0)
+
+
+def batch_depth(depths, depth_confidences, idxs):
+    """(depth, confidence) rows [n,1,H,W] of one batch from `depths` / `depth_confidences` as `restore_image`'s keyword arguments, or
+    {} when none of its images has a map; an image without one gets z = 0 (no valid range: confidence 0)."""
+    zs = _rows_of_batch(depths, idxs, lambda i: torch.zeros(1, 1, *next(d for d in (depths[j] for j in idxs) if d is not None).shape[-2:]),
+                     (1,), "depths")
+    if zs is None:
+        return {}
+    ms = []
+    for i, z in zip(idxs, zs):
+        c = None if depth_confidences is None else depth_confidences[i]
+        ms.append((torch.isfinite(z) & (z > 0)).to(torch.float32) if c is None else torch.as_tensor(c).to(torch.float32).reshape(z.shape))
+    return dict(depth=_cat_rows(zs), depth_confidence=_cat_rows(ms))
+
+
+def batch_mask(masks, images, cfg, idxs):
+    """`masks` (a list aligned with `images`: [1,1,H,W] / [1,3,H,W] each, or None for an image without one) of one batch [n,3,h,w], or
+    None when none of its images has one; an image without one gets ones on the measurement's grid (the mask lives there)."""
+    rows = _rows_of_batch(masks, idxs, lambda i: torch.ones(1, 3, *measurement_grid(cfg["measurement"]["operator"], images[i].shape[-2:])), (1, 3), "masks")
+    return None if rows is None else _cat_rows([m.expand(1, 3, *m.shape[2:]) for m in rows])
 
 
 def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None, observed=None):
@@ -835,11 +883,16 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     image without one): rows per image, chunked with the images (`restore_image(depth=, depth_confidence=)`); in a batch, an image
     without a map gets confidence 0 everywhere -- no prior for it.  The fit stays per image, also with `shared_water`.
 
-    `robust` goes to `restore_image` as it is (it wins over `measurement.robust`); every result carries its own `robust_weight` and
-    `robust_scale`, also in chunked batches."""
+    `robust` / `gain` are `restore_image`'s (they win over `measurement.robust` / `measurement.gain`); every result carries its own
+    `robust_weight` / `robust_scale` and `gain_field` / `gain_nodes` / `flat_fielded`, also in chunked batches.
+
+    Every batch is one chain (`_run_chains`, which takes `restore_image`'s other keyword arguments as they are), and every image's
+    result is built from what it left (`_image_result`): a batch of one gives `restore_image`'s result, a larger one every image's
+    own rows [1,...] of `sample` / `pred_xstart` / `measurement` / `mask` and of every option's values -- without the chain's
+    `solver` / `steps`, which only a single image's result names."""
     if robust is not None:
         loop_kwargs = dict(loop_kwargs, robust=robust)
-    if gain is not None:        # (goes to `restore_image` as it is; every result carries its own `gain_field` / `gain_nodes` / `flat_fielded`)
+    if gain is not None:
         loop_kwargs = dict(loop_kwargs, gain=gain)
     if shared_water:
         if tiling is not None or cfg.get("tiling") is not None:
@@ -861,72 +914,18 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     if depth_confidences is not None and depths is None:
         raise ValueError("depth_confidences come with depths")
 
-    def batch_depth(idxs):
-        """(depth, confidence) rows [n,1,H,W] of one batch from `depths` / `depth_confidences`, or {} when none of its images has a map."""
-        if depths is None or all(depths[i] is None for i in idxs):
-            return {}
-        zs, ms = [], []
-        for i in idxs:
-            hw = tuple(next(d for d in (depths[j] for j in idxs) if d is not None).shape[-2:])
-            z = torch.zeros(1, 1, *hw) if depths[i] is None else torch.as_tensor(depths[i]).to(torch.float32)
-            if z.dim() != 4 or z.shape[0] != 1 or z.shape[1] != 1:
-                raise ValueError(f"depths[{i}] must be [1,1,H,W], got {tuple(z.shape)}")
-            c = None if depth_confidences is None else depth_confidences[i]
-            m = (torch.isfinite(z) & (z > 0)).to(torch.float32) if c is None else torch.as_tensor(c).to(torch.float32).reshape(z.shape)
-            zs.append(z)
-            ms.append(m.to(z.device))
-        return dict(depth=torch.cat([z.to(zs[0].device) for z in zs], 0), depth_confidence=torch.cat([m.to(zs[0].device) for m in ms], 0))
-
-    def batch_mask(idxs):
-        """`masks` (a list aligned with `images`: [1,1,H,W] / [1,3,H,W] each, or None for an image without one) of one batch."""
-        if masks is None or all(masks[i] is None for i in idxs):
-            return None
-        rows = []
-        for i in idxs:
-            hw = measurement_grid(cfg["measurement"]["operator"], images[i].shape[-2:])      # the mask lives where the measurement does
-            m = torch.ones(1, 3, *hw) if masks[i] is None else torch.as_tensor(masks[i]).to(torch.float32)
-            if m.dim() != 4 or m.shape[0] != 1 or m.shape[1] not in (1, 3):
-                raise ValueError(f"masks[{i}] must be [1,1,H,W] or [1,3,H,W], got {tuple(m.shape)}")
-            rows.append(m.expand(1, 3, *m.shape[2:]))
-        return torch.cat([r.to(rows[0].device) for r in rows], 0)
     out = {}
     mine = shard_indices(len(images), rank, world)
     for k in range(0, len(mine), max(1, batch_size)):
         idxs = mine[k:k + max(1, batch_size)]
-        if len(idxs) == 1:
-            res = [restore_image(model, images[idxs[0]], cfg, device=device, image_idx=idxs[0], mask=batch_mask(idxs),
-                                 **batch_depth(idxs), **loop_kwargs)[-1]]
-        else:
-            ref = torch.cat([images[i] for i in idxs], 0)
-            bcfg = cfg
-            if shared_water:        # this batch is one water group (a copy: the caller's config stays as it is)
-                bcfg = dict(cfg, measurement=dict(cfg["measurement"], operator=dict(cfg["measurement"]["operator"], phi_groups="all")))
-            full = restore_image(model, ref, bcfg, device=device, image_idx=idxs[0], same_seed_per_image=True,
-                                 postprocess_batch=False, mask=batch_mask(idxs), **batch_depth(idxs), **loop_kwargs)[-1]
-            if "pred_xstart" in full:
-                res = postprocess_each(full["pred_xstart"], full["phi"], ref, cfg["measurement"]["operator"], full["loss"],
-                                       observed=full.get("observed"))
-                for b, r in enumerate(res):
-                    r.update(sample=full["sample"][b:b + 1], pred_xstart=full["pred_xstart"][b:b + 1],
-                             measurement=full["measurement"][b:b + 1])
-            else:
-                res = [rgb_guidance_result(full["sample"][b:b + 1], full["measurement"][b:b + 1]) for b in range(len(idxs))]
-            if full.get("depth_fit") is not None and "pred_xstart" in full:
-                fit = full["depth_fit"]
-                for b, r in enumerate(res):
-                    attach_depth_prior(r, fit["z"][b], fit["m"][b], fit["scale"][b], fit["shift"][b], fit["loss"][b], fit["align"])
-            if full.get("robust_fit") is not None:
-                for b, r in enumerate(res):
-                    attach_robust(r, full["robust_fit"]["weight"][b], full["robust_fit"]["scale"][b])
-            if full.get("gain_fit") is not None:
-                for b, r in enumerate(res):
-                    attach_gain(r, full["gain_fit"]["nodes"][b], full["gain_fit"]["field"][b], full["measurement"][b])
-            if full.get("mask") is not None:
-                for b, r in enumerate(res):
-                    r["mask"] = full["mask"][b:b + 1]
-            if full.get("kernel") is not None:      # `blind_blur`: ONE PSF was learnt for the batch (photos through one optical system)
-                for r in res:
-                    r["kernel"] = full["kernel"]
+        bcfg = cfg
+        if shared_water and len(idxs) > 1:      # this batch is one water group (a copy: the caller's config stays as it is)
+            bcfg = dict(cfg, measurement=dict(cfg["measurement"], operator=dict(cfg["measurement"]["operator"], phi_groups="all")))
+        *_, run = _run_chains(model, torch.cat([images[i] for i in idxs], 0), bcfg, device=device, image_idx=idxs[0],
+                              same_seed_per_image=len(idxs) > 1, mask=batch_mask(masks, images, cfg, idxs),
+                              **batch_depth(depths, depth_confidences, idxs), **loop_kwargs)
+        # one image: `restore_image`'s result; a batch: every image's own rows (`blind_blur`: ONE PSF was learnt for the batch)
+        res = [_image_result(run, b, whole=len(idxs) == 1) for b in range(len(idxs))]
         for i, r in zip(idxs, res):
             if shared_water:
                 r["water_group"] = list(idxs)

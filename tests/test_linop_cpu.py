@@ -208,15 +208,6 @@ def test_a_missing_mask_of_a_batch_is_ones_on_the_measurement_grid():
     assert sampling.measurement_grid({"name": "gaussian_blur", "kernel_size": 9, "intensity": 1.5}, (24, 36)) == (24, 36)
     assert sampling.measurement_grid({"name": "rgb_guidance"}, (24, 36)) == (24, 36)
     assert sampling.measurement_grid({"name": "underwater_physical_revised", "phi_a": "1,1,1"}, (24, 36)) == (24, 36)
-    seen = {}
-
-    def fake_restore_image(model, ref, cfg, mask=None, **kw):
-        seen["mask"] = mask
-        return [sampling.rgb_guidance_result(torch.zeros(ref.shape[0], 4, 24, 36), torch.zeros(ref.shape[0], 3, 6, 9))]
-    real, sampling.restore_image = sampling.restore_image, fake_restore_image
-    try:
-        images = [torch.zeros(1, 3, 24, 36), torch.zeros(1, 3, 24, 36)]
-        sampling.restore_images(None, images, {"measurement": {"operator": sr}}, batch_size=2, masks=[None, 0.5 * torch.ones(1, 1, 6, 9)])
-    finally:
-        sampling.restore_image = real
-    assert seen["mask"].shape == (2, 3, 6, 9) and float(seen["mask"][0].min()) == 1.0 and float(seen["mask"][1].max()) == 0.5
+    images = [torch.zeros(1, 3, 24, 36), torch.zeros(1, 3, 24, 36)]
+    mask = sampling.batch_mask([None, 0.5 * torch.ones(1, 1, 6, 9)], images, {"measurement": {"operator": sr}}, [0, 1])      # what `restore_images` hands its batch's chain
+    assert mask.shape == (2, 3, 6, 9) and float(mask[0].min()) == 1.0 and float(mask[1].max()) == 0.5
