@@ -1,6 +1,6 @@
 """ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
 include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h,
-include/osmosis_solver.h, include/osmosis_robust.h and include/osmosis_gain.h).
+include/osmosis_solver.h, include/osmosis_robust.h, include/osmosis_gain.h and include/osmosis_psfset.h).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -283,6 +283,13 @@ _SIGS_GAIN = {
     "osm_gain_prepare": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
 }
 EXPORTS_GAIN = sorted(_SIGS_GAIN)
+# the entry points of the eleventh header, include/osmosis_psfset.h (PSF weight sets: one per image and / or per colour plane)
+_SIGS_PSFSET = {
+    "osm_psf_apply_s": _SIGS_PSF["osm_psf_apply"][:-1] + [_LL, _LL, _P],
+    "osm_psf_tap_step_s": [_P, _P, _P, _I, _I, _I, _I, _LL, _D, _D, _I, _I, _P],
+    "osm_ps_blind_optimize_s": _SIGS_BLIND["osm_ps_blind_optimize"][:-1] + [_I, _I, _P],
+}
+EXPORTS_PSFSET = sorted(_SIGS_PSFSET)
 
 _lib = None
 _lock = threading.Lock()
@@ -303,7 +310,7 @@ def load():
             lib = C.CDLL(LIB_PATH)
             for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
                     list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()) + \
-                    list(_SIGS_ROBUST.items()) + list(_SIGS_GAIN.items()):
+                    list(_SIGS_ROBUST.items()) + list(_SIGS_GAIN.items()) + list(_SIGS_PSFSET.items()):
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
                 fn.restype = C.c_int

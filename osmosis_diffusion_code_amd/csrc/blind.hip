@@ -7,10 +7,11 @@
 // TAPS tid, tid + 256, ... and walks the tile's pixels row-major, one fp32 fma each: the r read is a broadcast (one address for the
 // wave), lanes on neighbouring dx read neighbouring window words.  Gather form: every element of `part` is written by exactly one
 // lane in a fixed order, no atomics -- the bits depend on neither the batch nor the launch shape.  Lanes idle when T < 256.
-// Step: one workgroup; the reduction of `part` and everything after it in fp64, sums over t as a strided pass and a halving tree.
+// Step: one workgroup per weight set (one set: osm_psf_tap_step; per image / per plane: include/osmosis_psfset.h); the reduction of `part` and everything after it in fp64, sums over t as a strided pass and a halving tree.
 #include "osm_common.h"
 #include "../../include/osmosis_psf.h"
 #include "../../include/osmosis_blind.h"
+#include "../../include/osmosis_psfset.h"
 
 namespace {
 
@@ -19,7 +20,7 @@ constexpr int TH = 32;
 constexpr int TW = 32;
 constexpr int RMAX = 32;                                   // largest halo per side
 constexpr int CAP = (TH + 2 * RMAX) * ((TW + 2 * RMAX) | 1);   // 96 x 97 floats (36.4 KB) + the 4 KB tile of r
-constexpr int SNT = 1024;                                  // lanes of the step's one workgroup
+constexpr int SNT = 1024;                                  // lanes of a step workgroup (one per weight set)
 
 __device__ __forceinline__ int refl(int c, const int n) { return c < 0 ? -c : (c >= n ? 2 * (n - 1) - c : c); }
 
@@ -82,18 +83,24 @@ __device__ __forceinline__ double block_sum(const double* __restrict__ a, const 
   return red[0];
 }
 
-__global__ __launch_bounds__(SNT) void tap_step_kernel(float* __restrict__ w, const float* __restrict__ part, const float* __restrict__ loss,
+// one workgroup per weight set (bi, ci) = blockIdx.x / nc, blockIdx.x % nc: its images b0 .. b1-1 and its partials q0 .. q1-1, ascending
+// (one set: all of them -- osm_psf_tap_step's loops)
+__global__ __launch_bounds__(SNT) void tap_step_kernel(float* __restrict__ wsets, const float* __restrict__ part, const float* __restrict__ loss,
                                                        const int B, const int nparts, const int T, const double hw3, const double eta,
-                                                       const double l1) {
+                                                       const double l1, const int per_image, const int nc, const int ntiles) {
   __shared__ double a[OSM_BLIND_MAX_TAPS];
   __shared__ double red[SNT];
   const int tid = threadIdx.x;
+  const int bi = (int)blockIdx.x / nc, ci = (int)blockIdx.x % nc;
+  const int b0 = per_image ? bi : 0, b1 = per_image ? bi + 1 : B;
+  const int q0 = nc > 1 ? ci * ntiles : 0, q1 = nc > 1 ? q0 + ntiles : nparts;
+  float* __restrict__ w = wsets + (long long)blockIdx.x * T;
   for (int t = tid; t < T; t += SNT) {
     double s = 0.0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = b0; b < b1; ++b) {
       const float* __restrict__ pb = part + (long long)b * nparts * T + t;
       double c = 0.0;
-      for (int q = 0; q < nparts; ++q) c = __dadd_rn(c, (double)pb[(long long)q * T]);
+      for (int q = q0; q < q1; ++q) c = __dadd_rn(c, (double)pb[(long long)q * T]);
       s = __dadd_rn(s, __dmul_rn((double)loss[b], c));
     }
     a[t] = s / hw3;
@@ -156,14 +163,32 @@ extern "C" int osm_psf_tap_step(float* w, const float* part, const float* loss, 
   const int rc = check_step(what, B, nparts, T, hw3, eta, l1);
   if (rc) return rc;
   hipLaunchKernelGGL(tap_step_kernel, dim3(1), dim3(SNT), 0, static_cast<hipStream_t>(stream), w, part, loss, B, nparts, T, (double)hw3,
-                     eta, l1);
+                     eta, l1, 0, 1, nparts);
   return osm::check_launch(what);
 }
 
-extern "C" int osm_ps_blind_optimize(const float* x0, const float* y, const float* mask, const int* dy, const int* dx, float* w, int T,
-                                     int Ry, int Rx, int B, int C, int H, int W, float* Ax, float* r, float* lpart, float* tpart,
-                                     float* loss, float* g, int n_iter, double eta, double l1, void* stream) {
-  const char* what = "osm_ps_blind_optimize";
+extern "C" int osm_psf_tap_step_s(float* w, const float* part, const float* loss, int B, int P, int ntiles, int T, long long hw3,
+                                  double eta, double l1, int per_image, int per_channel, void* stream) {
+  const char* what = "osm_psf_tap_step_s";
+  OSM_REQUIRE(w && part && loss, "%s: null pointer (w / part / loss)", what);
+  OSM_REQUIRE(P >= 1 && ntiles >= 1 && (long long)P * ntiles < (1LL << 31), "%s: bad plane count %d or tile count %d", what, P, ntiles);
+  OSM_REQUIRE((per_image == 0 || per_image == 1) && (per_channel == 0 || per_channel == 1), "%s: per_image / per_channel must be 0 or 1, got %d / %d",
+              what, per_image, per_channel);
+  const int rc = check_step(what, B, P * ntiles, T, hw3, eta, l1);
+  if (rc) return rc;
+  const int nc = per_channel ? P : 1;
+  const long long nsets = (long long)(per_image ? B : 1) * nc;
+  OSM_REQUIRE(nsets <= 65535, "%s: %lld weight sets are too many for one launch", what, nsets);
+  hipLaunchKernelGGL(tap_step_kernel, dim3((unsigned)nsets), dim3(SNT), 0, static_cast<hipStream_t>(stream), w, part, loss, B, P * ntiles, T,
+                     (double)hw3, eta, l1, per_image, nc, ntiles);
+  return osm::check_launch(what);
+}
+
+namespace {
+// osm_ps_blind_optimize (sets = false: the single-set entry points, launch for launch what it was) and osm_ps_blind_optimize_s
+int blind_optimize(const char* what, bool sets, const float* x0, const float* y, const float* mask, const int* dy, const int* dx, float* w,
+                   int T, int Ry, int Rx, int B, int C, int H, int W, float* Ax, float* r, float* lpart, float* tpart, float* loss,
+                   float* g, int n_iter, double eta, double l1, int per_image, int per_channel, void* stream) {
   OSM_REQUIRE(x0 && y && w && Ax && r && lpart && tpart && loss && g, "%s: null pointer", what);
   int rc = check_taps(what, dy, dx, T, Ry, Rx, H, W);
   if (rc) return rc;
@@ -172,17 +197,45 @@ extern "C" int osm_ps_blind_optimize(const float* x0, const float* y, const floa
   OSM_REQUIRE((long long)B * C <= 65535 && (H + TH - 1) / TH <= 65535, "%s: batch %d x %d planes / %d rows are too many for one launch", what, B,
               C, H);
   OSM_REQUIRE(n_iter >= 1, "%s: n_iter must be >= 1, got %d", what, n_iter);
+  OSM_REQUIRE((per_image == 0 || per_image == 1) && (per_channel == 0 || per_channel == 1), "%s: per_image / per_channel must be 0 or 1, got %d / %d",
+              what, per_image, per_channel);
   const int HW = H * W;
-  const int nparts = 3 * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+  const int ntiles = ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
+  const int nparts = 3 * ntiles;
   rc = check_step(what, B, nparts, T, 3LL * HW, eta, l1);
   if (rc) return rc;
+  const long long wp = per_channel ? T : 0, ws = per_image ? (long long)(per_channel ? 3 : 1) * T : 0;
   for (int i = 0; i < n_iter; ++i) {
-    if ((rc = osm_psf_apply(x0, Ax, dy, dx, w, T, Ry, Rx, B, 3, (long long)C * HW, 3LL * HW, H, W, 0, 0, stream))) return rc;
+    rc = sets ? osm_psf_apply_s(x0, Ax, dy, dx, w, T, Ry, Rx, B, 3, (long long)C * HW, 3LL * HW, H, W, 0, 0, ws, wp, stream)
+              : osm_psf_apply(x0, Ax, dy, dx, w, T, Ry, Rx, B, 3, (long long)C * HW, 3LL * HW, H, W, 0, 0, stream);
+    if (rc) return rc;
     rc = mask ? osm_ps_loss_grad_mc(Ax, y, mask, lpart, loss, r, B, 3, HW, stream) : osm_ps_loss_grad_c(Ax, y, lpart, loss, r, B, 3, HW, stream);
     if (rc) return rc;
     if ((rc = osm_psf_tap_grad(x0, r, dy, dx, T, Ry, Rx, B, 3, (long long)C * HW, 3LL * HW, H, W, tpart, stream))) return rc;
-    if (i == n_iter - 1 && (rc = osm_psf_apply(r, g, dy, dx, w, T, Ry, Rx, B, 3, 3LL * HW, (long long)C * HW, H, W, 1, C - 3, stream))) return rc;
-    if ((rc = osm_psf_tap_step(w, tpart, loss, B, nparts, T, 3LL * HW, eta, l1, stream))) return rc;
+    if (i == n_iter - 1) {
+      rc = sets ? osm_psf_apply_s(r, g, dy, dx, w, T, Ry, Rx, B, 3, 3LL * HW, (long long)C * HW, H, W, 1, C - 3, ws, wp, stream)
+                : osm_psf_apply(r, g, dy, dx, w, T, Ry, Rx, B, 3, 3LL * HW, (long long)C * HW, H, W, 1, C - 3, stream);
+      if (rc) return rc;
+    }
+    rc = sets ? osm_psf_tap_step_s(w, tpart, loss, B, 3, ntiles, T, 3LL * HW, eta, l1, per_image, per_channel, stream)
+              : osm_psf_tap_step(w, tpart, loss, B, nparts, T, 3LL * HW, eta, l1, stream);
+    if (rc) return rc;
   }
   return OSM_OK;
+}
+}  // namespace
+
+extern "C" int osm_ps_blind_optimize(const float* x0, const float* y, const float* mask, const int* dy, const int* dx, float* w, int T,
+                                     int Ry, int Rx, int B, int C, int H, int W, float* Ax, float* r, float* lpart, float* tpart,
+                                     float* loss, float* g, int n_iter, double eta, double l1, void* stream) {
+  return blind_optimize("osm_ps_blind_optimize", false, x0, y, mask, dy, dx, w, T, Ry, Rx, B, C, H, W, Ax, r, lpart, tpart, loss, g, n_iter,
+                        eta, l1, 0, 0, stream);
+}
+
+extern "C" int osm_ps_blind_optimize_s(const float* x0, const float* y, const float* mask, const int* dy, const int* dx, float* w, int T,
+                                       int Ry, int Rx, int B, int C, int H, int W, float* Ax, float* r, float* lpart, float* tpart,
+                                       float* loss, float* g, int n_iter, double eta, double l1, int per_image, int per_channel,
+                                       void* stream) {
+  return blind_optimize("osm_ps_blind_optimize_s", true, x0, y, mask, dy, dx, w, T, Ry, Rx, B, C, H, W, Ax, r, lpart, tpart, loss, g, n_iter,
+                        eta, l1, per_image, per_channel, stream);
 }

@@ -15,6 +15,7 @@
 // so the bits do not depend on which way a tile went.  A tap beyond (Ry, Rx) is skipped, never read.
 #include "osm_common.h"
 #include "../../include/osmosis_psf.h"
+#include "../../include/osmosis_psfset.h"
 
 namespace {
 
@@ -31,6 +32,7 @@ struct PsfArgs {
   int T, Ry, Rx, B, P, Z;
   long long xs, os;
   int H, W, adjoint;
+  long long ws, wp;       // the weight set of plane (b, p): w + b ws + p wp (include/osmosis_psfset.h; 0, 0: one set for all)
 };
 
 // the source element at (r, c) of the extended plane: reflected once (forward) or 0 outside the plane (adjoint; and the forward's
@@ -58,6 +60,7 @@ __global__ __launch_bounds__(NT) void psf_kernel(const float* __restrict__ x, fl
   float tot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (plane < a.P) {                                                     // (uniform per workgroup, as are `staged` and a skipped pass)
     const float* __restrict__ xp = x + (long long)b * a.xs + (long long)plane * H * W;
+    const float* __restrict__ wv = a.w + (long long)b * a.ws + (long long)plane * a.wp;     // uniform: the tap loop's weight loads stay scalar
     const int Hwin = TH + 2 * Ry, Wwin = TW + 2 * Rx, LS = Wwin | 1;
     const bool staged = (long long)Hwin * LS <= CAP;
     const int sd = a.adjoint ? -1 : 1;                                   // the source index moves with (forward) or against a tap's offset
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(NT) void psf_kernel(const float* __restrict__ x, fl
               for (int k = 0; k < 4; ++k) v[k] = p[sk * k];
             }
             have = true; pdy = dyt; pdx = dxt;
-            const float wt = a.w[t];
+            const float wt = wv[t];
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] = fmaf(wt, v[k], acc[k]);
           }
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(NT) void psf_kernel(const float* __restrict__ x, fl
           for (int t = 0; t < a.T; ++t) {
             const int dyt = a.dy[t], dxt = a.dx[t];
             if (dyt < -Ry || dyt > Ry || dxt < -Rx || dxt > Rx) continue;
-            const float wt = a.w[t];
+            const float wt = wv[t];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
               if (k < nx) acc[k] = fmaf(wt, src(xp, cr + sd * dyt, ce0 + sk * k + sd * dxt, H, W, a.adjoint), acc[k]);
@@ -135,10 +138,10 @@ __global__ __launch_bounds__(NT) void psf_kernel(const float* __restrict__ x, fl
 
 }  // namespace
 
-extern "C" int osm_psf_apply(const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx, int B,
-                             int P, long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes,
-                             void* stream) {
-  const char* what = "osm_psf_apply";
+namespace {
+int psf_launch(const char* what, const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx, int B,
+               int P, long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes, long long ws,
+               long long wp, void* stream) {
   OSM_REQUIRE(x && out && dy && dx && w, "%s: null pointer (x / out / a tap array)", what);
   OSM_REQUIRE(B >= 1 && P >= 1 && zero_planes >= 0, "%s: bad batch %d, plane count %d or zero_planes %d", what, B, P, zero_planes);
   OSM_REQUIRE(H >= 1 && W >= 1 && W <= (1 << 28) && ((long long)P + zero_planes) * H * W < (1LL << 31), "%s: bad image %d x %d x %d", what,
@@ -150,12 +153,31 @@ extern "C" int osm_psf_apply(const float* x, float* out, const int* dy, const in
   OSM_REQUIRE(x_img_stride >= (long long)P * H * W, "%s: x_img_stride %lld is less than the %d planes read", what, x_img_stride, P);
   OSM_REQUIRE(out_img_stride >= ((long long)P + zero_planes) * H * W, "%s: out_img_stride %lld is less than the %d planes written", what,
               out_img_stride, P + zero_planes);
+  OSM_REQUIRE(ws >= 0 && wp >= 0 && (wp == 0 || wp >= T), "%s: weight strides must be >= 0 and a non-zero w_plane_stride >= T %d, got %lld / %lld",
+              what, T, ws, wp);
+  OSM_REQUIRE(ws == 0 || ws >= (long long)(P - 1) * wp + T, "%s: w_img_stride %lld does not cover an image's %d planes at w_plane_stride %lld", what,
+              ws, P, wp);
   const long long gz = (long long)B * (P + zero_planes);
   const long long gy = (H + TH - 1) / TH;
   OSM_REQUIRE(gz <= 65535 && gy <= 65535, "%s: %lld planes / %lld row tiles are too many for one launch", what, gz, gy);
-  const PsfArgs a{dy, dx, w, T, Ry, Rx, B, P, zero_planes, x_img_stride, out_img_stride, H, W, adjoint};
+  const PsfArgs a{dy, dx, w, T, Ry, Rx, B, P, zero_planes, x_img_stride, out_img_stride, H, W, adjoint, ws, wp};
   const int aligned = osm::aligned16(out);
   hipLaunchKernelGGL(psf_kernel, dim3((unsigned)((W + TW - 1) / TW), (unsigned)gy, (unsigned)gz), dim3(NT), 0,
                      static_cast<hipStream_t>(stream), x, out, a, aligned);
   return osm::check_launch(what);
+}
+}  // namespace
+
+extern "C" int osm_psf_apply(const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx, int B,
+                             int P, long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes,
+                             void* stream) {
+  return psf_launch("osm_psf_apply", x, out, dy, dx, w, T, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint, zero_planes, 0, 0,
+                    stream);
+}
+
+extern "C" int osm_psf_apply_s(const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx, int B,
+                               int P, long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes,
+                               long long w_img_stride, long long w_plane_stride, void* stream) {
+  return psf_launch("osm_psf_apply_s", x, out, dy, dx, w, T, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint, zero_planes,
+                    w_img_stride, w_plane_stride, stream);
 }

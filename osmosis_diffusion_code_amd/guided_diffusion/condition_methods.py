@@ -273,6 +273,10 @@ class ConditioningMethod(ABC):
         that fits these shapes is kept; the routings that are not built are refused here.  A `set_*` call closes the batch."""
         self._robust_refuse()
         self._gain_refuse()
+        nb = getattr(self.operator, "weight_sets", (1, 1))[0]
+        if nb > 1 and int(B) != nb:      # one point-spread function per image (`per_image`): the weight rows ARE the batch's
+            raise ValueError(f"per_image: the operator carries one point-spread function per image of a batch of {nb}; the chain's "
+                             f"batch has {int(B)} images")
         (H, W), (h, w) = (int(v) for v in image_grid), (int(v) for v in measurement_grid)
         self.measurement_mask(B, h * w, device)
         if self._robust is not None:
@@ -1176,12 +1180,12 @@ class PosteriorSampling(ConditioningMethod):
         r0, r1 = self._batch_rows(rows, x0, y)
         mask = self._mask_rows(mask, r0, r1, y.shape[2] * y.shape[3])
         if self._blind() is not None:
-            if (r0, r1) != (0, self._batch[0]):
+            if self.operator.couples_batch and (r0, r1) != (0, self._batch[0]):
                 raise ValueError(f"blind_blur: the learnt PSF is shared by the batch -- the data term got rows {r0}:{r1} of the batch's "
                                  f"{self._batch[0]}; it takes ONE call over all its images")
-            return self._loss_grad_x0_blind(x0, y, g_out, loss_out, mask)
+            return self._loss_grad_x0_blind(x0, y, g_out, loss_out, mask, r0)
         if isinstance(self.operator, GRID_OPERATORS):
-            return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask)
+            return self._loss_grad_x0_separable(x0, y, g_out, loss_out, mask, r0)
         B, C, HW = x0.shape[0], x0.shape[1], x0.shape[2] * x0.shape[3]
         if y.shape[0] != B or y.shape[1] != 3 or C not in (3, 4):
             raise ValueError("expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,H,W]")
@@ -1216,12 +1220,19 @@ class PosteriorSampling(ConditioningMethod):
             ops.ps_loss_grad_c(x0.contiguous(), y.contiguous(), st["part"], loss, g, B, C, HW)
         return g.view(x0.shape), loss
 
-    def _loss_grad_x0_separable(self, x0, y, g_out=None, loss_out=None, mask=None):
+    @staticmethod
+    def _weight_rows(w, r0, B):
+        """The weight sets of a call on the B images from row r0 of the open batch: those rows of w [nb,nc,T] with one set per image,
+        else w."""
+        return w[r0:r0 + B] if w.shape[0] > 1 else w
+
+    def _loss_grad_x0_separable(self, x0, y, g_out=None, loss_out=None, mask=None, r0=0):
         """The data term through a separable linear operator, three stream-ordered launches and no host sync:
         Ax = A x0[:, 0:3] (osm_linop_apply, P = 3, image stride C HW); loss[b] = ||M (y - Ax)|| and r = d loss / d Ax (the identity
         term's own reduction, osm_ps_loss_grad_c / _mc at C = 3 on the measurement's h w); g[:, 0:3] = A^T r with the transposed
         tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3).
-        A `PSFOperator`: the same three launches with osm_psf_apply in the place of osm_linop_apply, `adjoint` set for A^T."""
+        A `PSFOperator`: the same three launches with osm_psf_apply in the place of osm_linop_apply, `adjoint` set for A^T; with more
+        than one weight set (`per_image` / `per_channel`) osm_psf_apply_s on the weight rows [r0:r0 + B] of the open batch."""
         from .measurements import PSFOperator
         B, C, H, W = x0.shape
         h, w = self.operator.out_shape(H, W)
@@ -1240,9 +1251,13 @@ class PosteriorSampling(ConditioningMethod):
         g = g_out if g_out is not None else st["g"]
         loss = loss_out if loss_out is not None else st["loss"]
         Ax, r = st["Ax"], st["r"]
+        sets = isinstance(self.operator, PSFOperator) and self.operator.weight_sets != (1, 1)
         if isinstance(self.operator, PSFOperator):
             taps, (Ry, Rx) = self.operator.taps(x0.device), self.operator.radius()
-            ops.psf_apply(x0.contiguous(), Ax, *taps, Ry, Rx, B, 3, C * HW, 3 * hw, H, W)
+            if sets:
+                taps = (taps[0], taps[1], self._weight_rows(taps[2], r0, B))
+            psf = ops.psf_apply_s if sets else ops.psf_apply
+            psf(x0.contiguous(), Ax, *taps, Ry, Rx, B, 3, C * HW, 3 * hw, H, W)
         else:
             tabs = self.operator.tables(H, W, x0.device)
             ops.linop_apply(x0.contiguous(), Ax, *tabs["fwd"], B, 3, C * HW, 3 * hw, H, W)
@@ -1251,13 +1266,15 @@ class PosteriorSampling(ConditioningMethod):
         else:
             ops.ps_loss_grad_c(Ax, y.contiguous(), st["part"], loss, r, B, 3, hw)
         if isinstance(self.operator, PSFOperator):
-            ops.psf_apply(r, g, *taps, Ry, Rx, B, 3, 3 * hw, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+            psf(r, g, *taps, Ry, Rx, B, 3, 3 * hw, C * HW, H, W, adjoint=True, zero_planes=C - 3)
         else:
             ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)
         return g.view(x0.shape), loss
 
-    def _loss_grad_x0_blind(self, x0, y, g_out=None, loss_out=None, mask=None):
-        """The data term through a `blind_blur` operator that learns its PSF: ONE call over the whole batch (the PSF is shared), the
+    def _loss_grad_x0_blind(self, x0, y, g_out=None, loss_out=None, mask=None, r0=0):
+        """The data term through a `blind_blur` operator that learns its PSF: ONE call over the whole batch (the PSF is shared) -- or,
+        with `per_image`, over any rows [r0:r0 + B] of it, each image stepping its own weight row (osm_ps_blind_optimize_s and the `_s`
+        single launches, include/osmosis_psfset.h; `per_channel`: one set per colour plane) -- the
         operator's n_iter inner iterations of  Ax = A(w) x0[:, 0:3];  loss, r = d loss / d Ax;  the tap gradient c = corr(r, x0);
         on the last iteration g[:, 0:3] = A(w)^T r;  the projected step of w  -- enqueued by one C call (osm_ps_blind_optimize,
         5 n_iter + 1 launches, no host sync); OSM_PHYS_PY_LOOP=1 walks the single-launch entry points.  loss and g are those before
@@ -1270,7 +1287,10 @@ class PosteriorSampling(ConditioningMethod):
         HW = H * W
         dy, dx, w = op.taps(x0.device)
         Ry, Rx = op.radius()
-        T, nparts = int(w.numel()), ops.tap_grad_nparts(3, H, W)
+        sets = op.weight_sets != (1, 1)
+        if sets:
+            w = self._weight_rows(w, r0, B)
+        T, nparts = int(dy.numel()), ops.tap_grad_nparts(3, H, W)
         key = ("blind", B, H, W, str(x0.device), C)
         st = self._states.get(key)
         if st is None or st["tpart"].numel() < B * nparts * T:
@@ -1285,19 +1305,27 @@ class PosteriorSampling(ConditioningMethod):
         loss = loss_out if loss_out is not None else st["loss"]
         x0, y = x0.contiguous(), y.contiguous()
         Ax, r, tpart = st["Ax"], st["r"], st["tpart"]
+        if sets:
+            apply, fused = ops.psf_apply_s, ops.ps_blind_optimize_s
+        else:
+            apply, fused = ops.psf_apply, ops.ps_blind_optimize
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
-            ops.ps_blind_optimize(x0, y, mask, dy, dx, w, Ry, Rx, B, C, H, W, Ax, r, st["part"], tpart, loss, g, op.n_iter, op.eta, op.l1)
+            fused(x0, y, mask, dy, dx, w, Ry, Rx, B, C, H, W, Ax, r, st["part"], tpart, loss, g, op.n_iter, op.eta, op.l1)
             return g.view(x0.shape), loss
         for it in range(op.n_iter):
-            ops.psf_apply(x0, Ax, dy, dx, w, Ry, Rx, B, 3, C * HW, 3 * HW, H, W)
+            apply(x0, Ax, dy, dx, w, Ry, Rx, B, 3, C * HW, 3 * HW, H, W)
             if mask is not None:
                 ops.ps_loss_grad_mc(Ax, y, mask, st["part"], loss, r, B, 3, HW)
             else:
                 ops.ps_loss_grad_c(Ax, y, st["part"], loss, r, B, 3, HW)
             ops.psf_tap_grad(x0, r, dy, dx, Ry, Rx, B, 3, C * HW, 3 * HW, H, W, tpart)
             if it == op.n_iter - 1:
-                ops.psf_apply(r, g, dy, dx, w, Ry, Rx, B, 3, 3 * HW, C * HW, H, W, adjoint=True, zero_planes=C - 3)
-            ops.psf_tap_step(w, tpart, loss, B, nparts, 3 * HW, op.eta, op.l1)
+                apply(r, g, dy, dx, w, Ry, Rx, B, 3, 3 * HW, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+            if sets:
+                ops.psf_tap_step_s(w, tpart, loss, B, 3, nparts // 3, 3 * HW, op.eta, op.l1, per_image=w.shape[0] > 1,
+                                   per_channel=w.shape[1] > 1)
+            else:
+                ops.psf_tap_step(w, tpart, loss, B, nparts, 3 * HW, op.eta, op.l1)
         return g.view(x0.shape), loss
 
     def conditioning(self, x_prev, x_t, x_0_hat, measurement, **kwargs):

@@ -276,9 +276,32 @@ class SuperResolutionOperator(SeparableOperator):
 # A 2-D kernel that does not factor per axis (motion blur, a measured PSF) travels as a tap list: the offsets (dy, dx) of its non-zeros
 # from the anchor (the centre) and their weights (osm_psf_apply, include/osmosis_psf.h).  The adjoint is the same kernel launch with
 # `adjoint` set: the transpose of reflection padding folds the mirrored taps back.
-def _psf_op():
-    from .. import torch_ops  # noqa: F401  (registers osmosis::psf_apply)
-    return torch.ops.osmosis.psf_apply
+def _psf_op(sets=False):
+    from .. import torch_ops  # noqa: F401  (registers osmosis::psf_apply and osmosis::psf_apply_s)
+    return torch.ops.osmosis.psf_apply_s if sets else torch.ops.osmosis.psf_apply
+
+
+def check_kernel_sets(kernel, per_image, per_channel, batch_size, what="psf"):
+    """The float64 [nb,nc,kh,kw] array of the PSFs of an operator: `kernel` is [kh,kw], [3,kh,kw] with `per_channel`, [B,kh,kw] with
+    `per_image` and [B,3,kh,kw] with both (B = batch_size); ValueError for a shape that does not match the flags, and for any
+    kernel `check_kernel2d` refuses."""
+    try:
+        k = np.asarray(kernel, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: the kernel must be an array of numbers ({e})")
+    want = 2 + bool(per_image) + bool(per_channel)
+    if k.ndim != want:
+        raise ValueError(f"{what}: with per_image={bool(per_image)}, per_channel={bool(per_channel)} the kernel is "
+                         f"{'[B,' if per_image else '['}{'3,' if per_channel else ''}kh,kw], got shape {k.shape}")
+    k = k.reshape((k.shape[0] if per_image else 1, k.shape[-3] if per_channel else 1) + k.shape[-2:])
+    if per_channel and k.shape[1] != 3:
+        raise ValueError(f"{what}: per_channel takes one kernel per colour plane (3), got {k.shape[1]}")
+    if per_image and k.shape[0] != int(batch_size):
+        raise ValueError(f"{what}: per_image takes one kernel per image of the batch: {k.shape[0]} kernels for batch_size {batch_size}")
+    for b in range(k.shape[0]):
+        for c in range(k.shape[1]):
+            check_kernel2d(k[b, c], what)
+    return k
 
 
 def check_kernel2d(kernel, what="psf"):
@@ -305,23 +328,68 @@ class PSFOperator(LinearOperator):
     measurement has the image's size.  A subclass gives `kernel2d()` (float64 [kh, kw], both sides odd, anchor at the centre); the
     non-zero taps are taken in row-major order, their weights cast to fp32, and cached as device tensors per device.  `forward` /
     `transpose` run osm_psf_apply through `osmosis::psf_apply`, which is differentiable (its backward is the same operator with
-    `adjoint` flipped), so autograd conditioning works too."""
+    `adjoint` flipped), so autograd conditioning works too.
+    WEIGHT SETS (include/osmosis_psfset.h): `weight_sets` = (nb, nc), default (1, 1).  An operator with one PSF per image (nb =
+    batch_size) and / or per colour plane (nc = 3) keeps its kernels in `_kernels` float64 [nb,nc,kh,kw] (`kernels()`); the tap list
+    is then the row-major UNION of the kernels' non-zeros, a kernel without a tap there carries 0.0, and the weights are
+    w [nb,nc,T]: plane p of image b is blurred with set (nb > 1 ? b : 0, nc > 1 ? p : 0) through `osmosis::psf_apply_s`.  Such an
+    operator takes batches of exactly nb images (and nc planes); `kernel2d()` is what it was for one set and raises for more."""
+
+    _sets = (1, 1)
+    _kernels = None         # float64 [nb,nc,kh,kw] of an operator with more than one weight set
 
     def __init__(self, device, batch_size=1, **kwargs):
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
         self.batch_size = batch_size
         self._host, self._dev = None, {}
 
+    @property
+    def weight_sets(self):
+        """(nb, nc): how many PSFs the operator carries per batch and per image -- (1, 1): one for every plane of every image."""
+        return self._sets
+
+    def _name(self):
+        return getattr(self, "__name__", type(self).__name__)
+
     def kernel2d(self):
         raise NotImplementedError
 
+    def _single(self, k):
+        """`kernel2d()` of a subclass that may carry several kernels: the one kernel, or ValueError naming `kernels()`."""
+        if self.weight_sets != (1, 1):
+            raise ValueError(f"{self._name()}: the operator carries {self.weight_sets[0]} x {self.weight_sets[1]} point-spread functions "
+                             f"(per image x per channel); kernel2d() is one kernel -- use kernels()")
+        return k
+
+    def kernels(self):
+        """Every PSF of the operator, float64 [nb,nc,kh,kw]."""
+        if self.weight_sets == (1, 1):
+            return np.asarray(self.kernel2d(), dtype=np.float64)[None, None].copy()
+        return self._kernels.copy()
+
     def host_taps(self):
-        """(dy int32 [T], dx int32 [T], w fp32 [T]): the kernel's non-zeros in row-major order, offsets from the centre."""
+        """(dy int32 [T], dx int32 [T], w fp32): the kernel's non-zeros in row-major order, offsets from the centre, w [T]; with more
+        than one weight set the union of the kernels' non-zeros and w [nb,nc,T]."""
+        if self._host is None and self.weight_sets != (1, 1):
+            ks = self._kernels
+            iy, ix = np.nonzero((ks != 0).any(axis=(0, 1)))                         # row-major union
+            self._host = ((iy - ks.shape[2] // 2).astype(np.int32), (ix - ks.shape[3] // 2).astype(np.int32),
+                          np.ascontiguousarray(ks[:, :, iy, ix].astype(np.float32)))
         if self._host is None:
-            k = check_kernel2d(self.kernel2d(), getattr(self, "__name__", type(self).__name__))
+            k = check_kernel2d(self.kernel2d(), self._name())
             iy, ix = np.nonzero(k)                                                  # row-major
             self._host = ((iy - k.shape[0] // 2).astype(np.int32), (ix - k.shape[1] // 2).astype(np.int32), k[iy, ix].astype(np.float32))
         return self._host
+
+    def check_batch(self, B, P=3):
+        """ValueError unless a batch of B images with P planes is one the operator's weight sets serve (nb in (1, B), nc in (1, P))."""
+        nb, nc = self.weight_sets
+        if nb > 1 and int(B) != nb:
+            raise ValueError(f"{self._name()}: the operator carries one point-spread function per image of a batch of {nb} (per_image); "
+                             f"got a batch of {int(B)}")
+        if nc > 1 and int(P) != nc:
+            raise ValueError(f"{self._name()}: the operator carries one point-spread function per colour plane ({nc}, per_channel); "
+                             f"got {int(P)} planes")
 
     def radius(self):
         """(Ry, Rx): the largest |dy| and |dx| of the taps."""
@@ -348,6 +416,9 @@ class PSFOperator(LinearOperator):
 
     def _apply(self, data, adjoint):
         self.out_shape(*data.shape[-2:])
+        if self.weight_sets != (1, 1):
+            self.check_batch(data.shape[0], data.shape[1])
+            return _psf_op(True)(data, *self.taps(data.device), *self.radius(), adjoint)
         return _psf_op()(data, *self.taps(data.device), *self.radius(), adjoint)
 
     def forward(self, data, **kwargs):
@@ -413,31 +484,56 @@ def motion_kernel(kernel_size=61, intensity=0.5, seed=0):
 @register_operator(name="motion_blur")
 class MotionBlurOperator(PSFOperator):
     """Blur with a random camera-shake trajectory, `motion_kernel(kernel_size, intensity, seed)`.  DPS config keys: kernel_size (odd,
-    default 61), intensity (in [0, 1], default 0.5: 0 a straight streak, 1 the most erratic path); `seed` (default 0) picks the path."""
+    default 61), intensity (in [0, 1], default 0.5: 0 a straight streak, 1 the most erratic path); `seed` (default 0) picks the path.
+    A LIST of seeds gives every image of the batch its own trajectory (`per_image`: weight sets (batch_size, 1)); its length must
+    equal batch_size."""
 
     def __init__(self, device, kernel_size=61, intensity=0.5, seed=0, batch_size=1, **kwargs):
         super().__init__(device, batch_size, **kwargs)
-        self._kernel = motion_kernel(kernel_size, intensity, seed)                  # validates its arguments
+        self.per_image = isinstance(seed, (list, tuple))
+        if self.per_image:
+            if len(seed) != int(batch_size) or len(seed) < 1:
+                raise ValueError(f"motion_blur: a list under `seed` is one trajectory per image: {len(seed)} seeds for batch_size {batch_size}")
+            self._kernels = np.stack([motion_kernel(kernel_size, intensity, s) for s in seed])[:, None]
+            self._sets = (len(seed), 1)
+            self._kernel = self._kernels[0, 0]
+            seed = list(seed)
+        else:
+            self._kernel = motion_kernel(kernel_size, intensity, seed)              # validates its arguments
         self.kernel_size, self.intensity, self.seed = int(kernel_size), float(intensity), seed
 
     def kernel2d(self):
-        return self._kernel
+        return self._single(self._kernel)
 
 
 @register_operator(name="psf_blur")
 class PSFBlurOperator(PSFOperator):
     """Blur with a point-spread function of the user's: `kernel` is a 2-D array, a nested list, or the path of a .npy file holding one
     (both sides odd, finite; the anchor is the centre, applied as cross-correlation); `normalize` (default True) divides it by its
-    float64 sum, which must not be zero."""
+    float64 sum, which must not be zero.
+    `per_channel`: `kernel` is [3,kh,kw], one PSF per colour plane (lateral chromatic aberration, wavelength-dependent scattering);
+    `per_image`: [B,kh,kw] with B = batch_size, one per image; both: [B,3,kh,kw].  A shape that does not match the flags raises;
+    `normalize` acts per kernel."""
 
-    def __init__(self, device, kernel=None, normalize=True, batch_size=1, **kwargs):
+    def __init__(self, device, kernel=None, normalize=True, batch_size=1, per_image=False, per_channel=False, **kwargs):
         super().__init__(device, batch_size, **kwargs)
+        self.per_image, self.per_channel = bool(per_image), bool(per_channel)
         if kernel is None:
             raise ValueError("psf_blur: a `kernel` is required (a 2-D array, a nested list or the path of a .npy file)")
         if isinstance(kernel, (str, bytes)) or hasattr(kernel, "__fspath__"):
             kernel = np.load(kernel, allow_pickle=False)
         if isinstance(kernel, torch.Tensor):
             kernel = kernel.detach().cpu().numpy()
+        if self.per_image or self.per_channel:
+            ks = check_kernel_sets(kernel, self.per_image, self.per_channel, batch_size, "psf_blur")
+            if normalize:
+                totals = ks.sum(axis=(2, 3), keepdims=True)
+                if (totals == 0.0).any() or not np.isfinite(totals).all():
+                    raise ValueError(f"psf_blur: normalize divides every kernel by its sum; the sums are {totals.reshape(ks.shape[:2]).tolist()}")
+                ks = ks / totals
+            self._kernels, self._sets = ks, tuple(ks.shape[:2])
+            self._kernel, self.normalize = ks[0, 0], bool(normalize)
+            return
         k = check_kernel2d(kernel, "psf_blur")
         if normalize:
             total = float(k.sum())
@@ -447,7 +543,7 @@ class PSFBlurOperator(PSFOperator):
         self._kernel, self.normalize = k, bool(normalize)
 
     def kernel2d(self):
-        return self._kernel
+        return self._single(self._kernel)
 
 
 BLIND_MAX_KERNEL = 61      # the largest side of a learnt PSF (the window a workgroup of osm_psf_tap_grad stages: halo <= 32 per side)
@@ -499,27 +595,31 @@ class BlindBlurOperator(PSFOperator):
     in row-major order, Ry = Rx = k // 2) whose weights are LEARNT during sampling: they live in a device tensor `w` fp32 [T] that
     the step kernel overwrites between the network's forward and backward, with no host sync (osm_ps_blind_optimize,
     include/osmosis_blind.h: a projected gradient step on Q(w) = sum_b ||M (y_b - A(w) x0_b)||^2 / (2 * 3 h w) per inner iteration).
-    The PSF is shared by the batch (`couples_batch`): a batch is photos through one optical system, a single shaken photo is B = 1 --
-    `restore_images(batch_size > 1)` over photos with unrelated shakes is the wrong model (one kernel would be fitted to all).
+    By default the PSF is shared by the batch (`couples_batch`): photos through one optical system.  `per_image: True` learns one
+    PSF per image of the batch (photos with unrelated shakes; the images stay independent, `couples_batch` is False and a chunked
+    batch needs no grouped walk), `per_channel: True` one per colour plane (lateral chromatic aberration, wavelength-dependent
+    scattering); the live weights are then `w` fp32 [nb,nc,T] with nb = batch_size or 1, nc = 3 or 1, every set starting from the
+    init and stepped on its own simplex from its own images / planes (osm_ps_blind_optimize_s, include/osmosis_psfset.h).
     Config keys: kernel_size (odd, <= 61, default 31); init ('gaussian' with init_sigma default kernel_size / 6, 'delta', 'uniform',
     or a kernel: array / nested list / .npy path, non-negative, normalised to sum 1 in float64); eta (step size, 0.1), n_iter (inner
-    iterations per guided sub-step, 1), l1 (sparsity shrinkage, 0.0); learn (True).  The defaults are parameters, not tuned values.
+    iterations per guided sub-step, 1), l1 (sparsity shrinkage, 0.0); learn (True); per_image (False), per_channel (False).  The defaults are parameters, not tuned values.
     `learn: False` IS `psf_blur` with the init kernel (its non-zero taps, the three-launch data term, nothing stepped); the driver
     still treats it by its name: `simulate: True` needs `simulate_with`, so that switching `learn` does not change the measurement.
     An unknown config key raises ValueError.
     `taps(device)` returns (dy, dx, w_live); `forward` / `transpose` apply the current estimate; `kernel2d()` copies it from the
-    device on demand only; `reset()` puts the initial weights back (same tensors: recorded launches stay valid)."""
+    device on demand only (one set; `kernels()` [nb,nc,k,k] for any number); `reset()` puts the initial weights of every set back
+    (same tensors: recorded launches stay valid).  Not learning, the flags change nothing: every set would be the init."""
 
     couples_batch = True
 
     DRIVER_KEYS = ("simulate", "simulate_with")       # read by `sampling.restore_image`, not by the operator
 
     def __init__(self, device, kernel_size=31, init="gaussian", init_sigma=None, eta=0.1, n_iter=1, l1=0.0, learn=True, batch_size=1,
-                 **kwargs):
+                 per_image=False, per_channel=False, **kwargs):
         unknown = sorted(set(kwargs) - set(self.DRIVER_KEYS))
         if unknown:                                   # (a mistyped `n_iters` would otherwise run with the default, silently)
             raise ValueError(f"blind_blur: unknown config key(s) {unknown} (known: kernel_size, init, init_sigma, eta, n_iter, l1, learn, "
-                             f"simulate, simulate_with)")
+                             f"per_image, per_channel, simulate, simulate_with)")
         super().__init__(device, batch_size, **kwargs)
         self._init = blind_init_kernel(kernel_size, init, init_sigma)
         self.kernel_size = int(kernel_size)
@@ -532,7 +632,14 @@ class BlindBlurOperator(PSFOperator):
             raise ValueError(f"blind_blur: n_iter must be an integer >= 1, got {n_iter!r}")
         self.n_iter = int(n_iter)
         self.learn = bool(learn)
-        self.couples_batch = self.learn          # (a fixed kernel leaves the images of a batch independent)
+        for key, v in (("per_image", per_image), ("per_channel", per_channel)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError(f"blind_blur: {key} must be True or False, got {v!r}")
+        self.per_image, self.per_channel = bool(per_image), bool(per_channel)
+        if self.learn:
+            self._sets = (max(1, int(batch_size)) if self.per_image else 1, 3 if self.per_channel else 1)
+        # a fixed kernel leaves the images of a batch independent, and so does one learnt kernel per image
+        self.couples_batch = self.learn and not self.per_image
 
     def host_taps(self):
         if not self.learn:
@@ -540,7 +647,10 @@ class BlindBlurOperator(PSFOperator):
         if self._host is None:
             k = self.kernel_size
             iy, ix = np.divmod(np.arange(k * k), k)
-            self._host = ((iy - k // 2).astype(np.int32), (ix - k // 2).astype(np.int32), self._init.reshape(-1).astype(np.float32))
+            w = self._init.reshape(-1).astype(np.float32)
+            if self.weight_sets != (1, 1):
+                w = np.ascontiguousarray(np.broadcast_to(w, self.weight_sets + w.shape))
+            self._host = ((iy - k // 2).astype(np.int32), (ix - k // 2).astype(np.int32), w)
         return self._host
 
     def radius(self):
@@ -558,13 +668,18 @@ class BlindBlurOperator(PSFOperator):
         ('cuda' and 'cuda:0' are different keys there: an index-less device finds them all the same), else the ones made last."""
         if not self.learn:
             return self._init.copy()
+        return self._single(self.kernels()[0, 0])
+
+    def kernels(self):
+        """The current estimate of every set, float64 [nb,nc,k,k] (one device-to-host copy); not learning: the init [1,1,k,k]."""
+        if not self.learn:
+            return self._init[None, None].copy()
         t = self._dev.get(str(self.device))
         if t is None and self._dev:
             same = [v for v in self._dev.values() if v[2].device.type == self.device.type]
             t = (same or list(self._dev.values()))[-1]
-        if t is None:
-            return self.host_taps()[2].astype(np.float64).reshape(self._init.shape)
-        return t[2].detach().cpu().numpy().astype(np.float64).reshape(self._init.shape)
+        w = self.host_taps()[2] if t is None else t[2].detach().cpu().numpy()
+        return w.astype(np.float64).reshape(self.weight_sets + self._init.shape)
 
     def reset(self):
         """Put the initial weights back on every device the operator lives on, in place."""
@@ -612,12 +727,21 @@ def build_degradation(degradation, device, batch_size=1):
     keys} built here.  NameError for a name nobody registered, ValueError for one that is no `GRID_OPERATORS` class and for
     'blind_blur' (by name: it is a `PSFOperator`, but a learnt PSF inside the water / haze model is out of scope)."""
     if degradation is None or not isinstance(degradation, dict):
+        if getattr(degradation, "weight_sets", (1, 1)) != (1, 1):
+            raise ValueError(f"degradation: the operator carries more than one point-spread function (per_image / per_channel: weight sets "
+                             f"{degradation.weight_sets}), which a physical image-formation model does not take -- the composed route "
+                             f"applies the operator to the depth-weight plane too, which has no channel; give one kernel")
         return degradation
     cfg = dict(degradation)
     name = cfg.pop("name", None)
     if name == "blind_blur":
         raise ValueError("degradation: 'blind_blur' (a learnt PSF) inside a physical image-formation model is not supported -- its "
                          "weights and the water / haze parameters would have to be stepped together; give a fixed 'psf_blur' kernel")
+    many = [k for k in ("per_image", "per_channel") if cfg.get(k)] + (["seed (a list)"] if isinstance(cfg.get("seed"), (list, tuple)) else [])
+    if many:
+        raise ValueError(f"degradation: {name!r} with {', '.join(many)} carries more than one point-spread function, which a physical "
+                         f"image-formation model does not take -- the composed route applies the operator to the depth-weight plane "
+                         f"too, which has no channel; give one kernel")
     cls = __OPERATOR__.get(name)
     grid = sorted(n for n, c in __OPERATOR__.items() if issubclass(c, GRID_OPERATORS))
     if cls is None:

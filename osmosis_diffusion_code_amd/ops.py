@@ -805,6 +805,74 @@ def ps_blind_optimize(x0, y, mask, dy, dx, w, Ry, Rx, B, Cc, H, W, Ax, r, lpart,
          keep=(x0, y, mask, dy, dx, w, Ax, r, lpart, tpart, loss, g))
 
 
+# ----------------------------------------------------------------------------- PSF weight sets (include/osmosis_psfset.h)
+def _check_weight_sets(name, dy, dx, w, B, P):
+    """(nb, nc, T) of the weight sets w fp32 [nb,nc,T] beside the tap list dy, dx int32 [T]: nb in {1, B}, nc in {1, P}."""
+    _check_tap_lists(name, dy, dx)
+    T = int(dy.shape[0])
+    if w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 3 or w.shape[2] != T or w.shape[0] not in (1, int(B)) \
+            or w.shape[1] not in (1, int(P)):
+        raise _lib.OsmosisHipError(f"{name}: the weight sets are contiguous fp32 [nb,nc,T = {T}] with nb in (1, {int(B)}) and nc in (1, {int(P)}), "
+                                   f"got {tuple(w.shape)} {w.dtype}")
+    return int(w.shape[0]), int(w.shape[1]), T
+
+
+def psf_apply_s(x, out, dy, dx, w, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint=False, zero_planes=0):
+    """`psf_apply` with weight sets w fp32 [nb,nc,T] (osm_psf_apply_s, include/osmosis_psfset.h): plane p of image b is blurred with
+    set (nb > 1 ? b : 0, nc > 1 ? p : 0); nb in {1, B}, nc in {1, P}.  Everything else is `psf_apply`'s."""
+    for t in (x, out):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_apply_s takes contiguous fp32 tensors")
+    B, P, Z, H, W = int(B), int(P), int(zero_planes), int(H), int(W)
+    nb, nc, T = _check_weight_sets("psf_apply_s", dy, dx, w, B, P)
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * H * W
+                   or out.numel() < (B - 1) * int(out_img_stride) + (P + Z) * H * W):
+        raise _lib.OsmosisHipError(f"psf_apply_s: x ({x.numel()} elements) / out ({out.numel()}) are smaller than {B} images of "
+                                   f"{P} -> {P + Z} planes of {H} x {W} at strides {x_img_stride} / {out_img_stride}")
+    call("osm_psf_apply_s", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), B, P, int(x_img_stride),
+         int(out_img_stride), H, W, 1 if adjoint else 0, Z, nc * T if nb > 1 else 0, T if nc > 1 else 0, _s(), keep=(x, out, dy, dx, w))
+
+
+def psf_tap_step_s(w, part, loss, B, P, ntiles, hw3, eta, l1=0.0, per_image=False, per_channel=False):
+    """One projected step of every weight set of w fp32 [nb,nc,T], in place (osm_psf_tap_step_s): nb = B if per_image else 1,
+    nc = P if per_channel else 1; set (bi, ci) takes `psf_tap_step`'s step from its own images and its own plane's partials of
+    part [B][P ntiles][T], and is left untouched when its own sum is 0 or not finite."""
+    for t in (w, part, loss):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_tap_step_s takes contiguous fp32 tensors")
+    B, P, ntiles = int(B), int(P), int(ntiles)
+    want = (B if per_image else 1, P if per_channel else 1)
+    if w.dim() != 3 or tuple(w.shape[:2]) != want:
+        raise _lib.OsmosisHipError(f"psf_tap_step_s: the weight sets are [nb,nc,T] = [{want[0]},{want[1]},T] for per_image={bool(per_image)}, "
+                                   f"per_channel={bool(per_channel)} at B = {B}, P = {P}, got {tuple(w.shape)}")
+    T = int(w.shape[2])
+    if B >= 1 and (part.numel() < B * P * ntiles * T or loss.numel() < B):
+        raise _lib.OsmosisHipError(f"psf_tap_step_s: part ({part.numel()} elements) / loss ({loss.numel()}) are smaller than "
+                                   f"{B} x {P * ntiles} x {T} / {B}")
+    call("osm_psf_tap_step_s", ptr(w), ptr(part), ptr(loss), B, P, ntiles, T, int(hw3), float(eta), float(l1), 1 if per_image else 0,
+         1 if per_channel else 0, _s(), keep=(w, part, loss))
+
+
+def ps_blind_optimize_s(x0, y, mask, dy, dx, w, Ry, Rx, B, Cc, H, W, Ax, r, lpart, tpart, loss, g, n_iter, eta, l1=0.0):
+    """`ps_blind_optimize` with weight sets w fp32 [nb,nc,T], nb in {1, B}, nc in {1, 3} (osm_ps_blind_optimize_s): every set is
+    stepped from its own images / planes; the flags are read off w's shape."""
+    B, Cc, H, W = int(B), int(Cc), int(H), int(W)
+    HW = H * W
+    nb, nc, T = _check_weight_sets("ps_blind_optimize_s", dy, dx, w, B, 3)
+    need = dict(x0=B * Cc * HW, y=B * 3 * HW, Ax=B * 3 * HW, r=B * 3 * HW, lpart=B * phys_nblk(HW), tpart=B * tap_grad_nparts(3, H, W) * T,
+                loss=B, g=B * Cc * HW)
+    if mask is not None:
+        need["mask"] = B * 3 * HW
+    have = dict(x0=x0, y=y, Ax=Ax, r=r, lpart=lpart, tpart=tpart, loss=loss, g=g, mask=mask)
+    for k, n in need.items():
+        t = have[k]
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise _lib.OsmosisHipError(f"ps_blind_optimize_s: {k} must be contiguous fp32 with at least {n} elements, got {tuple(t.shape)} {t.dtype}")
+    call("osm_ps_blind_optimize_s", ptr(x0), ptr(y), ptr(mask), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), B, Cc, H, W, ptr(Ax), ptr(r),
+         ptr(lpart), ptr(tpart), ptr(loss), ptr(g), int(n_iter), float(eta), float(l1), 1 if nb > 1 else 0, 1 if nc > 1 else 0, _s(),
+         keep=(x0, y, mask, dy, dx, w, Ax, r, lpart, tpart, loss, g))
+
+
 # ----------------------------------------------------------------------------- the water / haze data term through a linear operator
 def lin_desc(operator, H, W, device) -> LinDesc:
     """The osm_lin_desc of a `measurements.GRID_OPERATORS` instance at the image grid H x W (include/osmosis_physlin.h).  The device
@@ -814,6 +882,9 @@ def lin_desc(operator, H, W, device) -> LinDesc:
     h, w = operator.out_shape(H, W)
     d.H, d.W, d.h, d.w = int(H), int(W), int(h), int(w)
     if isinstance(operator, PSFOperator):
+        if operator.weight_sets != (1, 1):
+            raise _lib.OsmosisHipError(f"lin_desc: the operator carries weight sets {operator.weight_sets} (per_image / per_channel); the "
+                                       "composed water / haze data term takes one point-spread function")
         dy, dx, tw = operator.taps(device)
         d.family, d.dy, d.dx, d.tap_w, d.T = 1, ptr(dy), ptr(dx), ptr(tw), int(tw.shape[0])
         d.Ry, d.Rx = operator.radius()

@@ -336,8 +336,15 @@ def output_images(post, ref_img, gt_rgb_01=None, gt_depth_01=None):
     `input` = the reference image in [0,1], `rgb` = the clipped restoration, `depth_color` = viridis of the percentile-normalised
     depth, `depth_raw` = the min-max-normalised depth (one channel), `grid` = make_grid([input, rgb, depth_color] (+ [zeros,
     gt rgb, gt depth colour] when a ground truth exists: :341-344), nrow=3, pad_value=1.) through the reference's
-    clip_image(scale=False, move=False, is_uint8=True) (clamp, truncate)."""
+    clip_image(scale=False, move=False, is_uint8=True) (clamp, truncate).
+    A result without depth entries (`rgb_guidance_result` of a 3-channel sample): `input`, `rgb` and the grid of those two tiles
+    (+ the ground-truth rgb)."""
     ref01 = 0.5 * (ref_img.detach().cpu()[0] + 1)
+    if "depth_pmm" not in post:
+        tiles = [_replicate_to(ref01, post["rgb_01_clip"].shape[-2:]), post["rgb_01_clip"]] + ([] if gt_rgb_01 is None else [gt_rgb_01])
+        grid = make_grid(tiles, nrow=3, pad_value=1.0)
+        grid = (grid * 255).clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
+        return {"input": _to_pil_u8(ref01), "rgb": _to_pil_u8(post["rgb_01_clip"]), "grid": grid}
     col = depth_color(post)
     tiles = [_replicate_to(ref01, post["rgb_01_clip"].shape[-2:]), post["rgb_01_clip"], col]
     if gt_rgb_01 is not None:
@@ -365,7 +372,7 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
     imgs = output_images(post, ref_img, gt_rgb_01, gt_depth_01)
     paths = {}
     if save_singles:
-        for kind in ("input", "rgb", "depth_color", "depth_raw"):
+        for kind in (k for k in ("input", "rgb", "depth_color", "depth_raw") if k in imgs):
             d = os.path.join(out_dir, "single_images", kind)
             os.makedirs(d, exist_ok=True)
             paths[kind] = os.path.join(d, f"{name}.png")
@@ -394,11 +401,12 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         paths["depth_prior"] = os.path.join(d, f"{name}_depth_prior.png")
         Image.fromarray(metric_u8, mode="RGB").save(paths["depth_metric"])
         Image.fromarray(prior_u8, mode="RGB").save(paths["depth_prior"])
-    if save_singles and post.get("kernel") is not None:     # only a `blind_blur` chain: the learnt PSF
+    if save_singles and post.get("kernel") is not None:     # only a `blind_blur` chain: the learnt PSF ([3,k,k] per channel: one RGB picture)
         d = os.path.join(out_dir, "single_images", "kernel")
         os.makedirs(d, exist_ok=True)
         paths["kernel"] = os.path.join(d, f"{name}_kernel.png")
-        Image.fromarray(kernel_image_u8(post["kernel"]), mode="L").save(paths["kernel"])
+        u8 = kernel_image_u8(post["kernel"])
+        Image.fromarray(u8, mode="L" if u8.ndim == 2 else "RGB").save(paths["kernel"])
     if save_grids:
         d = os.path.join(out_dir, "grid_results")
         os.makedirs(d, exist_ok=True)
@@ -432,13 +440,15 @@ def depth_metric_images_u8(post):
 
 def kernel_image_u8(kernel, side=128):
     """uint8 [k z, k z] picture of a PSF [k, k]: the kernel over its maximum (negative values clamped to 0), every tap replicated to a
-    z x z block of pixels, z = max(1, side // k) -- no interpolation, a tap stays a square."""
+    z x z block of pixels, z = max(1, side // k) -- no interpolation, a tap stays a square.  A per-channel PSF [3, k, k]: one RGB
+    picture uint8 [k z, k z, 3], every plane over the COMMON maximum."""
     k = torch.as_tensor(kernel, dtype=torch.float32).clamp(min=0)
     top = float(k.max())
     k = k / top if top > 0 else k
-    z = max(1, int(side) // int(max(k.shape)))
+    z = max(1, int(side) // int(max(k.shape[-2:])))
     u8 = (k * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
-    return u8.repeat_interleave(z, dim=0).repeat_interleave(z, dim=1).contiguous().numpy()
+    u8 = u8.repeat_interleave(z, dim=-2).repeat_interleave(z, dim=-1)
+    return (u8.permute(1, 2, 0) if u8.dim() == 3 else u8).contiguous().numpy()
 
 
 def full_depth_color_u8(full_res):
@@ -516,7 +526,10 @@ def depth_color(post):
 def rgb_guidance_result(sample, measurement):
     """What the reference driver derives from the sample of an rgb-guidance / non-osmosis chain (osmosis_sampling.py:366-380; image 0
     of `sample`): RGB and depth split, the clipped [0, 1] RGB, the min-max and the percentile-normalised three-channel depth.  No phi,
-    no recomposition.  CPU tensors."""
+    no recomposition.  CPU tensors.  A 3-channel sample (the RGB model family) has no depth plane: its three planes are `rgb`, and
+    the result has no depth entries."""
+    if sample.shape[1] == 3:
+        return {"sample": sample, "rgb": sample[0], "rgb_01_clip": torch.clamp(0.5 * (sample[0] + 1), 0, 1), "measurement": measurement}
     depth3 = sample[0, -1].repeat(3, 1, 1)
     return {"sample": sample, "rgb": sample[0, 0:-1], "rgb_01_clip": torch.clamp(0.5 * (sample[0, 0:-1] + 1), 0, 1),
             "depth_mm": utilso.min_max_norm_range(depth3, vmin=0, vmax=1, is_uint8=False),
@@ -544,6 +557,11 @@ def measurement_grid(operator_cfg, hw):
     if cls is None or not issubclass(cls, GRID_OPERATORS) or not operator_cfg.get("simulate", True):
         return tuple(hw)
     kw = {k: v for k, v in operator_cfg.items() if k != "name"}
+    if "batch_size" not in kw:          # per-image PSFs: the batch is as large as the list says (the grid does not depend on it)
+        if isinstance(kw.get("seed"), (list, tuple)):
+            kw["batch_size"] = len(kw["seed"])
+        elif kw.get("per_image") and isinstance(kw.get("kernel"), (list, tuple, np.ndarray, torch.Tensor)):
+            kw["batch_size"] = len(kw["kernel"])
     return tuple(cls(device="cpu", **kw).out_shape(int(hw[0]), int(hw[1])))
 
 
@@ -632,9 +650,11 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     also in chunked batches; `save_outputs` writes `<name>_gain.png`.  Without it nothing is passed and there are no such keys.
 
     Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
-    carries `kernel` fp32 [k,k] (the estimate at the end of its chain; `save_outputs` writes it as `<name>_kernel.png`), and
-    `simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` -- the blur that makes y = noiser(A* ref); it must keep the
-    image's size.  ONE PSF serves the whole batch: B > 1 means photos through one optical system, not unrelated shakes."""
+    carries `kernel` fp32 [k,k] (the estimate at the end of its chain; [3,k,k] with `per_channel`; `save_outputs` writes it as
+    `<name>_kernel.png`, a per-channel one as one RGB picture), and `simulate: True` needs `simulate_with: {name: <a grid operator>,
+    ...}` -- the blur that makes y = noiser(A* ref); it must keep the image's size.  Without `per_image` ONE PSF serves the whole
+    batch (photos through one optical system); with `per_image: True` every image of the batch learns -- and its result carries --
+    its own."""
     return [_image_result(run, 0, whole=True)
             for run in _run_chains(model, ref_img, cfg, device=device, image_idx=image_idx, x_scale=x_scale,
                                    same_seed_per_image=same_seed_per_image, mask=mask, tiling=tiling, depth=depth,
@@ -648,8 +668,8 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
     WHOLE batch, on the host -- what `_image_result` builds any image's result dict from.  Fields (None where the chain has no such
     thing): `sample`; on the Osmosis branch `variables`, `loss`, `pred_xstart`, `observed` [B,3,h,w] (`observed_image`, a
     degradation), `depth` {z, m [B,1,HW], scale, shift, loss [B], align}, `gain` {nodes, field} and `tiling`; `mask` [B,3,h,w];
-    `robust` {weight [B,3,h,w], scale [B]}; `kernel`; `solver` / `steps`; `measurement` (y_n); `ref_img` and `operator_cfg` for
-    `postprocess`."""
+    `robust` {weight [B,3,h,w], scale [B]}; `kernel` [nb,nc,k,k] (`operator.kernels()`); `solver` / `steps`; `measurement` (y_n);
+    `ref_img` and `operator_cfg` for `postprocess`."""
     tiling = tiling if tiling is not None else cfg.get("tiling")
     tiling_info = None
     if tiling is not None:
@@ -748,7 +768,7 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
             ref_img=ref_img, operator_cfg=measure["operator"], measurement=y_n.detach().cpu(), variables=None, loss=None,
             pred_xstart=None, observed=None, depth=None, gain=None, tiling=None, robust=None,
             mask=None if m_dev is None else m_dev.detach().cpu(),
-            kernel=torch.from_numpy(operator.kernel2d()).to(torch.float32) if is_blind else None,
+            kernel=_operator_kernels(operator) if is_blind else None,      # [nb,nc,k,k]
             solver=solver, steps=None if solver is None else sampler.num_timesteps)
         vals = None if robust is None else cond.robust_values()     # (None: no guided sub-step on a loop that never opened the state)
         if vals is not None:
@@ -770,6 +790,13 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
         if gain is not None:
             run.gain = {k: v.detach().cpu() for k, v in cond.gain_values().items()}
         yield run
+
+
+def _operator_kernels(operator):
+    """fp32 [nb,nc,k,k]: every PSF of a `blind_blur` operator at the end of its chain (`kernels()`; an operator that only knows
+    `kernel2d()` has the one)."""
+    ks = operator.kernels() if hasattr(operator, "kernels") else np.asarray(operator.kernel2d())[None, None]
+    return torch.from_numpy(np.ascontiguousarray(ks)).to(torch.float32)
 
 
 def _image_result(run, b, whole=False):
@@ -795,8 +822,9 @@ def _image_result(run, b, whole=False):
         post["mask"] = run.mask[rows]
     if run.robust is not None:
         attach_robust(post, run.robust["weight"][b], run.robust["scale"][b])
-    if run.kernel is not None:
-        post["kernel"] = run.kernel
+    if run.kernel is not None:          # image b's own PSF ([nb,nc,k,k]: one row for the batch, or one per image): [k,k], or [3,k,k] per channel
+        kb = run.kernel[b if run.kernel.shape[0] > 1 else 0]
+        post["kernel"] = kb[0] if kb.shape[0] == 1 else kb
     if whole and run.solver is not None:
         post.update(solver=run.solver, steps=run.steps)
     return post
@@ -857,6 +885,42 @@ def postprocess_each(out_xstart, variable_dict, ref_img, operator_cfg, loss=None
     return outs
 
 
+def batch_operator_config(cfg, idxs, n_images):
+    """`cfg` for the batch of images `idxs` out of `n_images`: what the operator config gives PER IMAGE of the whole list -- a list
+    under `seed` (`motion_blur`, also inside `simulate_with`) or a `psf_blur` `kernel` with `per_image` (also inside `simulate_with`)
+    -- is sliced to the batch's entries, as masks and depths are, on a COPY of the config; `cfg` itself when there is nothing to
+    slice.  ValueError when such a list does not have one entry per image."""
+    op = cfg.get("measurement", {}).get("operator")
+    if not isinstance(op, dict):
+        return cfg
+
+    def sliced(c, where):
+        out = None
+        if isinstance(c.get("seed"), (list, tuple)):
+            if len(c["seed"]) != n_images:
+                raise ValueError(f"{where}seed: a list has one entry per image: {len(c['seed'])} seeds for {n_images} images")
+            out = dict(c, seed=[c["seed"][i] for i in idxs])
+        if c.get("per_image") and c.get("name") == "psf_blur" and c.get("kernel") is not None:
+            k = c["kernel"]
+            if isinstance(k, (str, bytes)) or hasattr(k, "__fspath__"):
+                k = np.load(k, allow_pickle=False)
+            k = k.detach().cpu().numpy() if isinstance(k, torch.Tensor) else np.asarray(k, dtype=np.float64)
+            if k.ndim < 3 or k.shape[0] != n_images:
+                raise ValueError(f"{where}kernel: per_image takes one kernel per image: shape {k.shape} for {n_images} images")
+            out = dict(out if out is not None else c, kernel=k[list(idxs)])
+        return out
+
+    new_op = sliced(op, "measurement.operator.")
+    sim = op.get("simulate_with")
+    new_sim = sliced(sim, "measurement.operator.simulate_with.") if isinstance(sim, dict) else None
+    if new_op is None and new_sim is None:
+        return cfg
+    new_op = dict(new_op if new_op is not None else op)
+    if new_sim is not None:
+        new_op["simulate_with"] = new_sim
+    return dict(cfg, measurement=dict(cfg["measurement"], operator=new_op))
+
+
 def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None, batch_size=1, originals=None,
                    geometries=None, full_res_upsample="bilinear", masks=None, tiling=None, shared_water=False, depths=None,
                    depth_confidences=None, robust=None, gain=None, **loop_kwargs):
@@ -885,6 +949,11 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
 
     `robust` / `gain` are `restore_image`'s (they win over `measurement.robust` / `measurement.gain`); every result carries its own
     `robust_weight` / `robust_scale` and `gain_field` / `gain_nodes` / `flat_fielded`, also in chunked batches.
+
+    Per-image point-spread functions: a LIST under `seed` (`motion_blur`, also inside `blind_blur`'s `simulate_with`) or a `psf_blur`
+    `kernel` with `per_image: True` has one entry per image of `images`; every batch gets its slice on a copy of the config
+    (`batch_operator_config`), as `masks` / `depths` are sliced.  With `blind_blur: {per_image: True}` every image of a batch learns
+    its own PSF and its result carries it as `kernel`.
 
     Every batch is one chain (`_run_chains`, which takes `restore_image`'s other keyword arguments as they are), and every image's
     result is built from what it left (`_image_result`): a batch of one gives `restore_image`'s result, a larger one every image's
@@ -918,13 +987,14 @@ def restore_images(model, images, cfg, rank=0, world=1, device=None, gt_rgb=None
     mine = shard_indices(len(images), rank, world)
     for k in range(0, len(mine), max(1, batch_size)):
         idxs = mine[k:k + max(1, batch_size)]
-        bcfg = cfg
+        bcfg = batch_operator_config(cfg, idxs, len(images))     # per-image seeds / kernels: this batch's slice, on a copy
         if shared_water and len(idxs) > 1:      # this batch is one water group (a copy: the caller's config stays as it is)
-            bcfg = dict(cfg, measurement=dict(cfg["measurement"], operator=dict(cfg["measurement"]["operator"], phi_groups="all")))
+            bcfg = dict(bcfg, measurement=dict(bcfg["measurement"], operator=dict(bcfg["measurement"]["operator"], phi_groups="all")))
         *_, run = _run_chains(model, torch.cat([images[i] for i in idxs], 0), bcfg, device=device, image_idx=idxs[0],
-                              same_seed_per_image=len(idxs) > 1, mask=batch_mask(masks, images, cfg, idxs),
+                              same_seed_per_image=len(idxs) > 1, mask=batch_mask(masks, images, bcfg, idxs),
                               **batch_depth(depths, depth_confidences, idxs), **loop_kwargs)
-        # one image: `restore_image`'s result; a batch: every image's own rows (`blind_blur`: ONE PSF was learnt for the batch)
+        # one image: `restore_image`'s result; a batch: every image's own rows (`blind_blur`: ONE PSF for the batch, or with
+        # `per_image` every image's own)
         res = [_image_result(run, b, whole=len(idxs) == 1) for b in range(len(idxs))]
         for i, r in zip(idxs, res):
             if shared_water:

@@ -36,6 +36,10 @@ registered for the "cuda" device type only, which is HIP on ROCm).
                                                            downsampling) and, with the transposed tables, its adjoint = its backward
     osmosis::psf_apply(x, dy, dx, w, Ry, Rx, adjoint) -> out   a point-spread function (tap list) per plane over reflection padding
                                                            (motion blur, a measured PSF); its backward is itself with `adjoint` flipped
+    osmosis::psf_apply_s(x, dy, dx, w[nb,nc,T], Ry, Rx, adjoint) -> out
+                                                           the same with one weight set per image and / or per plane
+    osmosis::ps_blind_loss_grad_s(x0, y, mask, dy, dx, w[nb,nc,T], Ry, Rx, n_iter, eta, l1) -> (loss, g)
+                                                           blind deblurring with one learnt PSF per image / per colour plane (w mutated)
 
 `engine` is an integer handle (`engine_handle(eng)`) because operator schemas carry tensors and scalars only; the handle
 table holds weak references, so an engine dies with its model.  An engine keeps the activations of its LAST forward pass:
@@ -713,6 +717,38 @@ def _psf_backward(ctx, grad):
 psf_apply.register_autograd(_psf_backward, setup_context=_psf_setup)
 
 
+# ---- the same operator with weight SETS w [nb,nc,T]: one PSF per image (nb = B) and / or per plane (nc = P), include/osmosis_psfset.h
+@torch.library.custom_op("osmosis::psf_apply_s", mutates_args=(), device_types="cuda")
+def psf_apply_s(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor, Ry: int, Rx: int, adjoint: bool) -> torch.Tensor:
+    """out [B,P,H,W] of x [B,P,H,W] (osm_psf_apply_s): `osmosis::psf_apply` where plane p of image b takes the weights
+    w[nb > 1 ? b : 0, nc > 1 ? p : 0] of w fp32 [nb,nc,T], nb in {1, B}, nc in {1, P}; the tap list dy, dx int32 [T] is shared.
+    Differentiable w.r.t. x."""
+    if x.dim() != 4:
+        raise OsmosisHipError("osmosis::psf_apply_s: x must be [B,P,H,W]")
+    B, P, H, W = x.shape
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape) or w.dim() != 3 or w.shape[2] != dy.shape[0] or w.shape[0] not in (1, B) \
+            or w.shape[1] not in (1, P):
+        raise OsmosisHipError(f"osmosis::psf_apply_s: expected dy [T], dx [T], w [nb,nc,T] with nb in (1, {B}), nc in (1, {P}), got "
+                              f"{tuple(dy.shape)}, {tuple(dx.shape)}, {tuple(w.shape)}")
+    out = torch.empty((B, P, H, W), device=x.device, dtype=torch.float32)
+    ops.psf_apply_s(x.contiguous(), out, dy.contiguous(), dx.contiguous(), w.detach().contiguous(), Ry, Rx, B, P, P * H * W, P * H * W, H, W,
+                    adjoint=adjoint)
+    return out
+
+
+@psf_apply_s.register_fake
+def _psf_apply_s_fake(x, dy, dx, w, Ry, Rx, adjoint):
+    return x.new_empty(x.shape)
+
+
+def _psf_s_backward(ctx, grad):
+    dy, dx, w = ctx.saved_tensors
+    return (torch.ops.osmosis.psf_apply_s(grad.contiguous(), dy, dx, w, ctx.Ry, ctx.Rx, not ctx.adjoint),) + (None,) * 6
+
+
+psf_apply_s.register_autograd(_psf_s_backward, setup_context=_psf_setup)
+
+
 # ---- the water / haze data term through a linear operator (blur, super-resolution, a PSF) between the model and the photo
 def lin_config(operator, H, W, device) -> Tuple[int, List[torch.Tensor], List[int]]:
     """(family, tables, dims) of a `measurements.GRID_OPERATORS` instance for phys_loss_grad_lin at the image grid H x W:
@@ -720,6 +756,9 @@ def lin_config(operator, H, W, device) -> Tuple[int, List[torch.Tensor], List[in
     family 1 (psf): dy, dx, w, dims = [Ry, Rx]."""
     from .guided_diffusion.measurements import PSFOperator, SeparableOperator
     if isinstance(operator, PSFOperator):
+        if operator.weight_sets != (1, 1):
+            raise OsmosisHipError(f"lin_config: the operator carries weight sets {operator.weight_sets} (per_image / per_channel); the "
+                                  "composed water / haze data term takes one point-spread function")
         operator.out_shape(H, W)
         return 1, list(operator.taps(device)), list(operator.radius())
     if not isinstance(operator, SeparableOperator):
@@ -832,6 +871,35 @@ def ps_blind_loss_grad(x0: torch.Tensor, y: torch.Tensor, mask: Optional[torch.T
 
 @ps_blind_loss_grad.register_fake
 def _ps_blind_loss_grad_fake(x0, y, mask, dy, dx, w, Ry, Rx, n_iter, eta, l1):
+    return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
+
+
+@torch.library.custom_op("osmosis::ps_blind_loss_grad_s", mutates_args=("w",), device_types="cuda")
+def ps_blind_loss_grad_s(x0: torch.Tensor, y: torch.Tensor, mask: Optional[torch.Tensor], dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor,
+                         Ry: int, Rx: int, n_iter: int, eta: float, l1: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`osmosis::ps_blind_loss_grad` with weight sets (osm_ps_blind_optimize_s, include/osmosis_psfset.h): w fp32 [nb,nc,T], nb in
+    {1, B} (one PSF per image), nc in {1, 3} (one per colour plane), every set STEPPED IN PLACE n_iter times from its own images /
+    planes.  Returns (loss [B], g) for the weights before the last step."""
+    name = "osmosis::ps_blind_loss_grad_s"
+    B, HW = _chw(x0)
+    C, H, W = x0.shape[1], x0.shape[2], x0.shape[3]
+    if C < 3 or tuple(y.shape) != (B, 3, H, W):
+        raise OsmosisHipError(f"{name}: expected x0 [B,C>=3,H,W] and y [B,3,H,W], got {tuple(x0.shape)} and {tuple(y.shape)}")
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape) or w.dim() != 3 or w.shape[2] != dy.shape[0] or w.shape[0] not in (1, B) \
+            or w.shape[1] not in (1, 3) or not w.is_contiguous():
+        raise OsmosisHipError(f"{name}: expected dy [T], dx [T] and a contiguous w [nb,nc,T] with nb in (1, {B}), nc in (1, 3), got "
+                              f"{tuple(dy.shape)}, {tuple(dx.shape)}, {tuple(w.shape)}")
+    f32 = dict(device=x0.device, dtype=torch.float32)
+    loss, g = torch.zeros(B, **f32), torch.empty_like(x0)
+    ops.ps_blind_optimize_s(x0.contiguous(), y.contiguous(), None if mask is None else _mask_rows(name, mask, y), dy.contiguous(),
+                            dx.contiguous(), w, Ry, Rx, B, C, H, W, torch.empty(B, 3, HW, **f32), torch.empty(B, 3, HW, **f32),
+                            torch.empty(B * ops.phys_nblk(HW), **f32), torch.empty(B * ops.tap_grad_nparts(3, H, W) * w.shape[2], **f32),
+                            loss, g, n_iter, eta, l1)
+    return loss, g
+
+
+@ps_blind_loss_grad_s.register_fake
+def _ps_blind_loss_grad_s_fake(x0, y, mask, dy, dx, w, Ry, Rx, n_iter, eta, l1):
     return x0.new_empty((x0.shape[0],)), torch.empty_like(x0)
 
 
@@ -968,4 +1036,5 @@ OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd
          "ddim_update_c", "ps_loss_grad_c")
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
-       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask", "gain_prepare") + OPS_C
+       "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask", "gain_prepare", "psf_apply_s",
+       "ps_blind_loss_grad_s") + OPS_C
