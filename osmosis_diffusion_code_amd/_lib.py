@@ -1,6 +1,5 @@
-"""ctypes binding of libosmosis_hip.so (the C ABI declared in include/osmosis_hip.h, include/osmosis_linop.h, include/osmosis_psf.h,
-include/osmosis_physlin.h, include/osmosis_physgroup.h, include/osmosis_blind.h, include/osmosis_depthprior.h,
-include/osmosis_solver.h, include/osmosis_robust.h, include/osmosis_gain.h and include/osmosis_psfset.h).
+"""ctypes binding of libosmosis_hip.so: the C ABI declared by the headers of include/, restated once in the table `ABI` below (one
+sub-table per header file; tests/test_abi_cpu.py holds the two against each other type by type).
 
 PyTorch is plumbing here: it owns device memory and streams; every kernel is reached through a
 plain C call with raw device pointers.  There is NO CPU / eager fallback: if the library is not
@@ -124,19 +123,31 @@ class ReconDesc(C.Structure):
                 ("mode", C.c_int), ("radius", C.c_int), ("sigma_s", C.c_float), ("sigma_r", C.c_float)]
 
 
-# name -> argtypes (restype is int unless listed in _SPECIAL)
+class _Returns(list):
+    """The argument list of an entry point that does not return int."""
+    def __init__(self, restype, argtypes):
+        super().__init__(argtypes)
+        self.restype = restype
+
+
+# header file -> {entry point -> argtypes}, in header order; every entry point returns int unless its list is a _Returns
 _LL = C.c_longlong
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
-_SIGS = {
+_D = C.c_double
+ABI = {"osmosis_hip.h": {
+    "osm_version": [],
+    "osm_last_error": _Returns(C.c_char_p, []),
     "osm_conv2d_nhwc": [C.POINTER(ConvDesc), _P],
     "osm_pack_conv_weight": [_P, _P, _P, _I, _I, _I, _P],
+    "osm_packed_weight_elems": _Returns(_LL, [_I, _I, _I, _I, _I]),
     "osm_gemm": [C.POINTER(GemmDesc), _P],
     "osm_pack_conv_weight_bf16s": [_P, _P, _P, _I, _I, _I, _I, _P],
     "osm_splitk_hint": [_I, _I, _I, _I, _I],
     "osm_conv_splitk": [_I, _I, _I, _I, _I, _I, _I, _I],
     "osm_conv_winograd_ok": [_I, _I, _I, _I, _I, _I],
+    "osm_winograd_weight_elems": _Returns(_LL, [_I, _I, _I, _I]),
     "osm_pack_conv_weight_winograd": [_P, _P, _P, _I, _I, _I, _P],
     "osm_conv_stat_chunks": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
     "osm_gn_finalize_cols": [_P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _LL, _P, _P],
@@ -172,6 +183,7 @@ _SIGS = {
     "osm_posterior": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "osm_posterior_typed": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P],
     "osm_clamp_bwd": [_P, _P, _F, _F, _LL, _P],
+    "osm_quantile_abs_ws_bytes": _Returns(_LL, [_LL]),
     "osm_quantile_abs": [_P, _LL, _F, _P, _P, _P, _P],
     "osm_posterior_dynthr": [_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "osm_dynthr_bwd": [_P, _P, _P, _P, _F, _LL, _P, _P],
@@ -206,27 +218,20 @@ _SIGS = {
     "osm_recon_fullres": [C.POINTER(ReconDesc), _P],
     "osm_tile_gather": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "osm_tile_blend": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "osm_version": [],
-}
+    "osm_half_to_f32": [_P, _LL, _P, _LL, _LL, _I, _P],
+    "osm_f32_to_half": [_P, _LL, _P, _LL, _LL, _I, _P],
+}}
 # fp16-storage family (activations as IEEE half, `_h` suffix): same argument lists
 for _n in ("osm_conv2d_nhwc", "osm_gn_stats", "osm_gn_apply", "osm_gn_fwd", "osm_gn_prep", "osm_gn_bwd", "osm_gn_bwd_apply", "osm_pool2x2",
            "osm_resample_pair", "osm_upsample2x", "osm_stride2_pick", "osm_stride2_place", "osm_add_rowvec", "osm_nchw_to_nhwc", "osm_nhwc_to_nchw", "osm_copy2d"):
-    _SIGS[_n + "_h"] = _SIGS[_n]
-_SIGS["osm_half_to_f32"] = [_P, _LL, _P, _LL, _LL, _I, _P]
-_SIGS["osm_f32_to_half"] = [_P, _LL, _P, _LL, _LL, _I, _P]
-EXPORTS = sorted(list(_SIGS) + ["osm_last_error", "osm_packed_weight_elems", "osm_winograd_weight_elems", "osm_quantile_abs_ws_bytes"])
-# the entry points of the library's second header, include/osmosis_linop.h (separable banded linear operators)
-_SIGS_LINOP = {
+    ABI["osmosis_hip.h"][_n + "_h"] = ABI["osmosis_hip.h"][_n]
+ABI["osmosis_linop.h"] = {  # separable banded linear operators
     "osm_linop_apply": [_P, _P, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _I, _I, _I, _I, _I, _P],
 }
-EXPORTS_LINOP = sorted(_SIGS_LINOP)
-# the entry points of the third header, include/osmosis_psf.h (point-spread-function operators: 2-D kernels as tap lists)
-_SIGS_PSF = {
+ABI["osmosis_psf.h"] = {  # point-spread-function operators: 2-D kernels as tap lists
     "osm_psf_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _I, _I, _I, _I, _P],
 }
-EXPORTS_PSF = sorted(_SIGS_PSF)
-# the entry points of the fourth header, include/osmosis_physlin.h (the water / haze data term through a linear operator)
-_SIGS_PHYSLIN = {
+ABI["osmosis_physlin.h"] = {  # the water / haze data term through a linear operator
     "osm_phys_forward": [C.POINTER(PhysDesc), _P, _P, _P, _P],
     "osm_phys_resid": [C.POINTER(PhysDesc), _I, _P, _P, _P, _P, _P, _P],
     "osm_phys_reduce_lin": [C.POINTER(PhysDesc), _P, _P, _P, _P, _P],
@@ -234,62 +239,58 @@ _SIGS_PHYSLIN = {
     "osm_phys_grad_lin": [C.POINTER(PhysDesc), _I, _P, _P, _P, _P, _P, _I, _P],
     "osm_phys_optimize_lin": [C.POINTER(PhysDesc), C.POINTER(LinDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
 }
-EXPORTS_PHYSLIN = sorted(_SIGS_PHYSLIN)
-# the entry points of the fifth header, include/osmosis_physgroup.h (one phi step per group of images: shared water parameters)
-_SIGS_PHYSGROUP = {
+ABI["osmosis_physgroup.h"] = {  # one phi step per group of images: shared water parameters
     "osm_phys_finalize_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _P, _P, _P, _I, _P, _P, _I, _P],
     "osm_phys_finalize_lin_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _I, _P, _P, _P, _P, _I, _P, _P, _I, _P],
     "osm_phys_optimize_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
     "osm_phys_optimize_lin_g": [C.POINTER(PhysDesc), C.POINTER(GroupDesc), C.POINTER(LinDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _I, _I, _P, _P],
 }
-EXPORTS_PHYSGROUP = sorted(_SIGS_PHYSGROUP)
-# the entry points of the sixth header, include/osmosis_blind.h (blind deblurring: the tap gradient of a PSF and its projected step)
-_D = C.c_double
-_SIGS_BLIND = {
+ABI["osmosis_blind.h"] = {  # blind deblurring: the tap gradient of a PSF and its projected step
     "osm_psf_tap_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _I, _I, _P, _P],
     "osm_psf_tap_step": [_P, _P, _P, _I, _I, _I, _LL, _D, _D, _P],
     "osm_ps_blind_optimize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
 }
-EXPORTS_BLIND = sorted(_SIGS_BLIND)
-# the entry points of the seventh header, include/osmosis_depthprior.h (a range-map depth prior in the Osmosis data term)
-_SIGS_DEPTHPRIOR = {
+ABI["osmosis_depthprior.h"] = {  # a range-map depth prior in the Osmosis data term
     "osm_depth_nblk": [_I],
     "osm_depth_reduce": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P],
     "osm_depth_fit": [C.POINTER(DepthDesc), _P, _P, _P, _P],
     "osm_depth_grad": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P, _P],
     "osm_depth_loss_grad": [C.POINTER(DepthDesc), _P, _P, _P, _P, _P, _P, _P, _P],
 }
-EXPORTS_DEPTHPRIOR = sorted(_SIGS_DEPTHPRIOR)
-# the entry points of the eighth header, include/osmosis_solver.h (few-step solvers: the DDIM / DPM-Solver++ 2M state update)
-_SIGS_SOLVER = {
+ABI["osmosis_solver.h"] = {  # few-step solvers: the DDIM / DPM-Solver++ 2M state update
     "osm_solver_update_c": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _P],
     "osm_solver_update_rng_c": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _P],
 }
-EXPORTS_SOLVER = sorted(_SIGS_SOLVER)
-# the entry points of the ninth header, include/osmosis_robust.h (a robust data term: IRLS weights from an on-device MAD scale)
-_SIGS_ROBUST = {
+ABI["osmosis_robust.h"] = {  # a robust data term: IRLS weights from an on-device MAD scale
     "osm_robust_resid": [C.POINTER(RobustDesc), _P, _LL, _F, _F, _P, _P, _P],
     "osm_robust_scale": [C.POINTER(RobustDesc), _P, _P, _P, _P, _P],
     "osm_robust_weights": [C.POINTER(RobustDesc), _P, _P, _P, _P, _P, _P],
     "osm_robust_mask": [C.POINTER(RobustDesc), _P, _LL, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
 }
-EXPORTS_ROBUST = sorted(_SIGS_ROBUST)
-# the entry points of the tenth header, include/osmosis_gain.h (a learnt vignetting gain field in the Osmosis data term)
-_SIGS_GAIN = {
+ABI["osmosis_gain.h"] = {  # a learnt vignetting gain field in the Osmosis data term
     "osm_gain_expand": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "osm_gain_rows": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "osm_gain_step": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P],
     "osm_gain_prepare": [C.POINTER(GainDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
 }
-EXPORTS_GAIN = sorted(_SIGS_GAIN)
-# the entry points of the eleventh header, include/osmosis_psfset.h (PSF weight sets: one per image and / or per colour plane)
-_SIGS_PSFSET = {
-    "osm_psf_apply_s": _SIGS_PSF["osm_psf_apply"][:-1] + [_LL, _LL, _P],
+ABI["osmosis_psfset.h"] = {  # PSF weight sets: one per image and / or per colour plane
+    "osm_psf_apply_s": ABI["osmosis_psf.h"]["osm_psf_apply"][:-1] + [_LL, _LL, _P],
     "osm_psf_tap_step_s": [_P, _P, _P, _I, _I, _I, _I, _LL, _D, _D, _I, _I, _P],
-    "osm_ps_blind_optimize_s": _SIGS_BLIND["osm_ps_blind_optimize"][:-1] + [_I, _I, _P],
+    "osm_ps_blind_optimize_s": ABI["osmosis_blind.h"]["osm_ps_blind_optimize"][:-1] + [_I, _I, _P],
 }
-EXPORTS_PSFSET = sorted(_SIGS_PSFSET)
+
+SIGS = {}       # name -> argtypes, over all headers
+for _header, _entries in ABI.items():
+    if SIGS.keys() & _entries.keys():
+        raise ValueError(f"ABI[{_header!r}] repeats {sorted(SIGS.keys() & _entries.keys())} of an earlier header")
+    SIGS.update(_entries)
+
+
+def exports(header=None):
+    """Sorted names of the entry points of one header file of include/ (e.g. "osmosis_gain.h"), or of all of them."""
+    return sorted(SIGS if header is None else ABI[header])
+
 
 _lib = None
 _lock = threading.Lock()
@@ -308,20 +309,10 @@ def load():
                     "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
                     "There is no CPU fallback for the product path.")
             lib = C.CDLL(LIB_PATH)
-            for name, argtypes in list(_SIGS.items()) + list(_SIGS_LINOP.items()) + list(_SIGS_PSF.items()) + list(_SIGS_PHYSLIN.items()) + \
-                    list(_SIGS_PHYSGROUP.items()) + list(_SIGS_BLIND.items()) + list(_SIGS_DEPTHPRIOR.items()) + list(_SIGS_SOLVER.items()) + \
-                    list(_SIGS_ROBUST.items()) + list(_SIGS_GAIN.items()) + list(_SIGS_PSFSET.items()):
+            for name, argtypes in SIGS.items():
                 fn = getattr(lib, name)
                 fn.argtypes = argtypes
-                fn.restype = C.c_int
-            lib.osm_packed_weight_elems.argtypes = [_I, _I, _I, _I, _I]
-            lib.osm_packed_weight_elems.restype = C.c_longlong
-            lib.osm_winograd_weight_elems.argtypes = [_I, _I, _I, _I]
-            lib.osm_winograd_weight_elems.restype = C.c_longlong
-            lib.osm_quantile_abs_ws_bytes.argtypes = [_LL]
-            lib.osm_quantile_abs_ws_bytes.restype = C.c_longlong
-            lib.osm_last_error.argtypes = []
-            lib.osm_last_error.restype = C.c_char_p
+                fn.restype = getattr(argtypes, "restype", C.c_int)
             _lib = lib
     return _lib
 

