@@ -1232,8 +1232,10 @@ class PosteriorSampling(ConditioningMethod):
         term's own reduction, osm_ps_loss_grad_c / _mc at C = 3 on the measurement's h w); g[:, 0:3] = A^T r with the transposed
         tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3).
         A `PSFOperator`: the same three launches with osm_psf_apply in the place of osm_linop_apply, `adjoint` set for A^T; with more
-        than one weight set (`per_image` / `per_channel`) osm_psf_apply_s on the weight rows [r0:r0 + B] of the open batch."""
-        from .measurements import PSFOperator
+        than one weight set (`per_image` / `per_channel`) osm_psf_apply_s on the weight rows [r0:r0 + B] of the open batch.
+        A `PSFFieldOperator` (`field_blur`): the same three launches with osmx_psf_field_apply for A and A^T; the field is shared by
+        the batch, so a chunk needs no rows of it."""
+        from .measurements import PSFFieldOperator, PSFOperator
         B, C, H, W = x0.shape
         h, w = self.operator.out_shape(H, W)
         if C not in (3, 4) or tuple(y.shape) != (B, 3, h, w):
@@ -1252,7 +1254,11 @@ class PosteriorSampling(ConditioningMethod):
         loss = loss_out if loss_out is not None else st["loss"]
         Ax, r = st["Ax"], st["r"]
         sets = isinstance(self.operator, PSFOperator) and self.operator.weight_sets != (1, 1)
-        if isinstance(self.operator, PSFOperator):
+        if isinstance(self.operator, PSFFieldOperator):       # a field is never read as one PSF: its own kernel, same three launches
+            taps, (Ry, Rx) = self.operator.taps(x0.device), self.operator.radius()
+            tabs = self.operator.field_tables(H, W, x0.device)
+            ops.psf_field_apply(x0.contiguous(), Ax, *taps, tabs, Ry, Rx, B, 3, C * HW, 3 * hw, H, W)
+        elif isinstance(self.operator, PSFOperator):
             taps, (Ry, Rx) = self.operator.taps(x0.device), self.operator.radius()
             if sets:
                 taps = (taps[0], taps[1], self._weight_rows(taps[2], r0, B))
@@ -1265,7 +1271,9 @@ class PosteriorSampling(ConditioningMethod):
             ops.ps_loss_grad_mc(Ax, y.contiguous(), mask, st["part"], loss, r, B, 3, hw)
         else:
             ops.ps_loss_grad_c(Ax, y.contiguous(), st["part"], loss, r, B, 3, hw)
-        if isinstance(self.operator, PSFOperator):
+        if isinstance(self.operator, PSFFieldOperator):
+            ops.psf_field_apply(r, g, *taps, tabs, Ry, Rx, B, 3, 3 * hw, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+        elif isinstance(self.operator, PSFOperator):
             psf(r, g, *taps, Ry, Rx, B, 3, 3 * hw, C * HW, H, W, adjoint=True, zero_planes=C - 3)
         else:
             ops.linop_apply(r, g, *tabs["adj"], B, 3, 3 * hw, C * HW, h, w, zero_planes=C - 3)

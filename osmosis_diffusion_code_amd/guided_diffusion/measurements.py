@@ -466,8 +466,12 @@ def motion_kernel(kernel_size=61, intensity=0.5, seed=0):
     (a ? fy : 1 - fy) (b ? fx : 1 - fx), fy = y - floor y; a pixel beyond the kernel can only get weight 0 and is dropped), the sum
     normalised to 1.  Deterministic in its three arguments, non-negative, the centre pixel always hit.  (DPS draws its kernels from
     the `motionblur` package; this definition stands in for it and does not reproduce that package's random stream.)"""
-    pts = motion_trajectory(kernel_size, intensity, seed)
-    k = int(kernel_size)
+    return _splat_points(motion_trajectory(kernel_size, intensity, seed), int(kernel_size))
+
+
+def _splat_points(pts, k):
+    """float64 [k, k], sum 1: the points pts [n, 2] of (y, x) offsets from the centre (each within [-k // 2, k // 2] per axis), every
+    one splatted bilinearly with weight 1 as `motion_kernel` states."""
     r = k // 2
     ker = np.zeros((k, k), dtype=np.float64)
     fl = np.floor(pts)
@@ -544,6 +548,196 @@ class PSFBlurOperator(PSFOperator):
 
     def kernel2d(self):
         return self._single(self._kernel)
+
+
+# ----------------------------------------------------------------------------- a field of PSFs: spatially varying blur
+FIELD_MAX_GRID = 32        # nodes per axis (include/ext/osmosis_psffield.h; the gain field's limit)
+FIELD_MAX_KERNEL = 61      # the largest side of a node kernel (the window a workgroup stages: halo <= 32 per side, then slower)
+
+
+def _field_grid(grid, what):
+    try:
+        gh, gw = (int(v) for v in grid)
+        ok = (gh, gw) == tuple(grid)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (2 <= gh <= FIELD_MAX_GRID and 2 <= gw <= FIELD_MAX_GRID):
+        raise ValueError(f"{what}: grid must be a pair of ints (gh, gw) within 2 .. {FIELD_MAX_GRID} per side, got {grid!r}")
+    return gh, gw
+
+
+def _field_kernel_size(kernel_size, what):
+    k = kernel_size
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 or k % 2 == 0 or k > FIELD_MAX_KERNEL:
+        raise ValueError(f"{what}: kernel_size must be a positive odd integer <= {FIELD_MAX_KERNEL}, got {kernel_size!r}")
+    return int(k)
+
+
+def radial_defocus_field(kernel_size=31, sigma_center=0.5, sigma_corner=3.0, grid=(5, 5)):
+    """A dome port's field curvature, float64 [gh,gw,k,k]: node (jy, jx) carries the Gaussian of standard deviation
+    sigma = sigma_center + (sigma_corner - sigma_center) rho^2, sampled at the pixel centres and normalised to sum 1 in float64;
+    rho = sqrt((uy^2 + ux^2) / 2) with uy = 2 jy / (gh - 1) - 1, ux alike: the node's distance from the centre over the corner's,
+    each axis normalised by its own half side (0 at the centre, 1 at the four corners)."""
+    what = "field_blur: radial_defocus"
+    k = _field_kernel_size(kernel_size, what)
+    gh, gw = _field_grid(grid, what)
+    sc, se = float(sigma_center), float(sigma_corner)
+    if not (np.isfinite(sc) and np.isfinite(se) and sc > 0 and se > 0):
+        raise ValueError(f"{what}: sigma_center and sigma_corner must be positive numbers, got {sigma_center!r}, {sigma_corner!r}")
+    a = np.arange(k, dtype=np.float64) - k // 2
+    d2 = a[:, None] ** 2 + a[None, :] ** 2
+    out = np.empty((gh, gw, k, k), dtype=np.float64)
+    for jy in range(gh):
+        for jx in range(gw):
+            uy, ux = 2.0 * jy / (gh - 1) - 1.0, 2.0 * jx / (gw - 1) - 1.0
+            sigma = sc + (se - sc) * ((uy * uy + ux * ux) / 2.0)
+            ker = np.exp(-d2 / (2.0 * sigma * sigma))
+            out[jy, jx] = ker / ker.sum()
+    return out
+
+
+def roll_shake_field(kernel_size=31, angle_deg=1.0, grid=(5, 5), image_size=(256, 256)):
+    """A hand-held roll about the optical axis during the exposure, float64 [gh,gw,k,k]: node (jy, jx) sits at
+    (y, x) = (jy (H - 1) / (gh - 1), jx (W - 1) / (gw - 1)) of an image_size = (H, W) frame, at the offset (ry, rx) and the distance
+    r from the image centre ((H - 1) / 2, (W - 1) / 2); its PSF is a straight streak through the kernel's centre along the tangent
+    (rx, -ry) / r of the circle about the image centre through the node, of length angle r pixels (angle in radians): the points
+    i MOTION_STEP along the tangent for |i| <= floor(angle r / (2 MOTION_STEP)), each clamped to [-k // 2, k // 2] per axis and
+    splatted bilinearly as `motion_kernel` does, the sum normalised to 1.  A node at the image centre carries the delta."""
+    what = "field_blur: roll_shake"
+    k = _field_kernel_size(kernel_size, what)
+    gh, gw = _field_grid(grid, what)
+    ang = float(angle_deg)
+    if not (np.isfinite(ang) and ang >= 0.0):
+        raise ValueError(f"{what}: angle_deg must be a finite number >= 0, got {angle_deg!r}")
+    try:
+        H, W = (int(v) for v in image_size)
+        ok = (H, W) == tuple(image_size) and H >= 2 and W >= 2
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: image_size must be a pair of ints (H, W) >= 2, got {image_size!r}")
+    half = k // 2
+    out = np.empty((gh, gw, k, k), dtype=np.float64)
+    for jy in range(gh):
+        for jx in range(gw):
+            ry, rx = jy * (H - 1) / (gh - 1) - (H - 1) / 2.0, jx * (W - 1) / (gw - 1) - (W - 1) / 2.0
+            r = float(np.hypot(ry, rx))
+            n = int(np.floor(np.deg2rad(ang) * r / (2.0 * MOTION_STEP))) if r > 0 else 0
+            s = np.arange(-n, n + 1, dtype=np.float64) * MOTION_STEP
+            t = np.array([rx / r, -ry / r]) if r > 0 else np.zeros(2)
+            out[jy, jx] = _splat_points(np.clip(s[:, None] * t[None, :], -half, half), k)
+    return out
+
+
+def _field_op():
+    from .. import torch_ops  # noqa: F401  (registers osmosis::psf_field_apply)
+    return torch.ops.osmosis.psf_field_apply
+
+
+@register_operator(name="field_blur")
+class PSFFieldOperator(PSFOperator):
+    """Spatially varying blur: a FIELD of point-spread functions K_n on a gh x gw node grid that spans the frame (the nodes sit where
+    the gain field's do: on the image corners inclusive), every pixel p blurred with the bilinear interpolation sum_n hat_n(p) K_n of
+    the four corner kernels of its cell, over reflection padding, as cross-correlation (osmx_psf_field_apply of the staging library,
+    include/ext/osmosis_psffield.h; `forward` / `transpose` run it through `osmosis::psf_field_apply`, which is differentiable).
+    No learnable parameters; the measurement has the image's size.  The field is shared by the images of a batch and by the colour
+    planes: `weight_sets` stays (1, 1).
+    Config keys (an unknown one raises ValueError): EITHER `kernels`, a [gh,gw,kh,kw] array, nested list or the path of a .npy file
+    (odd sides, finite, no all-zero node: `check_kernel2d` per node) with `normalize` (default True: every node over its own float64
+    sum), OR `model`: 'radial_defocus' with {kernel_size=31, sigma_center=0.5, sigma_corner=3.0, grid=[5,5]}
+    (`radial_defocus_field`) or 'roll_shake' with {kernel_size=31, angle_deg=1.0, grid=[5,5], image_size=[256,256]}
+    (`roll_shake_field`); `simulate` is the driver's.  `per_image` / `per_channel` are refused: a field per image or per channel is
+    out of scope.
+    `kernels()` float64 [gh,gw,kh,kw]; `grid` (gh, gw); `host_taps()` the row-major union of the nodes' non-zeros with w fp32
+    [gh,gw,T]; `kernel2d()` raises: a field is never one PSF."""
+
+    DRIVER_KEYS = ("simulate",)
+    MODELS = {"radial_defocus": (radial_defocus_field, ("kernel_size", "sigma_center", "sigma_corner", "grid")),
+              "roll_shake": (roll_shake_field, ("kernel_size", "angle_deg", "grid", "image_size"))}
+
+    def __init__(self, device, kernels=None, normalize=True, model=None, batch_size=1, **kwargs):
+        many = [k for k in ("per_image", "per_channel") if k in kwargs]
+        if many:
+            raise ValueError(f"field_blur: {', '.join(many)} is not supported -- the field is shared by the images of a batch and by the "
+                             f"colour planes (a field per image or per channel is out of scope)")
+        if (kernels is None) == (model is None):
+            raise ValueError("field_blur: give either `kernels` ([gh,gw,kh,kw]) or `model` ('radial_defocus' | 'roll_shake'), not both")
+        if model is not None and model not in self.MODELS:
+            raise ValueError(f"field_blur: model must be one of {sorted(self.MODELS)}, got {model!r}")
+        known = self.MODELS[model][1] if model is not None else ()
+        unknown = sorted(set(kwargs) - set(self.DRIVER_KEYS) - set(known))
+        if unknown:
+            raise ValueError(f"field_blur: unknown config key(s) {unknown} (known: kernels, normalize, model"
+                             f"{''.join(', ' + k for k in known)}, simulate)")
+        super().__init__(device, batch_size)
+        if model is not None:
+            ks = self.MODELS[model][0](**{k: kwargs[k] for k in known if k in kwargs})
+        else:
+            if isinstance(kernels, (str, bytes)) or hasattr(kernels, "__fspath__"):
+                if not str(os.fspath(kernels) if hasattr(kernels, "__fspath__") else kernels).endswith(".npy"):
+                    raise ValueError(f"field_blur: kernels must be a [gh,gw,kh,kw] array of numbers, a nested list or the path of a .npy "
+                                     f"file, got {kernels!r}")
+                kernels = np.load(kernels, allow_pickle=False)
+            if isinstance(kernels, torch.Tensor):
+                kernels = kernels.detach().cpu().numpy()
+            try:
+                ks = np.asarray(kernels, dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"field_blur: kernels must be a [gh,gw,kh,kw] array of numbers ({e})")
+            if ks.ndim != 4:
+                raise ValueError(f"field_blur: kernels must be [gh,gw,kh,kw], got shape {ks.shape}")
+            _field_grid(ks.shape[:2], "field_blur")
+            for jy in range(ks.shape[0]):
+                for jx in range(ks.shape[1]):
+                    check_kernel2d(ks[jy, jx], f"field_blur: node ({jy}, {jx})")
+            if max(ks.shape[2:]) > FIELD_MAX_KERNEL:
+                raise ValueError(f"field_blur: a node kernel of {ks.shape[2]} x {ks.shape[3]} is larger than {FIELD_MAX_KERNEL} per side")
+            if normalize:
+                totals = ks.sum(axis=(2, 3), keepdims=True)
+                if (totals == 0.0).any() or not np.isfinite(totals).all():
+                    raise ValueError(f"field_blur: normalize divides every node by its sum; the sums are {totals.reshape(ks.shape[:2]).tolist()}")
+                ks = ks / totals
+        self._field = np.ascontiguousarray(ks)
+        self.model, self.normalize = model, bool(normalize)
+
+    @property
+    def grid(self):
+        """(gh, gw): the nodes per axis."""
+        return tuple(int(v) for v in self._field.shape[:2])
+
+    def kernel2d(self):
+        raise ValueError(f"{self._name()}: the operator carries a field of {self.grid[0]} x {self.grid[1]} point-spread functions; "
+                         f"kernel2d() is one kernel -- use kernels()")
+
+    def kernels(self):
+        """Every node's PSF, float64 [gh,gw,kh,kw]."""
+        return self._field.copy()
+
+    def host_taps(self):
+        """(dy int32 [T], dx int32 [T], w fp32 [gh,gw,T]): the row-major union of the nodes' non-zeros, offsets from the centre; a node
+        without a tap there carries 0.0."""
+        if self._host is None:
+            ks = self._field
+            iy, ix = np.nonzero((ks != 0).any(axis=(0, 1)))                         # row-major union
+            self._host = ((iy - ks.shape[2] // 2).astype(np.int32), (ix - ks.shape[3] // 2).astype(np.int32),
+                          np.ascontiguousarray(ks[:, :, iy, ix].astype(np.float32)))
+        return self._host
+
+    def out_shape(self, H, W):
+        gh, gw = self.grid
+        if gh > H or gw > W:
+            raise ValueError(f"{self._name()}: the node grid {gh} x {gw} has more nodes than the image has pixels ({H} x {W})")
+        return super().out_shape(H, W)
+
+    def field_tables(self, H, W, device=None):
+        """The interpolation tables (iy0, fy, ix0, fx) of the node grid on an H x W image, on the device (`ops.field_tables`)."""
+        from .. import ops
+        return ops.field_tables(H, W, *self.grid, torch.device(device if device is not None else self.device))
+
+    def _apply(self, data, adjoint):
+        H, W = data.shape[-2:]
+        self.out_shape(H, W)
+        return _field_op()(data, *self.taps(data.device), *self.field_tables(H, W, data.device), *self.radius(), adjoint)
 
 
 BLIND_MAX_KERNEL = 61      # the largest side of a learnt PSF (the window a workgroup of osm_psf_tap_grad stages: halo <= 32 per side)
@@ -725,8 +919,12 @@ def build_degradation(degradation, device, batch_size=1):
     """The linear operator between a physical image-formation model and the photo (`_PhysicalOperator(degradation=)`): None, an
     operator instance (handed through as it is), or a dict {name: <a registered blur / super-resolution / PSF operator>, ...its
     keys} built here.  NameError for a name nobody registered, ValueError for one that is no `GRID_OPERATORS` class and for
-    'blind_blur' (by name: it is a `PSFOperator`, but a learnt PSF inside the water / haze model is out of scope)."""
+    'blind_blur' and 'field_blur' (by name: they are `PSFOperator`s, but a learnt PSF or a field of PSFs inside the water / haze model
+    is out of scope)."""
     if degradation is None or not isinstance(degradation, dict):
+        if isinstance(degradation, PSFFieldOperator):
+            raise ValueError("degradation: 'field_blur' (a field of point-spread functions) inside a physical image-formation model is not "
+                             "supported -- the composed data term takes one point-spread function; give a fixed 'psf_blur' kernel")
         if getattr(degradation, "weight_sets", (1, 1)) != (1, 1):
             raise ValueError(f"degradation: the operator carries more than one point-spread function (per_image / per_channel: weight sets "
                              f"{degradation.weight_sets}), which a physical image-formation model does not take -- the composed route "
@@ -737,6 +935,9 @@ def build_degradation(degradation, device, batch_size=1):
     if name == "blind_blur":
         raise ValueError("degradation: 'blind_blur' (a learnt PSF) inside a physical image-formation model is not supported -- its "
                          "weights and the water / haze parameters would have to be stepped together; give a fixed 'psf_blur' kernel")
+    if name == "field_blur":
+        raise ValueError("degradation: 'field_blur' (a field of point-spread functions) inside a physical image-formation model is not "
+                         "supported -- the composed data term takes one point-spread function; give a fixed 'psf_blur' kernel")
     many = [k for k in ("per_image", "per_channel") if cfg.get(k)] + (["seed (a list)"] if isinstance(cfg.get("seed"), (list, tuple)) else [])
     if many:
         raise ValueError(f"degradation: {name!r} with {', '.join(many)} carries more than one point-spread function, which a physical "

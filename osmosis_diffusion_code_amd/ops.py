@@ -877,7 +877,10 @@ def ps_blind_optimize_s(x0, y, mask, dy, dx, w, Ry, Rx, B, Cc, H, W, Ax, r, lpar
 def lin_desc(operator, H, W, device) -> LinDesc:
     """The osm_lin_desc of a `measurements.GRID_OPERATORS` instance at the image grid H x W (include/osmosis_physlin.h).  The device
     tables / taps it points at are the operator's own cached tensors; they are also kept on the descriptor (`_keep`)."""
-    from .guided_diffusion.measurements import PSFOperator, SeparableOperator
+    from .guided_diffusion.measurements import PSFFieldOperator, PSFOperator, SeparableOperator
+    if isinstance(operator, PSFFieldOperator):
+        raise _lib.OsmosisHipError("lin_desc: 'field_blur' carries a field of point-spread functions; the composed water / haze data term "
+                                   "takes one (osm_lin_desc has no such family)")
     d = LinDesc()
     h, w = operator.out_shape(H, W)
     d.H, d.W, d.h, d.w = int(H), int(W), int(h), int(w)
@@ -1195,6 +1198,44 @@ def gain_tables(H, W, gh, gw, device):
             _gain_tables.pop(next(iter(_gain_tables)))
         tabs = _gain_tables[key] = tuple(torch.from_numpy(a).to(device) for a in gain_tables_host(H, W, gh, gw))
     return tabs
+
+
+# ----------------------------------------------------------------------------- a field of PSFs (include/ext/osmosis_psffield.h)
+def field_tables(H, W, gh, gw, device):
+    """The interpolation tables (iy0, fy, ix0, fx) of a gh x gw node grid on an H x W image as device tensors: the gain field's
+    (`gain_tables`: same nodes, same cache), after the limits 2 <= gh <= min(H, 32), 2 <= gw <= min(W, 32)."""
+    H, W, gh, gw = int(H), int(W), int(gh), int(gw)
+    if not (2 <= gh <= min(H, GAIN_MAX_GRID) and 2 <= gw <= min(W, GAIN_MAX_GRID)):
+        raise ValueError(f"field_tables: the node grid must be within 2 .. min({GAIN_MAX_GRID}, the image side) per axis, got {gh} x {gw} "
+                         f"on a {H} x {W} image")
+    return gain_tables(H, W, gh, gw, device)
+
+
+def psf_field_apply(x, out, dy, dx, w, tabs, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint=False, zero_planes=0):
+    """The blur of planes p < P with a FIELD of point-spread functions (osmx_psf_field_apply of the staging library,
+    include/ext/osmosis_psffield.h): w fp32 [gh,gw,T] holds one PSF per node over the shared tap list dy, dx int32 [T], the nodes sit
+    on the image corners inclusive and every pixel is blurred with the bilinear interpolation of its cell's four corner PSFs; with
+    `adjoint` the exact transpose.  tabs = `field_tables(H, W, gh, gw, device)`.  Everything else is `psf_apply`'s."""
+    for t in (x, out, w):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("psf_field_apply takes contiguous fp32 tensors")
+    _check_tap_lists("psf_field_apply", dy, dx)
+    T = int(dy.shape[0])
+    if w.dim() != 3 or w.shape[2] != T:
+        raise _lib.OsmosisHipError(f"psf_field_apply: the node weights are fp32 [gh,gw,T = {T}], got {tuple(w.shape)}")
+    gh, gw = int(w.shape[0]), int(w.shape[1])
+    B, P, Z, H, W = int(B), int(P), int(zero_planes), int(H), int(W)
+    iy0, fy, ix0, fx = tabs
+    for k, t, n, dt in (("iy0", iy0, H, torch.int32), ("fy", fy, H, torch.float32), ("ix0", ix0, W, torch.int32), ("fx", fx, W, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise _lib.OsmosisHipError(f"psf_field_apply: table `{k}` must be contiguous {dt} [{n}], got {tuple(t.shape)} {t.dtype}")
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * H * W
+                   or out.numel() < (B - 1) * int(out_img_stride) + (P + Z) * H * W):
+        raise _lib.OsmosisHipError(f"psf_field_apply: x ({x.numel()} elements) / out ({out.numel()}) are smaller than {B} images of "
+                                   f"{P} -> {P + Z} planes of {H} x {W} at strides {x_img_stride} / {out_img_stride}")
+    call("osmx_psf_field_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0),
+         ptr(fx), B, P, int(x_img_stride), int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(),
+         keep=(x, out, dy, dx, w, iy0, fy, ix0, fx))
 
 
 def gain_check(grid, eta, n_iter, smooth, g_min, H=None, W=None):

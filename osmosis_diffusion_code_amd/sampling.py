@@ -28,7 +28,7 @@ import torch
 
 from .guided_diffusion.condition_methods import ConditioningMethod, PosteriorSamplingOsmosis, get_conditioning_method
 from .guided_diffusion.gaussian_diffusion import create_sampler, parse_tiling, tile_grid  # noqa: F401  (tile_grid: public helper)
-from .guided_diffusion.measurements import GRID_OPERATORS, get_noise, get_operator
+from .guided_diffusion.measurements import GRID_OPERATORS, PSFFieldOperator, get_noise, get_operator
 from .osmosis_utils import utils as utilso
 from .sharding import shard_indices
 
@@ -401,7 +401,7 @@ def save_outputs(post, ref_img, out_dir, name, global_ii=0, save_singles=True, s
         paths["depth_prior"] = os.path.join(d, f"{name}_depth_prior.png")
         Image.fromarray(metric_u8, mode="RGB").save(paths["depth_metric"])
         Image.fromarray(prior_u8, mode="RGB").save(paths["depth_prior"])
-    if save_singles and post.get("kernel") is not None:     # only a `blind_blur` chain: the learnt PSF ([3,k,k] per channel: one RGB picture)
+    if save_singles and post.get("kernel") is not None:     # a `blind_blur` chain: the learnt PSF ([3,k,k] per channel: one RGB picture); `field_blur`: the mosaic of the node kernels
         d = os.path.join(out_dir, "single_images", "kernel")
         os.makedirs(d, exist_ok=True)
         paths["kernel"] = os.path.join(d, f"{name}_kernel.png")
@@ -441,8 +441,12 @@ def depth_metric_images_u8(post):
 def kernel_image_u8(kernel, side=128):
     """uint8 [k z, k z] picture of a PSF [k, k]: the kernel over its maximum (negative values clamped to 0), every tap replicated to a
     z x z block of pixels, z = max(1, side // k) -- no interpolation, a tap stays a square.  A per-channel PSF [3, k, k]: one RGB
-    picture uint8 [k z, k z, 3], every plane over the COMMON maximum."""
+    picture uint8 [k z, k z, 3], every plane over the COMMON maximum.  A field [gh, gw, kh, kw]: the gh x gw mosaic of the node
+    kernels (node (jy, jx) in block row jy, block column jx) over their common maximum, uint8 [gh kh z, gw kw z]."""
     k = torch.as_tensor(kernel, dtype=torch.float32).clamp(min=0)
+    if k.dim() == 4:        # a field of PSFs [gh,gw,kh,kw] (`field_blur`): the gh x gw mosaic of the node kernels, one common maximum
+        gh, gw, kh, kw = k.shape
+        k = k.permute(0, 2, 1, 3).reshape(gh * kh, gw * kw)
     top = float(k.max())
     k = k / top if top > 0 else k
     z = max(1, int(side) // int(max(k.shape[-2:])))
@@ -649,6 +653,10 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     then carries `gain_field` [H,W], `gain_nodes` [gh,gw] and `flat_fielded` = clip((y + 1) / (2 G), 0, 1) -- each image's own,
     also in chunked batches; `save_outputs` writes `<name>_gain.png`.  Without it nothing is passed and there are no such keys.
 
+    Operator `field_blur` (a field of PSFs on a node grid, spatially varying blur): simulated as `psf_blur` is (y = noiser(A ref);
+    `simulate: False` as there), the field shared by every image of a batch; every result carries `kernel` fp32 [gh,gw,kh,kw] (the
+    node kernels) and `save_outputs` writes `<name>_kernel.png`, their gh x gw mosaic over the common maximum.
+
     Operator `blind_blur` (the PSF is learnt during the chain): `operator.reset()` before every global iteration, every result
     carries `kernel` fp32 [k,k] (the estimate at the end of its chain; [3,k,k] with `per_channel`; `save_outputs` writes it as
     `<name>_kernel.png`, a per-channel one as one RGB picture), and `simulate: True` needs `simulate_with: {name: <a grid operator>,
@@ -694,6 +702,7 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
     shape = list(ref_img.shape)
     y_clean = ref_img
     is_blind = op_cfg.get("name") == "blind_blur"
+    is_field = isinstance(operator, PSFFieldOperator)       # a field of PSFs: every result carries the node kernels
     if isinstance(operator, GRID_OPERATORS):
         # a blur / super-resolution operator: the measurement is simulated from the clean image, y = noiser(A ref), as the DPS driver
         # does; `measurement.operator.simulate: False` takes ref_img as the measurement itself, on the operator's own grid
@@ -768,7 +777,8 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
             ref_img=ref_img, operator_cfg=measure["operator"], measurement=y_n.detach().cpu(), variables=None, loss=None,
             pred_xstart=None, observed=None, depth=None, gain=None, tiling=None, robust=None,
             mask=None if m_dev is None else m_dev.detach().cpu(),
-            kernel=_operator_kernels(operator) if is_blind else None,      # [nb,nc,k,k]
+            kernel=_operator_kernels(operator) if is_blind or is_field else None,      # [nb,nc,k,k]; a field: [gh,gw,kh,kw]
+            kernel_field=is_field,
             solver=solver, steps=None if solver is None else sampler.num_timesteps)
         vals = None if robust is None else cond.robust_values()     # (None: no guided sub-step on a loop that never opened the state)
         if vals is not None:
@@ -822,7 +832,9 @@ def _image_result(run, b, whole=False):
         post["mask"] = run.mask[rows]
     if run.robust is not None:
         attach_robust(post, run.robust["weight"][b], run.robust["scale"][b])
-    if run.kernel is not None:          # image b's own PSF ([nb,nc,k,k]: one row for the batch, or one per image): [k,k], or [3,k,k] per channel
+    if run.kernel is not None and getattr(run, "kernel_field", False):     # `field_blur`: the whole field [gh,gw,kh,kw], shared by the batch
+        post["kernel"] = run.kernel
+    elif run.kernel is not None:        # image b's own PSF ([nb,nc,k,k]: one row for the batch, or one per image): [k,k], or [3,k,k] per channel
         kb = run.kernel[b if run.kernel.shape[0] > 1 else 0]
         post["kernel"] = kb[0] if kb.shape[0] == 1 else kb
     if whole and run.solver is not None:

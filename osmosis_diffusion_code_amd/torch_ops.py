@@ -38,6 +38,8 @@ registered for the "cuda" device type only, which is HIP on ROCm).
                                                            (motion blur, a measured PSF); its backward is itself with `adjoint` flipped
     osmosis::psf_apply_s(x, dy, dx, w[nb,nc,T], Ry, Rx, adjoint) -> out
                                                            the same with one weight set per image and / or per plane
+    osmosis::psf_field_apply(x, dy, dx, w[gh,gw,T], iy0, fy, ix0, fx, Ry, Rx, adjoint) -> out
+                                                           a field of PSFs on a node grid, interpolated bilinearly over the frame
     osmosis::ps_blind_loss_grad_s(x0, y, mask, dy, dx, w[nb,nc,T], Ry, Rx, n_iter, eta, l1) -> (loss, g)
                                                            blind deblurring with one learnt PSF per image / per colour plane (w mutated)
 
@@ -749,12 +751,52 @@ def _psf_s_backward(ctx, grad):
 psf_apply_s.register_autograd(_psf_s_backward, setup_context=_psf_setup)
 
 
+# ---- a FIELD of point-spread functions w [gh,gw,T] on a node grid, interpolated bilinearly (include/ext/osmosis_psffield.h)
+@torch.library.custom_op("osmosis::psf_field_apply", mutates_args=(), device_types="cuda")
+def psf_field_apply(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor, iy0: torch.Tensor, fy: torch.Tensor,
+                    ix0: torch.Tensor, fx: torch.Tensor, Ry: int, Rx: int, adjoint: bool) -> torch.Tensor:
+    """out [B,P,H,W] of x [B,P,H,W] (osmx_psf_field_apply): every pixel blurred with the bilinear interpolation of the four corner PSFs
+    of its cell of the gh x gw node grid -- w fp32 [gh,gw,T] over the shared tap list dy, dx int32 [T]; (iy0, fy, ix0, fx) =
+    `ops.field_tables(H, W, gh, gw, device)` -- or with `adjoint` the transpose of that map.  Differentiable w.r.t. x."""
+    if x.dim() != 4:
+        raise OsmosisHipError("osmosis::psf_field_apply: x must be [B,P,H,W]")
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape) or w.dim() != 3 or w.shape[2] != dy.shape[0]:
+        raise OsmosisHipError(f"osmosis::psf_field_apply: expected dy [T], dx [T], w [gh,gw,T], got {tuple(dy.shape)}, {tuple(dx.shape)}, "
+                              f"{tuple(w.shape)}")
+    B, P, H, W = x.shape
+    out = torch.empty((B, P, H, W), device=x.device, dtype=torch.float32)
+    ops.psf_field_apply(x.contiguous(), out, dy.contiguous(), dx.contiguous(), w.detach().contiguous(),
+                        (iy0.contiguous(), fy.contiguous(), ix0.contiguous(), fx.contiguous()), Ry, Rx, B, P, P * H * W, P * H * W, H, W,
+                        adjoint=adjoint)
+    return out
+
+
+@psf_field_apply.register_fake
+def _psf_field_apply_fake(x, dy, dx, w, iy0, fy, ix0, fx, Ry, Rx, adjoint):
+    return x.new_empty(x.shape)
+
+
+def _psf_field_setup(ctx, inputs, output):
+    _x, dy, dx, w, iy0, fy, ix0, fx, ctx.Ry, ctx.Rx, ctx.adjoint = inputs
+    ctx.save_for_backward(dy, dx, w, iy0, fy, ix0, fx)
+
+
+def _psf_field_backward(ctx, grad):
+    return (torch.ops.osmosis.psf_field_apply(grad.contiguous(), *ctx.saved_tensors, ctx.Ry, ctx.Rx, not ctx.adjoint),) + (None,) * 10
+
+
+psf_field_apply.register_autograd(_psf_field_backward, setup_context=_psf_field_setup)
+
+
 # ---- the water / haze data term through a linear operator (blur, super-resolution, a PSF) between the model and the photo
 def lin_config(operator, H, W, device) -> Tuple[int, List[torch.Tensor], List[int]]:
     """(family, tables, dims) of a `measurements.GRID_OPERATORS` instance for phys_loss_grad_lin at the image grid H x W:
     family 0 (separable): the four forward band tables then the four transposed ones, dims = [h, w];
     family 1 (psf): dy, dx, w, dims = [Ry, Rx]."""
-    from .guided_diffusion.measurements import PSFOperator, SeparableOperator
+    from .guided_diffusion.measurements import PSFFieldOperator, PSFOperator, SeparableOperator
+    if isinstance(operator, PSFFieldOperator):
+        raise OsmosisHipError("lin_config: 'field_blur' carries a field of point-spread functions; the composed water / haze data term "
+                              "takes one (osm_lin_desc has no such family)")
     if isinstance(operator, PSFOperator):
         if operator.weight_sets != (1, 1):
             raise OsmosisHipError(f"lin_config: the operator carries weight sets {operator.weight_sets} (per_image / per_channel); the "
@@ -1037,4 +1079,4 @@ OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
        "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask", "gain_prepare", "psf_apply_s",
-       "ps_blind_loss_grad_s") + OPS_C
+       "ps_blind_loss_grad_s", "psf_field_apply") + OPS_C
