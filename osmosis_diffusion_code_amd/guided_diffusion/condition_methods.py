@@ -1148,13 +1148,21 @@ class PosteriorSampling(ConditioningMethod):
                                   "y - A x0[:, 0:3]); the 'osmosis' conditioner has one")
 
     def _blind(self):
-        """The operator when it is a `blind_blur` that learns its PSF (its data term steps the weights and couples the batch), else None."""
-        from .measurements import BlindBlurOperator
-        return self.operator if isinstance(self.operator, BlindBlurOperator) and self.operator.learn else None
+        """The operator when it is a `blind_blur` that learns its PSF, or a `blind_field_blur` that learns its field (the data term steps
+        the weights and couples the batch), else None."""
+        from .measurements import BlindBlurOperator, BlindFieldOperator
+        return self.operator if isinstance(self.operator, (BlindBlurOperator, BlindFieldOperator)) and self.operator.learn else None
+
+    def _blind_field(self):
+        """The operator when it is a `blind_field_blur` that learns its field, else None."""
+        from .measurements import BlindFieldOperator
+        return self.operator if isinstance(self.operator, BlindFieldOperator) and self.operator.learn else None
 
     def hip_ok(self, channels: int = 4) -> bool:
         from .measurements import GRID_OPERATORS, _IdentityOperator
         if self._blind() is not None and getattr(self.noiser, "__name__", None) == "poisson":
+            if self._blind_field() is not None:
+                raise NotImplementedError("blind_field_blur learns its field on the gaussian data term only: the poisson noiser is not supported")
             raise NotImplementedError("blind_blur learns its PSF on the gaussian data term only: the poisson noiser is not supported")
         return isinstance(self.operator, (_IdentityOperator,) + GRID_OPERATORS) and \
             getattr(self.noiser, "__name__", None) == "gaussian" and self.scale.numel() in (1, channels)
@@ -1179,6 +1187,11 @@ class PosteriorSampling(ConditioningMethod):
         from .measurements import GRID_OPERATORS
         r0, r1 = self._batch_rows(rows, x0, y)
         mask = self._mask_rows(mask, r0, r1, y.shape[2] * y.shape[3])
+        if self._blind_field() is not None:
+            if (r0, r1) != (0, self._batch[0]):
+                raise ValueError(f"blind_field_blur: the learnt field is shared by the batch -- the data term got rows {r0}:{r1} of the "
+                                 f"batch's {self._batch[0]}; it takes ONE call over all its images")
+            return self._loss_grad_x0_blind_field(x0, y, g_out, loss_out, mask)
         if self._blind() is not None:
             if self.operator.couples_batch and (r0, r1) != (0, self._batch[0]):
                 raise ValueError(f"blind_blur: the learnt PSF is shared by the batch -- the data term got rows {r0}:{r1} of the batch's "
@@ -1334,6 +1347,52 @@ class PosteriorSampling(ConditioningMethod):
                                    per_channel=w.shape[1] > 1)
             else:
                 ops.psf_tap_step(w, tpart, loss, B, nparts, 3 * HW, op.eta, op.l1)
+        return g.view(x0.shape), loss
+
+    def _loss_grad_x0_blind_field(self, x0, y, g_out=None, loss_out=None, mask=None):
+        """The data term through a `blind_field_blur` operator that learns its field: ONE call over the whole batch (the field is
+        shared), the operator's n_iter inner iterations of  Ax = A(w) x0[:, 0:3] (osmx_psf_field_apply);  loss, r = d loss / d Ax
+        (osm_ps_loss_grad_c / _mc);  the per-node tap partials of (r, x0) (osmx2_field_tap_grad);  on the last iteration
+        g[:, 0:3] = A(w)^T r, planes beyond the colours written as 0;  the projected step of every node (osmx2_field_tap_step).  The
+        sub-step spans three libraries, so it is enqueued here, stream-ordered, no host sync (include/ext2/osmosis_blindfield.h).
+        loss and g are those before the last step of w, as the Osmosis conditioner treats phi."""
+        op = self.operator
+        B, C, H, W = x0.shape
+        op.out_shape(H, W)
+        if C not in (3, 4) or tuple(y.shape) != (B, 3, H, W):
+            raise ValueError(f"expected x0 [B,4,H,W] or [B,3,H,W] and measurement [B,3,{H},{W}], got {tuple(x0.shape)} and {tuple(y.shape)}")
+        HW = H * W
+        dy, dx, w = op.taps(x0.device)
+        Ry, Rx = op.radius()
+        gh, gw = op.grid
+        tabs = op.field_tables(H, W, x0.device)
+        lay, NP, _ = ops.field_tap_layout(H, W, gh, gw, 3, x0.device)
+        T = int(dy.numel())
+        key = ("blind_field", B, H, W, str(x0.device), C)
+        st = self._states.get(key)
+        if st is None or st["tpart"].numel() < B * NP * T or st["w_new"].shape != w.shape:
+            f32 = dict(device=x0.device, dtype=torch.float32)
+            st = {"part": torch.empty(B * ops.phys_nblk(HW), **f32), "loss": torch.zeros(B, **f32), "g": torch.empty(B, C, HW, **f32),
+                  "Ax": torch.empty(B, 3, HW, **f32), "r": torch.empty(B, 3, HW, **f32), "tpart": torch.empty(B * NP * T, **f32),
+                  "w_new": torch.empty_like(w)}
+            self._states.pop(key, None)
+            while len(self._states) >= 4:
+                self._states.pop(next(iter(self._states)))
+            self._states[key] = st
+        g = g_out if g_out is not None else st["g"]
+        loss = loss_out if loss_out is not None else st["loss"]
+        x0, y = x0.contiguous(), y.contiguous()
+        Ax, r, tpart = st["Ax"], st["r"], st["tpart"]
+        for it in range(op.n_iter):
+            ops.psf_field_apply(x0, Ax, dy, dx, w, tabs, Ry, Rx, B, 3, C * HW, 3 * HW, H, W)
+            if mask is not None:
+                ops.ps_loss_grad_mc(Ax, y, mask, st["part"], loss, r, B, 3, HW)
+            else:
+                ops.ps_loss_grad_c(Ax, y, st["part"], loss, r, B, 3, HW)
+            ops.field_tap_grad(x0, r, dy, dx, tabs, lay, NP, gh, gw, Ry, Rx, B, 3, C * HW, 3 * HW, H, W, tpart)
+            if it == op.n_iter - 1:
+                ops.psf_field_apply(r, g, dy, dx, w, tabs, Ry, Rx, B, 3, 3 * HW, C * HW, H, W, adjoint=True, zero_planes=C - 3)
+            ops.field_tap_step(w, st["w_new"], tpart, loss, lay, NP, B, 3 * HW, op.eta, op.l1, op.smooth)
         return g.view(x0.shape), loss
 
     def conditioning(self, x_prev, x_t, x_0_hat, measurement, **kwargs):

@@ -883,6 +883,113 @@ class BlindBlurOperator(PSFOperator):
         return self
 
 
+def blind_field_init(kernel_size, grid, init="gaussian", init_sigma=None):
+    """The starting point of a learnt field, float64 [gh,gw,k,k], every node non-negative and summing to 1: `init` is one of
+    `blind_init_kernel`'s forms (the same kernel at every node), or a field of the user's -- a [gh,gw,kh,kw] array, nested list or
+    the path of a .npy file holding one (every node as `blind_init_kernel` takes a kernel: centred in the k x k support)."""
+    what = "blind_field_blur"
+    k = _field_kernel_size(kernel_size, what)
+    gh, gw = _field_grid(grid, what)
+    if (isinstance(init, (str, bytes)) or hasattr(init, "__fspath__")) and str(os.fspath(init) if hasattr(init, "__fspath__") else init).endswith(".npy"):
+        init = np.load(init, allow_pickle=False)
+    if isinstance(init, torch.Tensor):
+        init = init.detach().cpu().numpy()
+    try:
+        if not isinstance(init, (str, bytes)) and np.ndim(init) == 4:
+            nodes = np.asarray(init, dtype=np.float64)
+            if nodes.shape[:2] != (gh, gw):
+                raise ValueError(f"{what}: the init field has {nodes.shape[0]} x {nodes.shape[1]} nodes, the grid is {gh} x {gw}")
+            return np.stack([np.stack([blind_init_kernel(k, nodes[jy, jx]) for jx in range(gw)]) for jy in range(gh)])
+        one = blind_init_kernel(k, init, init_sigma)
+    except ValueError as e:
+        raise ValueError(str(e).replace("blind_blur", what, 1)) from None
+    return np.ascontiguousarray(np.broadcast_to(one, (gh, gw, k, k)))
+
+
+@register_operator(name="blind_field_blur")
+class BlindFieldOperator(PSFFieldOperator):
+    """Blind spatially varying deblurring: `field_blur`'s operator -- a FIELD of point-spread functions on a gh x gw node grid,
+    interpolated bilinearly over the frame -- whose node kernels are unknown and LEARNT during sampling.  Every node carries the dense
+    support kernel_size x kernel_size (T = k^2 taps in row-major order, Ry = Rx = k // 2); the weights live in ONE device tensor `w`
+    fp32 [gh,gw,T] that the step kernel overwrites between the network's forward and backward, with no host sync
+    (osmx2_field_tap_grad / osmx2_field_tap_step of the second staging library, include/ext2/osmosis_blindfield.h: per inner
+    iteration a projected gradient step of every node on Q(w) = sum_b ||M (y_b - A(w) x0_b)||^2 / (2 * 3 h w), each node on its own
+    simplex, optionally tied to its 4-neighbours by `smooth`).  The field is shared by the batch (`couples_batch`) and by the planes.
+    Config keys (an unknown one raises ValueError): kernel_size (odd, <= 61, default 31); grid ([gh, gw], default [3, 3], the
+    field's limits); init (`blind_init_kernel`'s forms -- the same kernel at every node -- or a [gh,gw,kh,kw] array / .npy path)
+    with init_sigma; eta (0.1), n_iter (1), l1 (0.0), smooth (0.0: >= 0, finite), learn (True).  The defaults are parameters, not
+    tuned values.  `per_image` / `per_channel` are refused.  `learn: False` IS `field_blur` with the init field (its non-zero taps,
+    the three-launch data term, nothing stepped); the driver still treats it by its name: `simulate: True` needs `simulate_with`.
+    `taps(device)` returns (dy, dx, w_live); `forward` / `transpose` apply the current estimate; `kernels()` copies it from the device
+    on demand, float64 [gh,gw,k,k]; `reset()` puts the initial field back in place (same tensor: recorded launches stay valid)."""
+
+    couples_batch = True
+
+    DRIVER_KEYS = ("simulate", "simulate_with")
+
+    def __init__(self, device, kernel_size=31, grid=(3, 3), init="gaussian", init_sigma=None, eta=0.1, n_iter=1, l1=0.0, smooth=0.0,
+                 learn=True, batch_size=1, **kwargs):
+        what = "blind_field_blur"
+        many = [k for k in ("per_image", "per_channel") if k in kwargs]
+        if many:
+            raise ValueError(f"{what}: {', '.join(many)} is not supported -- the learnt field is shared by the images of a batch and by "
+                             f"the colour planes (a field per image or per channel is out of scope)")
+        unknown = sorted(set(kwargs) - set(self.DRIVER_KEYS))
+        if unknown:
+            raise ValueError(f"{what}: unknown config key(s) {unknown} (known: kernel_size, grid, init, init_sigma, eta, n_iter, l1, "
+                             f"smooth, learn, simulate, simulate_with)")
+        PSFOperator.__init__(self, device, batch_size)
+        self._field = self._init = np.ascontiguousarray(blind_field_init(kernel_size, grid, init, init_sigma))
+        self.model, self.normalize = None, True
+        self.kernel_size = int(kernel_size)
+        self.eta, self.l1, self.smooth = float(eta), float(l1), float(smooth)
+        for key, v, given in (("eta", self.eta, eta), ("l1", self.l1, l1), ("smooth", self.smooth, smooth)):
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{what}: {key} must be a finite number >= 0, got {given!r}")
+        if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 1:
+            raise ValueError(f"{what}: n_iter must be an integer >= 1, got {n_iter!r}")
+        self.n_iter = int(n_iter)
+        self.learn = bool(learn)
+        self.couples_batch = self.learn       # a fixed field leaves the images of a batch independent
+
+    def host_taps(self):
+        if not self.learn:
+            return super().host_taps()           # the init field's non-zeros: field_blur
+        if self._host is None:
+            k = self.kernel_size
+            iy, ix = np.divmod(np.arange(k * k), k)
+            w = np.ascontiguousarray(self._init.reshape(*self._init.shape[:2], k * k).astype(np.float32))
+            self._host = ((iy - k // 2).astype(np.int32), (ix - k // 2).astype(np.int32), w)
+        return self._host
+
+    def radius(self):
+        if not self.learn:
+            return super().radius()
+        return self.kernel_size // 2, self.kernel_size // 2
+
+    def _to_device(self, a, device):
+        # the live weights are a copy of their own: on the CPU `from_numpy` would alias the host's init, which `reset()` reads
+        return super()._to_device(a.copy() if self.learn else a, device)
+
+    def kernels(self):
+        """The current estimate of every node, float64 [gh,gw,k,k] (one device-to-host copy); not learning: the init field."""
+        if not self.learn:
+            return self._init.copy()
+        t = self._dev.get(str(self.device))
+        if t is None and self._dev:
+            same = [v for v in self._dev.values() if v[2].device.type == self.device.type]
+            t = (same or list(self._dev.values()))[-1]
+        w = self.host_taps()[2] if t is None else t[2].detach().cpu().numpy()
+        return w.astype(np.float64).reshape(self._init.shape)
+
+    def reset(self):
+        """Put the initial field back on every device the operator lives on, in place."""
+        if self.learn:
+            for dev, (_, _, w) in self._dev.items():
+                w.copy_(torch.from_numpy(self.host_taps()[2]))
+        return self
+
+
 class LearnableOperator(ABC):
     @abstractmethod
     def forward(self, data, **kwargs):
@@ -922,6 +1029,9 @@ def build_degradation(degradation, device, batch_size=1):
     'blind_blur' and 'field_blur' (by name: they are `PSFOperator`s, but a learnt PSF or a field of PSFs inside the water / haze model
     is out of scope)."""
     if degradation is None or not isinstance(degradation, dict):
+        if isinstance(degradation, BlindFieldOperator):
+            raise ValueError("degradation: 'blind_field_blur' (a learnt field of point-spread functions) inside a physical image-formation "
+                             "model is not supported -- the composed data term takes one fixed point-spread function; give a 'psf_blur' kernel")
         if isinstance(degradation, PSFFieldOperator):
             raise ValueError("degradation: 'field_blur' (a field of point-spread functions) inside a physical image-formation model is not "
                              "supported -- the composed data term takes one point-spread function; give a fixed 'psf_blur' kernel")
@@ -935,6 +1045,9 @@ def build_degradation(degradation, device, batch_size=1):
     if name == "blind_blur":
         raise ValueError("degradation: 'blind_blur' (a learnt PSF) inside a physical image-formation model is not supported -- its "
                          "weights and the water / haze parameters would have to be stepped together; give a fixed 'psf_blur' kernel")
+    if name == "blind_field_blur":
+        raise ValueError("degradation: 'blind_field_blur' (a learnt field of point-spread functions) inside a physical image-formation "
+                         "model is not supported -- the composed data term takes one fixed point-spread function; give a 'psf_blur' kernel")
     if name == "field_blur":
         raise ValueError("degradation: 'field_blur' (a field of point-spread functions) inside a physical image-formation model is not "
                          "supported -- the composed data term takes one point-spread function; give a fixed 'psf_blur' kernel")

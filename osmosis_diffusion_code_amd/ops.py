@@ -877,7 +877,10 @@ def ps_blind_optimize_s(x0, y, mask, dy, dx, w, Ry, Rx, B, Cc, H, W, Ax, r, lpar
 def lin_desc(operator, H, W, device) -> LinDesc:
     """The osm_lin_desc of a `measurements.GRID_OPERATORS` instance at the image grid H x W (include/osmosis_physlin.h).  The device
     tables / taps it points at are the operator's own cached tensors; they are also kept on the descriptor (`_keep`)."""
-    from .guided_diffusion.measurements import PSFFieldOperator, PSFOperator, SeparableOperator
+    from .guided_diffusion.measurements import BlindFieldOperator, PSFFieldOperator, PSFOperator, SeparableOperator
+    if isinstance(operator, BlindFieldOperator):
+        raise _lib.OsmosisHipError("lin_desc: 'blind_field_blur' carries a learnt field of point-spread functions; the composed water / "
+                                   "haze data term takes one fixed point-spread function (osm_lin_desc has no such family)")
     if isinstance(operator, PSFFieldOperator):
         raise _lib.OsmosisHipError("lin_desc: 'field_blur' carries a field of point-spread functions; the composed water / haze data term "
                                    "takes one (osm_lin_desc has no such family)")
@@ -1236,6 +1239,84 @@ def psf_field_apply(x, out, dy, dx, w, tabs, Ry, Rx, B, P, x_img_stride, out_img
     call("osmx_psf_field_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0),
          ptr(fx), B, P, int(x_img_stride), int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(),
          keep=(x, out, dy, dx, w, iy0, fy, ix0, fx))
+
+
+# ----------------------------------------------------------------------------- learning a field of PSFs (include/ext2/osmosis_blindfield.h)
+_field_layouts = {}     # (H, W, gh, gw, P, device) -> (lay on the device, partials per image, lay on the host)
+
+
+def field_tap_layout(H, W, gh, gw, P=3, device=None):
+    """The compact layout of the per-node tap partials (osmx2_field_tap_layout of the second staging library, host only): returns
+    (lay, NP, host) -- `lay` int32 [2 gh + 2 gw + gh gw + 1] = ty0[gh], ty1[gh], tx0[gw], tx1[gw], off[gh gw + 1] (the 32 x 32 tile
+    rows / columns every node row / column reaches and the nodes' offsets in partials per image), on `device` when one is given
+    (cached), else None; NP = off[-1] partials of T floats per image; `host` the same array as numpy."""
+    import ctypes as C
+    import numpy as np
+    H, W, gh, gw, P = int(H), int(W), int(gh), int(gw), int(P)
+    key = (H, W, gh, gw, P, str(device))
+    hit = _field_layouts.get(key)
+    if hit is not None:
+        return hit
+    iy0, _, ix0, _ = gain_tables_host(H, W, gh, gw) if 2 <= gh <= H and 2 <= gw <= W else (np.zeros(1, np.int32),) * 4
+    lay = np.zeros(2 * gh + 2 * gw + gh * gw + 1 if gh > 0 and gw > 0 else 1, dtype=np.int32)
+    lib = _lib.load_ext2()
+    n = lib.osmx2_field_tap_layout(gh, gw, iy0.ctypes.data_as(C.c_void_p), ix0.ctypes.data_as(C.c_void_p), H, W, P, 1, 1,
+                                   lay.ctypes.data_as(C.c_void_p))
+    if n < 0:
+        raise _lib.OsmosisHipError(f"osmx2_field_tap_layout failed ({n}): {_lib.last_error('osmx2_field_tap_layout')}")
+    while len(_field_layouts) >= 16:
+        _field_layouts.pop(next(iter(_field_layouts)))
+    out = _field_layouts[key] = (None if device is None else torch.from_numpy(lay).to(device), int(n), lay)
+    return out
+
+
+def _check_field_lay(name, lay, gh, gw):
+    if lay.dtype != torch.int32 or not lay.is_contiguous() or lay.numel() != 2 * gh + 2 * gw + gh * gw + 1:
+        raise _lib.OsmosisHipError(f"{name}: the layout is int32 [{2 * gh + 2 * gw + gh * gw + 1}] (`field_tap_layout`), got "
+                                   f"{tuple(lay.shape)} {lay.dtype}")
+
+
+def field_tap_grad(x, r, dy, dx, tabs, lay, NP, gh, gw, Ry, Rx, B, P, x_img_stride, r_img_stride, H, W, part):
+    """The per-node tile partials of c_n[b][t] = sum_p sum_ij hat_n(i,j) r[b,p,i,j] x[b,p,refl(i+dy[t]),refl(j+dx[t])]
+    (osmx2_field_tap_grad): the tap gradient of the field operator `psf_field_apply`, in the compact layout of
+    `field_tap_layout(H, W, gh, gw, P, device)` = (lay, NP, _); part fp32 with at least B NP T elements, every one written.
+    tabs = `field_tables(H, W, gh, gw, device)`.  Deterministic (gather form, no atomics)."""
+    for t in (x, r, part):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("field_tap_grad takes contiguous fp32 tensors")
+    _check_tap_lists("field_tap_grad", dy, dx)
+    B, P, H, W, T, gh, gw, NP = int(B), int(P), int(H), int(W), int(dy.shape[0]), int(gh), int(gw), int(NP)
+    _check_field_lay("field_tap_grad", lay, gh, gw)
+    iy0, fy, ix0, fx = tabs
+    for k, t, n, dt in (("iy0", iy0, H, torch.int32), ("fy", fy, H, torch.float32), ("ix0", ix0, W, torch.int32), ("fx", fx, W, torch.float32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise _lib.OsmosisHipError(f"field_tap_grad: table `{k}` must be contiguous {dt} [{n}], got {tuple(t.shape)} {t.dtype}")
+    if NP != field_tap_layout(H, W, gh, gw, P)[1]:
+        raise _lib.OsmosisHipError(f"field_tap_grad: NP {NP} is not the layout's partial count for {P} x {H} x {W} under {gh} x {gw} nodes")
+    if B >= 1 and (x.numel() < (B - 1) * int(x_img_stride) + P * H * W or r.numel() < (B - 1) * int(r_img_stride) + P * H * W
+                   or part.numel() < B * NP * T):
+        raise _lib.OsmosisHipError(f"field_tap_grad: x ({x.numel()} elements) / r ({r.numel()}) / part ({part.numel()}) are smaller than "
+                                   f"{B} images of {P} x {H} x {W} at strides {x_img_stride} / {r_img_stride} with {NP} partials of {T} taps")
+    call("osmx2_field_tap_grad", ptr(x), ptr(r), ptr(dy), ptr(dx), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0), ptr(fx),
+         ptr(lay), B, P, int(x_img_stride), int(r_img_stride), H, W, ptr(part), _s(), keep=(x, r, dy, dx, iy0, fy, ix0, fx, lay, part))
+
+
+def field_tap_step(w, w_new, part, loss, lay, NP, B, hw3, eta, l1=0.0, smooth=0.0):
+    """One projected step of every node of the field w fp32 [gh,gw,T], in place (osmx2_field_tap_step): per node `psf_tap_step`'s fp64
+    arithmetic on that node's partials, plus eta smooth times the 4-neighbour Laplacian of the field; w_new fp32 [gh,gw,T] is the
+    workspace the kernel writes (nodes read their neighbours while they step) before w_new is copied over w on the same stream."""
+    for t in (w, w_new, part, loss):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.OsmosisHipError("field_tap_step takes contiguous fp32 tensors")
+    if w.dim() != 3 or w_new.shape != w.shape:
+        raise _lib.OsmosisHipError(f"field_tap_step: w and w_new are fp32 [gh,gw,T], got {tuple(w.shape)} and {tuple(w_new.shape)}")
+    gh, gw, T = (int(v) for v in w.shape)
+    _check_field_lay("field_tap_step", lay, gh, gw)
+    B, NP = int(B), int(NP)
+    if B >= 1 and (part.numel() < B * NP * T or loss.numel() < B):
+        raise _lib.OsmosisHipError(f"field_tap_step: part ({part.numel()} elements) / loss ({loss.numel()}) are smaller than {B} x {NP} x {T} / {B}")
+    call("osmx2_field_tap_step", ptr(w), ptr(w_new), ptr(part), ptr(loss), ptr(lay), gh, gw, B, T, int(hw3), float(eta), float(l1),
+         float(smooth), _s(), keep=(w, w_new, part, loss, lay))
 
 
 def gain_check(grid, eta, n_iter, smooth, g_min, H=None, W=None):

@@ -662,7 +662,12 @@ def restore_image(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, sa
     `<name>_kernel.png`, a per-channel one as one RGB picture), and `simulate: True` needs `simulate_with: {name: <a grid operator>,
     ...}` -- the blur that makes y = noiser(A* ref); it must keep the image's size.  Without `per_image` ONE PSF serves the whole
     batch (photos through one optical system); with `per_image: True` every image of the batch learns -- and its result carries --
-    its own."""
+    its own.
+
+    Operator `blind_field_blur` (the FIELD is learnt during the chain): as `blind_blur` -- `operator.reset()` before every global
+    iteration, `simulate: True` needs `simulate_with` (typically `field_blur`) -- with `field_blur`'s results: `kernel` fp32
+    [gh,gw,k,k], the node kernels at the end of the chain, and their mosaic as `<name>_kernel.png`.  One field serves the whole
+    batch; not tiled."""
     return [_image_result(run, 0, whole=True)
             for run in _run_chains(model, ref_img, cfg, device=device, image_idx=image_idx, x_scale=x_scale,
                                    same_seed_per_image=same_seed_per_image, mask=mask, tiling=tiling, depth=depth,
@@ -701,7 +706,10 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
     pretrain = cfg["unet_model"]["pretrain_model"]
     shape = list(ref_img.shape)
     y_clean = ref_img
-    is_blind = op_cfg.get("name") == "blind_blur"
+    is_blind = op_cfg.get("name") in ("blind_blur", "blind_field_blur")
+    blind_name = op_cfg.get("name")
+    if blind_name == "blind_field_blur" and tiling is not None:
+        raise NotImplementedError("blind_field_blur: tiling is not supported (the learnt field spans one frame; the 'ps' branch is not tiled)")
     is_field = isinstance(operator, PSFFieldOperator)       # a field of PSFs: every result carries the node kernels
     if isinstance(operator, GRID_OPERATORS):
         # a blur / super-resolution operator: the measurement is simulated from the clean image, y = noiser(A ref), as the DPS driver
@@ -711,15 +719,15 @@ def _run_chains(model, ref_img, cfg, device=None, image_idx=0, x_scale=1.0, same
             # for the unknown optics, y = noiser(A* ref)
             sim_cfg = op_cfg.get("simulate_with")
             if not isinstance(sim_cfg, dict) or sim_cfg.get("name") is None:
-                raise ValueError("blind_blur: `simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` (the blur that produces "
+                raise ValueError(f"{blind_name}: " "`simulate: True` needs `simulate_with: {name: <a grid operator>, ...}` (the blur that produces "
                                  "the measurement); `simulate: False` takes the photo as it is")
             sim_cfg = dict(sim_cfg)
             sim_cfg["batch_size"] = ref_img.shape[0]
             truth = get_operator(device=device, **sim_cfg)
             if not isinstance(truth, GRID_OPERATORS):
-                raise ValueError(f"blind_blur: simulate_with {sim_cfg['name']!r} is not a linear operator with a grid of its own")
+                raise ValueError(f"{blind_name}: simulate_with {sim_cfg['name']!r} is not a linear operator with a grid of its own")
             if tuple(truth.out_shape(*ref_img.shape[-2:])) != tuple(ref_img.shape[-2:]):
-                raise ValueError(f"blind_blur: simulate_with {sim_cfg['name']!r} changes the image's size {tuple(ref_img.shape[-2:])} -> "
+                raise ValueError(f"{blind_name}: simulate_with {sim_cfg['name']!r} changes the image's size {tuple(ref_img.shape[-2:])} -> "
                                  f"{tuple(truth.out_shape(*ref_img.shape[-2:]))}; a PSF keeps it")
             y_clean = truth.forward(ref_img[:, 0:3].to(torch.float32).contiguous())
         elif op_cfg.get("simulate", True):

@@ -40,6 +40,9 @@ registered for the "cuda" device type only, which is HIP on ROCm).
                                                            the same with one weight set per image and / or per plane
     osmosis::psf_field_apply(x, dy, dx, w[gh,gw,T], iy0, fy, ix0, fx, Ry, Rx, adjoint) -> out
                                                            a field of PSFs on a node grid, interpolated bilinearly over the frame
+    osmosis::field_tap_grad(x, r, dy, dx, iy0, fy, ix0, fx, gh, gw, Ry, Rx) -> part[B,NP,T]
+    osmosis::field_tap_step(w[gh,gw,T], part, loss, H, W, P, eta, l1, smooth)
+                                                           learning that field: the per-node tap partials, one projected step (w mutated)
     osmosis::ps_blind_loss_grad_s(x0, y, mask, dy, dx, w[nb,nc,T], Ry, Rx, n_iter, eta, l1) -> (loss, g)
                                                            blind deblurring with one learnt PSF per image / per colour plane (w mutated)
 
@@ -788,12 +791,64 @@ def _psf_field_backward(ctx, grad):
 psf_field_apply.register_autograd(_psf_field_backward, setup_context=_psf_field_setup)
 
 
+# ---- learning that field (include/ext2/osmosis_blindfield.h): the per-node tap partials and the projected step of every node
+@torch.library.custom_op("osmosis::field_tap_grad", mutates_args=(), device_types="cuda")
+def field_tap_grad(x: torch.Tensor, r: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, iy0: torch.Tensor, fy: torch.Tensor,
+                   ix0: torch.Tensor, fx: torch.Tensor, gh: int, gw: int, Ry: int, Rx: int) -> torch.Tensor:
+    """part [B, NP, T] of x, r [B,P,H,W] (osmx2_field_tap_grad): the 32 x 32 tile partials of the tap gradient c_n of every node n of the
+    gh x gw field, in the compact layout of `ops.field_tap_layout(H, W, gh, gw, P)` (per image; per node; plane-major; the node's
+    tiles row-major); (iy0, fy, ix0, fx) = `ops.field_tables(H, W, gh, gw, device)`.  No autograd formula."""
+    name = "osmosis::field_tap_grad"
+    if x.dim() != 4 or tuple(r.shape) != tuple(x.shape):
+        raise OsmosisHipError(f"{name}: x and r must be [B,P,H,W] alike, got {tuple(x.shape)} and {tuple(r.shape)}")
+    if dy.dim() != 1 or tuple(dx.shape) != tuple(dy.shape):
+        raise OsmosisHipError(f"{name}: expected dy [T], dx [T], got {tuple(dy.shape)}, {tuple(dx.shape)}")
+    B, P, H, W = x.shape
+    lay, NP, _ = ops.field_tap_layout(H, W, gh, gw, P, x.device)
+    part = torch.empty((B, NP, dy.shape[0]), device=x.device, dtype=torch.float32)
+    ops.field_tap_grad(x.contiguous(), r.contiguous(), dy.contiguous(), dx.contiguous(),
+                       (iy0.contiguous(), fy.contiguous(), ix0.contiguous(), fx.contiguous()), lay, NP, gh, gw, Ry, Rx, B, P, P * H * W,
+                       P * H * W, H, W, part)
+    return part
+
+
+@field_tap_grad.register_fake
+def _field_tap_grad_fake(x, r, dy, dx, iy0, fy, ix0, fx, gh, gw, Ry, Rx):
+    B, P, H, W = x.shape
+    return x.new_empty((B, ops.field_tap_layout(int(H), int(W), gh, gw, int(P))[1], dy.shape[0]))
+
+
+@torch.library.custom_op("osmosis::field_tap_step", mutates_args=("w",), device_types="cuda")
+def field_tap_step(w: torch.Tensor, part: torch.Tensor, loss: torch.Tensor, H: int, W: int, P: int, eta: float, l1: float,
+                   smooth: float) -> None:
+    """One projected step of every node of the field w fp32 [gh,gw,T], IN PLACE (osmx2_field_tap_step): part [B, NP, T] as
+    `osmosis::field_tap_grad` returns it for P planes of H x W, loss [B]; the normaliser is 3 H W."""
+    name = "osmosis::field_tap_step"
+    if w.dim() != 3 or not w.is_contiguous() or part.dim() != 3 or part.shape[2] != w.shape[2] or loss.dim() != 1 \
+            or loss.shape[0] != part.shape[0]:
+        raise OsmosisHipError(f"{name}: expected a contiguous w [gh,gw,T], part [B,NP,T] and loss [B], got {tuple(w.shape)}, "
+                              f"{tuple(part.shape)}, {tuple(loss.shape)}")
+    gh, gw = int(w.shape[0]), int(w.shape[1])
+    lay, NP, _ = ops.field_tap_layout(H, W, gh, gw, P, w.device)
+    if part.shape[1] != NP:
+        raise OsmosisHipError(f"{name}: part has {part.shape[1]} partials per image, the layout of {P} x {H} x {W} under {gh} x {gw} has {NP}")
+    ops.field_tap_step(w, torch.empty_like(w), part.contiguous(), loss.contiguous(), lay, NP, part.shape[0], 3 * H * W, eta, l1, smooth)
+
+
+@field_tap_step.register_fake
+def _field_tap_step_fake(w, part, loss, H, W, P, eta, l1, smooth):
+    return None
+
+
 # ---- the water / haze data term through a linear operator (blur, super-resolution, a PSF) between the model and the photo
 def lin_config(operator, H, W, device) -> Tuple[int, List[torch.Tensor], List[int]]:
     """(family, tables, dims) of a `measurements.GRID_OPERATORS` instance for phys_loss_grad_lin at the image grid H x W:
     family 0 (separable): the four forward band tables then the four transposed ones, dims = [h, w];
     family 1 (psf): dy, dx, w, dims = [Ry, Rx]."""
-    from .guided_diffusion.measurements import PSFFieldOperator, PSFOperator, SeparableOperator
+    from .guided_diffusion.measurements import BlindFieldOperator, PSFFieldOperator, PSFOperator, SeparableOperator
+    if isinstance(operator, BlindFieldOperator):
+        raise OsmosisHipError("lin_config: 'blind_field_blur' carries a learnt field of point-spread functions; the composed water / haze "
+                              "data term takes one fixed point-spread function (osm_lin_desc has no such family)")
     if isinstance(operator, PSFFieldOperator):
         raise OsmosisHipError("lin_config: 'field_blur' carries a field of point-spread functions; the composed water / haze data term "
                               "takes one (osm_lin_desc has no such family)")
@@ -1079,4 +1134,4 @@ OPS_C = ("posterior_c", "posterior_clip_c", "posterior_dynthr_c", "posterior_bwd
 OPS = ("unet_fwd", "unet_bwd_data", "posterior", "posterior_clip", "clamp_bwd", "quantile_abs", "posterior_dynthr", "dynthr_bwd", "posterior_bwd", "guide_update", "guide_update_rng", "ddim_update", "phys_loss_grad", "phys_loss_grad_m",
        "ps_loss_grad_mc", "exposure_mask", "recon_fullres", "tile_gather", "tile_blend", "linop_apply", "psf_apply", "phys_loss_grad_lin",
        "phys_loss_grad_g", "ps_blind_loss_grad", "depth_prior_loss_grad", "solver_update", "robust_mask", "gain_prepare", "psf_apply_s",
-       "ps_blind_loss_grad_s", "psf_field_apply") + OPS_C
+       "ps_blind_loss_grad_s", "psf_field_apply", "field_tap_grad", "field_tap_step") + OPS_C

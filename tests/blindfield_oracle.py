@@ -1,0 +1,173 @@
+"""The oracle of blind spatially varying deblurring (operator `blind_field_blur`, include/ext2/osmosis_blindfield.h): torch on the CPU,
+float64 unless told otherwise.  The reference has no such operator; the definition is the header's.
+
+  A(K) x      = sum_n hat_n (.) conv(pad(x, reflect), K_n)                 (`psffield_oracle.forward_sum`, K [gh,gw,kh,kw] a leaf)
+  loss_b, r   = `blind_oracle.loss_and_r`
+  c_n[b]      = d <r_b, A(K) x_b> / d K_n  by autograd (`tap_corr`);  `tap_corr_direct`: a double loop over pixels per node and tap
+  step        = the header's, numpy float64, per node `blind_oracle.step`'s arithmetic plus the 4-neighbour term (`step`)
+`inner_loop` runs n_iter of them in the header's order (loss and g before the last step); `ps_chain` drives a DDPM 'ps' chain as
+`blind_oracle.ps_chain` does; `recover` is the recovery experiment of the README bullet."""
+import numpy as np
+import torch
+
+import blind_oracle as BO
+import psffield_oracle as FO
+
+
+def tap_corr(r, x, gh, gw, kh, kw):
+    """c [B, gh, gw, kh, kw] by autograd w.r.t. the node kernels."""
+    out = []
+    for b in range(x.shape[0]):
+        K = torch.zeros(gh, gw, kh, kw, dtype=x.dtype, requires_grad=True)
+        (c,) = torch.autograd.grad((r[b:b + 1] * FO.forward_sum(x[b:b + 1], K)).sum(), K)
+        out.append(c)
+    return torch.stack(out)
+
+
+def tap_corr_direct(r, x, gh, gw, dy, dx):
+    """c [B, gh, gw, T] by the definition: per node and tap a sum over the pixels (small images only)."""
+    B, P, H, W = x.shape
+    hat = FO.hat_field(H, W, gh, gw).numpy()
+    rn, xn = r.numpy().astype(np.float64), x.numpy().astype(np.float64)
+    c = np.zeros((B, gh, gw, len(dy)))
+    for t, (a, e) in enumerate(zip(dy, dx)):
+        rows = [BO.refl(i + int(a), H) for i in range(H)]
+        cols = [BO.refl(j + int(e), W) for j in range(W)]
+        prod = rn * xn[:, :, rows][:, :, :, cols]                               # [B,P,H,W]
+        c[:, :, :, t] = np.einsum("nmij,bpij->bnm", hat, prod)
+    return c
+
+
+def laplace(w):
+    """s_n[t] = sum over the existing 4-neighbours m in the order up, left, right, down of (w_n[t] - w_m[t]); w float64 [gh,gw,T]."""
+    gh, gw, _ = w.shape
+    s = np.zeros_like(w)
+    for jy in range(gh):
+        for jx in range(gw):
+            acc = np.zeros(w.shape[2])
+            for my, mx in ((jy - 1, jx), (jy, jx - 1), (jy, jx + 1), (jy + 1, jx)):
+                if 0 <= my < gh and 0 <= mx < gw:
+                    acc = acc + (w[jy, jx] - w[my, mx])
+            s[jy, jx] = acc
+    return s
+
+
+def step(w, c, loss, hw3, eta, l1=0.0, smooth=0.0):
+    """One projected step of every node: w fp32 [gh,gw,T], c float64 [B,gh,gw,T], loss [B] (fp32 values) -> w_new fp32 [gh,gw,T].
+    Every node reads the field as it was before the step."""
+    w = np.asarray(w, dtype=np.float32)
+    c = np.asarray(c, dtype=np.float64)
+    loss = np.asarray(loss, dtype=np.float64)
+    gh, gw, T = w.shape
+    lap = laplace(w.astype(np.float64)) if smooth != 0.0 else None
+    out = w.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for jy in range(gh):
+            for jx in range(gw):
+                s = np.zeros(T)
+                for b in range(c.shape[0]):
+                    s = s + loss[b] * c[b, jy, jx]
+                g = s / float(hw3)
+                gbar = BO.sum_t(g) / T
+                v = (w[jy, jx].astype(np.float64) - eta * (g - gbar)) - eta * l1
+                if smooth != 0.0:
+                    v = v - (eta * smooth) * lap[jy, jx]
+                u = np.where(v > 0, v, 0.0)
+                S = BO.sum_t(u)
+                if S > 0 and not np.isinf(S):
+                    out[jy, jx] = (u / S).astype(np.float32)
+    return out
+
+
+def field_of(w, kh, kw, dtype=torch.float64):
+    """K [gh,gw,kh,kw] of dense row-major weights w [gh,gw,kh kw]."""
+    w = np.asarray(w)
+    return torch.from_numpy(w.reshape(w.shape[0], w.shape[1], kh, kw).astype(np.float64)).to(dtype)
+
+
+def inner_loop(x0, y, mask, w0, kh, kw, n_iter, eta, l1=0.0, smooth=0.0, dtype=torch.float64):
+    """n_iter iterations in the header's order.  x0 [B,C,H,W], y [B,3,H,W], mask [B,3,H,W] or None, w0 fp32 [gh,gw,kh kw] (dense,
+    row-major).  The image side (A, loss, r, c, g) in `dtype`, the step always in float64 from fp32-rounded losses.
+    Returns dict(loss [B], g [B,C,H,W], w fp32 [gh,gw,T], c [B,gh,gw,T], first_loss)."""
+    x0 = x0.to(dtype)
+    y = y.to(dtype)
+    mask = None if mask is None else mask.to(dtype)
+    w = np.asarray(w0, dtype=np.float32).copy()
+    gh, gw, _ = w.shape
+    B, C, H, W = x0.shape
+    first = None
+    for it in range(n_iter):
+        K = field_of(w, kh, kw, dtype)
+        xs = x0[:, 0:3].detach().clone().requires_grad_(True)
+        Ax = FO.forward_sum(xs, K).to(dtype)
+        loss, r = BO.loss_and_r(Ax.detach(), y, mask)
+        c = tap_corr(r.to(dtype), x0[:, 0:3], gh, gw, kh, kw).reshape(B, gh, gw, -1)
+        if first is None:
+            first = loss.clone()
+        if it == n_iter - 1:
+            (gx,) = torch.autograd.grad(Ax, xs, r.to(dtype))
+            g = torch.zeros_like(x0)
+            g[:, 0:3] = gx
+        w = step(w, c.double().numpy(), loss.float().double().numpy(), 3 * H * W, eta, l1, smooth)
+    return dict(loss=loss, g=g, w=w, c=c, first_loss=first)
+
+
+def ps_chain(unet_fn, tb, x_T, y, noises, w0, kh, kw, n_iter, eta, l1, smooth, scale, mask=None):
+    """`blind_oracle.ps_chain` with the field's data term.  Returns (img, w fp32 [gh,gw,T])."""
+    from oracle import diffusion_ref as D
+    img = x_T.clone()
+    w = np.asarray(w0, dtype=np.float32).copy()
+    T = tb.num_timesteps
+    for k_, idx in enumerate(range(T - 1, -1, -1)):
+        img = img.detach().requires_grad_(True)
+        out = D.p_mean_variance(tb, unet_fn(img, torch.tensor([tb.timestep_map[idx]] * img.shape[0])), img, idx)
+        sample = out["mean"].detach()
+        if idx != 0:
+            sample = sample + torch.exp(0.5 * out["log_variance"].detach()) * noises[k_]
+        res = inner_loop(out["pred_xstart"].detach(), y, mask, w, kh, kw, n_iter, eta, l1, smooth)
+        w = res["w"]
+        (grad,) = torch.autograd.grad(out["pred_xstart"], img, res["g"].to(img.dtype))
+        img = sample - scale * grad
+    return img.detach(), w
+
+
+def recovery_problem(seed, B=1, H=36, W=44, grid=(3, 3), k=5, noise=0.005):
+    """The recovery experiment's data: x = torch.rand [B,3,H,W] float64 under torch.manual_seed(seed), K* =
+    radial_defocus_field(k, 0.5, 2.0, grid), y = A(K*) x + noise N(0, 1), the init a gaussian of sigma 1 at every node.
+    Returns (x, y, K* float64 [gh,gw,k,k], w0 fp32 [gh,gw,k k])."""
+    from osmosis_diffusion_code_amd.guided_diffusion.measurements import blind_field_init, radial_defocus_field
+    torch.manual_seed(seed)
+    x = torch.rand(B, 3, H, W, dtype=torch.float64)
+    kstar = radial_defocus_field(k, 0.5, 2.0, grid)
+    y = FO.forward_sum(x, torch.from_numpy(kstar)) + noise * torch.randn(B, 3, H, W, dtype=torch.float64)
+    w0 = blind_field_init(k, grid, "gaussian", 1.0).reshape(grid[0], grid[1], k * k).astype(np.float32)
+    return x, y, kstar, w0
+
+
+def node_l1(w, kstar):
+    """||w_n - k*_n||_1 per node, [gh,gw]."""
+    gh, gw = kstar.shape[:2]
+    return np.abs(np.asarray(w, dtype=np.float64).reshape(gh, gw, -1) - kstar.reshape(gh, gw, -1)).sum(axis=2)
+
+
+def recover(x, y, kstar, w0, steps, eta, l1=0.0, smooth=0.0, shared=False):
+    """`steps` single-iteration sub-steps on the known image.  shared: ONE PSF fitted to the same data (the node gradients summed,
+    every node carrying the same weights).  Returns dict(first, last: the summed losses; err_first, err_last: `node_l1`; w)."""
+    k = kstar.shape[2]
+    w = np.asarray(w0, dtype=np.float32).copy()
+    gh, gw, T = w.shape
+    B, _, H, W = x.shape
+    first = err_first = None
+    for _ in range(steps):
+        K = field_of(w, k, k)
+        loss, r = BO.loss_and_r(FO.forward_sum(x, K), y)
+        if first is None:
+            first, err_first = float(loss.sum()), node_l1(w, kstar)
+        c = tap_corr(r, x, gh, gw, k, k).reshape(B, gh, gw, T).numpy()
+        if shared:
+            one, _, _ = BO.step(w[0, 0], c.sum(axis=(1, 2)), loss.float().double().numpy(), 3 * H * W, eta, l1)
+            w = np.ascontiguousarray(np.broadcast_to(one, w.shape))
+        else:
+            w = step(w, c, loss.float().double().numpy(), 3 * H * W, eta, l1, smooth)
+    loss, _ = BO.loss_and_r(FO.forward_sum(x, field_of(w, k, k)), y)
+    return dict(first=first, last=float(loss.sum()), err_first=err_first, err_last=node_l1(w, kstar), w=w)
