@@ -1,19 +1,16 @@
-/* osmosis_blindfield.h -- blind spatially varying deblurring: learning a FIELD of point-spread functions on the device.  The header
- * of the second STAGING library libosmosis_ext2.so (prefix osmx2_), built beside libosmosis_hip.so and libosmosis_ext.so by the same
- * Makefile, from csrc/blindfield.hip alone; it shares no symbol and no state with either, exports the five entry points below and
- * nothing else, and keeps its own error text (osmx2_last_error; osm_last_error and osmx_last_error never change through a call
- * here).  Strict C99, no struct.  Both staging tables are folded into the main ABI by the next maintenance change of that table.
- *
- * Conventions (restated because this header stands alone): 0 on success; on failure -1 (a bad argument: nothing was launched) or -2
- * (a launch or the copy failed), with osmx2_last_error() naming it, per thread; device pointers are owned by the caller; `stream` is
- * a hipStream_t, NULL = the default stream.
+/* osmosis_blindfield.h -- blind spatially varying deblurring: learning a FIELD of point-spread functions on the device.  The
+ * thirteenth header of libosmosis_hip.so's C ABI, beside osmosis_hip.h (whose conventions hold: 0 on success, a negative osm_status
+ * on failure -- OSM_ERR_INVALID for a bad argument: nothing was launched; OSM_ERR_LAUNCH for a failed launch or copy -- with
+ * osm_last_error() naming it, device pointers owned by the caller, `stream` a hipStream_t, NULL = default stream),
+ * osmosis_psffield.h (the field operator A(w), its nodes, tables and hats) and osmosis_blind.h (the objective, osm_psf_tap_grad and
+ * osm_psf_tap_step).  Strict C99, no struct.
  *
  * The reference has no such operator; these definitions are the contract.
  *
  * Tap list  dy[T], dx[T] int offsets from the anchor, shared by the nodes;  refl_n(c) = -c if c < 0;  2 (n - 1) - c if c >= n;  c
  *           otherwise;  Ry, Rx: the largest |dy|, |dx|, stated by the caller, 0 <= Ry <= 32, Ry < H, Rx alike with W; a tap beyond
- *           them is never read.  1 <= T <= OSMX2_MAX_TAPS.  Weights w[gh][gw][T] fp32 contiguous: one PSF per node.
- * Nodes     those of include/ext/osmosis_psffield.h: node j of a row at x = j (W - 1) / (gw - 1), rows alike; 2 <= gh <= min(H, 32),
+ *           them is never read.  1 <= T <= OSM_FIELD_MAX_TAPS.  Weights w[gh][gw][T] fp32 contiguous: one PSF per node.
+ * Nodes     those of osmosis_psffield.h: node j of a row at x = j (W - 1) / (gw - 1), rows alike; 2 <= gh <= min(H, 32),
  *           2 <= gw <= min(W, 32).  Tables iy0[H] int32, fy[H] fp32, ix0[W] int32, fx[W] fp32: the cell index (non-decreasing; clamped
  *           into [0, gh - 2] / [0, gw - 2] wherever it is read) and the position inside the cell.
  * Hats      a = 1 - fx;  b = 1 - fy  (fp32, one rounding each);  hatx_jx(x) = a where ix0[x] = jx, fx where ix0[x] = jx - 1, and
@@ -28,16 +25,16 @@
  * Tiles and layout.  The image is cut into 32 x 32 tiles (ragged at the far edges), ntx = ceil(W / 32), nty = ceil(H / 32).  Node
  * (jy, jx) REACHES tile (ty, tx) when some row i of the tile has iy0[i] in {jy - 1, jy} and some column j has ix0[j] in {jx - 1, jx}: a
  * test on the tables alone, not on the hat's value.  The tables are non-decreasing, so the tile rows a node reaches are an interval
- * [ty0[jy], ty1[jy]) and the tile columns an interval [tx0[jx], tx1[jx]).  osmx2_field_tap_layout (HOST only: it reads host copies of
+ * [ty0[jy], ty1[jy]) and the tile columns an interval [tx0[jx], tx1[jx]).  osm_field_tap_layout (HOST only: it reads host copies of
  * iy0, ix0 and touches no device) fills the int array
- *     lay = ty0[gh], ty1[gh], tx0[gw], tx1[gw], off[gh gw + 1]                          (OSMX2_LAY_INTS(gh, gw) ints)
+ *     lay = ty0[gh], ty1[gh], tx0[gw], tx1[gw], off[gh gw + 1]                          (OSM_FIELD_LAY_INTS(gh, gw) ints)
  * with off[0] = 0, off[n + 1] = off[n] + P (ty1 - ty0)(tx1 - tx0) for n = jy gw + jx ascending, and returns the float count
  * B off[gh gw] T of `part` (< 0 on failure).  The partial of image b, node n, plane p, tile (ty, tx) is the T floats at
  *     part[((b NP + off[n] + (p nty_n + (ty - ty0[jy])) ntx_n + (tx - tx0[jx])) T],   NP = off[gh gw], nty_n = ty1 - ty0, ntx_n alike
  * (per image; per node; plane-major; the node's tiles row-major).  Elements outside do not exist; every element inside is written.
  * The two kernels take `lay` as a DEVICE copy of that array.
  *
- * osmx2_field_tap_grad -- the per-node partials of c.  Gather form, no atomics, every element written by exactly one lane.  A
+ * osm_field_tap_grad -- the per-node partials of c.  Gather form, no atomics, every element written by exactly one lane.  A
  * workgroup owns one tile of one plane of one image.  For every node n that reaches the tile and every tap t:
  *     part(b, n, p, tile)[t] = (acc = +0; for i ascending, j ascending over the tile's pixels where hat_n is present:
  *                               acc = fma(fl(hat_n(i, j) r[b,p,i,j]), x[b,p, refl_H(i + dy[t]), refl_W(j + dx[t])], acc))
@@ -49,7 +46,7 @@
  * Error against float64 on the same fp32 inputs, first order, u = 2^-24, per partial of n pixels:  (n + 3) u sum hat_n |r| |x|
  * (a, b, the hat, the product with r, then the chain).
  *
- * osmx2_field_tap_step -- one projected step of EVERY node, one 1024-lane workgroup per node, all arithmetic fp64 in this order:
+ * osm_field_tap_step -- one projected step of EVERY node, one 1024-lane workgroup per node, all arithmetic fp64 in this order:
  *     c_n[b][t] = (s = 0; for q = 0 .. P nty_n ntx_n - 1 ascending (plane, then tile): s += part(b, n, q)[t])
  *     g_n[t]    = (s = 0; for b ascending: s += loss[b] * c_n[b][t]) / hw3
  *     s_n[t]    = (s = 0; for the EXISTING 4-neighbours m in the order up (jy - 1), left (jx - 1), right, down: s += (w_n[t] - w_m[t]))
@@ -63,9 +60,9 @@
  * tensor.  With smooth = 0 a node's step is bit for bit osm_psf_tap_step on that node's partials repacked as [B][nparts][T].
  * smooth >= 0 and finite; eta, l1 not NaN; hw3 = 3 h w >= 1.
  *
- * There is no "optimize" entry point: a guided sub-step spans three libraries and is enqueued by the caller, stream-ordered:
- * osmx_psf_field_apply; osm_ps_loss_grad_c / _mc; osmx2_field_tap_grad; on the last iteration only the adjoint
- * osmx_psf_field_apply into g; osmx2_field_tap_step.
+ * There is no "optimize" entry point: a guided sub-step is enqueued by the caller, launch by launch, stream-ordered:
+ * osm_psf_field_apply; osm_ps_loss_grad_c / _mc; osm_field_tap_grad; on the last iteration only the adjoint
+ * osm_psf_field_apply into g; osm_field_tap_step.
  *
  * Kernels (csrc/blindfield.hip, compiled without floating-point contraction): gfx950, wave64.  Tap gradient: 256-thread workgroups;
  * the reflected window of x and the tile of r are staged in LDS once; per reaching node the tile of q_n is formed in LDS and lanes
@@ -77,28 +74,25 @@
 extern "C" {
 #endif
 
-#define OSMX2_MAX_TAPS 4225                                   /* (2 * 32 + 1)^2 */
-#define OSMX2_LAY_INTS(gh, gw) (2 * (gh) + 2 * (gw) + (gh) * (gw) + 1)
+#define OSM_FIELD_MAX_TAPS 4225                               /* (2 * 32 + 1)^2 */
+#define OSM_FIELD_LAY_INTS(gh, gw) (2 * (gh) + 2 * (gw) + (gh) * (gw) + 1)
 
-int osmx2_version(void);                 /* (major<<16)|(minor<<8)|patch of this library */
-const char* osmx2_last_error(void);      /* the text of this thread's last failure in libosmosis_ext2.so ("" before any) */
+/* HOST only.  iy0 [H], ix0 [W]: host arrays; lay: host, OSM_FIELD_LAY_INTS(gh, gw) ints.  Returns the float count of `part`, < 0 on failure */
+long long osm_field_tap_layout(int gh, int gw, const int* iy0, const int* ix0,
+                               int H, int W, int P, int B, int T, int* lay);
 
-/* HOST only.  iy0 [H], ix0 [W]: host arrays; lay: host, OSMX2_LAY_INTS(gh, gw) ints.  Returns the float count of `part`, < 0 on failure */
-long long osmx2_field_tap_layout(int gh, int gw, const int* iy0, const int* ix0,
-                                 int H, int W, int P, int B, int T, int* lay);
+int osm_field_tap_grad(const float* x, const float* r,
+                       const int* dy, const int* dx, int T,   /* [T] each */
+                       int Ry, int Rx,
+                       int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx,
+                       const int* lay,                        /* device copy of the layout */
+                       int B, int P, long long x_img_stride, long long r_img_stride,
+                       int H, int W,
+                       float* part, void* stream);
 
-int osmx2_field_tap_grad(const float* x, const float* r,
-                         const int* dy, const int* dx, int T,   /* [T] each */
-                         int Ry, int Rx,
-                         int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx,
-                         const int* lay,                        /* device copy of the layout */
-                         int B, int P, long long x_img_stride, long long r_img_stride,
-                         int H, int W,
-                         float* part, void* stream);
-
-int osmx2_field_tap_step(float* w, float* w_new, const float* part, const float* loss,
-                         const int* lay, int gh, int gw,
-                         int B, int T, long long hw3, double eta, double l1, double smooth, void* stream);
+int osm_field_tap_step(float* w, float* w_new, const float* part, const float* loss,
+                       const int* lay, int gh, int gw,
+                       int B, int T, long long hw3, double eta, double l1, double smooth, void* stream);
 
 #ifdef __cplusplus
 }

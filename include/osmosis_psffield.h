@@ -1,12 +1,8 @@
 /* osmosis_psffield.h -- spatially varying blur: a FIELD of point-spread functions on a coarse node grid, interpolated bilinearly over
- * the frame.  The header of the STAGING library libosmosis_ext.so (prefix osmx_), which is built beside libosmosis_hip.so by the same
- * Makefile and shares no symbol and no state with it: it exports the three entry points below and nothing else, and keeps its own
- * error text (osmx_last_error; osm_last_error never changes through a call here).  The staging table is folded into the main ABI
- * by the next maintenance change of that table.  Strict C99, no struct.
- *
- * Conventions (those of osmosis_hip.h, restated because this header stands alone): 0 on success; on failure -1 (a bad argument:
- * nothing was launched) or -2 (the launch failed), with osmx_last_error() naming it, per thread; device pointers are owned by the
- * caller; `stream` is a hipStream_t, NULL = the default stream.
+ * the frame.  The twelfth header of libosmosis_hip.so's C ABI, beside osmosis_hip.h (whose conventions hold: 0 on success, a
+ * negative osm_status on failure -- OSM_ERR_INVALID for a bad argument: nothing was launched; OSM_ERR_LAUNCH for a failed launch --
+ * with osm_last_error() naming it, device pointers owned by the caller, `stream` a hipStream_t, NULL = default stream),
+ * osmosis_psf.h (the tap list, refl_n, the forward / adjoint maps) and osmosis_gain.h (the node grid).  Strict C99, no struct.
  *
  * The reference has no such operator; these definitions are the contract.
  *
@@ -61,16 +57,13 @@
 extern "C" {
 #endif
 
-int osmx_version(void);                  /* (major<<16)|(minor<<8)|patch of the staging library */
-const char* osmx_last_error(void);       /* the text of this thread's last failure in libosmosis_ext.so ("" before any) */
-
-int osmx_psf_field_apply(const float* x, float* out,
-                         const int* dy, const int* dx, const float* w, int T,   /* dy, dx [T]; w [gh][gw][T] */
-                         int Ry, int Rx,
-                         int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx,
-                         int B, int P, long long x_img_stride, long long out_img_stride,
-                         int H, int W,
-                         int adjoint, int zero_planes, void* stream);
+int osm_psf_field_apply(const float* x, float* out,
+                        const int* dy, const int* dx, const float* w, int T,   /* dy, dx [T]; w [gh][gw][T] */
+                        int Ry, int Rx,
+                        int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx,
+                        int B, int P, long long x_img_stride, long long out_img_stride,
+                        int H, int W,
+                        int adjoint, int zero_planes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,8 +18,6 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OSM_LIB") or os.path.join(_HERE, "libosmosis_hip.so")   # OSM_LIB: A/B builds
-EXT_LIB_PATH = os.environ.get("OSM_EXT_LIB") or os.path.join(_HERE, "libosmosis_ext.so")   # the staging library (`EXT_ABI`)
-EXT2_LIB_PATH = os.environ.get("OSM_EXT2_LIB") or os.path.join(_HERE, "libosmosis_ext2.so")   # the second one (`EXT2_ABI`)
 
 c_float_p = C.c_void_p  # device pointers travel as opaque addresses
 
@@ -281,43 +279,20 @@ ABI["osmosis_psfset.h"] = {  # PSF weight sets: one per image and / or per colou
     "osm_psf_tap_step_s": [_P, _P, _P, _I, _I, _I, _I, _LL, _D, _D, _I, _I, _P],
     "osm_ps_blind_optimize_s": ABI["osmosis_blind.h"]["osm_ps_blind_optimize"][:-1] + [_I, _I, _P],
 }
+ABI["osmosis_psffield.h"] = {  # a field of point-spread functions: spatially varying blur
+    "osm_psf_field_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _I, _I, _P],
+}
+ABI["osmosis_blindfield.h"] = {  # learning a field of point-spread functions: blind spatially varying deblurring
+    "osm_field_tap_layout": _Returns(_LL, [_I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "osm_field_tap_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _P, _P],
+    "osm_field_tap_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _D, _D, _D, _P],
+}
 
 SIGS = {}       # name -> argtypes, over all headers
 for _header, _entries in ABI.items():
     if SIGS.keys() & _entries.keys():
         raise ValueError(f"ABI[{_header!r}] repeats {sorted(SIGS.keys() & _entries.keys())} of an earlier header")
     SIGS.update(_entries)
-
-
-# The STAGING table: entry points of libosmosis_ext.so (prefix osmx_, headers under include/ext/), held to the same standard as `ABI`
-# by tests/test_abi_ext_cpu.py.  They wait here, outside `ABI` / `SIGS` / `exports()`, until the next maintenance change of the main
-# table folds them in; `call()` reaches both libraries by name.
-EXT_ABI = {"ext/osmosis_psffield.h": {  # a field of point-spread functions: spatially varying blur
-    "osmx_version": [],
-    "osmx_last_error": _Returns(C.c_char_p, []),
-    "osmx_psf_field_apply": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _I, _I, _P],
-}}
-EXT_SIGS = {}   # name -> argtypes, over the staging headers
-for _header, _entries in EXT_ABI.items():
-    if (SIGS.keys() | EXT_SIGS.keys()) & _entries.keys():
-        raise ValueError(f"EXT_ABI[{_header!r}] repeats {sorted((SIGS.keys() | EXT_SIGS.keys()) & _entries.keys())}")
-    EXT_SIGS.update(_entries)
-
-
-# The SECOND staging table: entry points of libosmosis_ext2.so (prefix osmx2_, headers under include/ext2/), on the same terms and held
-# to the same standard by tests/test_abi_ext2_cpu.py.
-EXT2_ABI = {"ext2/osmosis_blindfield.h": {  # learning a field of point-spread functions: blind spatially varying deblurring
-    "osmx2_version": [],
-    "osmx2_last_error": _Returns(C.c_char_p, []),
-    "osmx2_field_tap_layout": _Returns(_LL, [_I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "osmx2_field_tap_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _LL, _LL, _I, _I, _P, _P],
-    "osmx2_field_tap_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _D, _D, _D, _P],
-}}
-EXT2_SIGS = {}  # name -> argtypes, over the second staging library's headers
-for _header, _entries in EXT2_ABI.items():
-    if (SIGS.keys() | EXT_SIGS.keys() | EXT2_SIGS.keys()) & _entries.keys():
-        raise ValueError(f"EXT2_ABI[{_header!r}] repeats {sorted((SIGS.keys() | EXT_SIGS.keys() | EXT2_SIGS.keys()) & _entries.keys())}")
-    EXT2_SIGS.update(_entries)
 
 
 def exports(header=None):
@@ -350,60 +325,8 @@ def load():
     return _lib
 
 
-_ext = None
-
-
-def load_ext():
-    """Load the staging library libosmosis_ext.so (once) and bind it to `EXT_SIGS`.  Raises loudly when it has not been built."""
-    global _ext
-    if _ext is not None:
-        return _ext
-    with _lock:
-        if _ext is None:
-            if not os.path.exists(EXT_LIB_PATH):
-                raise OsmosisHipError(
-                    f"{EXT_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                    "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
-                    "There is no CPU fallback for the product path.")
-            lib = C.CDLL(EXT_LIB_PATH)
-            for name, argtypes in EXT_SIGS.items():
-                fn = getattr(lib, name)
-                fn.argtypes = argtypes
-                fn.restype = getattr(argtypes, "restype", C.c_int)
-            _ext = lib
-    return _ext
-
-
-_ext2 = None
-
-
-def load_ext2():
-    """Load the second staging library libosmosis_ext2.so (once) and bind it to `EXT2_SIGS`.  Raises loudly when it has not been built."""
-    global _ext2
-    if _ext2 is not None:
-        return _ext2
-    with _lock:
-        if _ext2 is None:
-            if not os.path.exists(EXT2_LIB_PATH):
-                raise OsmosisHipError(
-                    f"{EXT2_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                    "or `make -C osmosis_diffusion_code_amd/csrc` (hipcc, --offload-arch=gfx950). "
-                    "There is no CPU fallback for the product path.")
-            lib = C.CDLL(EXT2_LIB_PATH)
-            for name, argtypes in EXT2_SIGS.items():
-                fn = getattr(lib, name)
-                fn.argtypes = argtypes
-                fn.restype = getattr(argtypes, "restype", C.c_int)
-            _ext2 = lib
-    return _ext2
-
-
 def last_error(name: str) -> str:
-    """The error text of the library that owns entry point `name`: each library keeps its own."""
-    if name in EXT2_SIGS:
-        return load_ext2().osmx2_last_error().decode()
-    if name in EXT_SIGS:
-        return load_ext().osmx_last_error().decode()
+    """The text of this thread's last failure (osm_last_error), whichever entry point `name` it was."""
     return load().osm_last_error().decode()
 
 
@@ -500,15 +423,9 @@ def current_stream_ptr() -> int:
 
 def call(name: str, *args, keep=()):
     """Invoke a status-returning entry point; raise on failure; record if a Recorder is active."""
-    if name in SIGS:
-        lib = load()
-    elif name in EXT_SIGS:
-        lib = load_ext()
-    elif name in EXT2_SIGS:
-        lib = load_ext2()
-    else:
-        raise OsmosisHipError(f"{name} is an entry point of neither table (`SIGS`, `EXT_SIGS`) nor of `EXT2_SIGS`")
-    fn = getattr(lib, name)
+    if name not in SIGS:
+        raise OsmosisHipError(f"{name} is no entry point of the table `SIGS`")
+    fn = getattr(load(), name)
     rc = fn(*args)
     if rc != 0:
         raise OsmosisHipError(f"{name} failed ({rc}): {last_error(name)}")

@@ -1,7 +1,5 @@
 // Blind spatially varying deblurring: the gradient of the 'ps' data term with respect to the weights of a FIELD of point-spread
-// functions, and a projected step of every node (include/ext2/osmosis_blindfield.h, which is the contract).  The one source of the
-// second staging library libosmosis_ext2.so: it includes nothing of the other two libraries, is compiled with hidden visibility and
-// exports the five osmx2_ entry points only.
+// functions, and a projected step of every node (include/osmosis_blindfield.h, which is the contract).
 //   tap gradient   part(b, n, p, tile)[t] = sum over the tile's pixels where hat_n is present of fl(hat_n r) x[refl(p + d_t)]
 //   step           w_n <- max(w_n - eta (g_n - mean g_n) - eta l1 - eta smooth s_n, 0) / sum,  fp64, s_n the 4-neighbour Laplacian
 // Tap gradient: tap_grad_kernel's tiling (csrc/blind.hip).  A workgroup owns a TH x TW tile of one plane of one image and stages the
@@ -11,39 +9,18 @@
 // a tile in a cell's interior has four, and a lane's registers hold one accumulator however many reach it.  Gather form: every
 // element of `part` is written by exactly one lane in a fixed order, no atomics.
 // Step: one workgroup per node reads w (its own and its neighbours') and writes w_new; the entry point copies w_new over w.
-#include <hip/hip_runtime.h>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include "../../include/ext2/osmosis_blindfield.h"
+#include "osm_common.h"
+#include "../../include/osmosis_blindfield.h"
 
 // the hats and their product with r: every product is rounded once (the Makefile passes -ffp-contract=off as well); the tap walk
 // calls fmaf explicitly, the step uses the __d*_rn intrinsics
 #pragma clang fp contract(off)
 
-#define OSMX2_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 
-constexpr int OSMX2_VERSION = (0 << 16) | (1 << 8) | 0;
-constexpr int ERR_INVALID = -1, ERR_LAUNCH = -2;
 constexpr int MAX_GRID = 32;
-
-thread_local char err_text[512] = {0};
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_text, sizeof(err_text), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define OSMX2_REQUIRE(cond, ...) \
-  do {                           \
-    if (!(cond)) return fail(ERR_INVALID, __VA_ARGS__); \
-  } while (0)
 
 constexpr int NT = 256;
 constexpr int TH = 32;
@@ -187,7 +164,7 @@ __global__ __launch_bounds__(SNT) void field_tap_step_kernel(const float* __rest
                                                              const int* __restrict__ lay, const int gh, const int gw, const int B,
                                                              const int T, const double hw3, const double eta, const double l1,
                                                              const double smooth) {
-  __shared__ double a[OSMX2_MAX_TAPS];
+  __shared__ double a[OSM_FIELD_MAX_TAPS];
   __shared__ double red[SNT];
   const int tid = threadIdx.x;
   const int n = (int)blockIdx.x, jy = n / gw, jx = n % gw;
@@ -229,11 +206,11 @@ __global__ __launch_bounds__(SNT) void field_tap_step_kernel(const float* __rest
 }
 
 int check_grid(const char* what, int gh, int gw, int H, int W) {
-  OSMX2_REQUIRE(H >= 1 && W >= 1 && W <= (1 << 28), "%s: bad image %d x %d", what, H, W);
-  OSMX2_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID && gh <= H && gw <= W,
-                "%s: the node grid must be within 2 .. min(%d, the image side) per axis, got %d x %d on a %d x %d image", what, MAX_GRID, gh,
-                gw, H, W);
-  return 0;
+  OSM_REQUIRE(H >= 1 && W >= 1 && W <= (1 << 28), "%s: bad image %d x %d", what, H, W);
+  OSM_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID && gh <= H && gw <= W,
+              "%s: the node grid must be within 2 .. min(%d, the image side) per axis, got %d x %d on a %d x %d image", what, MAX_GRID, gh,
+              gw, H, W);
+  return OSM_OK;
 }
 
 // [first, end) of the 32-wide tiles along one axis of n positions that hold a position whose (clamped) cell is j - 1 or j
@@ -252,17 +229,13 @@ void axis_range(const int* i0, int n, int g, int j, int* first, int* end) {
 
 }  // namespace
 
-OSMX2_EXPORT int osmx2_version(void) { return OSMX2_VERSION; }
-
-OSMX2_EXPORT const char* osmx2_last_error(void) { return err_text; }
-
-OSMX2_EXPORT long long osmx2_field_tap_layout(int gh, int gw, const int* iy0, const int* ix0, int H, int W, int P, int B, int T,
-                                              int* lay) {
-  const char* what = "osmx2_field_tap_layout";
-  OSMX2_REQUIRE(iy0 && ix0 && lay, "%s: null pointer (iy0 / ix0 / lay)", what);
-  if (check_grid(what, gh, gw, H, W)) return ERR_INVALID;
-  OSMX2_REQUIRE(B >= 1 && P >= 1, "%s: bad batch %d or plane count %d", what, B, P);
-  OSMX2_REQUIRE(T >= 1 && T <= OSMX2_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSMX2_MAX_TAPS);
+extern "C" long long osm_field_tap_layout(int gh, int gw, const int* iy0, const int* ix0, int H, int W, int P, int B, int T,
+                                          int* lay) {
+  const char* what = "osm_field_tap_layout";
+  OSM_REQUIRE(iy0 && ix0 && lay, "%s: null pointer (iy0 / ix0 / lay)", what);
+  if (check_grid(what, gh, gw, H, W)) return OSM_ERR_INVALID;
+  OSM_REQUIRE(B >= 1 && P >= 1, "%s: bad batch %d or plane count %d", what, B, P);
+  OSM_REQUIRE(T >= 1 && T <= OSM_FIELD_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSM_FIELD_MAX_TAPS);
   int* ty0 = lay, * ty1 = lay + gh, * tx0 = lay + 2 * gh, * tx1 = lay + 2 * gh + gw, * off = lay + 2 * gh + 2 * gw;
   for (int jy = 0; jy < gh; ++jy) axis_range(iy0, H, gh, jy, ty0 + jy, ty1 + jy);
   for (int jx = 0; jx < gw; ++jx) axis_range(ix0, W, gw, jx, tx0 + jx, tx1 + jx);
@@ -271,55 +244,52 @@ OSMX2_EXPORT long long osmx2_field_tap_layout(int gh, int gw, const int* iy0, co
   for (int jy = 0; jy < gh; ++jy)
     for (int jx = 0; jx < gw; ++jx) {
       np += (long long)P * (ty1[jy] - ty0[jy]) * (tx1[jx] - tx0[jx]);
-      OSMX2_REQUIRE(np < (1LL << 31) / OSMX2_MAX_TAPS, "%s: %lld partials and more are too many", what, np);
+      OSM_REQUIRE(np < (1LL << 31) / OSM_FIELD_MAX_TAPS, "%s: %lld partials and more are too many", what, np);
       off[jy * gw + jx + 1] = (int)np;
     }
   return (long long)B * np * T;
 }
 
-OSMX2_EXPORT int osmx2_field_tap_grad(const float* x, const float* r, const int* dy, const int* dx, int T, int Ry, int Rx, int gh, int gw,
-                                      const int* iy0, const float* fy, const int* ix0, const float* fx, const int* lay, int B, int P,
-                                      long long x_img_stride, long long r_img_stride, int H, int W, float* part, void* stream) {
-  const char* what = "osmx2_field_tap_grad";
-  OSMX2_REQUIRE(x && r && part && dy && dx, "%s: null pointer (x / r / part / a tap array)", what);
-  OSMX2_REQUIRE(iy0 && fy && ix0 && fx && lay, "%s: null pointer (an interpolation table: iy0 / fy / ix0 / fx, or the layout)", what);
-  if (check_grid(what, gh, gw, H, W)) return ERR_INVALID;
-  OSMX2_REQUIRE(T >= 1 && T <= OSMX2_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSMX2_MAX_TAPS);
-  OSMX2_REQUIRE(Ry >= 0 && Rx >= 0 && Ry <= RMAX && Rx <= RMAX, "%s: the radius Ry %d, Rx %d must lie in 0 .. %d (kernels up to %d per side)",
-                what, Ry, Rx, RMAX, 2 * RMAX + 1);
-  OSMX2_REQUIRE(Ry < H && Rx < W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d", what, Ry, H, Rx, W);
-  OSMX2_REQUIRE(B >= 1 && P >= 1, "%s: bad batch %d or plane count %d", what, B, P);
-  OSMX2_REQUIRE((long long)P * H * W < (1LL << 31), "%s: bad image %d x %d x %d", what, P, H, W);
-  OSMX2_REQUIRE(x_img_stride >= (long long)P * H * W, "%s: x_img_stride %lld is less than the %d planes read", what, x_img_stride, P);
-  OSMX2_REQUIRE(r_img_stride >= (long long)P * H * W, "%s: r_img_stride %lld is less than the %d planes read", what, r_img_stride, P);
+extern "C" int osm_field_tap_grad(const float* x, const float* r, const int* dy, const int* dx, int T, int Ry, int Rx, int gh, int gw,
+                                  const int* iy0, const float* fy, const int* ix0, const float* fx, const int* lay, int B, int P,
+                                  long long x_img_stride, long long r_img_stride, int H, int W, float* part, void* stream) {
+  const char* what = "osm_field_tap_grad";
+  OSM_REQUIRE(x && r && part && dy && dx, "%s: null pointer (x / r / part / a tap array)", what);
+  OSM_REQUIRE(iy0 && fy && ix0 && fx && lay, "%s: null pointer (an interpolation table: iy0 / fy / ix0 / fx, or the layout)", what);
+  if (check_grid(what, gh, gw, H, W)) return OSM_ERR_INVALID;
+  OSM_REQUIRE(T >= 1 && T <= OSM_FIELD_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSM_FIELD_MAX_TAPS);
+  OSM_REQUIRE(Ry >= 0 && Rx >= 0 && Ry <= RMAX && Rx <= RMAX, "%s: the radius Ry %d, Rx %d must lie in 0 .. %d (kernels up to %d per side)",
+              what, Ry, Rx, RMAX, 2 * RMAX + 1);
+  OSM_REQUIRE(Ry < H && Rx < W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d", what, Ry, H, Rx, W);
+  OSM_REQUIRE(B >= 1 && P >= 1, "%s: bad batch %d or plane count %d", what, B, P);
+  OSM_REQUIRE((long long)P * H * W < (1LL << 31), "%s: bad image %d x %d x %d", what, P, H, W);
+  OSM_REQUIRE(x_img_stride >= (long long)P * H * W, "%s: x_img_stride %lld is less than the %d planes read", what, x_img_stride, P);
+  OSM_REQUIRE(r_img_stride >= (long long)P * H * W, "%s: r_img_stride %lld is less than the %d planes read", what, r_img_stride, P);
   const long long gz = (long long)B * P, gy = (H + TH - 1) / TH;
-  OSMX2_REQUIRE(gz <= 65535 && gy <= 65535, "%s: %lld planes / %lld row tiles are too many for one launch", what, gz, gy);
+  OSM_REQUIRE(gz <= 65535 && gy <= 65535, "%s: %lld planes / %lld row tiles are too many for one launch", what, gz, gy);
   const GradArgs a{dy, dx, T, Ry, Rx, gh, gw, iy0, fy, ix0, fx, lay, P, x_img_stride, r_img_stride, H, W};
   hipLaunchKernelGGL(field_tap_grad_kernel, dim3((unsigned)((W + TW - 1) / TW), (unsigned)gy, (unsigned)gz), dim3(NT), 0,
                      static_cast<hipStream_t>(stream), x, r, a, part);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return 0;
+  return osm::check_launch(what);
 }
 
-OSMX2_EXPORT int osmx2_field_tap_step(float* w, float* w_new, const float* part, const float* loss, const int* lay, int gh, int gw, int B,
-                                      int T, long long hw3, double eta, double l1, double smooth, void* stream) {
-  const char* what = "osmx2_field_tap_step";
-  OSMX2_REQUIRE(w && w_new && part && loss && lay, "%s: null pointer (w / w_new / part / loss / lay)", what);
-  OSMX2_REQUIRE(w != w_new, "%s: w_new must not alias w (a node reads its neighbours while they step)", what);
-  OSMX2_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID, "%s: the node grid must be within 2 .. %d per axis, got %d x %d", what,
-                MAX_GRID, gh, gw);
-  OSMX2_REQUIRE(B >= 1, "%s: bad batch %d", what, B);
-  OSMX2_REQUIRE(T >= 1 && T <= OSMX2_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSMX2_MAX_TAPS);
-  OSMX2_REQUIRE(hw3 >= 1, "%s: bad normaliser hw3 %lld (3 h w)", what, hw3);
-  OSMX2_REQUIRE(eta == eta && l1 == l1, "%s: eta / l1 is NaN", what);
-  OSMX2_REQUIRE(smooth >= 0.0 && !std::isinf(smooth), "%s: smooth must be >= 0 and finite, got %g", what, smooth);
+extern "C" int osm_field_tap_step(float* w, float* w_new, const float* part, const float* loss, const int* lay, int gh, int gw, int B,
+                                  int T, long long hw3, double eta, double l1, double smooth, void* stream) {
+  const char* what = "osm_field_tap_step";
+  OSM_REQUIRE(w && w_new && part && loss && lay, "%s: null pointer (w / w_new / part / loss / lay)", what);
+  OSM_REQUIRE(w != w_new, "%s: w_new must not alias w (a node reads its neighbours while they step)", what);
+  OSM_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID, "%s: the node grid must be within 2 .. %d per axis, got %d x %d", what,
+              MAX_GRID, gh, gw);
+  OSM_REQUIRE(B >= 1, "%s: bad batch %d", what, B);
+  OSM_REQUIRE(T >= 1 && T <= OSM_FIELD_MAX_TAPS, "%s: tap count T %d must lie in 1 .. %d", what, T, OSM_FIELD_MAX_TAPS);
+  OSM_REQUIRE(hw3 >= 1, "%s: bad normaliser hw3 %lld (3 h w)", what, hw3);
+  OSM_REQUIRE(eta == eta && l1 == l1, "%s: eta / l1 is NaN", what);
+  OSM_REQUIRE(smooth >= 0.0 && !std::isinf(smooth), "%s: smooth must be >= 0 and finite, got %g", what, smooth);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(field_tap_step_kernel, dim3((unsigned)(gh * gw)), dim3(SNT), 0, s, w, w_new, part, loss, lay, gh, gw, B, T, (double)hw3,
                      eta, l1, smooth);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  e = hipMemcpyAsync(w, w_new, sizeof(float) * (size_t)gh * gw * T, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return fail(ERR_LAUNCH, "%s: copying w_new over w: %s", what, hipGetErrorString(e));
-  return 0;
+  if (const int rc = osm::check_launch(what)) return rc;
+  const hipError_t e = hipMemcpyAsync(w, w_new, sizeof(float) * (size_t)gh * gw * T, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return osm::fail(OSM_ERR_LAUNCH, "%s: copying w_new over w: %s", what, hipGetErrorString(e));
+  return OSM_OK;
 }

@@ -592,6 +592,6 @@ extern "C" int osm_linear(const float* x, const float* W, const float* b, float*
   return osm::check_launch("linear_kernel");
 }
 
-extern "C" int osm_version(void) { return (0 << 16) | (3 << 8) | 0; }
+extern "C" int osm_version(void) { return (0 << 16) | (4 << 8) | 0; }
 extern "C" const char* osm_last_error(void) { return osm::err_buf(); }
 #endif   // !OSM_ACT_F16

@@ -1,7 +1,5 @@
 // Spatially varying blur: a field of point-spread functions on a gh x gw node grid, interpolated bilinearly over the frame
-// (include/ext/osmosis_psffield.h, which is the contract).  The one source of the staging library libosmosis_ext.so: it includes
-// nothing of libosmosis_hip.so (no osm_common.h: the error text below is this library's own), is compiled with hidden visibility
-// and exports the three osmx_ entry points only.
+// (include/osmosis_psffield.h, which is the contract).
 //   forward  out(p) = b (a c_00 + fx c_01) + fy (a c_10 + fx c_11),  c_kl = the tap-list convolution of csrc/psf.hip at p with the
 //            weights of corner (k, l) of p's cell: the OUTPUTS of the four corner PSFs are interpolated, which is the blur with the
 //            interpolated kernel because the convolution is linear in its weights
@@ -16,38 +14,17 @@
 // are walked, and the passes, then the nodes, are added in the header's order.  A node / pass that is left out would have added +0.
 // A window larger than the LDS buffer is not staged: the lanes take the same values in the same order from global memory.
 // Gather form: every output element is written by one lane; no atomics; the bits depend on neither the batch nor the launch shape.
-#include <hip/hip_runtime.h>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include "../../include/ext/osmosis_psffield.h"
+#include "osm_common.h"
+#include "../../include/osmosis_psffield.h"
 
 // the hats and the combine: every product and every sum is rounded once, in the order written (the Makefile passes
 // -ffp-contract=off as well); the tap loops call fmaf explicitly
 #pragma clang fp contract(off)
 
-#define OSMX_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace {
 
-constexpr int OSMX_VERSION = (0 << 16) | (1 << 8) | 0;
-constexpr int ERR_INVALID = -1, ERR_LAUNCH = -2;
 constexpr int MAX_GRID = 32;
-
-thread_local char err_text[512] = {0};
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_text, sizeof(err_text), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define OSMX_REQUIRE(cond, ...) \
-  do {                          \
-    if (!(cond)) return fail(ERR_INVALID, __VA_ARGS__); \
-  } while (0)
 
 constexpr int NT = 256;
 constexpr int TH = 32;          // output rows of a tile
@@ -262,38 +239,32 @@ __global__ __launch_bounds__(NT) void psf_field_kernel(const float* __restrict__
 
 }  // namespace
 
-OSMX_EXPORT int osmx_version(void) { return OSMX_VERSION; }
-
-OSMX_EXPORT const char* osmx_last_error(void) { return err_text; }
-
-OSMX_EXPORT int osmx_psf_field_apply(const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx,
-                                     int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx, int B, int P,
-                                     long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes,
-                                     void* stream) {
-  const char* what = "osmx_psf_field_apply";
-  OSMX_REQUIRE(x && out && dy && dx && w, "%s: null pointer (x / out / a tap array)", what);
-  OSMX_REQUIRE(iy0 && fy && ix0 && fx, "%s: null pointer (an interpolation table: iy0 / fy / ix0 / fx)", what);
-  OSMX_REQUIRE(B >= 1 && P >= 1 && zero_planes >= 0, "%s: bad batch %d, plane count %d or zero_planes %d", what, B, P, zero_planes);
-  OSMX_REQUIRE(H >= 1 && W >= 1 && W <= (1 << 28) && ((long long)P + zero_planes) * H * W < (1LL << 31), "%s: bad image %d x %d x %d", what,
-               P + zero_planes, H, W);
-  OSMX_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID && gh <= H && gw <= W,
-               "%s: the node grid must be within 2 .. min(%d, the image side) per axis, got %d x %d on a %d x %d image", what, MAX_GRID, gh,
-               gw, H, W);
-  OSMX_REQUIRE(T >= 1, "%s: bad tap count T %d", what, T);
-  OSMX_REQUIRE(Ry >= 0 && Rx >= 0 && Ry < H && Rx < W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d", what,
-               Ry, H, Rx, W);
-  OSMX_REQUIRE(adjoint == 0 || adjoint == 1, "%s: adjoint must be 0 or 1, got %d", what, adjoint);
-  OSMX_REQUIRE(x_img_stride >= (long long)P * H * W, "%s: x_img_stride %lld is less than the %d planes read", what, x_img_stride, P);
-  OSMX_REQUIRE(out_img_stride >= ((long long)P + zero_planes) * H * W, "%s: out_img_stride %lld is less than the %d planes written", what,
-               out_img_stride, P + zero_planes);
+extern "C" int osm_psf_field_apply(const float* x, float* out, const int* dy, const int* dx, const float* w, int T, int Ry, int Rx,
+                                   int gh, int gw, const int* iy0, const float* fy, const int* ix0, const float* fx, int B, int P,
+                                   long long x_img_stride, long long out_img_stride, int H, int W, int adjoint, int zero_planes,
+                                   void* stream) {
+  const char* what = "osm_psf_field_apply";
+  OSM_REQUIRE(x && out && dy && dx && w, "%s: null pointer (x / out / a tap array)", what);
+  OSM_REQUIRE(iy0 && fy && ix0 && fx, "%s: null pointer (an interpolation table: iy0 / fy / ix0 / fx)", what);
+  OSM_REQUIRE(B >= 1 && P >= 1 && zero_planes >= 0, "%s: bad batch %d, plane count %d or zero_planes %d", what, B, P, zero_planes);
+  OSM_REQUIRE(H >= 1 && W >= 1 && W <= (1 << 28) && ((long long)P + zero_planes) * H * W < (1LL << 31), "%s: bad image %d x %d x %d", what,
+              P + zero_planes, H, W);
+  OSM_REQUIRE(gh >= 2 && gw >= 2 && gh <= MAX_GRID && gw <= MAX_GRID && gh <= H && gw <= W,
+              "%s: the node grid must be within 2 .. min(%d, the image side) per axis, got %d x %d on a %d x %d image", what, MAX_GRID, gh,
+              gw, H, W);
+  OSM_REQUIRE(T >= 1, "%s: bad tap count T %d", what, T);
+  OSM_REQUIRE(Ry >= 0 && Rx >= 0 && Ry < H && Rx < W, "%s: reflection padding needs the radius 0 <= Ry %d < H %d and 0 <= Rx %d < W %d", what,
+              Ry, H, Rx, W);
+  OSM_REQUIRE(adjoint == 0 || adjoint == 1, "%s: adjoint must be 0 or 1, got %d", what, adjoint);
+  OSM_REQUIRE(x_img_stride >= (long long)P * H * W, "%s: x_img_stride %lld is less than the %d planes read", what, x_img_stride, P);
+  OSM_REQUIRE(out_img_stride >= ((long long)P + zero_planes) * H * W, "%s: out_img_stride %lld is less than the %d planes written", what,
+              out_img_stride, P + zero_planes);
   const long long gz = (long long)B * (P + zero_planes);
   const long long gy = (H + TH - 1) / TH;
-  OSMX_REQUIRE(gz <= 65535 && gy <= 65535, "%s: %lld planes / %lld row tiles are too many for one launch", what, gz, gy);
+  OSM_REQUIRE(gz <= 65535 && gy <= 65535, "%s: %lld planes / %lld row tiles are too many for one launch", what, gz, gy);
   const FieldArgs a{dy, dx, w, T, Ry, Rx, gh, gw, iy0, fy, ix0, fx, B, P, zero_planes, x_img_stride, out_img_stride, H, W, adjoint};
   const int aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   hipLaunchKernelGGL(psf_field_kernel, dim3((unsigned)((W + TW - 1) / TW), (unsigned)gy, (unsigned)gz), dim3(NT), 0,
                      static_cast<hipStream_t>(stream), x, out, a, aligned);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return 0;
+  return osm::check_launch(what);
 }

@@ -1246,7 +1246,7 @@ class PosteriorSampling(ConditioningMethod):
         tables, any channel beyond the colours written as 0 by the same launch (zero_planes = C - 3).
         A `PSFOperator`: the same three launches with osm_psf_apply in the place of osm_linop_apply, `adjoint` set for A^T; with more
         than one weight set (`per_image` / `per_channel`) osm_psf_apply_s on the weight rows [r0:r0 + B] of the open batch.
-        A `PSFFieldOperator` (`field_blur`): the same three launches with osmx_psf_field_apply for A and A^T; the field is shared by
+        A `PSFFieldOperator` (`field_blur`): the same three launches with osm_psf_field_apply for A and A^T; the field is shared by
         the batch, so a chunk needs no rows of it."""
         from .measurements import PSFFieldOperator, PSFOperator
         B, C, H, W = x0.shape
@@ -1351,10 +1351,10 @@ class PosteriorSampling(ConditioningMethod):
 
     def _loss_grad_x0_blind_field(self, x0, y, g_out=None, loss_out=None, mask=None):
         """The data term through a `blind_field_blur` operator that learns its field: ONE call over the whole batch (the field is
-        shared), the operator's n_iter inner iterations of  Ax = A(w) x0[:, 0:3] (osmx_psf_field_apply);  loss, r = d loss / d Ax
-        (osm_ps_loss_grad_c / _mc);  the per-node tap partials of (r, x0) (osmx2_field_tap_grad);  on the last iteration
-        g[:, 0:3] = A(w)^T r, planes beyond the colours written as 0;  the projected step of every node (osmx2_field_tap_step).  The
-        sub-step spans three libraries, so it is enqueued here, stream-ordered, no host sync (include/ext2/osmosis_blindfield.h).
+        shared), the operator's n_iter inner iterations of  Ax = A(w) x0[:, 0:3] (osm_psf_field_apply);  loss, r = d loss / d Ax
+        (osm_ps_loss_grad_c / _mc);  the per-node tap partials of (r, x0) (osm_field_tap_grad);  on the last iteration
+        g[:, 0:3] = A(w)^T r, planes beyond the colours written as 0;  the projected step of every node (osm_field_tap_step).  The
+        sub-step has no entry point of its own: it is enqueued here, stream-ordered, no host sync (include/osmosis_blindfield.h).
         loss and g are those before the last step of w, as the Osmosis conditioner treats phi."""
         op = self.operator
         B, C, H, W = x0.shape

@@ -551,7 +551,7 @@ class PSFBlurOperator(PSFOperator):
 
 
 # ----------------------------------------------------------------------------- a field of PSFs: spatially varying blur
-FIELD_MAX_GRID = 32        # nodes per axis (include/ext/osmosis_psffield.h; the gain field's limit)
+FIELD_MAX_GRID = 32        # nodes per axis (include/osmosis_psffield.h; the gain field's limit)
 FIELD_MAX_KERNEL = 61      # the largest side of a node kernel (the window a workgroup stages: halo <= 32 per side, then slower)
 
 
@@ -638,8 +638,8 @@ def _field_op():
 class PSFFieldOperator(PSFOperator):
     """Spatially varying blur: a FIELD of point-spread functions K_n on a gh x gw node grid that spans the frame (the nodes sit where
     the gain field's do: on the image corners inclusive), every pixel p blurred with the bilinear interpolation sum_n hat_n(p) K_n of
-    the four corner kernels of its cell, over reflection padding, as cross-correlation (osmx_psf_field_apply of the staging library,
-    include/ext/osmosis_psffield.h; `forward` / `transpose` run it through `osmosis::psf_field_apply`, which is differentiable).
+    the four corner kernels of its cell, over reflection padding, as cross-correlation (osm_psf_field_apply,
+    include/osmosis_psffield.h; `forward` / `transpose` run it through `osmosis::psf_field_apply`, which is differentiable).
     No learnable parameters; the measurement has the image's size.  The field is shared by the images of a batch and by the colour
     planes: `weight_sets` stays (1, 1).
     Config keys (an unknown one raises ValueError): EITHER `kernels`, a [gh,gw,kh,kw] array, nested list or the path of a .npy file
@@ -912,7 +912,7 @@ class BlindFieldOperator(PSFFieldOperator):
     interpolated bilinearly over the frame -- whose node kernels are unknown and LEARNT during sampling.  Every node carries the dense
     support kernel_size x kernel_size (T = k^2 taps in row-major order, Ry = Rx = k // 2); the weights live in ONE device tensor `w`
     fp32 [gh,gw,T] that the step kernel overwrites between the network's forward and backward, with no host sync
-    (osmx2_field_tap_grad / osmx2_field_tap_step of the second staging library, include/ext2/osmosis_blindfield.h: per inner
+    (osm_field_tap_grad / osm_field_tap_step, include/osmosis_blindfield.h: per inner
     iteration a projected gradient step of every node on Q(w) = sum_b ||M (y_b - A(w) x0_b)||^2 / (2 * 3 h w), each node on its own
     simplex, optionally tied to its 4-neighbours by `smooth`).  The field is shared by the batch (`couples_batch`) and by the planes.
     Config keys (an unknown one raises ValueError): kernel_size (odd, <= 61, default 31); grid ([gh, gw], default [3, 3], the

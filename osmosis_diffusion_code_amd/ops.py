@@ -1203,7 +1203,7 @@ def gain_tables(H, W, gh, gw, device):
     return tabs
 
 
-# ----------------------------------------------------------------------------- a field of PSFs (include/ext/osmosis_psffield.h)
+# ----------------------------------------------------------------------------- a field of PSFs (include/osmosis_psffield.h)
 def field_tables(H, W, gh, gw, device):
     """The interpolation tables (iy0, fy, ix0, fx) of a gh x gw node grid on an H x W image as device tensors: the gain field's
     (`gain_tables`: same nodes, same cache), after the limits 2 <= gh <= min(H, 32), 2 <= gw <= min(W, 32)."""
@@ -1215,8 +1215,8 @@ def field_tables(H, W, gh, gw, device):
 
 
 def psf_field_apply(x, out, dy, dx, w, tabs, Ry, Rx, B, P, x_img_stride, out_img_stride, H, W, adjoint=False, zero_planes=0):
-    """The blur of planes p < P with a FIELD of point-spread functions (osmx_psf_field_apply of the staging library,
-    include/ext/osmosis_psffield.h): w fp32 [gh,gw,T] holds one PSF per node over the shared tap list dy, dx int32 [T], the nodes sit
+    """The blur of planes p < P with a FIELD of point-spread functions (osm_psf_field_apply,
+    include/osmosis_psffield.h): w fp32 [gh,gw,T] holds one PSF per node over the shared tap list dy, dx int32 [T], the nodes sit
     on the image corners inclusive and every pixel is blurred with the bilinear interpolation of its cell's four corner PSFs; with
     `adjoint` the exact transpose.  tabs = `field_tables(H, W, gh, gw, device)`.  Everything else is `psf_apply`'s."""
     for t in (x, out, w):
@@ -1236,17 +1236,17 @@ def psf_field_apply(x, out, dy, dx, w, tabs, Ry, Rx, B, P, x_img_stride, out_img
                    or out.numel() < (B - 1) * int(out_img_stride) + (P + Z) * H * W):
         raise _lib.OsmosisHipError(f"psf_field_apply: x ({x.numel()} elements) / out ({out.numel()}) are smaller than {B} images of "
                                    f"{P} -> {P + Z} planes of {H} x {W} at strides {x_img_stride} / {out_img_stride}")
-    call("osmx_psf_field_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0),
+    call("osm_psf_field_apply", ptr(x), ptr(out), ptr(dy), ptr(dx), ptr(w), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0),
          ptr(fx), B, P, int(x_img_stride), int(out_img_stride), H, W, 1 if adjoint else 0, Z, _s(),
          keep=(x, out, dy, dx, w, iy0, fy, ix0, fx))
 
 
-# ----------------------------------------------------------------------------- learning a field of PSFs (include/ext2/osmosis_blindfield.h)
+# ----------------------------------------------------------------------------- learning a field of PSFs (include/osmosis_blindfield.h)
 _field_layouts = {}     # (H, W, gh, gw, P, device) -> (lay on the device, partials per image, lay on the host)
 
 
 def field_tap_layout(H, W, gh, gw, P=3, device=None):
-    """The compact layout of the per-node tap partials (osmx2_field_tap_layout of the second staging library, host only): returns
+    """The compact layout of the per-node tap partials (osm_field_tap_layout, host only): returns
     (lay, NP, host) -- `lay` int32 [2 gh + 2 gw + gh gw + 1] = ty0[gh], ty1[gh], tx0[gw], tx1[gw], off[gh gw + 1] (the 32 x 32 tile
     rows / columns every node row / column reaches and the nodes' offsets in partials per image), on `device` when one is given
     (cached), else None; NP = off[-1] partials of T floats per image; `host` the same array as numpy."""
@@ -1259,11 +1259,10 @@ def field_tap_layout(H, W, gh, gw, P=3, device=None):
         return hit
     iy0, _, ix0, _ = gain_tables_host(H, W, gh, gw) if 2 <= gh <= H and 2 <= gw <= W else (np.zeros(1, np.int32),) * 4
     lay = np.zeros(2 * gh + 2 * gw + gh * gw + 1 if gh > 0 and gw > 0 else 1, dtype=np.int32)
-    lib = _lib.load_ext2()
-    n = lib.osmx2_field_tap_layout(gh, gw, iy0.ctypes.data_as(C.c_void_p), ix0.ctypes.data_as(C.c_void_p), H, W, P, 1, 1,
-                                   lay.ctypes.data_as(C.c_void_p))
+    n = _lib.query("osm_field_tap_layout", gh, gw, iy0.ctypes.data_as(C.c_void_p), ix0.ctypes.data_as(C.c_void_p), H, W, P, 1, 1,
+                   lay.ctypes.data_as(C.c_void_p))
     if n < 0:
-        raise _lib.OsmosisHipError(f"osmx2_field_tap_layout failed ({n}): {_lib.last_error('osmx2_field_tap_layout')}")
+        raise _lib.OsmosisHipError(f"osm_field_tap_layout failed ({n}): {_lib.last_error('osm_field_tap_layout')}")
     while len(_field_layouts) >= 16:
         _field_layouts.pop(next(iter(_field_layouts)))
     out = _field_layouts[key] = (None if device is None else torch.from_numpy(lay).to(device), int(n), lay)
@@ -1278,7 +1277,7 @@ def _check_field_lay(name, lay, gh, gw):
 
 def field_tap_grad(x, r, dy, dx, tabs, lay, NP, gh, gw, Ry, Rx, B, P, x_img_stride, r_img_stride, H, W, part):
     """The per-node tile partials of c_n[b][t] = sum_p sum_ij hat_n(i,j) r[b,p,i,j] x[b,p,refl(i+dy[t]),refl(j+dx[t])]
-    (osmx2_field_tap_grad): the tap gradient of the field operator `psf_field_apply`, in the compact layout of
+    (osm_field_tap_grad): the tap gradient of the field operator `psf_field_apply`, in the compact layout of
     `field_tap_layout(H, W, gh, gw, P, device)` = (lay, NP, _); part fp32 with at least B NP T elements, every one written.
     tabs = `field_tables(H, W, gh, gw, device)`.  Deterministic (gather form, no atomics)."""
     for t in (x, r, part):
@@ -1297,12 +1296,12 @@ def field_tap_grad(x, r, dy, dx, tabs, lay, NP, gh, gw, Ry, Rx, B, P, x_img_stri
                    or part.numel() < B * NP * T):
         raise _lib.OsmosisHipError(f"field_tap_grad: x ({x.numel()} elements) / r ({r.numel()}) / part ({part.numel()}) are smaller than "
                                    f"{B} images of {P} x {H} x {W} at strides {x_img_stride} / {r_img_stride} with {NP} partials of {T} taps")
-    call("osmx2_field_tap_grad", ptr(x), ptr(r), ptr(dy), ptr(dx), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0), ptr(fx),
+    call("osm_field_tap_grad", ptr(x), ptr(r), ptr(dy), ptr(dx), T, int(Ry), int(Rx), gh, gw, ptr(iy0), ptr(fy), ptr(ix0), ptr(fx),
          ptr(lay), B, P, int(x_img_stride), int(r_img_stride), H, W, ptr(part), _s(), keep=(x, r, dy, dx, iy0, fy, ix0, fx, lay, part))
 
 
 def field_tap_step(w, w_new, part, loss, lay, NP, B, hw3, eta, l1=0.0, smooth=0.0):
-    """One projected step of every node of the field w fp32 [gh,gw,T], in place (osmx2_field_tap_step): per node `psf_tap_step`'s fp64
+    """One projected step of every node of the field w fp32 [gh,gw,T], in place (osm_field_tap_step): per node `psf_tap_step`'s fp64
     arithmetic on that node's partials, plus eta smooth times the 4-neighbour Laplacian of the field; w_new fp32 [gh,gw,T] is the
     workspace the kernel writes (nodes read their neighbours while they step) before w_new is copied over w on the same stream."""
     for t in (w, w_new, part, loss):
@@ -1315,7 +1314,7 @@ def field_tap_step(w, w_new, part, loss, lay, NP, B, hw3, eta, l1=0.0, smooth=0.
     B, NP = int(B), int(NP)
     if B >= 1 and (part.numel() < B * NP * T or loss.numel() < B):
         raise _lib.OsmosisHipError(f"field_tap_step: part ({part.numel()} elements) / loss ({loss.numel()}) are smaller than {B} x {NP} x {T} / {B}")
-    call("osmx2_field_tap_step", ptr(w), ptr(w_new), ptr(part), ptr(loss), ptr(lay), gh, gw, B, T, int(hw3), float(eta), float(l1),
+    call("osm_field_tap_step", ptr(w), ptr(w_new), ptr(part), ptr(loss), ptr(lay), gh, gw, B, T, int(hw3), float(eta), float(l1),
          float(smooth), _s(), keep=(w, w_new, part, loss, lay))
 
 

@@ -754,11 +754,11 @@ def _psf_s_backward(ctx, grad):
 psf_apply_s.register_autograd(_psf_s_backward, setup_context=_psf_setup)
 
 
-# ---- a FIELD of point-spread functions w [gh,gw,T] on a node grid, interpolated bilinearly (include/ext/osmosis_psffield.h)
+# ---- a FIELD of point-spread functions w [gh,gw,T] on a node grid, interpolated bilinearly (include/osmosis_psffield.h)
 @torch.library.custom_op("osmosis::psf_field_apply", mutates_args=(), device_types="cuda")
 def psf_field_apply(x: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, w: torch.Tensor, iy0: torch.Tensor, fy: torch.Tensor,
                     ix0: torch.Tensor, fx: torch.Tensor, Ry: int, Rx: int, adjoint: bool) -> torch.Tensor:
-    """out [B,P,H,W] of x [B,P,H,W] (osmx_psf_field_apply): every pixel blurred with the bilinear interpolation of the four corner PSFs
+    """out [B,P,H,W] of x [B,P,H,W] (osm_psf_field_apply): every pixel blurred with the bilinear interpolation of the four corner PSFs
     of its cell of the gh x gw node grid -- w fp32 [gh,gw,T] over the shared tap list dy, dx int32 [T]; (iy0, fy, ix0, fx) =
     `ops.field_tables(H, W, gh, gw, device)` -- or with `adjoint` the transpose of that map.  Differentiable w.r.t. x."""
     if x.dim() != 4:
@@ -791,11 +791,11 @@ def _psf_field_backward(ctx, grad):
 psf_field_apply.register_autograd(_psf_field_backward, setup_context=_psf_field_setup)
 
 
-# ---- learning that field (include/ext2/osmosis_blindfield.h): the per-node tap partials and the projected step of every node
+# ---- learning that field (include/osmosis_blindfield.h): the per-node tap partials and the projected step of every node
 @torch.library.custom_op("osmosis::field_tap_grad", mutates_args=(), device_types="cuda")
 def field_tap_grad(x: torch.Tensor, r: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor, iy0: torch.Tensor, fy: torch.Tensor,
                    ix0: torch.Tensor, fx: torch.Tensor, gh: int, gw: int, Ry: int, Rx: int) -> torch.Tensor:
-    """part [B, NP, T] of x, r [B,P,H,W] (osmx2_field_tap_grad): the 32 x 32 tile partials of the tap gradient c_n of every node n of the
+    """part [B, NP, T] of x, r [B,P,H,W] (osm_field_tap_grad): the 32 x 32 tile partials of the tap gradient c_n of every node n of the
     gh x gw field, in the compact layout of `ops.field_tap_layout(H, W, gh, gw, P)` (per image; per node; plane-major; the node's
     tiles row-major); (iy0, fy, ix0, fx) = `ops.field_tables(H, W, gh, gw, device)`.  No autograd formula."""
     name = "osmosis::field_tap_grad"
@@ -821,7 +821,7 @@ def _field_tap_grad_fake(x, r, dy, dx, iy0, fy, ix0, fx, gh, gw, Ry, Rx):
 @torch.library.custom_op("osmosis::field_tap_step", mutates_args=("w",), device_types="cuda")
 def field_tap_step(w: torch.Tensor, part: torch.Tensor, loss: torch.Tensor, H: int, W: int, P: int, eta: float, l1: float,
                    smooth: float) -> None:
-    """One projected step of every node of the field w fp32 [gh,gw,T], IN PLACE (osmx2_field_tap_step): part [B, NP, T] as
+    """One projected step of every node of the field w fp32 [gh,gw,T], IN PLACE (osm_field_tap_step): part [B, NP, T] as
     `osmosis::field_tap_grad` returns it for P planes of H x W, loss [B]; the normaliser is 3 H W."""
     name = "osmosis::field_tap_step"
     if w.dim() != 3 or not w.is_contiguous() or part.dim() != 3 or part.shape[2] != w.shape[2] or loss.dim() != 1 \

@@ -1,4 +1,4 @@
-"""The oracle of blind spatially varying deblurring (operator `blind_field_blur`, include/ext2/osmosis_blindfield.h): torch on the CPU,
+"""The oracle of blind spatially varying deblurring (operator `blind_field_blur`, include/osmosis_blindfield.h): torch on the CPU,
 float64 unless told otherwise.  The reference has no such operator; the definition is the header's.
 
   A(K) x      = sum_n hat_n (.) conv(pad(x, reflect), K_n)                 (`psffield_oracle.forward_sum`, K [gh,gw,kh,kw] a leaf)

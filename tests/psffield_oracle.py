@@ -1,4 +1,4 @@
-"""Float64 oracle of the spatially varying blur of include/ext/osmosis_psffield.h (torch on the CPU; the reference has no such operator).
+"""Float64 oracle of the spatially varying blur of include/osmosis_psffield.h (torch on the CPU; the reference has no such operator).
 
 The DEFINITION is per pixel: the output at p is the interpolated kernel sum_n hat_n(p) K_n applied at p over reflection padding
 (`forward_pixelwise`).  Because the blur is linear in its kernel this equals sum_n hat_n (.) conv(pad(x), K_n) (`forward_sum`, the

@@ -17,7 +17,7 @@ INC = os.path.join(ROOT, "include")
 HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(INC, "*.h")))
 COUNTS = {"osmosis_hip.h": 99, "osmosis_linop.h": 1, "osmosis_psf.h": 1, "osmosis_physlin.h": 6, "osmosis_physgroup.h": 4,
           "osmosis_blind.h": 3, "osmosis_depthprior.h": 5, "osmosis_solver.h": 2, "osmosis_robust.h": 4, "osmosis_gain.h": 4,
-          "osmosis_psfset.h": 3}
+          "osmosis_psfset.h": 3, "osmosis_psffield.h": 1, "osmosis_blindfield.h": 3}
 SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
            "unsigned long long": ctypes.c_ulonglong, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint}
 STRUCTS = {"osm_conv_desc": _lib.ConvDesc, "osm_conv_desc_h": _lib.ConvDesc, "osm_gemm_desc": _lib.GemmDesc, "osm_attn_desc": _lib.AttnDesc,
@@ -84,7 +84,7 @@ def test_every_name_is_declared_once_and_the_table_has_no_other():
     assert list(_lib.ABI) == list(COUNTS) and sorted(COUNTS) == HEADERS               # one sub-table per header file, in header order
     names = [p[0] for header in HEADERS for p in prototypes(header)]
     assert not {n for n in names if names.count(n) > 1}, "declared in two headers"
-    assert sorted(names) == _lib.exports() == sorted(_lib.SIGS) and len(names) == sum(COUNTS.values()) == 132
+    assert sorted(names) == _lib.exports() == sorted(_lib.SIGS) and len(names) == sum(COUNTS.values()) == 136
     print(f"{len(names)} entry points in {len(HEADERS)} headers")
 
 

@@ -1,4 +1,4 @@
-"""Blind spatially varying deblurring on the GPU (operator `blind_field_blur`, include/ext2/osmosis_blindfield.h): the per-node
+"""Blind spatially varying deblurring on the GPU (operator `blind_field_blur`, include/osmosis_blindfield.h): the per-node
 tap-gradient kernel bit for bit against osm_psf_tap_grad on q_n = fl(hat_n r) and against the float64 oracle of
 tests/blindfield_oracle.py, the step of every node against the numpy restatement and against osm_psf_tap_step, the data term
 `loss_grad_x0` with its inner loop, the recovery of a known field, the fused sampler loop against `_generic_loop` and against the
@@ -84,7 +84,7 @@ def tap_reference(case):
 
 
 def run_field_tap_grad(ref, x, r, R=None):
-    """osmx2_field_tap_grad into a NaN-filled workspace -> part [B, NP, T] (device)."""
+    """osm_field_tap_grad into a NaN-filled workspace -> part [B, NP, T] (device)."""
     from osmosis_diffusion_code_amd import ops
     B, C, H, W = x.shape[0], x.shape[1], ref["H"], ref["W"]
     gh, gw = ref["grid"]
@@ -244,13 +244,13 @@ def test_a_tap_beyond_the_radius_is_written_as_zero_and_bad_arguments_launch_not
     lay, NP, _ = ops.field_tap_layout(H, W, gh, gw, 3, DEV)
     tabs = ops.field_tables(H, W, gh, gw, DEV)
     part = torch.full((2, NP, 81), float("nan"), device=DEV)
-    lib, p = _lib.load_ext2(), _lib.ptr
+    lib, p = _lib.load(), _lib.ptr
     good = [p(x), p(r), p(dy), p(dx), 81, 4, 4, gh, gw] + [p(t) for t in tabs] + [p(lay), 2, 3, 4 * H * W, 3 * H * W, H, W, p(part), None]
     for pos, val in ((0, None), (20, None), (13, None), (9, None), (4, 0), (4, 4226), (5, 33), (5, H), (6, W), (7, 1), (8, 33), (7, H + 1),
                      (14, 0), (15, 0), (16, 10), (17, 10)):
         args = list(good)
         args[pos] = val
-        assert lib.osmx2_field_tap_grad(*args) == -1 and lib.osmx2_last_error().decode().startswith("osmx2_field_tap_grad"), (pos, val)
+        assert lib.osm_field_tap_grad(*args) == -1 and lib.osm_last_error().decode().startswith("osm_field_tap_grad"), (pos, val)
     torch.cuda.synchronize()
     assert bool(torch.isnan(part).all())
     with pytest.raises(_lib.OsmosisHipError, match="smaller"):
@@ -259,7 +259,7 @@ def test_a_tap_beyond_the_radius_is_written_as_zero_and_bad_arguments_launch_not
         ops.field_tap_grad(x, r, dy, dx, tabs, lay[:-1].contiguous(), NP, gh, gw, 4, 4, 2, 3, 4 * H * W, 3 * H * W, H, W, part)
     with pytest.raises(_lib.OsmosisHipError, match="partial count"):
         ops.field_tap_grad(x, r, dy, dx, tabs, lay, NP - 1, gh, gw, 4, 4, 2, 3, 4 * H * W, 3 * H * W, H, W, part)
-    assert lib.osmx2_field_tap_grad(*good) == 0
+    assert lib.osm_field_tap_grad(*good) == 0
     torch.cuda.synchronize()
     assert torch.equal(part, full)
 

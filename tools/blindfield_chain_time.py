@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""What LEARNING a field of point-spread functions costs (include/ext2/osmosis_blindfield.h), in ONE process, device-synchronised.
+"""What LEARNING a field of point-spread functions costs (include/osmosis_blindfield.h), in ONE process, device-synchronised.
 
 Kernel level (`launch_us`, microseconds per launch; device events around `--reps` back-to-back launches after a warm-up), B = 1,
 3 planes of 256 x 256, a dense k = 31 support (961 taps) under 5 x 5 nodes:
-    field_tap_grad     osmx2_field_tap_grad, one launch
+    field_tap_grad     osm_field_tap_grad, one launch
     single_tap_grad    ONE osm_psf_tap_grad over the same image and tap list
     composed           the baseline a user could build from the single-PSF kernel: 25 torch products hat_n r plus 25 osm_psf_tap_grad
                        launches
-    field_tap_step     osmx2_field_tap_step (the kernel and the copy of the workspace over w)
+    field_tap_step     osm_field_tap_step (the kernel and the copy of the workspace over w)
 alternated in this order, `field_tap_grad` timed again at the end.
 
 Chain level (`ms_per_step`): full-size `ps` chains (DDPM.p_sample, clip_denoised, gaussian noiser with sigma 0) on the 3 -> 6 network

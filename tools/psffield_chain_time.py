@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""What a FIELD of point-spread functions costs (include/ext/osmosis_psffield.h), in ONE process, device-synchronised.
+"""What a FIELD of point-spread functions costs (include/osmosis_psffield.h), in ONE process, device-synchronised.
 
 Kernel level (`apply_us`, microseconds per launch; device events around `--reps` back-to-back launches after a warm-up), B = 1,
 3 planes of 256 x 256, forward and adjoint, for a 5 x 5 `roll_shake` field (k = 31, 6 degrees: sparse streaks) and a dense 5 x 5
 `radial_defocus` field (k = 31):
-    field          osmx_psf_field_apply, one launch
+    field          osm_psf_field_apply, one launch
     single         osm_psf_apply with the centre node's weights over the same tap list
     composed       the baseline a user could build from the single-PSF kernel: 25 osm_psf_apply launches plus the torch combine
                    (forward: the hat-weighted sum of the 25 outputs; adjoint: 25 hat products, 25 launches, the running sum)
