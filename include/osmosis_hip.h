@@ -355,10 +355,12 @@ typedef struct osm_phys_desc {
   int optimizer;       /* 0: plain gradient descent ('sgd' / 'GD', measurements.py:157-177); otherwise the torch.optim class of
                           utils.py:494-524 with ITS DEFAULT hyper-parameters (the reference passes none) and lr = eta per group:
                           1 Adam, 2 AdamW (weight_decay 0.01), 3 Adamax, 4 RMSprop, 5 Adagrad, 6 Adadelta, 7 ASGD, 8 Rprop.
-                          ('sparseadam' and 'lbfgs' raise in the reference itself: dense gradients / step() without a closure) */
+                          ('sparseadam' and 'lbfgs' raise in the reference itself: dense gradients / step() without a closure)
+                          9: the Levenberg-Marquardt phi solver (no reference counterpart; see below).  eta only says which slots
+                          are live (0 removes one); kind 3 and the composed (`_lin`) and grouped (`_g`) entry points refuse it */
 } osm_phys_desc;
 /* phi: device float [B][9] = phi_a[3] | phi_b[3] | phi_inf[3]  (kinds 1,2 use phi_a as phi_ab;
- * haze uses phi_a[0] only).  part: workspace B*nblk*16 floats, nblk = osm_phys_nblk(HW).
+ * haze uses phi_a[0] only).  part: workspace B*nblk*16 floats, nblk = osm_phys_nblk(HW); B*nblk*32 floats when optimizer == 9.
  * red: device float [B][16]: 0 sum r^2, 1..9 raw phi-gradient sums, 10..12 sum rgb_c, 13 val-loss sum.
  * loss_out: [B] data-term loss per image (the reference's sep_loss). */
 int osm_phys_nblk(int HW);
@@ -368,6 +370,26 @@ int osm_phys_reduce(const osm_phys_desc* d, const float* x0, const float* y, con
  * see csrc/guidance.hip), zero-initialised by the caller, required when d->optimizer != 0 and do_update != 0; NULL otherwise. */
 int osm_phys_finalize(const osm_phys_desc* d, const float* part, float* red, float* phi, int do_update,
                       float* loss_out, float* opt_state, void* stream);
+/* optimizer == 9, the Levenberg-Marquardt solver: a damped Gauss-Newton step on S = sum r^2 from normal equations reduced on the
+ * device.  The residual r_c = (y_c - (2 I_c - 1)) wm_c is linear in the image, whose columns are col_a = -d J_c Ea_c,
+ * col_b = phi_inf_c d Eb_c, col_i = 1 - Eb_c; sums 1..9 are J^T r already, and osm_phys_reduce(_m) with optimizer == 9 writes 32 floats
+ * per workgroup: slots 0..13 as above, then per channel the six entries aa, ab, ai, bb, bi, ii of sum 4 wm^2 col_p col_q (slot
+ * 14 + 6 c + e).  osm_phys_finalize(_m) carries the mode in do_update (for optimizers 0..8 any non-zero value is "step"):
+ *   0  loss only: the plain finalize, on the 16 floats per workgroup of a plain reduce (optimizer 0..8 in the descriptor)
+ *   1  decide + step, on the 32 floats per workgroup     2  the same as the first iteration of a call (S_base is forgotten: x0 moved)
+ *   3  close: decide only, on the 16 floats per workgroup of a plain reduce at the trial phi
+ * Decision, from the S just reduced at the current phi: accept iff there is no base yet or S <= (1 + 1e-5) S_base -- base <- (phi, S),
+ * lambda <- lambda / 10 unless this was the re-evaluation after a reject, then (modes 1, 2) phi <- phi_base + delta with
+ * (A + lambda (diag A + 1e-12 max diag A)) delta = -J^T r over the live slots, assembled and solved (Cholesky) in fp64 by one thread
+ * (kind 0: a 3 x 3 block per channel; kind 1: columns (col_a + col_b, col_i) per channel; kind 2: one phi_ab column over the three
+ * channels plus the three phi_inf, a 4 x 4 arrow).  Reject, also on a non-finite S or sum and on a non-positive pivot: lambda <- 10
+ * lambda, phi <- phi_base, retry set, no step (the next iteration re-evaluates at the base; the Gram is not stored); mode 3 also writes
+ * red[0] = S_base and the loss of S_base.  lambda stays in [1e-6, 1e6].  With no base yet a reject takes no step and phi stays; phi
+ * never becomes non-finite through the solver.  S == 0 (a fully masked image): phi and the state are untouched; J^T r == 0: no step.
+ * opt_state row [20]: phi_base[9] | S_base | lambda | retry | reserved; a zero lambda means 1.0 (the caller may seed another).
+ * osm_phys_optimize(_m) with optimizer == 9: n_inner x { reduce (32); finalize mode 2 then 1 }, the plain reduce (16) at the trial phi,
+ * finalize mode 3, osm_phys_grad -- 2 n_inner + 3 launches; loss and g are taken at an accepted phi.  freeze_phi: the plain three
+ * launches, phi and state untouched. */
 /* g[B,4,HW] = d(total loss)/d(x0) for the current phi and the reductions in `red`. */
 int osm_phys_grad(const osm_phys_desc* d, const float* x0, const float* y, const float* phi,
                   const float* red, float* g, void* stream);

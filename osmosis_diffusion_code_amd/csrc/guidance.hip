@@ -419,6 +419,236 @@ __global__ __launch_bounds__(64 * GWAVES) void phys_finalize_group_kernel(osm_ph
   }
 }
 
+// ---------------------------------------------------------------- the Levenberg-Marquardt phi solver (osm_phys_desc.optimizer = 9)
+// The residual r_c = (y_c - (2 I_c - 1)) wm_c is linear in the image, and the image has three parameters per channel, with the
+// model columns col_a = -d J_c Ea_c, col_b = phi_inf_c d Eb_c, col_i = 1 - Eb_c (d I_c / d phi).  The Jacobian of r is -2 wm col, so
+// sums 1..9 of the plain reduce (sum k2 col, k2 = -2 wm r) are J^T r already, and J^T J is per channel the six entries
+// aa, ab, ai, bb, bi, ii of sum 4 wm^2 col_p col_q: 18 more sums over the same pixel pass.
+constexpr int NLM = 32;               // floats per reduce workgroup: the NRED slots of phys_reduce_kernel (0..13 used), then 18 Gram sums
+constexpr int LM_GRAM = 14;           // slot of channel c's entry e (aa, ab, ai, bb, bi, ii): LM_GRAM + 6 c + e
+constexpr int LM_STATE_S = 9, LM_STATE_LAMBDA = 10, LM_STATE_RETRY = 11;   // opt_state row: phi_base [9] | S_base | lambda | retry | reserved
+constexpr double LM_LAMBDA0 = 1.0;                  // the lambda of a zero-initialised state row
+constexpr double LM_LAMBDA_MIN = 1e-6, LM_LAMBDA_MAX = 1e6, LM_LAMBDA_FACTOR = 10.0;
+constexpr double LM_ACCEPT_SLACK = 1e-5;            // accept iff S <= (1 + slack) S_base: converged ties do not flip on rounding
+constexpr double LM_DIAG_EPS = 1e-12;               // the damping is lambda (diag A + eps max diag A): a dead column keeps a pivot
+
+// Slots 0..13: phys_reduce_kernel's expressions in its order; the same tiling, wave sums and pairwise fold of the four waves.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void phys_lm_reduce_kernel(osm_phys_desc ds, const float* __restrict__ x0,
+                                                              const float* __restrict__ y, const float* __restrict__ mask,
+                                                              const float* __restrict__ phi, float* __restrict__ part, int nblk) {
+  __shared__ float red[4][NLM];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  float s[NLM];
+#pragma unroll
+  for (int k = 0; k < NLM; ++k) s[k] = 0.f;
+  const int pend = min(ds.HW, (blk + 1) * PPB);
+  const float* ph = phi + b * 9;
+  for (int p = blk * PPB + threadIdx.x; p < pend; p += 256) {
+    Pix<MASKED> q;
+    eval_pixel<MASKED, false, false>(ds, x0, y, mask, phi, b, p, q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float pinf = ph[6 + c];
+      float wc = q.w;
+      if constexpr (MASKED) wc = q.wm[c];
+      const float k2 = -2.0f * wc * q.r[c];
+      const float ca = -q.d * q.J[c] * q.Ea[c], cb = pinf * q.d * q.Eb[c], ci = 1.0f - q.Eb[c];
+      s[0] += q.r[c] * q.r[c];
+      s[1 + c] += k2 * ca;
+      s[4 + c] += k2 * cb;
+      s[7 + c] += k2 * ci;
+      s[10 + c] += q.rgb[c];
+      const float e = fmaxf(fabsf(q.rgb[c]) - 0.7f, 0.0f);
+      s[13] += e * e;
+      const float w4 = 4.0f * wc * wc;
+      const float wa = w4 * ca, wb = w4 * cb;
+      s[LM_GRAM + 6 * c + 0] += wa * ca;
+      s[LM_GRAM + 6 * c + 1] += wa * cb;
+      s[LM_GRAM + 6 * c + 2] += wa * ci;
+      s[LM_GRAM + 6 * c + 3] += wb * cb;
+      s[LM_GRAM + 6 * c + 4] += wb * ci;
+      s[LM_GRAM + 6 * c + 5] += w4 * ci * ci;
+    }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NLM; ++k) {
+    const float t = osm::wave_sum(s[k]);
+    if (lane == 0) red[wv][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < NLM) {
+    const int k = threadIdx.x;
+    part[((long long)b * nblk + blk) * NLM + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  }
+}
+
+// The normal equations of image b over the live slots of phys_param_lr (a zero eta removes a slot; its value is otherwise ignored),
+// assembled in fp64 from the totals: A [9][9] over the phi slots (kind 0: a block (a_c, b_c, i_c) per channel; kind 1: the column
+// col_a + col_b in slot c; kind 2: slot 0 carries col_a + col_b of all three channels, an arrow with the three phi_inf), g = J^T r.
+// Then (A + lambda (diag A + eps max diag A)) delta = -g by Cholesky on the live slots.  False: a non-positive pivot or a
+// non-finite delta.
+__device__ __forceinline__ bool lm_solve(const osm_phys_desc& ds, const double* tot, double lambda, double (*A)[9], double* delta) {
+  float lr[9];
+  const int mask = phys_param_lr(ds, lr);
+  int idx[9], n = 0;
+  for (int i = 0; i < 9; ++i)
+    if (((mask >> i) & 1) && lr[i] != 0.f) idx[n++] = i;
+  double g[9];
+  for (int i = 0; i < 9; ++i) {
+    g[i] = 0.0;
+    delta[i] = 0.0;
+    for (int j = 0; j < 9; ++j) A[i][j] = 0.0;
+  }
+  for (int c = 0; c < 3; ++c) {
+    const double* G = tot + LM_GRAM + 6 * c;
+    const double aa = G[0], ab = G[1], ai = G[2], bb = G[3], bi = G[4], ii = G[5];
+    const int pi = 6 + c;
+    if (ds.kind == 0) {
+      const int pa = c, pb = 3 + c;
+      A[pa][pa] = aa; A[pa][pb] = A[pb][pa] = ab; A[pa][pi] = A[pi][pa] = ai;
+      A[pb][pb] = bb; A[pb][pi] = A[pi][pb] = bi;
+      g[pa] = tot[1 + c]; g[pb] = tot[4 + c];
+    } else {
+      const int pa = ds.kind == 1 ? c : 0;
+      A[pa][pa] += aa + 2.0 * ab + bb;
+      A[pa][pi] += ai + bi;
+      A[pi][pa] = A[pa][pi];
+      g[pa] += tot[1 + c] + tot[4 + c];
+    }
+    A[pi][pi] = ii;
+    g[pi] = tot[7 + c];
+  }
+  double dmax = 0.0;
+  for (int k = 0; k < n; ++k) dmax = fmax(dmax, A[idx[k]][idx[k]]);
+  for (int k = 0; k < n; ++k) A[idx[k]][idx[k]] += lambda * (A[idx[k]][idx[k]] + LM_DIAG_EPS * dmax);
+  // Cholesky A = L L^T in place (lower triangle), on the live slots
+  for (int k = 0; k < n; ++k) {
+    const int p = idx[k];
+    double dk = A[p][p];
+    for (int m = 0; m < k; ++m) dk -= A[p][idx[m]] * A[p][idx[m]];
+    if (!(dk > 0.0) || !isfinite(dk)) return false;
+    dk = sqrt(dk);
+    A[p][p] = dk;
+    for (int r = k + 1; r < n; ++r) {
+      const int q = idx[r];
+      double v = A[q][p];
+      for (int m = 0; m < k; ++m) v -= A[q][idx[m]] * A[p][idx[m]];
+      A[q][p] = v / dk;
+    }
+  }
+  double z[9];
+  for (int k = 0; k < n; ++k) {          // L z = -g
+    const int p = idx[k];
+    double v = -g[p];
+    for (int m = 0; m < k; ++m) v -= A[p][idx[m]] * z[m];
+    z[k] = v / A[p][p];
+  }
+  for (int k = n - 1; k >= 0; --k) {     // L^T delta = z
+    const int p = idx[k];
+    double v = z[k];
+    for (int m = k + 1; m < n; ++m) v -= A[idx[m]][p] * delta[idx[m]];
+    delta[p] = v / A[p][p];
+    if (!isfinite(delta[p])) return false;
+  }
+  return true;
+}
+
+// The LM finalize, one wave per image (lane 0 decides and solves), grid B.  mode (the entry points' do_update): 1 decide + step, 2 the same as the first
+// iteration of a call (S_base is forgotten: x0 has changed), 3 close -- decide only, on the NRED sums of a plain reduce at the trial phi.
+//   accept (no base yet, or S <= (1 + slack) S_base): base <- (phi, S); lambda <- lambda / 10 unless this was the re-evaluation after
+//     a reject; then (modes 1, 2) phi <- phi_base + delta.  A failed solve counts as a reject at the new base.
+//   reject (also a non-finite S or sum): lambda <- 10 lambda, phi <- phi_base, retry set, no step; the next iteration re-evaluates at
+//     the base and steps with the larger lambda.  Close: red[0] and the loss become those of S_base.  With no base yet: no step,
+//     the base stays unset (S_base = -1) and phi stays.
+//   S == 0 (a fully masked image): phi and the state stay as they are.  J^T r == 0: no step.
+// mode 1, 2 read NLM floats per workgroup of `part`, mode 3 reads NRED.
+__global__ void phys_lm_finalize_kernel(osm_phys_desc ds, const float* __restrict__ part, float* __restrict__ red,
+                                        float* __restrict__ phi, int mode, float* __restrict__ loss_out,
+                                        float* __restrict__ opt_state, int nblk) {
+  __shared__ double tot[NLM];
+  __shared__ double A[9][9];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const bool close = mode == 3;
+  if (close) {
+    fin_walk(part, red, nblk, FinLin<false>{}, b, lane, tot);
+  } else {              // component lane >> 1, two lanes share its partials (fixed order), fp64, one shuffle fold
+    const int comp = lane >> 1, sub = lane & 1;
+    double a = 0.0;
+#pragma unroll 4
+    for (int k = sub; k < nblk; k += 2) a += (double)part[((long long)b * nblk + k) * NLM + comp];
+    a += __shfl_xor(a, 1, 64);
+    if (sub == 0) {
+      tot[comp] = a;
+      if (comp < NRED) red[b * NRED + comp] = (float)a;
+    }
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  const double n3 = 3.0 * (double)ds.HW;
+  double S = tot[0];
+  float* ph = phi + b * 9;
+  float* st = opt_state + b * 20;
+  bool finite = isfinite(S);
+  for (int k = 1; k < 10; ++k) finite = finite && isfinite(tot[k]);
+  if (!close)
+    for (int k = LM_GRAM; k < NLM; ++k) finite = finite && isfinite(tot[k]);
+  bool restored = false;
+  if (!(finite && S == 0.0)) {
+    double lambda = (double)st[LM_STATE_LAMBDA];
+    if (!(lambda > 0.0) || !isfinite(lambda)) lambda = LM_LAMBDA0;
+    lambda = fmin(fmax(lambda, LM_LAMBDA_MIN), LM_LAMBDA_MAX);
+    const bool nobase = mode == 2 || !(st[LM_STATE_S] > 0.f);     // (S == 0 never becomes a base: a zero row has none)
+    const bool retry = st[LM_STATE_RETRY] != 0.f;
+    bool reject;
+    if (!finite) {
+      reject = true;
+    } else {
+      reject = !(nobase || S <= (1.0 + LM_ACCEPT_SLACK) * (double)st[LM_STATE_S]);
+    }
+    if (!reject) {
+      for (int i = 0; i < 9; ++i) st[i] = ph[i];
+      st[LM_STATE_S] = (float)S;
+      if (!retry) lambda = fmax(lambda / LM_LAMBDA_FACTOR, LM_LAMBDA_MIN);
+      st[LM_STATE_RETRY] = 0.f;
+      bool zero_g = true;
+      for (int k = 1; k < 10; ++k) zero_g = zero_g && tot[k] == 0.0;
+      if (!close && !zero_g) {
+        double delta[9];
+        bool ok = lm_solve(ds, tot, lambda, A, delta);
+        float np[9];
+        for (int i = 0; ok && i < 9; ++i) {
+          np[i] = (float)((double)ph[i] + delta[i]);
+          ok = isfinite(np[i]);
+        }
+        if (ok) {
+          for (int i = 0; i < 9; ++i) ph[i] = np[i];
+          if (ds.kind == 2) ph[1] = ph[2] = ph[0];
+        } else {          // phi stays the base just taken
+          lambda = fmin(lambda * LM_LAMBDA_FACTOR, LM_LAMBDA_MAX);
+          st[LM_STATE_RETRY] = 1.f;
+        }
+      }
+    } else if (nobase) {  // nothing to fall back to: phi stays, and the next iteration still has no base
+      for (int i = 0; i < 9; ++i) st[i] = ph[i];
+      st[LM_STATE_S] = -1.f;
+      st[LM_STATE_RETRY] = 0.f;
+    } else {
+      lambda = fmin(lambda * LM_LAMBDA_FACTOR, LM_LAMBDA_MAX);
+      for (int i = 0; i < 9; ++i) ph[i] = st[i];
+      st[LM_STATE_RETRY] = 1.f;
+      restored = true;
+    }
+    st[LM_STATE_LAMBDA] = (float)lambda;
+  }
+  if (close && restored) {
+    S = (double)st[LM_STATE_S];
+    red[b * NRED] = st[LM_STATE_S];
+  }
+  if (loss_out) loss_out[b] = (float)(ds.loss_type == 0 ? sqrt(S) : S / n3);
+}
+
 // LIN: dL/dI_c = v_c gscale with v = A^T u where the plain instantiations form -2 w r gscale inline; mse normalises by the measurement's
 // 3 hw (the auxiliary losses by the image's 3 HW), and the zero guard of a fully masked image is the launch's flag (the mask lives
 // on the measurement's grid, in phys_resid_kernel).
@@ -954,8 +1184,15 @@ int check_lin_desc(const osm_phys_desc* d, const char* who) {
 }
 
 // What a phi step needs.  The schedules ask before their first launch: a failure of a later finalize would leave phi half-stepped.
-int check_phi_step(const char* who, const osm_phys_desc* d, int do_update, const float* opt_state) {
-  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 8, "%s: optimizer must be 0 (sgd / GD) .. 8 (see osm_phys_desc)", who);
+int check_phi_step(const char* who, const osm_phys_desc* d, int do_update, const float* opt_state, bool routed = false) {
+  OSM_REQUIRE(d->optimizer >= 0 && d->optimizer <= 9, "%s: optimizer must be 0 (sgd / GD) .. 9 (see osm_phys_desc)", who);
+  if (d->optimizer == 9) {
+    OSM_REQUIRE(!routed, "%s: optimizer 9 (lm, the Levenberg-Marquardt phi solver) does not run on the composed (degradation) or "
+                "grouped (phi_groups) routes", who);
+    OSM_REQUIRE(d->kind != 3, "%s: optimizer 9 (lm) needs an image-formation model: the identity operator (kind 3) has no parameters", who);
+    OSM_REQUIRE(do_update >= 0 && do_update <= 3, "%s: optimizer 9 (lm) takes do_update 0 (loss only), 1 (step), 2 (first step of a call) "
+                "or 3 (close), got %d", who, do_update);
+  }
   OSM_REQUIRE(!(d->optimizer != 0 && do_update) || opt_state, "%s: a stateful optimizer needs opt_state [B][20]", who);
   OSM_REQUIRE(!(d->kind == 3 && do_update), "%s: the identity operator (kind 3) has no parameters to step", who);
   return OSM_OK;
@@ -966,13 +1203,19 @@ int check_phi_step(const char* who, const osm_phys_desc* d, int do_update, const
 struct LinArgs { int hw; const float* v; const float* part_r; };
 
 int phys_reduce_launch(const char* who, const osm_phys_desc* d, const float* x0, const float* y, const float* mask, const float* phi,
-                       float* part, void* stream, const LinArgs* la = nullptr) {
+                       float* part, void* stream, const LinArgs* la = nullptr, bool plain = false) {
   int rc = la ? check_lin_desc(d, who) : check_desc(d, who);
   if (rc) return rc;
   OSM_REQUIRE(x0 && phi && part && (la ? la->v != nullptr : y != nullptr), "%s: null pointer", who);
   const int nblk = osm_phys_nblk(d->HW);
   const dim3 grid(nblk, d->B), block(256);
   hipStream_t st = (hipStream_t)stream;
+  if (d->optimizer == 9 && !plain) {      // the LM solver's reduce: 32 floats per workgroup (`plain`: its schedule's closing evaluation)
+    if ((rc = check_phi_step(who, d, 0, nullptr, la != nullptr))) return rc;
+    if (mask) hipLaunchKernelGGL(phys_lm_reduce_kernel<true>, grid, block, 0, st, *d, x0, y, mask, phi, part, nblk);
+    else hipLaunchKernelGGL(phys_lm_reduce_kernel<false>, grid, block, 0, st, *d, x0, y, nullptr, phi, part, nblk);
+    return osm::check_launch("phys_lm_reduce_kernel");
+  }
   if (la) hipLaunchKernelGGL((phys_reduce_kernel<false, true>), grid, block, 0, st, *d, x0, nullptr, nullptr, phi, la->v, part, nblk);
   else if (mask) hipLaunchKernelGGL((phys_reduce_kernel<true, false>), grid, block, 0, st, *d, x0, y, mask, phi, nullptr, part, nblk);
   else hipLaunchKernelGGL((phys_reduce_kernel<false, false>), grid, block, 0, st, *d, x0, y, nullptr, phi, nullptr, part, nblk);
@@ -1004,10 +1247,14 @@ int phys_finalize_launch(const char* who, const osm_phys_desc* d, const float* p
   if (rc) return rc;
   OSM_REQUIRE(!la || (la->hw >= 1 && la->hw < (1 << 29)), "%s: bad measurement size hw = %d", who, la->hw);
   OSM_REQUIRE(part && red && phi && (!la || la->part_r), "%s: null pointer", who);
-  if ((rc = check_phi_step(who, d, do_update, opt_state))) return rc;
+  if ((rc = check_phi_step(who, d, do_update, opt_state, go || la))) return rc;
   const int nblk = osm_phys_nblk(d->HW);
   const dim3 grid(go ? go->G : d->B), block(go ? 64 * GWAVES : 64);
   hipStream_t st = (hipStream_t)stream;
+  if (d->optimizer == 9 && do_update) {   // the LM solver decides (and steps); do_update = 0 is the plain finalize below
+    hipLaunchKernelGGL(phys_lm_finalize_kernel, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk);
+    return osm::check_launch("phys_lm_finalize_kernel");
+  }
   if (go && la) {
     hipLaunchKernelGGL(phys_finalize_group_kernel<true>, grid, block, 0, st, *d, part, red, phi, do_update, loss_out, opt_state, nblk,
                        zero_guard, *go, FinLin<true>{la->part_r, osm_phys_nblk(la->hw), la->hw});
@@ -1174,10 +1421,23 @@ int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x
               "%s: null pointer", who);
   OSM_REQUIRE(n_inner >= 1, "%s: n_inner must be >= 1", who);
   OSM_REQUIRE(!(freeze_phi && n_inner != 1), "%s: freeze_phi goes with n_inner = 1", who);
-  if ((rc = check_phi_step(who, d, !freeze_phi, opt_state))) return rc;
+  if ((rc = check_phi_step(who, d, !freeze_phi, opt_state, go || lw))) return rc;
   OSM_REQUIRE(!lw || (long long)d->B * 4 <= 65535, "%s: batch %d is too large for one launch of the operator", who, d->B);
   const int zg = mask != nullptr, hw = lw ? lw->lin->h * lw->lin->w : 0, P = lin_planes(d);
   const LinArgs la_{hw, lw ? lw->v : nullptr, lw ? lw->part_r : nullptr}, *la = lw ? &la_ : nullptr;
+  const bool lm = d->optimizer == 9;
+  if (lm && !freeze_phi) {
+    // The LM schedule: n_inner x { LM reduce; LM finalize that decides and steps }, then a closing evaluation -- the plain reduce at
+    // the trial phi and the LM finalize in close mode, which on a reject puts phi_base back and writes red[0] = S_base (slots 10..13
+    // depend on x0 only) -- so the loss and g are taken at an accepted phi.  2 n_inner + 3 launches.
+    for (int it = 0; it < n_inner; ++it) {
+      if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream))) return rc;
+      if ((rc = phys_finalize_launch(who, d, part, red, phi, it == 0 ? 2 : 1, loss_out, opt_state, zg, stream))) return rc;
+    }
+    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream, nullptr, true))) return rc;
+    if ((rc = phys_finalize_launch(who, d, part, red, phi, 3, loss_out, opt_state, zg, stream))) return rc;
+    return phys_grad_launch(who, d, x0, y, mask, phi, red, g, stream, nullptr, zg);
+  }
   for (int it = 0; it < n_inner; ++it) {
     if (lw) {
       if ((rc = osm_phys_forward(d, x0, phi, lw->F, stream))) return rc;
@@ -1185,7 +1445,7 @@ int phys_optimize_launch(const char* who, const osm_phys_desc* d, const float* x
       if ((rc = osm_phys_resid(d, hw, lw->AF, y, mask, lw->u, lw->part_r, stream))) return rc;
       if ((rc = lin_apply(lw->lin, lw->u, lw->v, d->B, 3, 1, stream))) return rc;
     }
-    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream, la))) return rc;
+    if ((rc = phys_reduce_launch(who, d, x0, y, mask, phi, part, stream, la, lm))) return rc;   // (lm here: freeze_phi)
     if (it < n_inner - 1) {
       if ((rc = phys_finalize_launch(who, d, part, red, phi, 1, loss_out, opt_state, zg, stream, go, la))) return rc;
       continue;

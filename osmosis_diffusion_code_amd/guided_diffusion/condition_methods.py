@@ -803,15 +803,18 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         coefs = self.aux_loss.kernel_coefficients() if self.aux_loss is not None else {"gamma_avrg": 0.0, "gamma_val": 0.0}
         d.gamma_avrg, d.gamma_val = coefs["gamma_avrg"], coefs["gamma_val"]
         d.B, d.HW = B, HW
-        from .measurements import OPTIMIZER_CODES
-        d.optimizer = OPTIMIZER_CODES.get(getattr(op, "optimizer", "") or "", 0)
+        from .measurements import optimizer_code
+        d.optimizer = optimizer_code(getattr(op, "optimizer", ""))
+        lm = d.optimizer == 9   # the Levenberg-Marquardt solver: its reduce writes 32 floats per workgroup (include/osmosis_hip.h)
         nblk = ops.phys_nblk(HW)
         if d.optimizer != 0 and (self._opt is None or self._opt.shape[0] != op.phi.shape[0] or self._opt.device != op.phi.device):
             # optimizer state (Adam: moments + step) of the operator's phi (torch.optim state lives with the optimizer = with the operator,
             # which the driver rebuilds per image: osmosis_sampling.py:142-155)
             self._opt = torch.zeros(op.phi.shape[0], 20, device=device, dtype=torch.float32)
+            if lm:
+                self._opt[:, 10] = float(getattr(op, "lm_lambda", 1.0))     # the solver's initial damping
         st = {"key": key, "desc": d,
-              "part": torch.empty(B * nblk * 16, device=device, dtype=torch.float32),
+              "part": torch.empty(B * nblk * (32 if lm else 16), device=device, dtype=torch.float32),
               "red": torch.zeros(B * 16, device=device, dtype=torch.float32),
               "loss": torch.zeros(B, device=device, dtype=torch.float32),
               "g": torch.empty(B, 4, HW, device=device, dtype=torch.float32)}
@@ -819,8 +822,14 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             lin = ops.lin_desc(self._degradation(), grid[0], grid[1], device)
             hw, P = lin.h * lin.w, ops.phys_lin_planes(d)
             f32 = dict(device=device, dtype=torch.float32)
+            if lm:
+                raise NotImplementedError("optimizer 'lm' (the Levenberg-Marquardt phi solver) is not routed through a `degradation`")
             st.update(lin=lin, hw=hw, F=torch.empty(B, P, HW, **f32), AF=torch.empty(B, P, hw, **f32), u=torch.empty(B, 3, hw, **f32),
                       v=torch.empty(B, 3, HW, **f32), part_r=torch.empty(B * ops.phys_nblk(hw), **f32))
+        if lm:      # the plain 16-sum reduce of the solver's closing evaluation and of freeze_phi, for the single-launch schedule
+            d0 = PhysDesc.from_buffer_copy(d)
+            d0.optimizer = 0
+            st["desc_plain"] = d0
         while len(self._states) >= 4:          # a walk uses at most two chunk sizes; older shapes give their buffers back
             self._states.pop(next(iter(self._states)))
         self._states[st["key"]] = st
@@ -881,6 +890,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             ops.phys_forward(d, x0c, phi, F)
             mask = self._robust_mask_rows(F, 2.0, -1.0, yc, mask, r0, r1)
         # the route's four calls: reduce, finalize, grad, optimize (the schedule: _inner_loop)
+        if grp is not None and d.optimizer == 9:
+            raise NotImplementedError("optimizer 'lm' (the Levenberg-Marquardt phi solver) with phi_groups is not built")
         if grp is not None:         # shared water parameters: the grouped finalize in the place of the plain one
             route = (partial(ops.phys_reduce_m, d, x0c, yc, mask, phi, part),
                      partial(ops.phys_finalize_g, d, grp, part, red, phi, masked=mask is not None),
@@ -894,6 +905,8 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
             route = (partial(ops.phys_reduce, d, x0c, yc, phi, part), partial(ops.phys_finalize, d, part, red, phi),
                      partial(ops.phys_grad, d, x0c, yc, phi, red, g),
                      partial(ops.phys_optimize, d, x0c, yc, phi, part, red, loss, g))
+        if d.optimizer == 9:        # the solver's schedule also needs the plain reduce (the fifth call of its route)
+            route += (partial(ops.phys_reduce_m, st["desc_plain"], x0c, yc, mask, phi, part),)
         self._inner_loop(route, 1 if freeze_phi else self.n_iter, freeze_phi, loss, opt)
         if self._depth is not None:
             self._apply_depth_prior(st, x0c, g, r0, r1)
@@ -913,9 +926,26 @@ class PosteriorSamplingOsmosis(ConditioningMethod):
         the ONE C call that enqueues all 2 n_inner + 2 launches (one Python call per launch left the GPU idle between them).
         OSM_PHYS_PY_LOOP=1 walks the same launches through the single-launch entry points instead (A/B measurements, tests of the
         entry points)."""
-        reduce, finalize, grad, optimize = route
+        reduce, finalize, grad, optimize = route[:4]
         if os.environ.get("OSM_PHYS_PY_LOOP", "0") != "1":
             optimize(n_inner, freeze_phi, opt_state=rows)
+            return
+        if len(route) > 4:
+            # The Levenberg-Marquardt solver (optimizer 9): n_inner x { LM reduce; LM finalize that decides and steps (do_update 2 on
+            # the first iteration, then 1) }, then the closing evaluation -- the plain reduce at the trial phi, the LM finalize in close
+            # mode (3), which puts the base back on a reject -- and the gradient: 2 n_inner + 3 launches.  freeze_phi: the plain three.
+            reduce_plain = route[4]
+            if freeze_phi:
+                reduce_plain()
+                finalize(0, loss)
+                grad()
+                return
+            for it in range(n_inner):
+                reduce()
+                finalize(2 if it == 0 else 1, loss, opt_state=rows)
+            reduce_plain()
+            finalize(3, loss, opt_state=rows)
+            grad()
             return
         for it in range(n_inner):
             reduce()

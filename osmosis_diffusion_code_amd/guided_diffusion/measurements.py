@@ -1010,9 +1010,35 @@ OPTIMIZER_CODES = {"": 0, "gd": 0, "sgd": 0, "adam": 1, "adamw": 2, "adamax": 3,
                    "asgd": 7, "rprop": 8}
 
 
+# phi solvers that are not a torch.optim class of the reference's factory (its names stay in OPTIMIZER_CODES): the damped
+# Gauss-Newton / Levenberg-Marquardt solver of include/osmosis_hip.h (osm_phys_desc.optimizer = 9), which steps phi from the normal
+# equations the reduce kernel sums; `lm_lambda` is its initial damping.
+PHI_SOLVER_CODES = {"lm": 9, "levenberg_marquardt": 9}
+LM_LAMBDA_DEFAULT = 1.0
+
+
+def optimizer_code(name):
+    """osm_phys_desc.optimizer of an optimizer / solver name (`_check_optimizer` has vetted it)."""
+    n = (name or "").lower()
+    return PHI_SOLVER_CODES[n] if n in PHI_SOLVER_CODES else OPTIMIZER_CODES.get(n, 0)
+
+
+def parse_lm_lambda(value):
+    """`lm_lambda` of a physical operator: the initial damping of the `lm` solver, positive and finite (None: LM_LAMBDA_DEFAULT)."""
+    if value is None:
+        return LM_LAMBDA_DEFAULT
+    try:
+        lam = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"lm_lambda must be a positive finite number, got {value!r}") from None
+    if isinstance(value, bool) or not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError(f"lm_lambda must be a positive finite number, got {value!r}")
+    return lam
+
+
 def _check_optimizer(name):
     n = (name or "").lower()
-    if n in OPTIMIZER_CODES:
+    if n in OPTIMIZER_CODES or n in PHI_SOLVER_CODES:
         return n
     if n in ("sparseadam", "lbfgs"):
         # the reference builds these, and its optimize() then raises: SparseAdam refuses dense gradients, LBFGS.step() needs a
@@ -1091,7 +1117,10 @@ class _PhysicalOperator(LearnableOperator):
     `phi_groups=` (`parse_phi_groups`; default None) partitions the batch into contiguous groups of photos of ONE water body: a
     group's rows of `phi` (and of the optimizer state) are equal and stay equal, stepped once with the members' pooled gradient,
     `phi_reduce=` "mean" (default: the eta of the configs were chosen for one image's gradient) or "sum".  Attributes
-    `group_sizes` (None: ungrouped), `group_offsets`, `phi_reduce`."""
+    `group_sizes` (None: ungrouped), `group_offsets`, `phi_reduce`.
+    `optimizer=` one of the reference's names (`OPTIMIZER_CODES`) or a solver of `PHI_SOLVER_CODES`: "lm" steps phi by damped
+    Gauss-Newton from normal equations the kernels sum, `lm_lambda=` its initial damping (`parse_lm_lambda`); its etas only say which
+    parameters are learnt, and it takes neither `phi_groups` nor a `degradation`."""
     KIND = -1
     VARS = ()
 
@@ -1109,6 +1138,15 @@ class _PhysicalOperator(LearnableOperator):
         if self.phi_reduce not in ("mean", "sum"):
             raise ValueError(f"phi_reduce must be 'mean' or 'sum', got {self.phi_reduce!r}")
         self.group_offsets = None if self.group_sizes is None else tuple(int(v) for v in np.cumsum((0,) + self.group_sizes))
+        self.lm_lambda = parse_lm_lambda(kwargs.get("lm_lambda", None))
+        if self.optimizer in PHI_SOLVER_CODES:
+            # the solver's normal equations are those of ONE image's plain residual (include/osmosis_hip.h, optimizer 9)
+            if self.group_sizes is not None:
+                raise NotImplementedError(f"optimizer '{self.optimizer}' (lm, the Levenberg-Marquardt phi solver) with phi_groups is not "
+                                          f"built: a group's normal equations would pool its members' Gram sums")
+            if self.degradation is not None:
+                raise NotImplementedError(f"optimizer '{self.optimizer}' (lm, the Levenberg-Marquardt phi solver) with a degradation is not "
+                                          f"built: the operator would have to be applied to the Jacobian planes")
 
     # -- state ------------------------------------------------------------------------------
     def _init_phi(self, a, b, inf):
@@ -1170,6 +1208,10 @@ class _PhysicalOperator(LearnableOperator):
         gets the reference's step here: plain gradient descent phi -= eta * grad for 'GD' / 'sgd' / '', else the torch optimizer of
         `optimizer:` over one parameter group per variable (lr = eta), then the gradients are zeroed."""
         if not kwargs.get("freeze_phi", False) and any(v.grad is not None for v in self._leaves.values()):
+            if self.optimizer in PHI_SOLVER_CODES:
+                raise NotImplementedError(f"optimizer '{self.optimizer}' (lm, the Levenberg-Marquardt phi solver) cannot step from the "
+                                          f"parameters' .grad (operator.optimize() on the autograd route of a foreign degradation or "
+                                          f"loss): a gradient is not a Jacobian; the solver runs inside the osm_phys_* kernels only")
             if self.group_sizes is not None:
                 # shared water parameters: the rows of a group are one parameter, so its gradient is the members' pooled one (sum or
                 # mean), handed to every row -- the same optimizer code below then keeps the rows equal

@@ -425,7 +425,14 @@ def phys_nblk(HW):
     return query("osm_phys_nblk", HW)
 
 
+def _check_lm_part(desc, part):
+    """The Levenberg-Marquardt solver's reduce (desc.optimizer = 9) writes 32 floats per workgroup where the plain one writes 16."""
+    if desc.optimizer == 9 and part.numel() < desc.B * phys_nblk(desc.HW) * 32:
+        raise ValueError(f"optimizer 9 (lm): part must hold B * nblk * 32 = {desc.B * phys_nblk(desc.HW) * 32} floats, got {part.numel()}")
+
+
 def phys_reduce(desc: PhysDesc, x0, y, phi, part):
+    _check_lm_part(desc, part)
     call("osm_phys_reduce", C.byref(desc), ptr(x0), ptr(y), ptr(phi), ptr(part), _s(), keep=(desc, x0, y, phi, part))
 
 
@@ -442,6 +449,7 @@ def phys_grad(desc: PhysDesc, x0, y, phi, red, g):
 def phys_optimize(desc: PhysDesc, x0, y, phi, part, red, loss_out, g, n_inner: int, freeze_phi: bool, opt_state=None):
     """The whole inner phi loop of a guided step (n_inner reduce / finalize pairs, loss and dL/dx0 at the last phi, then its step)
     enqueued by one call."""
+    _check_lm_part(desc, part)
     call("osm_phys_optimize", C.byref(desc), ptr(x0), ptr(y), ptr(phi), ptr(part), ptr(red), ptr(loss_out), ptr(g), int(n_inner),
          int(bool(freeze_phi)), ptr(opt_state), _s(), keep=(desc, x0, y, phi, part, red, loss_out, g, opt_state))
 
@@ -456,6 +464,7 @@ def _check_mask(mask, y):
 def phys_reduce_m(desc: PhysDesc, x0, y, mask, phi, part):
     """osm_phys_reduce with a validity mask [B,3,HW] in the residual (None: the plain launch)."""
     _check_mask(mask, y)
+    _check_lm_part(desc, part)
     call("osm_phys_reduce_m", C.byref(desc), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(part), _s(), keep=(desc, x0, y, mask, phi, part))
 
 
@@ -474,6 +483,7 @@ def phys_grad_m(desc: PhysDesc, x0, y, mask, phi, red, g):
 def phys_optimize_m(desc: PhysDesc, x0, y, mask, phi, part, red, loss_out, g, n_inner: int, freeze_phi: bool, opt_state=None):
     """`phys_optimize` with a validity mask [B,3,HW] (None: the same launches as `phys_optimize`)."""
     _check_mask(mask, y)
+    _check_lm_part(desc, part)
     call("osm_phys_optimize_m", C.byref(desc), ptr(x0), ptr(y), ptr(mask), ptr(phi), ptr(part), ptr(red), ptr(loss_out), ptr(g),
          int(n_inner), int(bool(freeze_phi)), ptr(opt_state), _s(), keep=(desc, x0, y, mask, phi, part, red, loss_out, g, opt_state))
 
